@@ -71,7 +71,12 @@ def main():
     ap.add_argument("--e2e", type=int, default=1, help="1: add the end-to-end sub-record (N = 1, ~15 s); 0: skip it")
     ap.add_argument("--sub-steps", type=int, default=20, help="steps of the H2 / H3 sub-records at N = 1 (0: skip them)")
     ap.add_argument("--cpu-planes", type=int, default=-1, help="planes of the CPU-baseline sample (-1: auto, 0: skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the cost maps of the last step (rank 0) as DIR/<name>.npy: all of them up to 48 MB, else up to two whole "
+                         "slices and a fixed seeded sample (at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -114,6 +119,8 @@ def main():
     stream = torch.cuda.current_stream(dev)
     e.set_stream(stream.cuda_stream)
     out = torch.empty((D, H, W), device=dev, dtype=torch.float32)
+    if args.dump_outputs:
+        out.zero_()          # (H3 leaves pixels outside its cells unwritten: zeros, not stale memory, in the dumped maps)
 
     def barrier():
         torch.cuda.synchronize(dev)
@@ -213,8 +220,31 @@ def main():
         del a, b
         return best
 
+    def dump_outputs(d):
+        """The cost maps of the last timed step, as a caller of the path receives them ([D][H][W] float32, `out`).  Everything when it fits
+        in 48 MB; otherwise the first and the last slice whole as far as they fit in 32 MB, and 2 M values at positions drawn with a fixed
+        seed (their flat indices in cost_sample_index, float64: exact below 2^53)."""
+        os.makedirs(d, exist_ok=True)
+        torch.cuda.synchronize(dev)
+        files = {}
+        if out.numel() * 4 <= 48 << 20:
+            files["cost"] = out.cpu().numpy()
+        else:
+            if P * 4 <= 32 << 20:
+                files["cost_first_slice"] = out[0].cpu().numpy()
+            if D > 1 and 2 * P * 4 <= 32 << 20:
+                files["cost_last_slice"] = out[D - 1].cpu().numpy()
+            idx = np.unique(np.random.default_rng(20240607).integers(0, out.numel(), 2 << 20, dtype=np.int64))
+            files["cost_sample"] = out.view(-1)[torch.from_numpy(idx).to(dev)].cpu().numpy()
+            files["cost_sample_index"] = idx.astype(np.float64)
+        assert sum(a.nbytes for a in files.values()) <= 64 << 20
+        for name, a in files.items():
+            np.save(os.path.join(d, name + ".npy"), a)
+        return sorted(files)
+
     step, evals_rank, bytes_per_eval, batch, desc, planes = make_workload(args.workload)
     elapsed, kern_ms = measure(step, args.steps, args.warmup)
+    dumped = dump_outputs(args.dump_outputs) if args.dump_outputs and rank == 0 else None
     kind = batch.kernel_kind(0)
     kernel_name = ("les_march_kernel<R=10> (gather + guided filter fused: exact integer box sums, wave-specialised pipeline)" if kind == 1
                    else "les_strip_kernel<R=10> (gather + guided filter fused, fp64 running sums)")
@@ -309,6 +339,8 @@ def main():
             "kernel_source_sha1": kernel_source_hash(),
         },
     }
+    if dumped is not None:
+        result["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
 
     # ---- sub-records: the other two workloads of SURVEY.md 8(d) on the same context
     if world == 1 and args.sub_steps > 0 and args.workload == "h1":

@@ -18,12 +18,14 @@ def main():
     out, lib, H, W, D, pm_iters, gc_iters = sys.argv[1], sys.argv[2], int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5]), int(sys.argv[6]), int(sys.argv[7])
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     use_gpu = lib == "hip"
-    local = int(os.environ.get("LOCAL_RANK", "0"))
+    # LES_TEST_DIST_BACKEND=gloo LES_TEST_ONE_DEVICE=1: every rank on cuda:0 of a one-GPU box (see dist_worker.py)
+    backend = os.environ.get("LES_TEST_DIST_BACKEND", "nccl" if use_gpu else "gloo")
+    local = 0 if os.environ.get("LES_TEST_ONE_DEVICE") == "1" else int(os.environ.get("LOCAL_RANK", "0"))
     if use_gpu:
         import torch
         torch.cuda.set_device(local)
     if world > 1:
-        dist.init_process_group("nccl" if use_gpu else "gloo")
+        dist.init_process_group(backend)
     imL, imR = synth.make_guide(H, W, 1234), synth.make_guide(H, W, 1235)
     e = api.HipCostVolumeEnergy(imL, imR, synth.make_volume(D, H, W, 42), synth.make_volume(D, H, W, 43), lib=None if use_gpu else lib, device=local if use_gpu else 0)
     st = stereo.FastGCStereo(e, imL, imR, dict(lambda_=0.05), device=f"cuda:{local}" if use_gpu else "cpu", rank=rank, world=world, seed=3)
@@ -45,6 +47,9 @@ def main():
         st.close()                      # the per-view process groups of the run
         dist.destroy_process_group()
     e.close()
+    if not use_gpu:
+        import torch
+        assert not torch.cuda.is_initialized(), "a CPU (simulator) rank initialised the GPU runtime"
 
 
 if __name__ == "__main__":

@@ -21,7 +21,7 @@ sys.path.insert(0, ROOT)
 
 def main():
     from PIL import Image
-    ref = "/root/reference/data/MiddV2/cones"
+    ref = os.path.join(HERE, "cones")                       # the committed copy of the pair
     out = {}
     for name in ("imL", "imR"):
         rgb = np.asarray(Image.open(os.path.join(ref, name + ".png")).convert("RGB"))

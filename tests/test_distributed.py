@@ -38,7 +38,9 @@ def _run(world, out, H=64, W=88, D=10, iters=1, gc_iters=0, kernel=None, worker=
 def _run_uncached(world, out, H, W, D, iters, gc_iters, kernel, worker, port):
     from localexpstereo_amd import build
     lib = build.build_sim()
-    env = dict(os.environ, OMP_NUM_THREADS="2")
+    # the workers run the simulator build on the CPU: they must not initialise the GPU runtime (api.load would, to share torch's HIP
+    # runtime), or a world-8 run would hold the GPU open in nine processes at once on a GPU machine
+    env = dict(os.environ, OMP_NUM_THREADS="2", LES_HIP_NO_TORCH_PRELOAD="1")
     if kernel:
         env["LES_HIP_KERNEL"] = kernel       # "strip": the fiber simulator runs the 256-thread strip kernel ~4x faster than the 768-thread march kernel
     worker = os.path.join(ROOT, "tests", worker)

@@ -101,7 +101,7 @@ def test_host_demo_sharded_ranks_on_one_gpu(demo, world):
     assert r.returncode == 0 and "les_host_demo: OK" in r.stdout
 
 
-def test_push_relabel_equals_bk_on_real_graphs(monkeypatch):
+def test_push_relabel_equals_bk_on_real_graphs(monkeypatch, tmp_path):
     """Two 129 x 129 crops of a coarse-layer lock-step dumped from the Adirondack-shape run (89 % and 20 % of the nodes switch: the hard
     kind): the push-relabel solver and the Boykov-Kolmogorov solver of liblocalexp_host.so must return the same mask and the same flow,
     and the mask must be a minimum cut according to networkx."""
@@ -121,7 +121,7 @@ def test_push_relabel_equals_bk_on_real_graphs(monkeypatch):
                 "    lgc.solve_prebuilt(api._rects(np.array([(0, 0, w, h)], np.int32)), p, np.array([0], np.int64), m, nthreads=1, flows_out=f)\n"
                 "    out[k + '_mask'] = m; out[k + '_flow'] = f\n"
                 "np.savez(sys.argv[2], **out)\n")
-        outp = os.path.join(os.environ.get("TMPDIR", "/tmp"), f"hard_cells_{solver}.npz")
+        outp = str(tmp_path / f"hard_cells_{solver}.npz")
         env = dict(os.environ, LES_GC_PUSH_RELABEL_MIN_NODES=thr, LES_GC_BK_OPS_PER_NODE="1")     # ("pr": the budget of the BK phase runs out at once)
         if solver == "plain":
             env["LES_GC_PREPUSH"] = "0"           # the graphs loaded as they come: both search trees, segments read off the trees

@@ -6,7 +6,7 @@ import pytest
 
 from localexpstereo_amd import io as lio
 
-CONES = "/root/reference/data/MiddV2/cones"
+CONES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cones")
 
 
 def test_pfm_round_trip_and_layout(tmp_path):
@@ -67,7 +67,6 @@ def test_calib_parser(tmp_path):
     assert c["ndisp"] == 145 and c["width"] == 1436 and c["doffs"] == 2.5 and c["cam1"][0, 2] == 4
 
 
-@pytest.mark.skipif(not os.path.isdir(CONES), reason="reference data not present")
 def test_load_data_cones():
     pytest.importorskip("PIL")
     d = lio.load_data(CONES)

@@ -2,17 +2,16 @@
 The oracle's NaiveStereoEnergy restatement (LES/StereoEnergy.h:629-764) driven by the reference's own loop order
 (LES/FastGCStereo.h:22-72,94-115, doGC == false) on the reference's bundled cones pair, evaluated with the
 Evaluator's bad-pixel definition (LES/Evaluator.h:133-140, threshold 0.5 px, LES/main.cpp:280).
-The data set lives under /root/reference (not available on the GPU box): the test skips when it is absent."""
+The data set is the committed copy of the cones pair under tests/golden/cones."""
 import os
 import time
 
 import numpy as np
 import pytest
 
-CONES = "/root/reference/data/MiddV2/cones"
+CONES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cones")
 
 
-@pytest.mark.skipif(not os.path.isdir(CONES), reason="reference data not present")
 def test_config1_cones_cpu_path(oracle_mod):
     from PIL import Image
     om = oracle_mod
