@@ -191,10 +191,11 @@ int les_hip_batch_expansion_graph(les_hip_ctx* ctx, const les_hip_batch* batch, 
  * FastGCStereo::expansionMoveBK -- graph.maxflow(); graph.what_segment(i) == SOURCE (LES/FastGCStereo.h:553-559) -- on the
  * payload of les_hip_batch_expansion_graph, for all cells of the batch, one workgroup per cell with the whole graph on chip
  * (synchronous push-relabel; the cut is the canonical one of the reference's solver: SINK side = nodes that can still reach the
- * sink).  Two kernels: when every cell of the batch has at most 2048 nodes, (w + 2) * (h + 2) <= 2304 and h <= 70 -- the finest
- * layer's cells do -- csrc/les_maxflow_cell.h (residuals in registers, two barriers per iteration); otherwise csrc/les_maxflow.h
- * (residuals in LDS).  Same cut from both up to nodes on exact ties that float rounding moves; les_hip_batch_graph_solver_kind says
- * which one a call would launch (0 = les_maxflow_cell.h, 1 / 2 = les_maxflow.h with 1024 / 512 threads, -1 = a cell above the limit);
+ * sink).  Two kernels, chosen for every cell on its own shape: a cell of at most 2048 nodes with (w + 2) * (h + 2) <= 2304 and h <= 70 -- the
+ * finest layer's cells -- runs csrc/les_maxflow_cell.h (residuals in registers, two barriers per iteration), any other cell csrc/les_maxflow.h
+ * (residuals in LDS); a call launches once per kernel it needs.  Same cut from both up to nodes on exact ties that float rounding moves, which
+ * is why the choice never looks at the other cells.  les_hip_batch_graph_solver_kind says which kernels a call launches: the most general one of
+ * its cells (0 = only les_maxflow_cell.h, 1 / 2 = les_maxflow.h with 1024 / 512 threads for some cell, -1 = a cell above the limit);
  * LES_HIP_MAXFLOW_CELL_KERNEL=0 in the environment forces les_maxflow.h.  d_masks: one byte per graph node (255 = the node takes the proposal), the input of les_hip_batch_apply_masks;
  * d_status: n ints (0 = solved, 1 = iteration limit reached: cut that cell with the host solver instead); d_flows: n doubles or
  * NULL (flow through the n-links; add flow0 of les_hip_batch_expansion_graph for the value of the cut).
@@ -226,13 +227,15 @@ long long les_hip_batch_tiled_workspace_bytes(const les_hip_batch* batch);
 int les_hip_batch_solve_graphs_tiled(les_hip_ctx* ctx, const les_hip_batch* batch, const float* d_payload, unsigned char* d_masks, int* d_status,
                                      double* d_flows, void* d_workspace, long long workspace_bytes, int* launches_out, int* unsolved_out);
 /* Hand-over (round 6): a lock-step lasts as long as its slowest cell, and the launches are at their worst on the tail of a hard cell (a few
- * hundred small excesses, one cell's tiles on a 256-CU chip).  After 28 launches, once at most 8 cells of at most 140 000 nodes in total are
- * still open AND a whole group of 16 launches went by without a cell finishing, the open cells' residual graphs (8 residual capacities + the
- * excess per node, 36 bytes) go to host-mapped memory and the host cores -- idle during device cuts -- finish each with FIFO push-relabel from
- * the remaining excess nodes (host/ResidualCut.h; one thread per cell).  Larger open sets (the coarsest layer's 150 000-node cells) only after
- * 220 launches, everything that is still open after 300.  The residual graph of a feasible preflow has the minimum cuts of the graph it came
+ * hundred small excesses, one cell's tiles on a 256-CU chip).  At the progress checks (after launch 12, then every 16 launches) every open cell
+ * that has had 60 launches and has at most 40 000 nodes -- and after 220 launches every open cell -- goes to the host cores: its residual graph
+ * (8 residual capacities + the excess per node, 36 bytes) is written to host-mapped memory and finished with FIFO push-relabel from the remaining
+ * excess nodes (host/ResidualCut.h; one thread per cell).  The residual graph of a feasible preflow has the minimum cuts of the graph it came
  * from, so masks, status and flows mean what they mean without it.  LES_HIP_MAXFLOW_HANDOVER=0 switches it off.
- * The _stats form reports what happened (the plain form = the _stats form without the report). */
+ * The _stats form reports what happened (the plain form = the _stats form without the report).
+ * Both device max-flows keep one property that multi-rank runs (N ranks == 1 rank, bit for bit) and repeatable runs rest on: a cell's cut -- mask,
+ * status, flow value -- is a function of its graph and the solver parameters (environment knobs included), not of the other cells of the call, their
+ * order or their number; the hand-over decision looks at the cell alone.  tests/parity_cases.py: case_cut_is_a_function_of_the_cell holds it. */
 typedef struct les_hip_tiled_stats {
     int launches;            /* launches of les_maxflow_tiled_kernel enqueued */
     int unsolved;            /* cells that hit the launch limit (d_status non-zero) */

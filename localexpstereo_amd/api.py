@@ -311,7 +311,8 @@ class Batch:
 
     @property
     def graph_solver_kind(self):
-        """Which one-workgroup kernel solve_graphs would launch: 0 = les_maxflow_cell.h, 1 / 2 = les_maxflow.h, -1 = a cell above the limit."""
+        """The most general one-workgroup kernel solve_graphs launches (the kernel is chosen per cell): 0 = only les_maxflow_cell.h, 1 / 2 = les_maxflow.h
+        (1024 / 512 threads) for some cell, -1 = a cell above the limit."""
         return int(self.e.L.les_hip_batch_graph_solver_kind(self.h))
 
     def solve_graphs(self, payload_dev, masks_dev, status_dev, flows_dev=None, unsolved_total_dev=None):

@@ -156,6 +156,12 @@ struct les_hip_batch {
     mutable les::MtTile* d_mt_tiles = nullptr;
     mutable int* d_mt_tiles_per_cell = nullptr;
     mutable int mt_ntiles = -1;          // -1: not built yet
+    // one-workgroup device max-flow: the cells grouped by the kernel that cuts them (les_hip_cuts.inc), built on first use per value of
+    // LES_HIP_MAXFLOW_CELL_KERNEL (mf_list_key; -1: not built yet)
+    mutable std::mutex mf_mu;
+    mutable int* d_mf_list = nullptr;
+    mutable int mf_list_key = -1;
+    mutable int mf_count[3] = {0, 0, 0};
 };
 
 // Caller-owned scratch of the one-call operator (the reference's `Reusable`, LES/StereoEnergy.h:616-623): its own stream, a

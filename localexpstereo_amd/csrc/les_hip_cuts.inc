@@ -127,20 +127,55 @@ long long les_hip_batch_max_cell_nodes(const les_hip_batch* b)
     return m;
 }
 
-// One workgroup per cell either way.  When every cell of the lock-step fits it, the kernel with the tiled solver's two-barrier iteration and the
-// residuals in registers (les_maxflow_cell.h: 0); otherwise -- or with LES_HIP_MAXFLOW_CELL_KERNEL=0 (A/B, tests of the other path) -- les_maxflow.h
-// with two nodes per thread (1) or five (2).
+// One workgroup per cell either way, and the kernel is chosen for every cell on its own shape -- never on the other cells of the lock-step: the kernels
+// agree only up to nodes on float ties, and a cell's cut must not depend on the cells it shares a lock-step with (an N-rank run gives each rank
+// another band of a set's cells than one rank has).  A cell that fits it runs the kernel with the tiled solver's two-barrier iteration and the
+// residuals in registers (les_maxflow_cell.h: 0); any other cell -- or every cell with LES_HIP_MAXFLOW_CELL_KERNEL=0 (A/B, tests of the other
+// path) -- runs les_maxflow.h with two nodes per thread (1) or five (2).
+namespace {
+bool mf_cell_kernel_enabled()
+{
+    if (const char* ev = getenv("LES_HIP_MAXFLOW_CELL_KERNEL")) return atoi(ev) != 0;
+    return true;
+}
+int mf_cell_kind(const les_hip_rect& t, bool cell_kernel)
+{
+    if (t.w <= 0 || t.h <= 0) return 0;                      // (an empty cell is closed by whichever kernel gets it)
+    if (cell_kernel && les::mc_fits(t.w, t.h)) return 0;
+    return (long long)t.w * t.h <= 2048 ? 1 : 2;
+}
+// the batch's cells grouped by kernel (kind 0, then 1, then 2, batch order inside a group) on the device; mf_count[k]: the size of group k
+int mf_build_lists(const les_hip_batch* b, bool cell_kernel)
+{
+    std::lock_guard<std::mutex> lk(b->mf_mu);
+    const int key = cell_kernel ? 1 : 0;
+    if (b->mf_list_key == key) return LES_HIP_OK;
+    std::vector<int> list;
+    list.reserve((size_t)b->n);
+    int count[3] = {0, 0, 0};
+    for (int k = 0; k < 3; k++)
+        for (int i = 0; i < b->n; i++)
+            if (mf_cell_kind(b->targets[i], cell_kernel) == k) { list.push_back(i); count[k]++; }
+    if (!b->d_mf_list && hipMalloc((void**)&b->d_mf_list, std::max<size_t>(1, list.size()) * sizeof(int)) != hipSuccess) {
+        b->d_mf_list = nullptr;
+        return fail(LES_HIP_ERR_DEVICE, "les_hip_batch_solve_graphs: cell list allocation failed");
+    }
+    if (!list.empty() && hipMemcpy(b->d_mf_list, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(LES_HIP_ERR_DEVICE, "les_hip_batch_solve_graphs: cell list upload failed");
+    std::copy(count, count + 3, b->mf_count);
+    b->mf_list_key = key;
+    return LES_HIP_OK;
+}
+}  // namespace
+
 int les_hip_batch_graph_solver_kind(const les_hip_batch* b)
 {
     if (!b) return -1;
-    const long long maxn = les_hip_batch_max_cell_nodes(b);
-    if (maxn > LES_HIP_MAXFLOW_MAX_NODES) return -1;
-    bool cell_kernel = true;
-    if (const char* ev = getenv("LES_HIP_MAXFLOW_CELL_KERNEL")) cell_kernel = atoi(ev) != 0;
-    if (cell_kernel)
-        for (const les_hip_rect& t : b->targets)
-            if (t.w > 0 && t.h > 0 && !les::mc_fits(t.w, t.h)) { cell_kernel = false; break; }
-    return cell_kernel ? 0 : maxn <= 2048 ? 1 : 2;
+    if (les_hip_batch_max_cell_nodes(b) > LES_HIP_MAXFLOW_MAX_NODES) return -1;
+    const bool cell_kernel = mf_cell_kernel_enabled();
+    int kind = 0;
+    for (const les_hip_rect& t : b->targets) kind = std::max(kind, mf_cell_kind(t, cell_kernel));
+    return kind;
 }
 
 int les_hip_batch_solve_graphs(les_hip_ctx* c, const les_hip_batch* b, const float* d_payload, unsigned char* d_masks, int* d_status, double* d_flows)
@@ -157,8 +192,6 @@ int les_hip_batch_solve_graphs_counted(les_hip_ctx* c, const les_hip_batch* b, c
     const long long maxn = les_hip_batch_max_cell_nodes(b);
     if (maxn > LES_HIP_MAXFLOW_MAX_NODES) return fail(LES_HIP_ERR_ARG, "les_hip_batch_solve_graphs: a cell of %lld nodes exceeds the limit of %d", maxn, LES_HIP_MAXFLOW_MAX_NODES);
     static_assert(LES_HIP_MAXFLOW_MAX_NODES == les::kMfMaxNodes, "header constant out of date");
-    const int np = (int)((std::max<long long>(maxn, 1) + 7) / 8) * 8;
-    const size_t lds = les::mf_lds_bytes(np);
 #if !defined(LES_SIM)
     // The opt-in to more than 64 KB of dynamic LDS is a per-DEVICE function attribute: it is set once per context (a context is bound
     // to one device), under the context's mutex, with that device current -- a process-wide flag would leave the second GPU of a
@@ -183,17 +216,44 @@ int les_hip_batch_solve_graphs_counted(les_hip_ctx* c, const les_hip_batch* b, c
     const les::GraphCellMf* cells = reinterpret_cast<const les::GraphCellMf*>(b->d_targets);
     int max_iter = les::kMfMaxIter;
     if (const char* ev = getenv("LES_HIP_MAXFLOW_MAX_ITER")) max_iter = std::max(0, atoi(ev));      // tests of the callers' host fall-back
+    int round_iters = 16;                                   // (8 ... 64 measured on whole runs: flat within 3 %, tools/lab/ab_cell_kernel.sh)
+    if (const char* ev = getenv("LES_HIP_MAXFLOW_ROUND_ITERS")) round_iters = std::max(1, atoi(ev));
+    const bool cell_kernel = mf_cell_kernel_enabled();
     const int kind = les_hip_batch_graph_solver_kind(b);
-    if (kind == 0) {
-        int round_iters = 16;                               // (8 ... 64 measured on whole runs: flat within 3 %, tools/lab/ab_cell_kernel.sh)
-        if (const char* ev = getenv("LES_HIP_MAXFLOW_ROUND_ITERS")) round_iters = std::max(1, atoi(ev));
-        hipLaunchKernelGGL(les::les_maxflow_cell_kernel, dim3(b->n), dim3(les::kMcThreads), les::kMcLdsBytes, cur_stream(c), cells, b->d_graph_off, d_payload, max_iter, round_iters,
-                           d_masks, d_status, d_flows, d_unsolved_total);
-    } else if (kind == 1)
-        hipLaunchKernelGGL((les::les_maxflow_kernel<2, 1024>), dim3(b->n), dim3(1024), lds, cur_stream(c), cells, b->d_graph_off, d_payload, np, max_iter, d_masks, d_status, d_flows, d_unsolved_total);
-    else
-        hipLaunchKernelGGL((les::les_maxflow_kernel<5, 512>), dim3(b->n), dim3(512), lds, cur_stream(c), cells, b->d_graph_off, d_payload, np, max_iter, d_masks, d_status, d_flows, d_unsolved_total);
-    HIPCHECK(hipGetLastError());
+    // up to three launches on the same stream over disjoint groups of cells; a lock-step whose cells all go to one kernel is one launch over the
+    // whole batch (no list), as before
+    bool uniform = true;
+    for (const les_hip_rect& t : b->targets) uniform = uniform && mf_cell_kind(t, cell_kernel) == kind;
+    int count[3] = {0, 0, 0};
+    const int* lists[3] = {nullptr, nullptr, nullptr};
+    long long group_max[3] = {0, 0, 0};
+    if (uniform) count[kind] = b->n;
+    else {
+        const int rc = mf_build_lists(b, cell_kernel);
+        if (rc) return rc;
+        std::copy(b->mf_count, b->mf_count + 3, count);
+        lists[0] = b->d_mf_list; lists[1] = lists[0] + count[0]; lists[2] = lists[1] + count[1];
+    }
+    for (const les_hip_rect& t : b->targets) {
+        const int k = uniform ? kind : mf_cell_kind(t, cell_kernel);
+        group_max[k] = std::max(group_max[k], (long long)std::max(0, t.w) * std::max(0, t.h));
+    }
+    for (int k = 0; k < 3; k++) {
+        if (count[k] == 0) continue;
+        // the LDS pitch of les_maxflow.h is the largest cell of the launch: it places the arrays, it does not change the arithmetic
+        const int np = (int)((std::max<long long>(group_max[k], 1) + 7) / 8) * 8;
+        const size_t lds = les::mf_lds_bytes(np);
+        if (k == 0)
+            hipLaunchKernelGGL(les::les_maxflow_cell_kernel, dim3(count[k]), dim3(les::kMcThreads), les::kMcLdsBytes, cur_stream(c), cells, b->d_graph_off, d_payload, max_iter,
+                               round_iters, d_masks, d_status, d_flows, d_unsolved_total, lists[k]);
+        else if (k == 1)
+            hipLaunchKernelGGL((les::les_maxflow_kernel<2, 1024>), dim3(count[k]), dim3(1024), lds, cur_stream(c), cells, b->d_graph_off, d_payload, np, max_iter, d_masks, d_status,
+                               d_flows, d_unsolved_total, lists[k]);
+        else
+            hipLaunchKernelGGL((les::les_maxflow_kernel<5, 512>), dim3(count[k]), dim3(512), lds, cur_stream(c), cells, b->d_graph_off, d_payload, np, max_iter, d_masks, d_status,
+                               d_flows, d_unsolved_total, lists[k]);
+        HIPCHECK(hipGetLastError());
+    }
     return LES_HIP_OK;
 }
 
@@ -325,7 +385,7 @@ int les_hip_batch_solve_graphs_tiled_stats(les_hip_ctx* c, const les_hip_batch* 
     if (rc) return rc;
     MtHost& hf = *lease.m;
     volatile int* flags = hf.h_flags;
-    flags[0] = 0; flags[1] = 0; flags[2] = 0; flags[3] = 0;   // (nothing in flight writes them: the previous user of this MtHost has synchronised)
+    for (int i = 0; i < 6; i++) flags[i] = 0;   // (nothing in flight writes them: the previous user of this MtHost has synchronised)
     a.host_flags = hf.d_flags;
     hipLaunchKernelGGL(les::les_maxflow_tiled_init_kernel, dim3((b->n + 255) / 256), dim3(256), 0, st, a.ws, a.nodes, a.ncells, b->d_mt_tiles_per_cell, d_status, d_flows, a.host_flags);
     HIPCHECK(hipGetLastError());
@@ -333,65 +393,70 @@ int les_hip_batch_solve_graphs_tiled_stats(les_hip_ctx* c, const les_hip_batch* 
         HIPCHECK(hipStreamSynchronize(st));
         return LES_HIP_OK;
     }
-    // Hand-over policy (les_maxflow_tiled.h, host/ResidualCut.h): after `hand_after` launches, once at most `hand_cells` cells of at most
-    // `hand_nodes` nodes in total are still open AND no cell finished during the last group of launches, the host cores finish them from their
-    // residual graphs.  The last condition is what tells stragglers from a lock-step whose cells are all moderately slow (measured, profiles/
-    // round6_tiled_replay.md: cells that finish one after the other finish soon; a group of 16 launches without a single cell finishing means
-    // the open ones are outliers with hundreds of launches to go -- handing over cells that had 16 launches left costs more than it saves).  LES_HIP_MAXFLOW_HANDOVER=0 switches it off
-    // (every cell is then cut by launches alone, as in round 5); ..._AFTER / _CELLS / _NODES override the thresholds (A/B measurements).
-    // A lock-step that is still running after `hand_all_after` launches hands over whatever is open (the launches would go on for hundreds more: the
-    // status-1 exit of round 5 at 2 000 launches remains for a hand-over that is switched off).
-    // Cell size matters: a coarsest-layer cell (150 000 nodes) costs the host 3 ... 10 ms, more than the 20 ... 40 further launches an ordinary straggler of that
-    // layer needs, so early on only small problems go (<= hand_nodes: eight 129 x 129 cells); larger ones after `hand_late_after` launches, when the
-    // tail is the long kind (measured on whole runs, same box, hand-over of everything stalled / none: "three_surfaces" one view 3.18 / 2.89 s, two views
-    // 5.05 / 4.79 s -- its coarsest layer lost 25 % -- while "objects" two views gained 14 %, all of it on the middle layer).
-    int hand_after = 28, hand_cells = 8, hand_all_after = 300, hand_late_after = 220;
-    long long hand_nodes = 140000, hand_nodes_late = 400000, hand_cell_nodes = 40000;      // hand_cell_nodes: early on only SMALL cells go (round 6, after the launches became 30 % cheaper: the host finishing a 100 000-node cell of the coarsest layer lost 0.1 - 0.16 s per two-view run)
+    // Hand-over policy (les_maxflow_tiled.h, host/ResidualCut.h): at the progress checks -- after launch 12 and then every 16 launches, the same
+    // schedule in every lock-step -- the host cores finish from its residual graph every open cell that has had `hand_after` launches and has at
+    // most `hand_cell_nodes` nodes, and after `hand_late_after` launches every open cell whatever its size.  The decision looks at nothing but the
+    // cell itself (its launch count, its size, its phase): the host finisher and the launches may pick different minimum cuts where float capacities
+    // tie, so a rule that looked at the other cells of the lock-step -- how many are open, how large they are together, whether any finished lately
+    // (round 6) -- made a cell's mask depend on its neighbours in the lock-step, and an N-rank run, whose ranks hold other bands of a set's cells,
+    // differ from a single-rank run.  Cell size matters: a coarsest-layer cell (150 000 nodes) costs the host 3 ... 10 ms, more than the further
+    // launches an ordinary straggler of that layer needs, so early on only small cells go (<= hand_cell_nodes: layer-1 cells of 129 x 129).
+    // LES_HIP_MAXFLOW_HANDOVER=0 switches it off (every cell is then cut by launches alone, as in round 5); ..._AFTER / _CELL_NODES / _LATE_AFTER
+    // override the thresholds (A/B measurements, tests; ..._NODES sets the node limit as well).
+    int hand_after = 60, hand_late_after = 220;
+    long long hand_cell_nodes = 40000;
     bool hand = true;
     if (const char* ev = getenv("LES_HIP_MAXFLOW_HANDOVER")) hand = atoi(ev) != 0;
     if (const char* ev = getenv("LES_HIP_MAXFLOW_HANDOVER_AFTER")) hand_after = std::max(1, atoi(ev));
-    if (const char* ev = getenv("LES_HIP_MAXFLOW_HANDOVER_CELLS")) hand_cells = std::max(1, atoi(ev));
-    if (const char* ev = getenv("LES_HIP_MAXFLOW_HANDOVER_NODES")) hand_nodes = hand_nodes_late = hand_cell_nodes = std::max(1ll, atoll(ev));      // (one number for all three size limits)
+    if (const char* ev = getenv("LES_HIP_MAXFLOW_HANDOVER_NODES")) hand_cell_nodes = std::max(1ll, atoll(ev));
     if (const char* ev = getenv("LES_HIP_MAXFLOW_HANDOVER_CELL_NODES")) hand_cell_nodes = std::max(1ll, atoll(ev));
     if (const char* ev = getenv("LES_HIP_MAXFLOW_HANDOVER_LATE_AFTER")) hand_late_after = std::max(1, atoi(ev));
-    if (const char* ev = getenv("LES_HIP_MAXFLOW_HANDOVER_ALL_AFTER")) hand_all_after = std::max(1, atoi(ev));
+    long long smallest = b->graph_nodes;                    // (the host skips the check while no cell of the batch could qualify)
+    for (const les_hip_rect& t : b->targets)
+        if (t.w > 0 && t.h > 0) smallest = std::min(smallest, (long long)t.w * t.h);
     // Launches are enqueued in groups; after each group the host reads "cells done" (the only synchronisation).  Launches that come
     // after the last cell finished return at once.
-    int total = 0, group = 12, handed = 0, done_prev = -1;
-    const bool need_stall = !getenv("LES_HIP_MAXFLOW_HANDOVER_NO_STALL_RULE");      // (A/B: hand over as soon as few cells are open)
+    int total = 0, group = 12, handed = 0;
     for (;;) {
         for (int i = 0; i < group; i++)
             hipLaunchKernelGGL(les::les_maxflow_tiled_kernel, dim3(b->mt_ntiles), dim3(les::kMtThreads), les::kMtLdsBytes, st, a);
         total += group;
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipStreamSynchronize(st));
-        const int done = flags[0];
-        if (done >= b->n) break;
-        const bool everything = total >= hand_all_after;
-        const bool stalled = done == done_prev || !need_stall;
-        done_prev = done;
-        if (hand && total >= hand_after && ((b->n - done <= hand_cells && stalled) || everything)) {
-            const int want_cells = everything ? b->n - done : hand_cells;
-            const long long want_nodes = everything ? b->graph_nodes : std::min<long long>(total >= hand_late_after ? hand_nodes_late : hand_nodes, b->graph_nodes);
-            rc = mt_host_stage(&hf, want_nodes, want_cells);
-            if (rc) return rc;
+        const int done = flags[0];                          // (cells closed by the launches; the `handed` ones are closed as well)
+        if (done + handed >= b->n) break;
+        if (hand && total >= hand_after && (total >= hand_late_after || smallest <= hand_cell_nodes)) {
             les::MtHandArgs ha;
             ha.tiles = b->d_mt_tiles; ha.ws = a.ws; ha.nodes = a.nodes; ha.ncells = a.ncells; ha.cells = a.cells;
-            ha.max_cells = want_cells; ha.max_nodes = want_nodes; ha.cap_nodes = hf.cap_nodes;
-            ha.max_cell_nodes = (everything || total >= hand_late_after) ? b->graph_nodes : hand_cell_nodes;
-            ha.list = reinterpret_cast<les::MtHandCell*>(hf.d_stage + hf.off_list());
-            ha.rc8 = reinterpret_cast<float*>(hf.d_stage);
-            ha.ex = reinterpret_cast<float*>(hf.d_stage + hf.off_ex());
-            ha.hmasks = reinterpret_cast<const uint8_t*>(hf.d_stage + hf.off_masks());
-            ha.hflows = reinterpret_cast<const double*>(hf.d_stage + hf.off_flows());
+            ha.hand_after = hand_after; ha.late_after = hand_late_after; ha.cell_nodes = hand_cell_nodes;
             ha.masks = d_masks; ha.status = d_status; ha.flows = d_flows; ha.host_flags = hf.d_flags;
-            hipLaunchKernelGGL(les::les_maxflow_tiled_collect_kernel, dim3(1), dim3(64), 0, st, ha);
-            hipLaunchKernelGGL(les::les_maxflow_tiled_pack_kernel, dim3(b->mt_ntiles), dim3(les::kMtThreads), 0, st, ha);      // (nothing to pack when the policy said no)
-            HIPCHECK(hipGetLastError());
-            HIPCHECK(hipStreamSynchronize(st));
-            handed = flags[2];
-            if (handed > 0) {
-                handed_nodes = flags[3];
+            // the staging holds what the collect kernel selects; when it reports more than fits, it has parked nothing: grow the staging, collect again
+            // (nothing has run in between, the selection is the same)
+            for (int attempt = 0;; attempt++) {
+                if (attempt == 0 && hf.cap_nodes == 0) {
+                    rc = mt_host_stage(&hf, std::min<long long>(b->graph_nodes, 140000), std::min(b->n, 16));
+                    if (rc) return rc;
+                }
+                ha.cap_nodes = hf.cap_nodes; ha.cap_cells = hf.cap_cells;
+                ha.list = reinterpret_cast<les::MtHandCell*>(hf.d_stage + hf.off_list());
+                ha.rc8 = reinterpret_cast<float*>(hf.d_stage);
+                ha.ex = reinterpret_cast<float*>(hf.d_stage + hf.off_ex());
+                ha.hmasks = reinterpret_cast<const uint8_t*>(hf.d_stage + hf.off_masks());
+                ha.hflows = reinterpret_cast<const double*>(hf.d_stage + hf.off_flows());
+                hipLaunchKernelGGL(les::les_maxflow_tiled_collect_kernel, dim3(1), dim3(64), 0, st, ha);
+                hipLaunchKernelGGL(les::les_maxflow_tiled_pack_kernel, dim3(b->mt_ntiles), dim3(les::kMtThreads), 0, st, ha);      // (nothing to pack when no cell qualified)
+                HIPCHECK(hipGetLastError());
+                HIPCHECK(hipStreamSynchronize(st));
+                const int want_cells = flags[4], want_nodes = flags[5];
+                if (flags[2] > 0 || want_cells == 0) break;
+                if (attempt > 0) return fail(LES_HIP_ERR_DEVICE, "les_hip_batch_solve_graphs_tiled: hand-over staging of %lld nodes refused %d cells of %d nodes", hf.cap_nodes, want_cells, want_nodes);
+                rc = mt_host_stage(&hf, want_nodes, want_cells);
+                if (rc) return rc;
+            }
+            const int now = flags[2];
+            if (now > 0) {
+                handed += now;
+                handed_nodes += flags[3];
                 const auto h0 = std::chrono::steady_clock::now();
                 const float* h_rc8 = reinterpret_cast<const float*>(hf.h_stage);
                 const float* h_ex = reinterpret_cast<const float*>(hf.h_stage + hf.off_ex());
@@ -404,32 +469,32 @@ int les_hip_batch_solve_graphs_tiled_stats(les_hip_ctx* c, const les_hip_batch* 
                 if (const char* dump = getenv("LES_HIP_MAXFLOW_HANDOVER_DUMP")) {      // tooling: the residual graphs as handed over (tools/residual_probe.py)
                     if (FILE* f = fopen(dump, "wb")) {
                         const long long hn = flags[3];
-                        fwrite(&handed, sizeof(int), 1, f); fwrite(&hn, sizeof(long long), 1, f);
-                        for (int q = 0; q < handed; q++) { const int wh[2] = {tg[(size_t)list[q].cell].w, tg[(size_t)list[q].cell].h}; fwrite(wh, sizeof(int), 2, f); fwrite(&list[q].hoff, sizeof(long long), 1, f); }
+                        fwrite(&now, sizeof(int), 1, f); fwrite(&hn, sizeof(long long), 1, f);
+                        for (int q = 0; q < now; q++) { const int wh[2] = {tg[(size_t)list[q].cell].w, tg[(size_t)list[q].cell].h}; fwrite(wh, sizeof(int), 2, f); fwrite(&list[q].hoff, sizeof(long long), 1, f); }
                         fwrite(h_rc8, sizeof(float), (size_t)hn * 8, f); fwrite(h_ex, sizeof(float), (size_t)hn, f);
                         fclose(f);
                     }
                 }
                 // one host thread per cell, at most as many as the process may keep busy (a persistent team owned by the calling thread); the large
                 // cells split their phases over row bands as the host cuts do
-                const int team = std::max(1, std::min(handed, les_host::cpuBudget()));
+                const int team = std::max(1, std::min(now, les_host::cpuBudget()));
                 std::atomic<int> next{0};
                 les_host::BandPool::outer().run(team, [&](int) {
-                    for (int q = next.fetch_add(1); q < handed; q = next.fetch_add(1)) {
+                    for (int q = next.fetch_add(1); q < now; q = next.fetch_add(1)) {
                         const int cell = list[q].cell;
                         const int w = tg[(size_t)cell].w, h = tg[(size_t)cell].h;
                         hflows[q] = les_host::finishResidualCut(h_rc8 + 8 * list[q].hoff, h_ex + list[q].hoff, w, h, h_masks + list[q].hoff, les_host::residualBands(w, h), solver);
                     }
                 });
-                host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h0).count();
+                host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h0).count();
                 hipLaunchKernelGGL(les::les_maxflow_tiled_unpack_kernel, dim3(b->mt_ntiles), dim3(256), 0, st, ha);
                 HIPCHECK(hipGetLastError());
-                // the staging belongs to the next caller as soon as this MtHost is back in the pool: the unpack kernel must have read it
+                // the staging belongs to the next caller (and the next check) as soon as the unpack kernel has read it
                 HIPCHECK(hipStreamSynchronize(st));
                 if (done + handed >= b->n) break;
             }
         }
-        if (total >= a.max_launches + group) return fail(LES_HIP_ERR_DEVICE, "les_hip_batch_solve_graphs_tiled: %d of %d cells still open after %d launches", b->n - done, b->n, total);
+        if (total >= a.max_launches + group) return fail(LES_HIP_ERR_DEVICE, "les_hip_batch_solve_graphs_tiled: %d of %d cells still open after %d launches", b->n - done - handed, b->n, total);
         group = 16;
     }
     *launches_out = total;

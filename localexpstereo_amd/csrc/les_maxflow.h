@@ -61,10 +61,11 @@ template <int kMfNodesPerThread, int THREADS>
 __global__ void __launch_bounds__(THREADS, THREADS / 128)
 les_maxflow_kernel(const GraphCellMf* __restrict__ cells, const long long* __restrict__ offsets, const float* __restrict__ payload,
                    int nmax_padded, int max_iter, uint8_t* __restrict__ masks, int* __restrict__ status, double* __restrict__ flows,
-                   int* __restrict__ unsolved_total)         // optional: += 1 per cell that hits the iteration limit (callers that check once per several launches)
+                   int* __restrict__ unsolved_total,         // optional: += 1 per cell that hits the iteration limit (callers that check once per several launches)
+                   const int* __restrict__ cell_list)      // optional: workgroup -> cell index (a launch over some of the batch's cells)
 {
 #if defined(LES_SIM)
-    static thread_local float s_raw[(kMfMaxNodes * 46 + 4160) / 4 + 16];
+    alignas(16) static thread_local float s_raw[(kMfMaxNodes * 46 + 4160) / 4 + 16];
     char* base = reinterpret_cast<char*>(s_raw);
 #else
     extern __shared__ __attribute__((aligned(16))) char s_dyn[];
@@ -78,11 +79,12 @@ les_maxflow_kernel(const GraphCellMf* __restrict__ cells, const long long* __res
     uint16_t* hgt = reinterpret_cast<uint16_t*>(sentB + NP);
     int* flag = reinterpret_cast<int*>(hgt + NP);          // [0] any active, [1..3] relabel sweep changed something (rotating)
 
-    const GraphCellMf c = cells[blockIdx.x];
+    const int ci = cell_list ? cell_list[blockIdx.x] : (int)blockIdx.x;
+    const GraphCellMf c = cells[ci];
     const int W = c.w, H = c.h, N = W * H;
     const int tid = (int)threadIdx.x;
-    const float* p5 = payload + 5 * offsets[blockIdx.x];
-    if (N <= 0) { if (tid == 0) { status[blockIdx.x] = 0; if (flows) flows[blockIdx.x] = 0.0; } return; }
+    const float* p5 = payload + 5 * offsets[ci];
+    if (N <= 0) { if (tid == 0) { status[ci] = 0; if (flows) flows[ci] = 0.0; } return; }
     const int BIG = N + 2;                                 // "cannot reach the sink" (fits uint16: N <= 2304)
 
     // ---- own nodes: v = tid + j * THREADS
@@ -283,7 +285,7 @@ les_maxflow_kernel(const GraphCellMf* __restrict__ cells, const long long* __res
     }
     // ---- the cut: nodes that can still reach the sink keep the current label (SINK), the others take the proposal (SOURCE)
     global_relabel(false);
-    uint8_t* m = masks + offsets[blockIdx.x];
+    uint8_t* m = masks + offsets[ci];
     double t_out = 0.0;
 #pragma unroll
     for (int j = 0; j < kMfNodesPerThread; j++) {
@@ -304,11 +306,11 @@ les_maxflow_kernel(const GraphCellMf* __restrict__ cells, const long long* __res
     }
     if (tid == 0) {
 #if defined(LES_MF_DEBUG_ITERS)
-        status[blockIdx.x] = converged ? -it : 1;             // measurement builds: the iteration count, negated
-        if (flows) flows[blockIdx.x] = (double)dbg_sweeps;
+        status[ci] = converged ? -it : 1;             // measurement builds: the iteration count, negated
+        if (flows) flows[ci] = (double)dbg_sweeps;
 #else
-        status[blockIdx.x] = converged ? 0 : 1;
-        if (flows) flows[blockIdx.x] = red[0];
+        status[ci] = converged ? 0 : 1;
+        if (flows) flows[ci] = red[0];
         if (!converged && unsolved_total) atomicAdd(unsolved_total, 1);
 #endif
     }

@@ -13,7 +13,7 @@
 //     fell), one barrier per sweep; the heights are RESET to the exact distances every `round_iters` iterations (les_maxflow.h: raised to them).
 // LDS: two halo-pitched height arrays of uint16 (N + 2 <= 2050), 8 exchange words and a flag byte per node: 77 728 B, two workgroups per CU.
 // Cells of up to 2048 nodes whose halo-pitched rectangle (w + 2) x (h + 2) has at most 2304 entries and at most 72 rows qualify
-// (mc_fits); a lock-step with any other cell runs les_maxflow_kernel as before.  Masks are the unique sink-side set of a maximum preflow: equal to
+// (mc_fits); any other cell runs les_maxflow_kernel (chosen per cell: les_hip_cuts.inc).  Masks are the unique sink-side set of a maximum preflow: equal to
 // les_maxflow_kernel's up to ties that float rounding of the residuals moves; flow values agree to rounding.
 #pragma once
 
@@ -43,14 +43,15 @@ __host__ __device__ inline bool mc_fits(int w, int h)
     return w > 0 && h > 0 && (long long)w * h <= kMcMaxNodes && (long long)(w + 2) * (h + 2) <= kMcMaxHalo && h + 2 <= kMcMaxRows;
 }
 
-// grid = cells; block = kMcThreads; dynamic LDS = kMcLdsBytes.  Every cell of the launch must satisfy mc_fits (or be empty).
+// grid = cells (or the cells of cell_list); block = kMcThreads; dynamic LDS = kMcLdsBytes.  Every cell of the launch must satisfy mc_fits (or be empty).
 __global__ void __launch_bounds__(kMcThreads, kMcThreads / 128)          // two workgroups per CU (1024 threads: 8 waves per SIMD -> at most 64 VGPRs)
 les_maxflow_cell_kernel(const GraphCellMf* __restrict__ cells, const long long* __restrict__ offsets, const float* __restrict__ payload,
                         int max_iter, int round_iters, uint8_t* __restrict__ masks, int* __restrict__ status, double* __restrict__ flows,
-                        int* __restrict__ unsolved_total)
+                        int* __restrict__ unsolved_total,
+                        const int* __restrict__ cell_list)      // optional: workgroup -> cell index (a launch over some of the batch's cells)
 {
 #if defined(LES_SIM)
-    static thread_local int s_raw[kMcLdsBytes / 4 + 16];
+    alignas(16) static thread_local int s_raw[kMcLdsBytes / 4 + 16];
     char* base = reinterpret_cast<char*>(s_raw);
 #else
     extern __shared__ __attribute__((aligned(16))) char s_dyn_mc[];
@@ -64,11 +65,12 @@ les_maxflow_cell_kernel(const GraphCellMf* __restrict__ cells, const long long* 
     int* sflag = reinterpret_cast<int*>(flg + NP);                          // [0..2] rotating "changed" flags of relax, [4] any active node, [8..10] rotating "still active" flags of the iterations
     int* rowchg = sflag + 16;                                               // [3][72]: rows (halo rows included) in which a distance fell, per sweep
 
-    const GraphCellMf c = cells[blockIdx.x];
+    const int ci = cell_list ? cell_list[blockIdx.x] : (int)blockIdx.x;
+    const GraphCellMf c = cells[ci];
     const int W = c.w, H = c.h, N = W * H;
     const int tid = (int)threadIdx.x;
-    if (N <= 0) { if (tid == 0) { status[blockIdx.x] = 0; if (flows) flows[blockIdx.x] = 0.0; } return; }
-    const float* p5 = payload + 5 * offsets[blockIdx.x];
+    if (N <= 0) { if (tid == 0) { status[ci] = 0; if (flows) flows[ci] = 0.0; } return; }
+    const float* p5 = payload + 5 * offsets[ci];
     const int BIG = N + 2;                                                  // "cannot reach the sink" (fits uint16: N <= 2048)
     const int hp = W + 2;
     const float inv_w = 1.0f / (float)W;
@@ -278,7 +280,7 @@ les_maxflow_cell_kernel(const GraphCellMf* __restrict__ cells, const long long* 
     }
 
     // ---- the cut: nodes that can still reach the sink keep the current label (SINK), the others take the proposal (SOURCE)
-    uint8_t* m = masks + offsets[blockIdx.x];
+    uint8_t* m = masks + offsets[ci];
     double t_used = 0.0;               // sink capacity of the own nodes at load time (read again: two registers less through the whole kernel) minus what is left of it
 #pragma unroll
     for (int j = 0; j < kMcNpt; j++) {
@@ -299,8 +301,8 @@ les_maxflow_cell_kernel(const GraphCellMf* __restrict__ cells, const long long* 
         __syncthreads();
     }
     if (tid == 0) {
-        status[blockIdx.x] = converged ? 0 : 1;
-        if (flows) flows[blockIdx.x] = red[0];
+        status[ci] = converged ? 0 : 1;
+        if (flows) flows[ci] = red[0];
         if (!converged && unsolved_total) atomicAdd(unsolved_total, 1);
     }
 }

@@ -158,7 +158,7 @@ __global__ void __launch_bounds__(kMtThreads, 8)          // two 16-wave workgro
 les_maxflow_tiled_kernel(MtArgs a)
 {
 #if defined(LES_SIM)
-    static thread_local int s_raw[kMtLdsBytes / 4 + 16];
+    alignas(16) static thread_local int s_raw[kMtLdsBytes / 4 + 16];      // (read through double* by the reductions)
     char* base = reinterpret_cast<char*>(s_raw);
 #else
     extern __shared__ __attribute__((aligned(16))) char s_dyn_mt[];
@@ -677,9 +677,9 @@ __global__ void les_maxflow_tiled_init_kernel(char* ws, long long nodes, int nce
 
 // ---- hand-over of straggler cells to the host cores (round 6; host/ResidualCut.h) -------------------------------------------------
 // A lock-step lasts as long as its slowest cell, and the scheme above is at its worst on the tail of a hard cell (a few hundred small
-// excesses, hundreds of launches, one cell's tiles on a 256-CU chip).  Once few cells are still open the host stops enqueueing launches:
-//   collect  (one thread) lists the open cells if they are few enough -- all of them or none --, gives every one a slot and a node offset in
-//            the staging arrays and parks it in kMtHandover (launches leave it alone);
+// excesses, hundreds of launches, one cell's tiles on a 256-CU chip).  At its progress checks the host runs:
+//   collect  (one thread) lists the open cells that qualify -- by the cell's own launch count and size, nothing else (les_hip_cuts.inc) --,
+//            gives every one a slot and a node offset in the staging arrays and parks it in kMtHandover (launches leave it alone);
 //   pack     (grid = tiles) writes the residual graph of the parked cells -- 8 residual capacities and the excess of every node, with what
 //            the neighbouring tiles still had in flight folded in exactly as the next launch would have -- into host-mapped memory, and
 //            takes the sink capacity that is left out of the cell's flow value;
@@ -692,44 +692,54 @@ struct MtHandArgs {
     long long nodes;
     int ncells;
     const GraphCellMf* cells;
-    int max_cells;                   // policy: hand over only when at most this many cells ...
-    long long max_nodes;             // ... of at most this many nodes in total are still open
-    long long cap_nodes;             // capacity of the staging arrays (never exceeded, whatever the policy says)
-    long long max_cell_nodes;        // policy: ... and none of them is larger than this
-    MtHandCell* list;                // host-mapped, [max_cells]
-    float* rc8;                      // host-mapped staging: [max_nodes][8]
-    float* ex;                       // [max_nodes]
-    const uint8_t* hmasks;           // [max_nodes], written by the host
-    const double* hflows;            // [max_cells], written by the host: the flow it routed
+    int hand_after;                  // policy, per cell: an open cell goes after this many launches if it has at most `cell_nodes` nodes ...
+    int late_after;                  // ... and after this many whatever its size
+    long long cell_nodes;
+    long long cap_nodes;             // capacity of the staging arrays: a selection that does not fit parks nothing and reports its size
+    int cap_cells;
+    MtHandCell* list;                // host-mapped, [cap_cells]
+    float* rc8;                      // host-mapped staging: [cap_nodes][8]
+    float* ex;                       // [cap_nodes]
+    const uint8_t* hmasks;           // [cap_nodes], written by the host
+    const double* hflows;            // [cap_cells], written by the host: the flow it routed
     uint8_t* masks;
     int* status;
     double* flows;                   // optional
-    int* host_flags;                 // [2] cells handed over, [3] their nodes
+    int* host_flags;                 // [2] cells handed over, [3] their nodes; [4] / [5] cells / nodes selected (also when they did not fit the staging)
 };
+
+// does open cell `c` (w x h nodes) go to the host at this check?  (a cell in FINAL closes in the next launch)
+__host__ __device__ inline bool mt_hand_cell(const MtCtl& c, long long cn, int hand_after, int late_after, long long cell_nodes)
+{
+    if (c.phase >= kMtDone || c.phase == kMtFinal) return false;
+    return c.launches >= late_after || (c.launches >= hand_after && cn <= cell_nodes);
+}
 
 __global__ void les_maxflow_tiled_collect_kernel(MtHandArgs a)
 {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     const MtLayout L = mt_layout(a.nodes, a.ncells);
     MtCtl* ctl = reinterpret_cast<MtCtl*>(a.ws + L.ctl);
-    int open = 0;
+    int sel = 0;
     long long nodes = 0;
-    long long largest = 0;
-    for (int i = 0; i < a.ncells; i++)
-        if (ctl[i].phase < kMtDone) {
-            const long long cn = (long long)a.cells[i].w * a.cells[i].h;
-            open++; nodes += cn; largest = cn > largest ? cn : largest;
-        }
-    if (open == 0 || open > a.max_cells || nodes > a.max_nodes || nodes > a.cap_nodes || largest > a.max_cell_nodes) { mt_store(a.host_flags + 2, 0); return; }
+    for (int i = 0; i < a.ncells; i++) {
+        if (ctl[i].phase == kMtHandover) ctl[i].phase = kMtDone;            // handed over at an earlier check (and unpacked): pack / unpack must skip it now
+        const long long cn = (long long)a.cells[i].w * a.cells[i].h;
+        if (mt_hand_cell(ctl[i], cn, a.hand_after, a.late_after, a.cell_nodes)) { sel++; nodes += cn; }
+    }
+    mt_store(a.host_flags + 4, sel);
+    mt_store(a.host_flags + 5, (int)nodes);
+    if (sel == 0 || sel > a.cap_cells || nodes > a.cap_nodes) { mt_store(a.host_flags + 2, 0); mt_store(a.host_flags + 3, 0); return; }
     int slot = 0;
     long long hoff = 0;
     for (int i = 0; i < a.ncells; i++) {
-        if (ctl[i].phase >= kMtDone) continue;
+        const long long cn = (long long)a.cells[i].w * a.cells[i].h;
+        if (!mt_hand_cell(ctl[i], cn, a.hand_after, a.late_after, a.cell_nodes)) continue;
         ctl[i].hand = slot; ctl[i].hoff = hoff;
         ctl[i].phase = kMtHandover;
         a.list[slot].cell = i; a.list[slot].pad = 0; a.list[slot].hoff = hoff;
         slot++;
-        hoff += (long long)a.cells[i].w * a.cells[i].h;
+        hoff += cn;
     }
     mt_fence();
     mt_store(a.host_flags + 3, (int)hoff);
@@ -741,7 +751,7 @@ __global__ void __launch_bounds__(kMtThreads)
 les_maxflow_tiled_pack_kernel(MtHandArgs a)
 {
 #if defined(LES_SIM)
-    static thread_local double red[kMtThreads];
+    alignas(16) static thread_local double red[kMtThreads];
 #else
     __shared__ double red[kMtThreads];
 #endif

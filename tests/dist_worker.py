@@ -38,7 +38,8 @@ def main():
     labels, cur = r.run(iters, gc_iters, g)
     if rank == 0:
         np.savez(out, labels=labels.cpu().numpy(), cur=cur.cpu().numpy(), bytes_exchanged=r.bytes_exchanged,
-                 energy=(g.energy(0) if g else 0.0), host_labels=(g.labels[0] if g else 0))
+                 energy=(g.energy(0) if g else 0.0), host_labels=(g.labels[0] if g else 0),
+                 tiled_handed_cells=getattr(r, "gc_seconds", {}).get("tiled_handed_cells", 0))
     r.close()
     if not use_gpu:
         assert not torch.cuda.is_initialized(), "a CPU (simulator) rank initialised the GPU runtime"

@@ -1404,6 +1404,222 @@ def case_tiled_maxflow_handover(pr, monkeypatch, seed=13, shapes=None):
     return handed
 
 
+def _crop_payload(p, w, h, x0, y0, cw, ch):
+    """the cw x ch window at (x0, y0) of a w x h device-format payload as a cell of its own (arcs that would leave the window carry no capacity)"""
+    q = np.array(p.reshape(h, w, 5)[y0: y0 + ch, x0: x0 + cw], np.float32)
+    q[:, -1, 1] = 0; q[-1, :, 2] = 0; q[-1, :, 3] = 0; q[:, 0, 3] = 0; q[-1, :, 4] = 0; q[:, -1, 4] = 0
+    return np.ascontiguousarray(q.reshape(-1, 5))
+
+
+def _hard_cells():
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "hard_cells.npz"))
+    return [((z[k].shape[1], z[k].shape[0]), np.ascontiguousarray(z[k].reshape(-1, 5), np.float32)) for k in z.files]
+
+
+def _real_expansion_payloads(lib, device, units=(14, 43), sets=2, per_set=4):
+    """device-format payloads of real expansion moves -- the first cells of the first lock-steps of a graph-cut iteration on cones_ad_volume(),
+    built as case_device_cuts_vs_host_cuts builds them (float capacities: ties occur) -> [((w, h), payload)] per layer"""
+    from localexpstereo_amd import gc as lgc
+    from localexpstereo_amd import pm
+    imL, vol, _ = cones_ad_volume()
+    table = [[(api.PROPOSE_EXPANSION, 1), (api.PROPOSE_RANDOM, 1)]] * len(units)
+    e = api.HipCostVolumeEnergy(imL, None, vol, None, windR=20, eps=1e-4, th_col=0.12, max_disp=63.0, lib=lib)
+    r = pm.PMRunner(e, units, table, seed=11, device=device)
+    g = lgc.GraphCut(imL, None, lambda_=1.0)
+    out = []
+    try:
+        r.init_labels()
+        r.iteration(0)
+        r.device_cuts = True
+        r.begin_gc(g)
+        p = g.params
+        for li in range(len(units)):
+            cells = []
+            for sh in [s_ for s_ in r.shards[li] if s_.n][:sets]:
+                r._gc_buffers(sh)
+                for kind in (api.PROPOSE_EXPANSION, api.PROPOSE_RANDOM):
+                    sh.batch.propose(kind, r.labels.data_ptr(), sh.rng.data_ptr(), sh.planes.data_ptr(), m=0)
+                    sh.batch.run(sh.planes.data_ptr(), r.prop.data_ptr(), mode=0, check=True, planes_on_device=True)
+                    sh.batch.expansion_graph(sh.planes.data_ptr(), r.labels.data_ptr(), r.cur.data_ptr(), r.prop.data_ptr(), sh.payload.data_ptr(),
+                                             mode=0, lambda_=p["lambda_"], th_smooth=p["th_smooth"], omega=p["omega"], epsilon=p["epsilon"])
+                    e.synchronize()
+                    ph = sh.payload[: sh.graph_nodes * 5].cpu().numpy().reshape(-1, 5)
+                    for i in range(min(per_set, sh.n)):
+                        w, h = int(sh.regions[i]["w"]), int(sh.regions[i]["h"])
+                        o = int(sh.graph_off[i])
+                        cells.append(((w, h), np.ascontiguousarray(ph[o: o + w * h], np.float32)))
+            out.append(cells)
+    finally:
+        r.close(); e.close(); g.close()
+    return out
+
+
+def _world_bands(n, world):
+    """the contiguous bands of cells the ranks of a `world`-rank run own (localexpstereo_amd/pm.py)"""
+    bounds = np.linspace(0, n, world + 1).astype(int)
+    return [list(range(bounds[r], bounds[r + 1])) for r in range(world) if bounds[r + 1] > bounds[r]]
+
+
+def case_cut_is_a_function_of_the_cell(pr, solver, shapes, seed=17, real=(), monkeypatch=None, networkx_nodes=2304):
+    """THE property behind "N ranks == 1 rank, bit for bit" (localexpstereo_amd/pm.py gives each rank a contiguous band of a set's cells) and
+    behind repeatable runs: a cell's cut is a function of its graph and the solver parameters -- not of the other cells of the lock-step, their
+    order or their number.  The same payload bytes are cut in many lock-steps: each cell alone (the reference), the whole pool in order, reversed
+    and permuted, the bands of world 2, 4 and 8, and every cell with one neighbour that changes what a lock-step-wide rule would choose
+    (solver "workgroup": a cell on the other side of the les_maxflow_cell.h / les_maxflow.h boundary; "tiled": the largest cell of the pool).
+    Every cell: mask bytes, status and flow value bit-equal to its reference (each kernel's flow is a fixed-order reduction over one cell).
+    The reference itself is checked without product code: the fp64 capacity of every returned cut equals the networkx max-flow value.
+      solver "workgroup" (les_hip_batch_solve_graphs): the pool is dyadic and float random cells and windows of the committed hard crops at the
+        shapes where the kernel choice changes -- 2048 / 2050 nodes, (w + 2)(h + 2) = 2304 / 2310, h + 2 = 72 / 73, up to 2304 nodes --, once
+        with the product's choice and once with LES_HIP_MAXFLOW_CELL_KERNEL=0; the host solver (solve_prebuilt) on a subset of a lock-step's cells
+        equals those cells of the full host solve (the partial host re-cut of pm.py).
+      solver "tiled" (les_hip_batch_solve_graphs_tiled): cells of several tiles, one-row and one-column cells, the hard crops; every grouping twice,
+        with the hand-over at the product's thresholds and with LES_HIP_MAXFLOW_HANDOVER_AFTER=1 (it fires at the first check): the cells handed
+        over are the same in every grouping (asserted on their count), and a handed-over residual graph finished by solve_residual with one
+        thread, with the full budget and in forced row bands gives the same bytes.
+    real: extra ((w, h), payload) cells (real expansion moves).  -> dict of counts"""
+    from localexpstereo_amd import gc as lgc
+    assert solver in ("workgroup", "tiled") and monkeypatch is not None
+    tiled = solver == "tiled"
+    rng = np.random.default_rng(seed)
+    shapes = [(min(w, pr.W), min(h, pr.H)) for (w, h) in shapes]
+    pool = list(zip(shapes, _random_cell_payloads(rng, shapes, True))) + list(zip(shapes, _random_cell_payloads(rng, shapes, False)))
+    hard = _hard_cells()
+    if tiled:
+        pool += hard
+    else:                                                     # real graphs at one-workgroup sizes: windows of the hard crops
+        for ((w, h), p), (cw, ch, x0, y0) in zip(hard * 2, ((45, 45, 0, 0), (29, 70, 50, 10), (32, 64, 90, 60), (48, 48, 20, 70))):
+            pool.append(((cw, ch), _crop_payload(p, w, h, x0, y0, cw, ch)))
+    pool += [c for c in real if (c[0][0] * c[0][1] <= api.Batch.MAXFLOW_MAX_NODES) != tiled or tiled]
+    pool = [((w, h), p) for ((w, h), p) in pool if w <= pr.W and h <= pr.H]
+    n = len(pool)
+    nodes = np.array([w * h for (w, h), _ in pool])
+
+    def solve(idx, st=None):
+        off, status, masks, flows = _solve_cells_on_device(pr, [pool[i][0] for i in idx], [pool[i][1] for i in idx], tiled=tiled, stats=st)
+        return {i: (masks[off[k]: off[k] + nodes[i]].tobytes(), int(status[k]), float(flows[k])) for k, i in enumerate(idx)}
+
+    def flipper(i, cell_kernel):
+        """a neighbour that sends a lock-step-wide rule to another kernel (csrc/les_maxflow_cell.h: mc_fits; les_maxflow.h: 2048 nodes)"""
+        w, h = pool[i][0]
+        fits = cell_kernel and w * h <= 2048 and (w + 2) * (h + 2) <= 2304 and h + 2 <= 72
+        for j in range(n):                                    # a neighbour on the other side of the boundary
+            wj, hj = pool[j][0]
+            fj = cell_kernel and wj * hj <= 2048 and (wj + 2) * (hj + 2) <= 2304 and hj + 2 <= 72
+            if j != i and (fj != fits or (not fits and (w * h > 2048) != (wj * hj > 2048))):
+                return j
+        return (i + 1) % n
+
+    groupings = {"in order": [list(range(n))], "reversed": [list(range(n))[::-1]], "permuted": [[int(v) for v in rng.permutation(n)]]}
+    for world in (2, 4, 8):
+        groupings[f"world {world}"] = _world_bands(n, world)
+    settings = ([("product hand-over", {}), ("hand-over at the first check", {"LES_HIP_MAXFLOW_HANDOVER_AFTER": "1", "LES_HIP_MAXFLOW_HANDOVER_NODES": "100000000"})] if tiled else
+                [("product kernel choice", {}), ("LES_HIP_MAXFLOW_CELL_KERNEL=0", {"LES_HIP_MAXFLOW_CELL_KERNEL": "0"})])
+    counts = {"cells": n, "nodes": int(nodes.sum()), "groupings": 0, "handed": 0}
+    for sname, env in settings:
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        ref, ref_handed = {}, 0
+        for i in range(n):
+            st = {}
+            ref.update(solve([i], st))
+            ref_handed += st.get("handed_cells", 0)
+        assert not any(r[1] for r in ref.values()), f"{sname}: a cell hit the iteration limit"
+        if tiled and env:
+            assert ref_handed > 0, f"{sname}: nothing was handed over"
+            counts["handed"] = ref_handed
+        g = dict(groupings)
+        g["pairs"] = ([[i, largest_tiled] for i in range(n) for largest_tiled in [int(np.argmax(nodes))] if i != largest_tiled] if tiled else
+                      [[i, flipper(i, not env)] for i in range(n)])
+        for gname, batches in g.items():
+            got, handed = {}, 0
+            for idx in batches:
+                st = {}
+                res = solve(idx, st)
+                handed += st.get("handed_cells", 0)
+                for i, v in res.items():
+                    if gname == "pairs" and i != idx[0]:
+                        continue
+                    got[i] = v
+            for i, (m, s, f) in got.items():
+                (w, h), rm = pool[i][0], ref[i]
+                assert s == rm[1], f"{solver}, {sname}, {gname}: cell {i} ({w}x{h}) status {s}, alone {rm[1]}"
+                assert m == rm[0], (f"{solver}, {sname}, {gname}: cell {i} ({w}x{h}): "
+                                    f"{int((np.frombuffer(m, np.uint8) != np.frombuffer(rm[0], np.uint8)).sum())} mask bytes differ from the cell cut alone")
+                assert f == rm[2], f"{solver}, {sname}, {gname}: cell {i} ({w}x{h}) flow {f!r}, alone {rm[2]!r}"
+            if tiled and gname != "pairs":
+                # every cell is in exactly one lock-step of these groupings: the hand-over is a per-cell decision, so the count is the same
+                assert handed == ref_handed, f"{sname}, {gname}: {handed} cells handed over, {ref_handed} when each cell is cut alone"
+            counts["groupings"] += 1
+        # the reference against networkx (no product code): the cut is a minimum cut
+        for i in range(n):
+            (w, h), p = pool[i]
+            if w * h > networkx_nodes:
+                continue
+            ref_flow, _ = _grid_graph_reference(p, w, h)
+            scale = max(1.0, np.abs(p[:, 0]).astype(np.float64).sum())
+            cap = _cut_capacity(p, w, h, np.frombuffer(ref[i][0], np.uint8) != 0)
+            assert abs(cap - ref_flow) <= 1e-6 * scale, f"{solver}, {sname}: cell {i} ({w}x{h}) is not a minimum cut ({cap} vs {ref_flow})"
+            assert abs(ref[i][2] - ref_flow) <= 1e-6 * scale + 1e-5 * abs(ref_flow), (i, ref[i][2], ref_flow)
+        for k in env:
+            monkeypatch.delenv(k, raising=False)
+    if not tiled:
+        # the host solver on a subset of a lock-step's cells (pm.py's partial re-cut) == those cells of the full host solve
+        trs = api._rects(np.array([(0, 0, w, h) for (w, h), _ in pool], np.int32))
+        off = np.concatenate([[0], np.cumsum(nodes)[:-1]]).astype(np.int64)
+        pay = np.ascontiguousarray(np.concatenate([p for _, p in pool]).reshape(-1), np.float32)
+        full = np.zeros(int(nodes.sum()), np.uint8)
+        lgc.solve_prebuilt(trs, pay, off, full)
+        for sub in (np.arange(0, n, 3), np.array([n - 1]), np.arange(1, n, 2)):
+            part = np.zeros_like(full)
+            lgc.solve_prebuilt(np.ascontiguousarray(trs[sub]), pay, np.ascontiguousarray(off[sub]), part, nthreads=1 + len(sub) % 3)
+            for i in sub:
+                assert part[off[i]: off[i] + nodes[i]].tobytes() == full[off[i]: off[i] + nodes[i]].tobytes(), f"host re-cut of cell {i} differs"
+    else:
+        # a handed-over residual graph (as dumped by the solver) finished by the host with 1 thread, the full budget and forced row bands
+        import tempfile
+        with tempfile.TemporaryDirectory() as td:
+            dump = os.path.join(td, "residual.bin")
+            for k, v in (("LES_HIP_MAXFLOW_HANDOVER_AFTER", "1"), ("LES_HIP_MAXFLOW_HANDOVER_NODES", "100000000"), ("LES_HIP_MAXFLOW_HANDOVER_DUMP", dump)):
+                monkeypatch.setenv(k, v)
+            big = [i for i in range(n) if nodes[i] >= 4000]
+            st = {}
+            res = solve(big, st)
+            for k in ("LES_HIP_MAXFLOW_HANDOVER_AFTER", "LES_HIP_MAXFLOW_HANDOVER_NODES", "LES_HIP_MAXFLOW_HANDOVER_DUMP"):
+                monkeypatch.delenv(k, raising=False)
+            assert st["handed_cells"] > 0 and os.path.exists(dump)
+            raw = open(dump, "rb").read()
+            hc, hn = np.frombuffer(raw, np.int32, 1)[0], np.frombuffer(raw, np.int64, 1, 4)[0]
+            ent = np.frombuffer(raw, np.dtype([("w", np.int32), ("h", np.int32), ("hoff", np.int64)]), hc, 12)
+            o = 12 + ent.nbytes
+            rc8 = np.ascontiguousarray(np.frombuffer(raw, np.float32, hn * 8, o))
+            ex = np.ascontiguousarray(np.frombuffer(raw, np.float32, hn, o + hn * 32))
+            regions = api._rects(np.array([(0, 0, int(e_["w"]), int(e_["h"])) for e_ in ent], np.int32))
+            hoff = np.ascontiguousarray(ent["hoff"], np.int64)
+            outs = []
+            for nthreads, bands in ((1, None), (0, None), (0, "2000")):
+                if bands:
+                    monkeypatch.setenv("LES_GC_RESIDUAL_BAND_NODES", bands)
+                m_, f_ = np.zeros(int(hn), np.uint8), np.zeros(int(hc), np.float64)
+                lgc.solve_residual(regions, rc8, ex, hoff, m_, nthreads=nthreads, solver=1, flows_out=f_)
+                monkeypatch.delenv("LES_GC_RESIDUAL_BAND_NODES", raising=False)
+                outs.append((m_.tobytes(), f_.tobytes()))
+            # thread count: bit for bit.  Row bands are a solver parameter (the product runs one band, host/ResidualCut.h: residualBands): the same
+            # minimum cut, the flow routed along other paths (double sums in another order: equal to rounding)
+            assert outs[0] == outs[1], "the host finisher depends on its thread count"
+            assert outs[2][0] == outs[0][0], "the host finisher's cut depends on its row bands"
+            fa, fb = np.frombuffer(outs[0][1]), np.frombuffer(outs[2][1])
+            assert (np.abs(fa - fb) <= 1e-9 * np.abs(fa) + 1e-6).all(), (fa, fb)
+            # ... and they are the masks the solver returned for those cells (the same finisher, solver 1)
+            m0 = np.frombuffer(outs[0][0], np.uint8)
+            by_shape = {}
+            for i in big:
+                by_shape.setdefault(pool[i][0], []).append(i)
+            for e_ in ent:
+                cands = [res[i][0] for i in by_shape[(int(e_["w"]), int(e_["h"]))]]
+                assert m0[e_["hoff"]: e_["hoff"] + e_["w"] * e_["h"]].tobytes() in cands
+    return counts
+
+
 def case_refresh_volume(lib, H=90, W=130, D=10):
     """les_hip_refresh_volume: a context created on a DEVICE-resident volume keeps things derived from it (the cost range that fixes the march kernel's fixed-point
     scales, the tiled copy steep planes gather from).  After the caller refills the volume in place -- here with costs of another range, [-1, 2) instead of [0, 1) -- and

@@ -467,6 +467,20 @@ def test_gpu_tiled_maxflow_handover(oracle_mod, monkeypatch):
         pr.close()
 
 
+def test_gpu_cut_is_a_function_of_the_cell(mid, monkeypatch):
+    """A cell's device cut does not depend on the other cells of its lock-step (their kind, order, number): both one-workgroup kernels and the
+    tiled solver with and without the hand-over, against the cell cut alone, bit for bit -- full-size shapes, the committed hard crops and cells of
+    real expansion moves on the cones crop (tests/parity_cases.py)."""
+    real0, real1 = pc._real_expansion_payloads(None, "cuda", per_set=3)
+    c = pc.case_cut_is_a_function_of_the_cell(mid, "workgroup", [(32, 64), (41, 50), (126, 16), (152, 13), (29, 70), (27, 71), (48, 48), (45, 45), (440, 3), (250, 7),
+                                                                 (13, 7), (1, 17), (19, 1)], real=real0, monkeypatch=monkeypatch)
+    print("one workgroup per cell:", c)
+    c = pc.case_cut_is_a_function_of_the_cell(mid, "tiled", [(300, 260), (150, 130), (65, 31), (450, 1), (1, 375), (200, 45), (31, 65), (64, 30)], real=real1,
+                                              monkeypatch=monkeypatch, networkx_nodes=2500)
+    print("tiled:", c)
+    assert c["handed"] > 0
+
+
 def test_gpu_gc_sets_without_round_trips(oracle_mod, monkeypatch):
     """pm.PMRunner: the finest layer's disjoint sets enqueued without per-lock-step status reads == the per-lock-step path, bit for bit, and the roll-back of a
     set whose cuts hit the iteration limit == host cuts."""
@@ -843,7 +857,9 @@ def test_two_ranks_rccl_equal_one_rank(tmp_path):
     same runs go over gloo with every rank on cuda:0 -- RCCL refuses two ranks on one device -- and (c) uses the demo's loop-back transport,
     so the HIP build's multi-rank path is still checked bit for bit against one rank):
       (a) pm.PMRunner with backend nccl (= RCCL over xGMI) and the HIP build on 2 GPUs: PatchMatch iterations AND a graph-cut iteration with every
-          cut on the ranks' own GPUs reproduce the 1-rank labels and costs bit for bit;
+          cut on the ranks' own GPUs reproduce the 1-rank labels and costs bit for bit -- once more with the tiled solver's hand-over firing
+          (LES_HIP_MAXFLOW_HANDOVER_AFTER=1: straggler cells finished by the host cores in both runs; a cell's cut must not depend on which cells
+          share its lock-step, and a rank's lock-steps hold other cells than the single rank's);
       (b) the two-view run with the view split (stereo.FastGCStereo.run: one rank group per view, per-set all-gathers inside a group, one broadcast
           per view, post-processing replicated) on 2 -- and, with 4 GPUs, 4 -- ranks reproduces the 1-rank labelling and raw labelling bit for bit;
       (c) the C++ host: `les_host_demo ranks ... nccl` = PMStereo::runDevice with rank / world and a real ncclComm_t per rank (ncclCommInitAll, one
@@ -859,21 +875,26 @@ def test_two_ranks_rccl_equal_one_rank(tmp_path):
         # (at most 4 ranks + this process hold the GPU open at once)
         env.update(LES_TEST_DIST_BACKEND="gloo", LES_TEST_ONE_DEVICE="1")
 
-    def launch(worker, world, args, port):
+    def launch(worker, world, args, port, extra_env=None):
         cmd = ([sys.executable, worker] if world == 1 else
                [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
                 "--master-port", str(port), worker]) + args
-        subprocess.run(cmd, check=True, timeout=900, cwd=root, env=env)
+        subprocess.run(cmd, check=True, timeout=900, cwd=root, env=dict(env, **(extra_env or {})))
     # (a)
     worker = os.path.join(root, "tests", "dist_worker.py")
-    for gc_iters in ("0", "1"):
+    handover = {"LES_HIP_MAXFLOW_HANDOVER_AFTER": "1", "LES_HIP_MAXFLOW_HANDOVER_NODES": "100000000"}
+    for gc_iters, extra in (("0", None), ("1", None), ("1", handover)):
         outs = []
         for world in (1, 2):
-            out = str(tmp_path / f"a{gc_iters}_w{world}.npz")
-            launch(worker, world, [out, "hip", "200", "260", "24", "1", gc_iters], 29531)
+            out = str(tmp_path / f"a{gc_iters}_w{world}{'_h' if extra else ''}.npz")
+            launch(worker, world, [out, "hip", "200", "260", "24", "1", gc_iters], 29531, extra)
             outs.append(np.load(out))
         assert int(outs[1]["bytes_exchanged"]) > 0
-        assert outs[0]["labels"].tobytes() == outs[1]["labels"].tobytes() and outs[0]["cur"].tobytes() == outs[1]["cur"].tobytes(), f"gc_iters={gc_iters}"
+        assert outs[0]["labels"].tobytes() == outs[1]["labels"].tobytes() and outs[0]["cur"].tobytes() == outs[1]["cur"].tobytes(), f"gc_iters={gc_iters}, {extra}"
+        if extra:
+            handed = [int(o["tiled_handed_cells"]) for o in outs]
+            print(f"hand-over firing: cells handed over to the host cores, world 1 / world 2 (rank 0): {handed[0]} / {handed[1]}")
+            assert handed[0] > 0 and handed[1] > 0, handed
     # (b)
     worker = os.path.join(root, "tests", "dist_worker_dual.py")
     ref = None

@@ -269,6 +269,24 @@ def test_sim_tiled_maxflow_handover(sim_lib, oracle_mod, monkeypatch):
         pr.close()
 
 
+def test_sim_cut_is_a_function_of_the_cell(sim_lib, oracle_mod, monkeypatch):
+    """A cell's device cut does not depend on the other cells of its lock-step (their kind, order, number): both one-workgroup kernels and the
+    tiled solver with and without the hand-over, against the cell cut alone, bit for bit (tests/parity_cases.py).  Sizes of the simulator pair."""
+    from localexpstereo_amd import build
+    build.build_host_lib()
+    pr = pc.synth_pair(sim_lib, 140, 210, 4)
+    try:
+        c = pc.case_cut_is_a_function_of_the_cell(pr, "workgroup", [(32, 64), (41, 50), (126, 16), (152, 13), (29, 70), (27, 71), (48, 48), (42, 42), (13, 7), (1, 17), (19, 1)],
+                                                  monkeypatch=monkeypatch)
+        print("one workgroup per cell:", c)
+        c = pc.case_cut_is_a_function_of_the_cell(pr, "tiled", [(100, 70), (65, 31), (210, 1), (1, 140), (31, 65), (64, 30), (40, 40)], monkeypatch=monkeypatch,
+                                                  networkx_nodes=2500)
+        print("tiled:", c)
+        assert c["handed"] > 0
+    finally:
+        pr.close()
+
+
 def test_sim_device_maxflow_against_independent_checkers(cones):
     """The same kernel source against networkx and brute force (no product code as the checker); the full-size version runs on the GPU."""
     cells, nodes, diff = pc.case_device_maxflow_vs_networkx(cones, seed=5, ncells=8, max_side=24, kind=0)
