@@ -80,6 +80,28 @@ int les_hip_refresh_volume(les_hip_ctx* ctx, int mode);
  * allocated on the view's first les_hip_batch_run): runs of the same batch and view must be stream-ordered. */
 int les_hip_create_naive(les_hip_ctx** out, const les_hip_params* params, const uint8_t* imL, const uint8_t* imR,
                          float alpha, float th_grad);
+
+/* ---- choice of the cost aggregation: Parameters::filterName (LES/StereoEnergy.h:25-39; CostVolumeEnergy.h:23-42,
+ * StereoEnergy.h:666-688).  les_hip_create / les_hip_create_naive always build the guided filter ("GF").
+ *   LES_HIP_FILTER_GF         "GF": FastGuidedImageFilter<double>, radius windR / 2, eps = params->eps -- exactly les_hip_create(_naive).
+ *   LES_HIP_FILTER_BILATERAL  "BF" (NaiveStereoEnergy) / "BL" (CostVolumeEnergy): BilateralFilter (LES/GuidedFilter.h:329-374) on the
+ *                             sub-region I(filterRect): q(p) = sum over the (2 windR + 1)^2 window of p clipped to the filterRect of
+ *                             exp(-|dI|_1 / sig2) raw(s), NOT normalised; I = the 8-bit BGR guide on its 0..255 scale, radius windR,
+ *                             sig2 = params->eps (Parameters::filter_param1, 10 in paramsBF, LES/main.cpp:72), which must be > 0.
+ *                             Supported windR: 0 .. 31 (20 is the shipped value); others give LES_HIP_ERR_UNSUPPORTED.
+ *   LES_HIP_FILTER_NONE       "": no aggregation, q = raw (bit for bit); windR >= 0 (only the callers' cell geometry uses it), eps ignored.
+ * Both then apply the targetRect crop and the 1e6 overwrite of invalid labels (check != 0) of the guided filter.  Every evaluation entry
+ * point (les_hip_unary_one / _one_scratch / _unary_batch / les_hip_batch_run, any out_slabs, check 0 / 1) honours the context's filter;
+ * the bilateral and unfiltered ones need no guided-filter kernel instantiation (csrc/les_bilateral.h), and les_hip_get_stats has no
+ * statistics to return on them.  Everything else (proposals, WTA, graphs, cuts, post-processing, exchange) is independent of the filter. */
+enum { LES_HIP_FILTER_GF = 0, LES_HIP_FILTER_BILATERAL = 1, LES_HIP_FILTER_NONE = 2 };
+/* les_hip_create with a filter: replaces CostVolumeEnergy::CostVolumeEnergy for any filterName ("BF" and "BL" both select the bilateral
+ * filter; the reference's CostVolumeEnergy only knows "BL"). */
+int les_hip_create_filtered(les_hip_ctx** out, const les_hip_params* params, int filter, const uint8_t* imL, const uint8_t* imR,
+                            const float* volL, const float* volR);
+/* les_hip_create_naive with a filter: replaces NaiveStereoEnergy::NaiveStereoEnergy for any filterName. */
+int les_hip_create_naive_filtered(les_hip_ctx** out, const les_hip_params* params, int filter, const uint8_t* imL, const uint8_t* imR,
+                                  float alpha, float th_grad);
 void les_hip_destroy(les_hip_ctx* ctx);                 /* replaces: ~CostVolumeEnergy (:50-52)          */
 const char* les_hip_last_error(void);                   /* thread-local description of the last failure  */
 
@@ -135,7 +157,8 @@ int les_hip_batch_num_jobs(const les_hip_batch* b);     /* workgroups one run la
 /* Diagnostic: which kernel les_hip_batch_run launches for this batch and view: 1 = the fixed-point march kernel
  * (csrc/les_march.h; needs a finite volume with th_col - min <= 8 th_col, a guided-filter radius of 2 .. 10 and every target at least 2 x radius away from
  * filterRect borders that are not image borders -- the geometry of every LayerManager cell), 0 = the fp64 strip kernel
- * (csrc/les_kernels.h; any input), -1 = bad argument.  Both implement LES/CostVolumeEnergy.h:55-183. */
+ * (csrc/les_kernels.h; any input), -1 = bad argument.  Both implement LES/CostVolumeEnergy.h:55-183.  2 = the bilateral / unfiltered
+ * kernel (csrc/les_bilateral.h): every batch of a context made with LES_HIP_FILTER_BILATERAL or LES_HIP_FILTER_NONE. */
 int les_hip_batch_kernel_kind(const les_hip_ctx* ctx, const les_hip_batch* b, int mode);
 /* planes: n labels, HOST (planes_on_device == 0) or DEVICE memory; out: DEVICE memory.  Asynchronous
  * on the context's stream. */

@@ -17,7 +17,7 @@ PLANE_DT = np.dtype([("a", "<f4"), ("b", "<f4"), ("c", "<f4"), ("v", "<f4")])
 
 # every symbol include/localexp_hip.h declares (tests check the .so exports all of them)
 SYMBOLS = [
-    "les_hip_create", "les_hip_create_naive", "les_hip_destroy", "les_hip_last_error", "les_hip_set_stream", "les_hip_set_thread_stream", "les_hip_synchronize",
+    "les_hip_create", "les_hip_create_naive", "les_hip_create_filtered", "les_hip_create_naive_filtered", "les_hip_destroy", "les_hip_last_error", "les_hip_set_stream", "les_hip_set_thread_stream", "les_hip_synchronize",
     "les_hip_unary_one", "les_hip_unary_one_scratch", "les_hip_scratch_create", "les_hip_scratch_destroy", "les_hip_unary_batch", "les_hip_batch_create", "les_hip_batch_destroy",
     "les_hip_batch_num_jobs", "les_hip_batch_kernel_kind", "les_hip_batch_graph_nodes", "les_hip_batch_graph_offsets", "les_hip_batch_expansion_graph", "les_hip_batch_max_cell_nodes", "les_hip_batch_graph_solver_kind", "les_hip_refresh_volume", "les_hip_batch_solve_graphs", "les_hip_batch_solve_graphs_counted", "les_hip_batch_solve_graphs_tiled", "les_hip_batch_solve_graphs_tiled_stats", "les_hip_batch_tiled_workspace_bytes", "les_hip_batch_apply_masks", "les_hip_batch_run", "les_hip_batch_set_units", "les_hip_batch_propose", "les_hip_batch_wta",
     "les_hip_wta_update", "les_hip_malloc", "les_hip_free",
@@ -28,6 +28,18 @@ SYMBOLS = [
 
 
 PROPOSE_EXPANSION, PROPOSE_RANDOM, PROPOSE_RANSAC, PROPOSE_INIT = 0, 1, 2, 3
+
+# Parameters::filterName (LES/StereoEnergy.h:25) -> les_hip_create_filtered's filter.  The reference's CostVolumeEnergy knows the bilateral
+# filter as "BL" and NaiveStereoEnergy as "BF" (CostVolumeEnergy given "BF" dereferences a null filter): both names select it for both energies.
+FILTER_GF, FILTER_BILATERAL, FILTER_NONE = 0, 1, 2
+FILTER_NAMES = {"GF": FILTER_GF, "BF": FILTER_BILATERAL, "BL": FILTER_BILATERAL, "": FILTER_NONE}
+
+
+def filter_kind(name):
+    """les_hip filter enum of a Parameters::filterName ("GFfloat" is not implemented)."""
+    if name not in FILTER_NAMES:
+        raise ValueError(f"unsupported filter {name!r}: one of {sorted(FILTER_NAMES)}")
+    return FILTER_NAMES[name]
 
 
 class LesHipError(RuntimeError):
@@ -102,6 +114,8 @@ def load(path=None):
         "les_hip_consistency_check": (ci, [vp, vp, vp, C.c_float, vp, vp]),
         "les_hip_post_process": (ci, [vp, vp, vp, C.c_float, C.c_float]),
         "les_hip_create_naive": (ci, [C.POINTER(vp), C.POINTER(Params), vp, vp, C.c_float, C.c_float]),
+        "les_hip_create_filtered": (ci, [C.POINTER(vp), C.POINTER(Params), ci, vp, vp, vp, vp]),
+        "les_hip_create_naive_filtered": (ci, [C.POINTER(vp), C.POINTER(Params), ci, vp, vp, C.c_float, C.c_float]),
         "les_hip_destroy": (None, [vp]),
         "les_hip_last_error": (C.c_char_p, []),
         "les_hip_set_stream": (ci, [vp, vp]),
@@ -257,7 +271,7 @@ class Batch:
         return self.e.L.les_hip_batch_num_jobs(self.h)
 
     def kernel_kind(self, mode=0):
-        """1: the fixed-point march kernel serves this batch, 0: the fp64 strip kernel."""
+        """1: the fixed-point march kernel serves this batch, 0: the fp64 strip kernel, 2: the bilateral / unfiltered kernel."""
         return self.e.L.les_hip_batch_kernel_kind(self.e.h, self.h, mode)
 
     def run(self, planes, out_dev_ptr, mode=0, check=True, planes_on_device=False):
@@ -352,10 +366,12 @@ class Batch:
 
 
 class HipCostVolumeEnergy:
-    """Python mirror of CostVolumeEnergy (LES/CostVolumeEnergy.h:6-184) over the C ABI."""
+    """Python mirror of CostVolumeEnergy (LES/CostVolumeEnergy.h:6-184) over the C ABI.  filter: Parameters::filterName -- "GF" (the guided
+    filter, radius windR // 2, eps), "BF" / "BL" (the joint bilateral filter, radius windR, sig2 = eps) or "" (no aggregation)."""
 
     def __init__(self, imL, imR, volL, volR, windR=20, eps=1e-4, th_col=0.5, max_disp=None, min_disp=0.0,
-                 device=0, volumes_on_device=False, shape=None, lib=None):
+                 device=0, volumes_on_device=False, shape=None, lib=None, filter="GF"):
+        self.filter = filter_kind(filter)
         self.L = load(lib)
         self.imL = np.ascontiguousarray(imL, np.uint8) if imL is not None else None
         self.imR = np.ascontiguousarray(imR, np.uint8) if imR is not None else None
@@ -375,15 +391,21 @@ class HipCostVolumeEnergy:
                              int(bool(volumes_on_device)))
         h = C.c_void_p()
         self.h = None
-        self._chk(self.L.les_hip_create(C.byref(h), C.byref(self.params), _ptr(self.imL), _ptr(self.imR), vl, vr))
+        if self.filter == FILTER_GF:
+            self._chk(self.L.les_hip_create(C.byref(h), C.byref(self.params), _ptr(self.imL), _ptr(self.imR), vl, vr))
+        else:
+            self._chk(self.L.les_hip_create_filtered(C.byref(h), C.byref(self.params), self.filter, _ptr(self.imL), _ptr(self.imR), vl, vr))
         self.h = h
         self._keep = None     # host volumes were copied to HBM
 
     @classmethod
-    def naive(cls, imL, imR, windR=20, eps=1e-4, alpha=0.9, th_col=10.0, th_grad=2.0, max_disp=63.0, min_disp=0.0, device=0, lib=None):
+    def naive(cls, imL, imR, windR=20, eps=1e-4, alpha=0.9, th_col=10.0, th_grad=2.0, max_disp=63.0, min_disp=0.0, device=0, lib=None,
+              filter="GF"):
         """Python mirror of NaiveStereoEnergy (LES/StereoEnergy.h:629-764; MiddV2 parameters LES/main.cpp:86-121):
-        image-based matching cost, no volume.  Every method of the volume-based operator works on it."""
+        image-based matching cost, no volume.  Every method of the volume-based operator works on it.  filter: as for the constructor."""
         self = cls.__new__(cls)
+        self.h = None
+        self.filter = filter_kind(filter)
         self.L = load(lib)
         self.imL = np.ascontiguousarray(imL, np.uint8)
         self.imR = np.ascontiguousarray(imR, np.uint8)
@@ -394,7 +416,11 @@ class HipCostVolumeEnergy:
         self._keep = None
         h = C.c_void_p()
         self.h = None
-        self._chk(self.L.les_hip_create_naive(C.byref(h), C.byref(self.params), _ptr(self.imL), _ptr(self.imR), C.c_float(alpha), C.c_float(th_grad)))
+        if self.filter == FILTER_GF:
+            self._chk(self.L.les_hip_create_naive(C.byref(h), C.byref(self.params), _ptr(self.imL), _ptr(self.imR), C.c_float(alpha), C.c_float(th_grad)))
+        else:
+            self._chk(self.L.les_hip_create_naive_filtered(C.byref(h), C.byref(self.params), self.filter, _ptr(self.imL), _ptr(self.imR),
+                                                           C.c_float(alpha), C.c_float(th_grad)))
         self.h = h
         return self
 

@@ -13,12 +13,15 @@
 #include "les_maxflow.h"
 #include "les_maxflow_tiled.h"
 #include "les_maxflow_cell.h"
+#include "les_bilateral.h"
 
 #include "../host/ResidualCut.h"      // the host cores' finisher of the tiled max-flow (plain C++: search trees / push-relabel on a residual graph)
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <mutex>
 #if !defined(LES_SIM)
@@ -95,7 +98,9 @@ namespace { void mt_host_free(MtHost* m); }
 
 struct les_hip_ctx {
     les_hip_params p;
-    int R;
+    int filter = LES_HIP_FILTER_GF;      // aggregation (les_hip_create_filtered); the bilateral / unfiltered ones run les_hip_bilateral.inc
+    int R;                               // its radius: windR / 2 (guided filter), windR (bilateral), 0 (unfiltered)
+    float* d_bf_tab = nullptr;           // bilateral / unfiltered: the weight table exp(-|dI|_1 / sig2), 766 floats
     const StripEntry* strip;
     const MarchEntry* march = nullptr;   // null: radius not instantiated (or LES_HIP_KERNEL=strip)
     int ncu = 256;                       // compute units of the device (job cutting of the march kernel)
@@ -138,6 +143,9 @@ struct les_hip_batch {
     long long raw_floats = 0;
     int raw_chunks = 1;
     mutable float* d_raw[2] = {nullptr, nullptr};
+    // bilateral / unfiltered context: tiles of calls that share their rects (les_hip_bilateral.inc); the raw-cost patches above serve it too
+    les::BfJob* d_bfjobs = nullptr;
+    int bf_np = 1;                       // most calls per tile (1: the one-plane instantiation of the kernel)
     std::vector<les_hip_rect> targets;
     int device = 0;
     // cell geometry for the proposers / WTA
@@ -178,6 +186,9 @@ struct les_hip_scratch {
     float* d_raw = nullptr; size_t raw_cap = 0;
     les::RawCall* d_rawcall = nullptr; long long* d_raw_off = nullptr;
     les_hip_rect raw_f = {-1, -1, -1, -1};
+    // bilateral / unfiltered context: the tiles of the last rect pair
+    les::BfJob* d_bfjobs = nullptr; size_t bf_cap = 0; int bf_njobs = 0;
+    les_hip_rect bf_f = {-1, -1, -1, -1}, bf_t = {-1, -1, -1, -1};
     std::vector<Entry> cache;
     unsigned long long clock = 0;
 };
@@ -209,6 +220,8 @@ inline hipStream_t cur_stream(const les_hip_ctx* c) { return (tl_stream_gen != 0
 #include "les_hip_march.inc"             // job tables, launches and per-view set-up of the unary-cost kernels (hashed with the kernel headers by bench.py)
 
 float naive_alpha(const les_hip_ctx* c) { return c->naive_alpha; }
+
+#include "les_hip_bilateral.inc"         // the bilateral / unfiltered aggregation: per-view set-up, weight table, tiles, launches
 
 }  // namespace
 

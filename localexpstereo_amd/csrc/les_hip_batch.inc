@@ -10,7 +10,9 @@ int les_hip_batch_create(les_hip_ctx* c, int n, const les_hip_rect* frs, const l
     if (out_slabs > 1 && n % out_slabs != 0) return fail(LES_HIP_ERR_ARG, "out_slabs = %d does not divide the %d calls of the batch (slab i / out_slabs holds out_slabs consecutive calls; pass 1 for one slab per call)", out_slabs, n);
     *out = nullptr;
     std::vector<les::Job> jobs;
-    int rc = build_jobs(c, n, frs, trs, out_slabs, jobs);
+    int rc = LES_HIP_OK;
+    if (c->filter == LES_HIP_FILTER_GF) rc = build_jobs(c, n, frs, trs, out_slabs, jobs);
+    else for (int i = 0; i < n && !rc; i++) rc = check_rects(c, frs[i], trs[i]);      // (the bilateral / unfiltered tiles are cut below)
     if (rc) return rc;
     les_hip_batch* b = new les_hip_batch();
     b->n = n; b->njobs = (int)jobs.size(); b->out_slabs = out_slabs; b->R = c->R; b->device = c->p.device;
@@ -83,6 +85,10 @@ int les_hip_batch_create(les_hip_ctx* c, int n, const les_hip_rect* frs, const l
             }
         }
     }
+    if (c->filter != LES_HIP_FILTER_GF) {
+        rc = build_bf_batch(c, b, n, frs, trs, out_slabs);
+        if (rc) { les_hip_batch_destroy(b); return rc; }
+    }
     if (!jobs.empty()) {
         if (hipMalloc((void**)&b->d_jobs, jobs.size() * sizeof(les::Job)) != hipSuccess) { les_hip_batch_destroy(b); return fail(LES_HIP_ERR_DEVICE, "hipMalloc(jobs) failed"); }
         if (hipMemcpy(b->d_jobs, jobs.data(), jobs.size() * sizeof(les::Job), hipMemcpyHostToDevice) != hipSuccess) {
@@ -99,6 +105,7 @@ void les_hip_batch_destroy(les_hip_batch* b)
     if (b->d_jobs) (void)hipFree(b->d_jobs);
     if (b->d_mjobs) (void)hipFree(b->d_mjobs);
     if (b->d_rawcalls) (void)hipFree(b->d_rawcalls);
+    if (b->d_bfjobs) (void)hipFree(b->d_bfjobs);
     if (b->d_raw_off) (void)hipFree(b->d_raw_off);
     for (int m = 0; m < 2; m++) if (b->d_raw[m]) (void)hipFree(b->d_raw[m]);
     if (b->d_units) (void)hipFree(b->d_units);
@@ -207,6 +214,7 @@ int les_hip_batch_num_jobs(const les_hip_batch* b) { return b ? (b->march_ok ? b
 int les_hip_batch_kernel_kind(const les_hip_ctx* c, const les_hip_batch* b, int mode)
 {
     if (!c || !b || mode < 0 || mode > 1) return -1;
+    if (c->filter != LES_HIP_FILTER_GF) return 2;
     return (b->march_ok && c->march && c->v[mode].march_ok) ? 1 : 0;
 }
 
@@ -223,6 +231,7 @@ int les_hip_batch_run(les_hip_ctx* c, const les_hip_batch* b, int mode, const le
         HIPCHECK(hipMemcpyAsync(c->d_planes, planes, (size_t)b->n * sizeof(float4), hipMemcpyHostToDevice, cur_stream(c)));
         d_planes = c->d_planes;
     }
+    if (c->filter != LES_HIP_FILTER_GF) return run_bf_batch(c, b, mode, d_planes, out_dev, check);
     if (b->march_ok && mode >= 0 && mode <= 1 && c->march && c->v[mode].march_ok) {
         if (!c->naive) return launch_march(c, b->mentry, mode, b->d_mjobs, b->nmgroups, d_planes, out_dev, check, cur_stream(c));
         {
@@ -285,6 +294,7 @@ void les_hip_scratch_destroy(les_hip_scratch* s)
     if (s->h_tile) (void)hipHostFree(s->h_tile);
     if (s->d_raw) (void)hipFree(s->d_raw);
     if (s->d_rawcall) (void)hipFree(s->d_rawcall);
+    if (s->d_bfjobs) (void)hipFree(s->d_bfjobs);
     if (s->d_raw_off) (void)hipFree(s->d_raw_off);
     if (s->d_plane) (void)hipFree(s->d_plane);
     if (s->h_plane) (void)hipHostFree(s->h_plane);
@@ -296,6 +306,7 @@ int les_hip_unary_one_scratch(les_hip_ctx* c, les_hip_scratch* s, int mode, cons
 {
     if (!c || !s || !fr || !tr || !plane || !costs) return fail(LES_HIP_ERR_ARG, "null argument");
     if (s->c != c) return fail(LES_HIP_ERR_ARG, "scratch belongs to another context");
+    if (c->filter != LES_HIP_FILTER_GF) return bf_unary_one(c, s, mode, fr, tr, plane, costs, row_stride, check);
     if (mode < 0 || mode > 1 || !c->v[mode].stats || (c->naive ? !c->v[1 - mode].feat : !c->v[mode].vol))
         return fail(LES_HIP_ERR_ARG, "view %d was not supplied at creation", mode);
     HIPCHECK(hipSetDevice(c->p.device));                  // HIP's current device is per host thread

@@ -21,17 +21,22 @@ int les_hip_strip_width(int R)
 }
 
 static int create_common(les_hip_ctx** out, const les_hip_params* params, const uint8_t* imL, const uint8_t* imR,
-                         const float* volL, const float* volR, int naive, float alpha, float th_grad)
+                         const float* volL, const float* volR, int naive, float alpha, float th_grad, int filter = LES_HIP_FILTER_GF)
 {
     if (!out || !params) return fail(LES_HIP_ERR_ARG, "null argument");
     *out = nullptr;
     les_hip_params p = *params;
     if (naive) { p.D = 1; p.volumes_on_device = 0; }
-    if (p.H <= 0 || p.W <= 0 || p.D <= 0 || p.windR < 2) return fail(LES_HIP_ERR_ARG, "bad dimensions");
+    const bool gf = filter == LES_HIP_FILTER_GF;
+    if (!gf && filter != LES_HIP_FILTER_BILATERAL && filter != LES_HIP_FILTER_NONE) return fail(LES_HIP_ERR_ARG, "unknown filter %d", filter);
+    if (p.H <= 0 || p.W <= 0 || p.D <= 0 || p.windR < (gf ? 2 : 0)) return fail(LES_HIP_ERR_ARG, "bad dimensions");
+    if (filter == LES_HIP_FILTER_BILATERAL && p.windR > les::kBfMaxR)
+        return fail(LES_HIP_ERR_UNSUPPORTED, "bilateral filter radius windR = %d (supported: 0 .. %d)", p.windR, les::kBfMaxR);
+    if (filter == LES_HIP_FILTER_BILATERAL && !(p.eps > 0.0)) return fail(LES_HIP_ERR_ARG, "the bilateral filter needs sig2 = eps > 0 (got %g)", p.eps);
     if (naive && (!imL || !imR)) return fail(LES_HIP_ERR_ARG, "the image-based matching cost needs both views");
     if ((unsigned long long)p.H * p.W * p.D >= (1ull << 32)) return fail(LES_HIP_ERR_UNSUPPORTED, "volumes of 2^32 or more floats are not supported (32-bit element offsets)");
-    const StripEntry* strip = naive ? find_naive_strip(p.windR / 2) : find_strip(p.windR / 2);
-    if (!strip) return fail(LES_HIP_ERR_UNSUPPORTED, "no kernel instantiated for guided-filter radius %d (windR %d)", p.windR / 2, p.windR);
+    const StripEntry* strip = !gf ? nullptr : naive ? find_naive_strip(p.windR / 2) : find_strip(p.windR / 2);
+    if (gf && !strip) return fail(LES_HIP_ERR_UNSUPPORTED, "no kernel instantiated for guided-filter radius %d (windR %d)", p.windR / 2, p.windR);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(LES_HIP_ERR_DEVICE, "no HIP device available (this library has no CPU fallback)");
     if (p.device < 0 || p.device >= ndev) return fail(LES_HIP_ERR_ARG, "device %d out of range (%d devices)", p.device, ndev);
@@ -40,10 +45,11 @@ static int create_common(les_hip_ctx** out, const les_hip_params* params, const 
     c->gen = ++g_ctx_gen;
     { std::lock_guard<std::mutex> lk(g_live_mu); g_live.emplace_back(c->gen, c); }
     c->p = p;
-    c->R = p.windR / 2;
+    c->filter = filter;
+    c->R = gf ? p.windR / 2 : (filter == LES_HIP_FILTER_BILATERAL ? p.windR : 0);
     c->strip = strip;
-    c->march = find_march(p.windR / 2);
-    if (!c->march && !(getenv("LES_HIP_KERNEL") && !strcmp(getenv("LES_HIP_KERNEL"), "strip")))
+    c->march = gf ? find_march(p.windR / 2) : nullptr;
+    if (gf && !c->march && !(getenv("LES_HIP_KERNEL") && !strcmp(getenv("LES_HIP_KERNEL"), "strip")))
         note_fallback(c->fallback_seen, FB_RADIUS, "no march kernel for guided-filter radius %d (windR %d; instantiated: 2 .. 10)", p.windR / 2, p.windR);
 #if !defined(LES_SIM)
     {
@@ -65,7 +71,11 @@ static int create_common(les_hip_ctx** out, const les_hip_params* params, const 
     const uint8_t* ims[2] = {imL, imR};
     const float* vols[2] = {volL, volR};
     for (int m = 0; m < 2; m++) {
-        int rc = build_view(c, m, ims[m], vols[m]);
+        int rc = gf ? build_view(c, m, ims[m], vols[m]) : build_bf_view(c, m, ims[m], vols[m]);
+        if (rc) { les_hip_destroy(c); return rc; }
+    }
+    if (!gf) {
+        int rc = build_bf_table(c);
         if (rc) { les_hip_destroy(c); return rc; }
     }
     if (hipMalloc((void**)&c->d_map, (size_t)p.H * p.W * sizeof(float)) != hipSuccess) {
@@ -85,6 +95,18 @@ int les_hip_create(les_hip_ctx** out, const les_hip_params* params, const uint8_
 int les_hip_create_naive(les_hip_ctx** out, const les_hip_params* params, const uint8_t* imL, const uint8_t* imR, float alpha, float th_grad)
 {
     return create_common(out, params, imL, imR, nullptr, nullptr, 1, alpha, th_grad);
+}
+
+int les_hip_create_filtered(les_hip_ctx** out, const les_hip_params* params, int filter, const uint8_t* imL, const uint8_t* imR,
+                            const float* volL, const float* volR)
+{
+    return create_common(out, params, imL, imR, volL, volR, 0, 0.0f, 0.0f, filter);
+}
+
+int les_hip_create_naive_filtered(les_hip_ctx** out, const les_hip_params* params, int filter, const uint8_t* imL, const uint8_t* imR,
+                                  float alpha, float th_grad)
+{
+    return create_common(out, params, imL, imR, nullptr, nullptr, 1, alpha, th_grad, filter);
 }
 
 void les_hip_destroy(les_hip_ctx* c)
@@ -115,6 +137,7 @@ void les_hip_destroy(les_hip_ctx* c)
     if (c->d_wta) (void)hipFree(c->d_wta);
     if (c->d_wta_planes) (void)hipFree(c->d_wta_planes);
     if (c->d_pw_tab) (void)hipFree(c->d_pw_tab);
+    if (c->d_bf_tab) (void)hipFree(c->d_bf_tab);
     delete c;
 }
 

@@ -21,20 +21,31 @@ namespace les_host {
 
 class HipCostVolumeEnergy : public StereoEnergy {
 public:
+    // Parameters::filterName -> the aggregation of les_hip_create_filtered (LES/StereoEnergy.h:25): "GF" the guided filter, "BF" and
+    // "BL" the joint bilateral filter (NaiveStereoEnergy calls it "BF", CostVolumeEnergy "BL" -- and dereferences a null filter given
+    // "BF"; both names mean it for both energies here), "" no aggregation.  "GFfloat" is not implemented.
+    static int filter_kind(const std::string& name)
+    {
+        if (name == "GF") return LES_HIP_FILTER_GF;
+        if (name == "BF" || name == "BL") return LES_HIP_FILTER_BILATERAL;
+        if (name.empty()) return LES_HIP_FILTER_NONE;
+        throw std::runtime_error("HipCostVolumeEnergy: unsupported filterName \"" + name + "\" (GF, BF / BL or \"\")");
+    }
+
     // imL/imR: H x W x 3 uint8 BGR (cv::imread layout); volL/volR: float [D][H][W] (shared with the caller in
     // the reference, copied to HBM once here).
     HipCostVolumeEnergy(const uint8_t* imL, const uint8_t* imR, int width, int height, const float* volL, const float* volR,
                         int ndisp, Parameters p, float MAX_DISPARITY, float MIN_DISPARITY = 0, int device = 0)
         : StereoEnergy(width, height, std::move(p), MAX_DISPARITY, MIN_DISPARITY), ctx_(nullptr)
     {
-        if (params.filterName != "GF") throw std::runtime_error("HipCostVolumeEnergy implements the default \"GF\" joint filter");
+        const int filter = filter_kind(params.filterName);
         les_hip_params hp;
         hp.H = height; hp.W = width; hp.D = ndisp;
         hp.windR = params.windR; hp.eps = params.filter_param1; hp.th_col = params.th_col;
         hp.max_disparity = MAX_DISPARITY; hp.min_disparity = MIN_DISPARITY;
         hp.device = device; hp.volumes_on_device = 0;
-        if (les_hip_create(&ctx_, &hp, imL, imR, volL, volR) != LES_HIP_OK)
-            throw std::runtime_error(std::string("les_hip_create: ") + les_hip_last_error());
+        if (les_hip_create_filtered(&ctx_, &hp, filter, imL, imR, volL, volR) != LES_HIP_OK)
+            throw std::runtime_error(std::string("les_hip_create_filtered: ") + les_hip_last_error());
         setImages(imL, imR);           // pairwise weights for the host graph cut
     }
     ~HipCostVolumeEnergy() override { les_hip_destroy(ctx_); }
@@ -46,14 +57,14 @@ protected:
                         float MIN_DISPARITY, int device)
         : StereoEnergy(width, height, std::move(p), MAX_DISPARITY, MIN_DISPARITY), ctx_(nullptr)
     {
-        if (params.filterName != "GF") throw std::runtime_error("HipNaiveStereoEnergy implements the default \"GF\" joint filter");
+        const int filter = filter_kind(params.filterName);
         les_hip_params hp;
         hp.H = height; hp.W = width; hp.D = 1;
         hp.windR = params.windR; hp.eps = params.filter_param1; hp.th_col = params.th_col;
         hp.max_disparity = MAX_DISPARITY; hp.min_disparity = MIN_DISPARITY;
         hp.device = device; hp.volumes_on_device = 0;
-        if (les_hip_create_naive(&ctx_, &hp, imL, imR, params.alpha, params.th_grad) != LES_HIP_OK)
-            throw std::runtime_error(std::string("les_hip_create_naive: ") + les_hip_last_error());
+        if (les_hip_create_naive_filtered(&ctx_, &hp, filter, imL, imR, params.alpha, params.th_grad) != LES_HIP_OK)
+            throw std::runtime_error(std::string("les_hip_create_naive_filtered: ") + les_hip_last_error());
         setImages(imL, imR);
     }
 

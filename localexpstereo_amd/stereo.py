@@ -13,12 +13,18 @@ import torch
 
 from . import api, gc, io, pm
 
-PARAMS_GF = dict(lambda_=1.0, windR=20, eps=1e-4, alpha=0.9, omega=10.0, th_grad=2.0, th_col=10.0, th_smooth=1.0, epsilon=0.01)   # paramsGF, LES/main.cpp:73
+PARAMS_GF = dict(lambda_=1.0, windR=20, eps=1e-4, alpha=0.9, omega=10.0, th_grad=2.0, th_col=10.0, th_smooth=1.0, epsilon=0.01, filter="GF")   # paramsGF, LES/main.cpp:73
+# paramsBF, LES/main.cpp:72 -- Parameters(20, 20, "BF", 10), the default of Parameters: joint bilateral filter of radius windR, sig2 = eps
+# (filter_param1); lambda 20 is scaled to its un-normalised window sums
+PARAMS_BF = dict(PARAMS_GF, lambda_=20.0, windR=20, eps=10.0, filter="BF")
 
 
 class FastGCStereo:
     def __init__(self, energy, imL, imR, params, device="cuda", rank=0, world=1, seed=1, host_threads=0, device_cuts=None):
         self.e, self.imL, self.imR, self.p = energy, imL, imR, dict(PARAMS_GF, **params)
+        # Parameters::filterName: the energy aggregates with the filter it was built with; a params dict that names another one is a mistake
+        if "filter" in params and api.filter_kind(params["filter"]) != getattr(energy, "filter", api.FILTER_GF):
+            raise ValueError(f"params name filter {params['filter']!r}, the energy was built with filter kind {energy.filter}")
         self.device, self.rank, self.world, self.seed = device, rank, world, seed
         self.units, self.table = [], []
         self.evaluator = None
@@ -250,14 +256,18 @@ def _layers(st, sizes):
     st.addLayer(sizes[2], [(e, 2), (r, 1)])
 
 
-def MidV2(data, iterations=5, pmIterations=2, doDual=False, smooth_weight=1.0, filterRadious=20, device="cuda", seed=1, lib=None, **kw):
+def MidV2(data, iterations=5, pmIterations=2, doDual=False, smooth_weight=None, filterRadious=20, device="cuda", seed=1, lib=None, params=None, **kw):
     """MidV2 (LES/main.cpp:270-328) on a data dict of io.load_data: image-based matching cost, layers 5/15/25, error
-    threshold 0.5, disparities quantised to the ground-truth precision before evaluation."""
+    threshold 0.5, disparities quantised to the ground-truth precision before evaluation.  params: PARAMS_GF (the reference's choice,
+    default) or PARAMS_BF (or a dict with their keys): filter, eps, alpha, th_col, th_grad; smooth_weight (default: params' lambda_)
+    and filterRadious override lambda_ and windR as the reference's options do (:284-286)."""
+    p = dict(PARAMS_GF if params is None else params)
+    lam = p["lambda_"] if smooth_weight is None else smooth_weight
     maxdisp = float(data["ndisp"] - 1)
-    e = api.HipCostVolumeEnergy.naive(data["imL"], data["imR"], windR=filterRadious, eps=PARAMS_GF["eps"], alpha=PARAMS_GF["alpha"],
-                                      th_col=PARAMS_GF["th_col"], th_grad=PARAMS_GF["th_grad"], max_disp=maxdisp,
-                                      device=torch.device(device).index or 0, lib=lib)
-    st = FastGCStereo(e, data["imL"], data["imR"], dict(lambda_=smooth_weight, windR=filterRadious), device=device, seed=seed, **kw)
+    e = api.HipCostVolumeEnergy.naive(data["imL"], data["imR"], windR=filterRadious, eps=p["eps"], alpha=p["alpha"],
+                                      th_col=p["th_col"], th_grad=p["th_grad"], max_disp=maxdisp,
+                                      device=torch.device(device).index or 0, lib=lib, filter=p["filter"])
+    st = FastGCStereo(e, data["imL"], data["imR"], dict(p, lambda_=lam, windR=filterRadious), device=device, seed=seed, **kw)
     st.setEvaluator(io.Evaluator(data["dispGT"], data["nonocc"], 0.5), precision=data.get("gt_prec", -1.0))
     _layers(st, (5, 15, 25))
     lab, raw = st.run(iterations, (0, 1) if doDual else (0,), pmIterations)
@@ -267,16 +277,18 @@ def MidV2(data, iterations=5, pmIterations=2, doDual=False, smooth_weight=1.0, f
 
 
 def MidV3(data, volL, volR, iterations=5, pmIterations=2, doDual=False, smooth_weight=0.5, mc_threshold=0.5, filterRadious=20,
-          error_threshold=1.0, device="cuda", seed=1, lib=None, **kw):
+          error_threshold=1.0, device="cuda", seed=1, lib=None, params=None, **kw):
     """MidV3 (LES/main.cpp:330-420): cost-volume energy (volumes ingested on the device), layers 1 % / 3 % / 9 % of the
-    image width.  volL / volR: host arrays / memmaps [ndisp][H][W] (volR None: synthesised from the left one)."""
+    image width.  volL / volR: host arrays / memmaps [ndisp][H][W] (volR None: synthesised from the left one).  params: PARAMS_GF
+    (default) or PARAMS_BF: filter and eps; smooth_weight, mc_threshold and filterRadious override lambda_, th_col and windR (:351-353)."""
+    p = dict(PARAMS_GF if params is None else params)
     maxdisp = float(data["ndisp"] - 1)
     tl, tr = io.ingest_volumes(volL, volR, device=device, lib=lib)
     D, H, W = tl.shape
-    e = api.HipCostVolumeEnergy(data["imL"], data["imR"], tl.data_ptr(), tr.data_ptr(), windR=filterRadious, eps=PARAMS_GF["eps"],
+    e = api.HipCostVolumeEnergy(data["imL"], data["imR"], tl.data_ptr(), tr.data_ptr(), windR=filterRadious, eps=p["eps"],
                                 th_col=mc_threshold, max_disp=maxdisp, device=torch.device(device).index or 0, volumes_on_device=True,
-                                shape=(D, H, W), lib=lib)
-    st = FastGCStereo(e, data["imL"], data["imR"], dict(lambda_=smooth_weight, windR=filterRadious, th_col=mc_threshold), device=device, seed=seed, **kw)
+                                shape=(D, H, W), lib=lib, filter=p["filter"])
+    st = FastGCStereo(e, data["imL"], data["imR"], dict(p, lambda_=smooth_weight, windR=filterRadious, th_col=mc_threshold), device=device, seed=seed, **kw)
     st.setEvaluator(io.Evaluator(data["dispGT"], data["nonocc"], error_threshold), precision=-1.0)
     _layers(st, (int(W * 0.01), int(W * 0.03), int(W * 0.09)))
     lab, raw = st.run(iterations, (0, 1) if doDual else (0,), pmIterations)
