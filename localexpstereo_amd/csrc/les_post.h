@@ -6,7 +6,8 @@
 //   * disparities  a*x + b*y + c  in float, un-fused (Plane::GetZ, LES/Plane.h:51-58)
 //   * weights exp(-|dI|_1 / omega) come from a 766-entry table built on the host (|dI|_1 of 8-bit colours is an integer)
 //   * the weighted median sorts (disparity at p, window scan index) -- the stable order -- and accumulates the weights
-//     in double, sequentially, exactly like the reference's loops (LES/PMStereoBase.h:218-247).
+//     in double, sequentially, exactly like the reference's loops (LES/PMStereoBase.h:218-247).  The order is total:
+//     -0 and +0 are equal, and every NaN ranks after +inf whatever its sign or payload (NaNs tie with each other).
 #pragma once
 
 #include "les_simt.h"
@@ -84,8 +85,10 @@ __global__ void les_nn_fill_kernel(const uint8_t* __restrict__ failb, const uint
 // One workgroup per failed pixel; NMAX = power of two >= (2 windR + 1)^2.
 __device__ __forceinline__ uint32_t float_order_key(float f)
 {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);     // monotone map float -> uint32 (-0 < +0; NaN at the ends)
+    uint32_t u = __float_as_uint(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;   // every NaN: one key above +inf (0xff800000)
+    if (u == 0x80000000u) u = 0u;                              // -0 -> +0
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);         // monotone map float -> uint32
 }
 
 template <int NMAX, int NT>

@@ -957,8 +957,9 @@ extern "C" void les_post_process(les_plane* labelsL, les_plane* labelsR, const u
                 else if (getz(*pl, x, y) < getz(*pr, x, y)) LR[i][row + x] = *pl;
                 else LR[i][row + x] = *pr;
             }
-    // weighted median filter, :207-250.  std::sort is not stable; equal disparities are ordered here by window scan
-    // position (the stable order), which is what the device kernel implements as well.
+    // weighted median filter, :207-250.  std::sort is not stable and its "<" is no strict weak order with NaN; the order
+    // here is total: disparity at p with -0 == +0 and every NaN after +inf (NaNs tie), then window scan position (the
+    // stable order).  The device kernel implements the same order.
     struct Cand { les_plane l; float w; float z; };
     for (int i = 0; i < 2; i++) {
         std::vector<les_plane> copy(LR[i], LR[i] + P);                                // :209
@@ -981,7 +982,9 @@ extern "C" void les_post_process(les_plane* labelsL, les_plane* labelsR, const u
                         const les_plane& l = copy[(size_t)yy * W + xx];
                         median.push_back(Cand{l, w, getz(l, x, y)});
                     }
-                std::stable_sort(median.begin(), median.end(), [](const Cand& a, const Cand& b) { return a.z < b.z; });
+                std::stable_sort(median.begin(), median.end(), [](const Cand& a, const Cand& b) {
+                    return !std::isnan(a.z) && (std::isnan(b.z) || a.z < b.z);
+                });
                 const double center = sumw / 2.0;
                 sumw = 0;
                 for (size_t j = 0; j < median.size(); j++) {
