@@ -70,6 +70,15 @@ int les_hip_create(les_hip_ctx** out, const les_hip_params* params, const uint8_
  * not run concurrently with evaluations on the same context. */
 int les_hip_refresh_volume(les_hip_ctx* ctx, int mode);
 
+/* replaces: CostVolumeEnergy::setInterpolationMethod (LES/CostVolumeEnergy.h:45-48): how a plane's disparity reads the volume --
+ * 0 nearest slice (:99-119), 1 linear (:70-98, the default), 2 three-point quadratic (:120-167).  Applies to every later evaluation of the
+ * context on both views (les_hip_unary_one[_scratch], les_hip_unary_batch, les_hip_batch_run, batches created before the call included) and
+ * survives les_hip_refresh_volume.  The reference's (int) conversion of a double is MSVC's (NaN, +-inf and out-of-range values give INT_MIN);
+ * mode 2 returns NaN raw costs at the end slices, as the reference does.  LES_HIP_ERR_ARG for values outside 0 .. 2 and for contexts of the
+ * image-based energy (les_hip_create_naive*: no volume).  Like the reference's setter it is not synchronised: it must not be called while
+ * another host thread evaluates on the same context (launches already queued keep the mode they were made with). */
+int les_hip_set_interpolation(les_hip_ctx* ctx, int none_lin_quad);
+
 /* replaces: NaiveStereoEnergy::NaiveStereoEnergy (LES/StereoEnergy.h:638-689) -- the image-based matching cost of the
  * MiddV2 configuration (LES/main.cpp:86-121, PMStereoBase.h:37): no cost volume; the raw cost of a plane is the truncated
  * colour + x-gradient difference between this view and the other view warped by the plane (StereoEnergy.h:702-742), then
@@ -158,7 +167,10 @@ int les_hip_batch_num_jobs(const les_hip_batch* b);     /* workgroups one run la
  * (csrc/les_march.h; needs a finite volume with th_col - min <= 8 th_col, a guided-filter radius of 2 .. 10 and every target at least 2 x radius away from
  * filterRect borders that are not image borders -- the geometry of every LayerManager cell), 0 = the fp64 strip kernel
  * (csrc/les_kernels.h; any input), -1 = bad argument.  Both implement LES/CostVolumeEnergy.h:55-183.  2 = the bilateral / unfiltered
- * kernel (csrc/les_bilateral.h): every batch of a context made with LES_HIP_FILTER_BILATERAL or LES_HIP_FILTER_NONE. */
+ * kernel (csrc/les_bilateral.h): every batch of a context made with LES_HIP_FILTER_BILATERAL or LES_HIP_FILTER_NONE.
+ * Under les_hip_set_interpolation 0 or 2 (guided filter, cost volume): 1 = a raw-cost pre-pass plus the march kernel serve the batch (the same
+ * geometric conditions, and for 2 a volume range that leaves room below its minimum); at 2 the calls whose raw cost holds a NaN or leaves
+ * that room are recomputed on the device by the strip kernel, which this value does not report.  0 = the strip kernel serves every call. */
 int les_hip_batch_kernel_kind(const les_hip_ctx* ctx, const les_hip_batch* b, int mode);
 /* planes: n labels, HOST (planes_on_device == 0) or DEVICE memory; out: DEVICE memory.  Asynchronous
  * on the context's stream. */

@@ -19,7 +19,7 @@ PLANE_DT = np.dtype([("a", "<f4"), ("b", "<f4"), ("c", "<f4"), ("v", "<f4")])
 SYMBOLS = [
     "les_hip_create", "les_hip_create_naive", "les_hip_create_filtered", "les_hip_create_naive_filtered", "les_hip_destroy", "les_hip_last_error", "les_hip_set_stream", "les_hip_set_thread_stream", "les_hip_synchronize",
     "les_hip_unary_one", "les_hip_unary_one_scratch", "les_hip_scratch_create", "les_hip_scratch_destroy", "les_hip_unary_batch", "les_hip_batch_create", "les_hip_batch_destroy",
-    "les_hip_batch_num_jobs", "les_hip_batch_kernel_kind", "les_hip_batch_graph_nodes", "les_hip_batch_graph_offsets", "les_hip_batch_expansion_graph", "les_hip_batch_max_cell_nodes", "les_hip_batch_graph_solver_kind", "les_hip_refresh_volume", "les_hip_batch_solve_graphs", "les_hip_batch_solve_graphs_counted", "les_hip_batch_solve_graphs_tiled", "les_hip_batch_solve_graphs_tiled_stats", "les_hip_batch_tiled_workspace_bytes", "les_hip_batch_apply_masks", "les_hip_batch_run", "les_hip_batch_set_units", "les_hip_batch_propose", "les_hip_batch_wta",
+    "les_hip_batch_num_jobs", "les_hip_batch_kernel_kind", "les_hip_batch_graph_nodes", "les_hip_batch_graph_offsets", "les_hip_batch_expansion_graph", "les_hip_batch_max_cell_nodes", "les_hip_batch_graph_solver_kind", "les_hip_refresh_volume", "les_hip_set_interpolation", "les_hip_batch_solve_graphs", "les_hip_batch_solve_graphs_counted", "les_hip_batch_solve_graphs_tiled", "les_hip_batch_solve_graphs_tiled_stats", "les_hip_batch_tiled_workspace_bytes", "les_hip_batch_apply_masks", "les_hip_batch_run", "les_hip_batch_set_units", "les_hip_batch_propose", "les_hip_batch_wta",
     "les_hip_wta_update", "les_hip_malloc", "les_hip_free",
     "les_hip_memcpy_h2d", "les_hip_memcpy_d2h", "les_hip_memset", "les_hip_get_stats", "les_hip_strip_width", "les_hip_tiled_volume_bytes",
     "les_hip_calib_copy", "les_hip_calib_copy_wide", "les_hip_exchange_create", "les_hip_exchange_destroy", "les_hip_exchange_slot_floats",
@@ -130,6 +130,7 @@ def load(path=None):
         "les_hip_batch_destroy": (None, [vp]),
         "les_hip_batch_num_jobs": (ci, [vp]),
         "les_hip_batch_kernel_kind": (ci, [vp, vp, ci]),
+        "les_hip_set_interpolation": (ci, [vp, ci]),
         "les_hip_batch_run": (ci, [vp, vp, ci, vp, ci, vp, ci]),
         "les_hip_batch_set_units": (ci, [vp, vp, vp]),
         "les_hip_batch_propose": (ci, [vp, vp, ci, ci, vp, vp, vp]),
@@ -367,10 +368,11 @@ class Batch:
 
 class HipCostVolumeEnergy:
     """Python mirror of CostVolumeEnergy (LES/CostVolumeEnergy.h:6-184) over the C ABI.  filter: Parameters::filterName -- "GF" (the guided
-    filter, radius windR // 2, eps), "BF" / "BL" (the joint bilateral filter, radius windR, sig2 = eps) or "" (no aggregation)."""
+    filter, radius windR // 2, eps), "BF" / "BL" (the joint bilateral filter, radius windR, sig2 = eps) or "" (no aggregation).
+    interpolate: setInterpolationMethod -- 0 nearest slice, 1 linear (the default), 2 three-point quadratic."""
 
     def __init__(self, imL, imR, volL, volR, windR=20, eps=1e-4, th_col=0.5, max_disp=None, min_disp=0.0,
-                 device=0, volumes_on_device=False, shape=None, lib=None, filter="GF"):
+                 device=0, volumes_on_device=False, shape=None, lib=None, filter="GF", interpolate=1):
         self.filter = filter_kind(filter)
         self.L = load(lib)
         self.imL = np.ascontiguousarray(imL, np.uint8) if imL is not None else None
@@ -397,6 +399,9 @@ class HipCostVolumeEnergy:
             self._chk(self.L.les_hip_create_filtered(C.byref(h), C.byref(self.params), self.filter, _ptr(self.imL), _ptr(self.imR), vl, vr))
         self.h = h
         self._keep = None     # host volumes were copied to HBM
+        self.interpolate = 1
+        if interpolate != 1:
+            self.setInterpolationMethod(interpolate)
 
     @classmethod
     def naive(cls, imL, imR, windR=20, eps=1e-4, alpha=0.9, th_col=10.0, th_grad=2.0, max_disp=63.0, min_disp=0.0, device=0, lib=None,
@@ -422,6 +427,7 @@ class HipCostVolumeEnergy:
             self._chk(self.L.les_hip_create_naive_filtered(C.byref(h), C.byref(self.params), self.filter, _ptr(self.imL), _ptr(self.imR),
                                                            C.c_float(alpha), C.c_float(th_grad)))
         self.h = h
+        self.interpolate = 1      # (no volume: les_hip_set_interpolation refuses this context)
         return self
 
     def _chk(self, rc):
@@ -451,6 +457,12 @@ class HipCostVolumeEnergy:
 
     def strip_width(self):
         return self.L.les_hip_strip_width(self.params.windR // 2)
+
+    def setInterpolationMethod(self, none_lin_quad):
+        """CostVolumeEnergy::setInterpolationMethod (LES/CostVolumeEnergy.h:45-48): 0 nearest, 1 linear, 2 quadratic, for every later
+        evaluation (prepared batches included).  Not for the image-based energy, and not while another thread evaluates on this context."""
+        self._chk(self.L.les_hip_set_interpolation(self.h, int(none_lin_quad)))
+        self.interpolate = int(none_lin_quad)
 
     def refresh_volume(self, mode=0):
         """After the caller refilled the device-resident volume of `mode` in place: cost range / fixed-point scales / tiled copy re-derived."""

@@ -89,6 +89,11 @@ struct ViewData {
     bool march_ok = false;               // volume finite, range condition met, tables built
     unsigned dmax_bits = 0;              // largest diagonal entry of the guide's inverse covariance (float bits): fixes the scale of a, b
     les::MarchView mv = {};
+    // interpolation 2 on the march kernel: the view scaled for the widened range [lo2, th_col] (the quadratic falls below the volume's
+    // minimum); calls whose raw cost leaves it are flagged and recomputed on the strip kernel
+    les::MarchView mv2 = {};
+    float lo2 = 0.0f;
+    bool march2_ok = false;
 };
 
 }  // namespace
@@ -102,6 +107,8 @@ struct les_hip_ctx {
     int R;                               // its radius: windR / 2 (guided filter), windR (bilateral), 0 (unfiltered)
     float* d_bf_tab = nullptr;           // bilateral / unfiltered: the weight table exp(-|dI|_1 / sig2), 766 floats
     const StripEntry* strip;
+    const StripEntry* istrip[2] = {nullptr, nullptr};   // cost-volume guided filter at interpolation 0 / 2 (find_interp_strip)
+    int interp = 1;                      // setInterpolationMethod (les_hip_set_interpolation): 0 nearest, 1 linear, 2 quadratic
     const MarchEntry* march = nullptr;   // null: radius not instantiated (or LES_HIP_KERNEL=strip)
     int ncu = 256;                       // compute units of the device (job cutting of the march kernel)
     std::atomic<unsigned> fallback_seen{0};   // reasons already reported by note_fallback
@@ -143,6 +150,13 @@ struct les_hip_batch {
     long long raw_floats = 0;
     int raw_chunks = 1;
     mutable float* d_raw[2] = {nullptr, nullptr};
+    // cost-volume context at interpolation 0 / 2 on the march kernel: the same patch tables, built on the first such run (ensure_interp_tables),
+    // per view a flag per call and the masked strip jobs of the recompute launch (interpolation 2)
+    std::vector<les_hip_rect> filters;
+    mutable bool interp_tables = false;
+    mutable long long* d_out_off = nullptr;      // float offset of each call's target corner in the output (les_nan_spread_kernel)
+    mutable unsigned* d_flags[2] = {nullptr, nullptr};
+    mutable les::Job* d_rjobs[2] = {nullptr, nullptr};
     // bilateral / unfiltered context: tiles of calls that share their rects (les_hip_bilateral.inc); the raw-cost patches above serve it too
     les::BfJob* d_bfjobs = nullptr;
     int bf_np = 1;                       // most calls per tile (1: the one-plane instantiation of the kernel)
@@ -181,7 +195,13 @@ struct les_hip_scratch {
     hipStream_t stream = nullptr;
     float* d_tile = nullptr; float* h_tile = nullptr; size_t tile_cap = 0;        // floats
     float4* d_plane = nullptr; float4* h_plane = nullptr;
-    struct Entry { les_hip_rect f, t; int want_march; const void* march; int njobs, ngroups; les::Job* d_jobs; unsigned long long stamp; };
+    struct Entry { les_hip_rect f, t; int want_march; const void* march; int njobs, ngroups; les::Job* d_jobs; unsigned long long stamp;
+                   les::Job* d_sjobs = nullptr; int nsjobs = 0; };     // (interpolation 2 on the march kernel: the strip jobs of the recompute launch)
+    // interpolation 2 on the march kernel: the call's flag and the masked strip jobs
+    unsigned* d_flag = nullptr;
+    // interpolation 0 / 2: the call's target rect and output offset (0: the compact tile) for les_nan_spread_kernel
+    les::WtaJob* d_target = nullptr; long long* d_zero = nullptr;
+    les::Job* d_rjobs = nullptr; size_t rjobs_cap = 0;
     // image-based energy on the march kernel: raw-cost patch of the call's filterRect and its one-entry call table
     float* d_raw = nullptr; size_t raw_cap = 0;
     les::RawCall* d_rawcall = nullptr; long long* d_raw_off = nullptr;

@@ -17,6 +17,7 @@ int les_hip_batch_create(les_hip_ctx* c, int n, const les_hip_rect* frs, const l
     les_hip_batch* b = new les_hip_batch();
     b->n = n; b->njobs = (int)jobs.size(); b->out_slabs = out_slabs; b->R = c->R; b->device = c->p.device;
     b->targets.assign(trs, trs + n);
+    if (!c->naive && c->filter == LES_HIP_FILTER_GF) b->filters.assign(frs, frs + n);     // (the raw-cost patch table of interpolation 0 / 2)
     {
         int max_area = 1;
         for (int i = 0; i < n; i++) max_area = std::max(max_area, trs[i].w * trs[i].h);
@@ -108,6 +109,9 @@ void les_hip_batch_destroy(les_hip_batch* b)
     if (b->d_bfjobs) (void)hipFree(b->d_bfjobs);
     if (b->d_raw_off) (void)hipFree(b->d_raw_off);
     for (int m = 0; m < 2; m++) if (b->d_raw[m]) (void)hipFree(b->d_raw[m]);
+    for (int m = 0; m < 2; m++) if (b->d_flags[m]) (void)hipFree(b->d_flags[m]);
+    if (b->d_out_off) (void)hipFree(b->d_out_off);
+    for (int m = 0; m < 2; m++) if (b->d_rjobs[m]) (void)hipFree(b->d_rjobs[m]);
     if (b->d_units) (void)hipFree(b->d_units);
     if (b->d_targets) (void)hipFree(b->d_targets);
     if (b->d_graph_off) (void)hipFree(b->d_graph_off);
@@ -215,7 +219,36 @@ int les_hip_batch_kernel_kind(const les_hip_ctx* c, const les_hip_batch* b, int 
 {
     if (!c || !b || mode < 0 || mode > 1) return -1;
     if (c->filter != LES_HIP_FILTER_GF) return 2;
+    if (!c->naive && c->interp != 1) return (b->march_ok && interp_march_ok(c, mode) && b->raw_floats <= kRawPatchCapFloats) ? 1 : 0;
     return (b->march_ok && c->march && c->v[mode].march_ok) ? 1 : 0;
+}
+
+// The raw-cost patch table of a cost-volume batch (interpolation 0 / 2 on the march kernel), built on the batch's first such run
+int ensure_interp_tables(les_hip_ctx* c, const les_hip_batch* b_)
+{
+    les_hip_batch* b = const_cast<les_hip_batch*>(b_);
+    if (b->interp_tables) return LES_HIP_OK;
+    std::vector<les::RawCall> calls;
+    long long tot = 0, amax = 1;
+    build_bf_raw_calls(b->n, b->filters.data(), b->targets.data(), calls, tot, amax);
+    b->raw_floats = tot;
+    std::vector<long long> offs((size_t)b->n), outs((size_t)b->n);
+    const long long P = (long long)c->p.H * c->p.W;
+    for (int i = 0; i < b->n; i++) {
+        offs[i] = calls[i].off;
+        outs[i] = (b->out_slabs ? (long long)(i / b->out_slabs) * P : 0) + (long long)b->targets[i].y * c->p.W + b->targets[i].x;
+    }
+    b->raw_chunks = (int)std::min<long long>(1024, std::max<long long>(1, (amax + 4095) / 4096));
+    if (b->n > 0) {
+        HIPCHECK(hipMalloc((void**)&b->d_rawcalls, (size_t)b->n * sizeof(les::RawCall)));
+        HIPCHECK(hipMemcpy(b->d_rawcalls, calls.data(), (size_t)b->n * sizeof(les::RawCall), hipMemcpyHostToDevice));
+        HIPCHECK(hipMalloc((void**)&b->d_raw_off, (size_t)b->n * sizeof(long long)));
+        HIPCHECK(hipMemcpy(b->d_raw_off, offs.data(), (size_t)b->n * sizeof(long long), hipMemcpyHostToDevice));
+        HIPCHECK(hipMalloc((void**)&b->d_out_off, (size_t)b->n * sizeof(long long)));
+        HIPCHECK(hipMemcpy(b->d_out_off, outs.data(), (size_t)b->n * sizeof(long long), hipMemcpyHostToDevice));
+    }
+    b->interp_tables = true;
+    return LES_HIP_OK;
 }
 
 int les_hip_batch_run(les_hip_ctx* c, const les_hip_batch* b, int mode, const les_hip_plane* planes, int planes_on_device,
@@ -232,7 +265,25 @@ int les_hip_batch_run(les_hip_ctx* c, const les_hip_batch* b, int mode, const le
         d_planes = c->d_planes;
     }
     if (c->filter != LES_HIP_FILTER_GF) return run_bf_batch(c, b, mode, d_planes, out_dev, check);
-    if (b->march_ok && mode >= 0 && mode <= 1 && c->march && c->v[mode].march_ok) {
+    if (!c->naive && c->interp != 1 && mode >= 0 && mode <= 1 && b->march_ok && interp_march_ok(c, mode)) {
+        {
+            std::lock_guard<std::mutex> lk(c->mu);
+            int rc = ensure_interp_tables(c, b);
+            if (rc) return rc;
+            if (b->raw_floats <= kRawPatchCapFloats) {
+                if (!b->d_raw[mode]) HIPCHECK(hipMalloc((void**)&b->d_raw[mode], (size_t)std::max<long long>(b->raw_floats, 1) * sizeof(float)));
+                if (c->interp == 2 && !b->d_flags[mode]) HIPCHECK(hipMalloc((void**)&b->d_flags[mode], (size_t)std::max(b->n, 1) * sizeof(unsigned)));
+                if (c->interp == 2 && !b->d_rjobs[mode]) HIPCHECK(hipMalloc((void**)&b->d_rjobs[mode], (size_t)std::max(b->njobs, 1) * sizeof(les::Job)));
+            }
+        }
+        if (b->raw_floats <= kRawPatchCapFloats) {
+            const RawPatches rp{b->d_rawcalls, b->d_raw_off, b->d_raw[mode], b->n, b->raw_chunks};
+            return launch_interp_march(c, b->mentry, mode, b->d_mjobs, b->nmgroups, rp, b->d_flags[mode], b->d_jobs, b->d_rjobs[mode], b->njobs,
+                                       b->d_targets, b->d_out_off, c->p.W, d_planes, out_dev, check, cur_stream(c));
+        }
+        note_fallback(c->fallback_seen, FB_PATCHES, "the raw-cost patches of one batch at interpolation %d exceed 4 GB", c->interp);
+    }
+    if (b->march_ok && mode >= 0 && mode <= 1 && c->march && c->v[mode].march_ok && (c->naive || c->interp == 1)) {
         if (!c->naive) return launch_march(c, b->mentry, mode, b->d_mjobs, b->nmgroups, d_planes, out_dev, check, cur_stream(c));
         {
             std::lock_guard<std::mutex> lk(c->mu);
@@ -240,6 +291,16 @@ int les_hip_batch_run(les_hip_ctx* c, const les_hip_batch* b, int mode, const le
         }
         const RawPatches rp{b->d_rawcalls, b->d_raw_off, b->d_raw[mode], b->n, b->raw_chunks};
         return launch_march(c, b->mentry, mode, b->d_mjobs, b->nmgroups, d_planes, out_dev, check, cur_stream(c), &rp);
+    }
+    if (!c->naive && c->interp != 1) {
+        {
+            std::lock_guard<std::mutex> lk(c->mu);
+            int rc = ensure_interp_tables(c, b);
+            if (rc) return rc;
+        }
+        int rc = launch_strips(c, mode, b->d_jobs, b->njobs, d_planes, out_dev, check, cur_stream(c));
+        if (rc) return rc;
+        return launch_nan_spread(c, mode, b->n, b->d_rawcalls, b->d_targets, b->d_out_off, c->p.W, d_planes, nullptr, out_dev, check, cur_stream(c));
     }
     return launch_strips(c, mode, b->d_jobs, b->njobs, d_planes, out_dev, check, cur_stream(c));
 }
@@ -290,6 +351,11 @@ void les_hip_scratch_destroy(les_hip_scratch* s)
     if (s->c) (void)hipSetDevice(s->c->p.device);
     if (s->stream) { (void)hipStreamSynchronize(s->stream); (void)hipStreamDestroy(s->stream); }
     for (auto& e : s->cache) if (e.d_jobs) (void)hipFree(e.d_jobs);
+    for (auto& e : s->cache) if (e.d_sjobs) (void)hipFree(e.d_sjobs);
+    if (s->d_flag) (void)hipFree(s->d_flag);
+    if (s->d_target) (void)hipFree(s->d_target);
+    if (s->d_zero) (void)hipFree(s->d_zero);
+    if (s->d_rjobs) (void)hipFree(s->d_rjobs);
     if (s->d_tile) (void)hipFree(s->d_tile);
     if (s->h_tile) (void)hipHostFree(s->h_tile);
     if (s->d_raw) (void)hipFree(s->d_raw);
@@ -314,7 +380,8 @@ int les_hip_unary_one_scratch(les_hip_ctx* c, les_hip_scratch* s, int mode, cons
     if (rc) return rc;
     if (tr->w <= 0 || tr->h <= 0) return LES_HIP_OK;
     // ---- job table of this rect pair (built and uploaded the first time it is seen; 16 pairs are remembered)
-    const int want_march = (c->march && c->v[mode].march_ok) ? 1 : 0;      // per view: the march kernel needs a finite, bounded volume
+    const bool lin = c->naive || c->interp == 1;
+    const int want_march = (lin ? (c->march && c->v[mode].march_ok) : interp_march_ok(c, mode)) ? 1 : 0;      // per view: the march kernel needs a finite, bounded volume
     les_hip_scratch::Entry* e = nullptr;
     for (auto& x : s->cache)
         if (x.want_march == want_march && !memcmp(&x.f, fr, sizeof *fr) && !memcmp(&x.t, tr, sizeof *tr)) { e = &x; break; }
@@ -339,6 +406,7 @@ int les_hip_unary_one_scratch(les_hip_ctx* c, les_hip_scratch* s, int mode, cons
             for (size_t i = 1; i < s->cache.size(); i++) if (s->cache[i].stamp < s->cache[k].stamp) k = i;
             HIPCHECK(hipStreamSynchronize(s->stream));
             if (s->cache[k].d_jobs) HIPCHECK(hipFree(s->cache[k].d_jobs));
+            if (s->cache[k].d_sjobs) HIPCHECK(hipFree(s->cache[k].d_sjobs));
             s->cache.erase(s->cache.begin() + (long)k);
         }
         HIPCHECK(hipMalloc((void**)&ne.d_jobs, jobs.size() * sizeof(les::Job)));
@@ -363,7 +431,25 @@ int les_hip_unary_one_scratch(les_hip_ctx* c, les_hip_scratch* s, int mode, cons
     }
     *s->h_plane = make_float4(plane->a, plane->b, plane->c, plane->v);
     HIPCHECK(hipMemcpyAsync(s->d_plane, s->h_plane, sizeof(float4), hipMemcpyHostToDevice, s->stream));
-    if (e->march && c->naive) {
+    if (e->march && !lin && c->interp == 2 && !e->d_sjobs) {
+        // the strip jobs of the recompute launch of this rect pair, and room for their masked copy
+        std::vector<les::Job> sj;
+        rc = build_jobs(c, 1, fr, tr, 0, sj);
+        if (rc) return rc;
+        for (auto& j : sj) { j.out_off = (long long)(j.ty0 - tr->y) * tr->w + (j.tx0 - tr->x); j.out_stride = tr->w; }
+        HIPCHECK(hipStreamSynchronize(s->stream));
+        HIPCHECK(hipMalloc((void**)&e->d_sjobs, sj.size() * sizeof(les::Job)));
+        HIPCHECK(hipMemcpy(e->d_sjobs, sj.data(), sj.size() * sizeof(les::Job), hipMemcpyHostToDevice));
+        e->nsjobs = (int)sj.size();
+        if (sj.size() > s->rjobs_cap) {
+            if (s->d_rjobs) HIPCHECK(hipFree(s->d_rjobs));
+            s->d_rjobs = nullptr; s->rjobs_cap = 0;
+            HIPCHECK(hipMalloc((void**)&s->d_rjobs, std::max<size_t>(sj.size(), 64) * sizeof(les::Job)));
+            s->rjobs_cap = std::max<size_t>(sj.size(), 64);
+        }
+        if (!s->d_flag) HIPCHECK(hipMalloc((void**)&s->d_flag, sizeof(unsigned)));
+    }
+    if ((e->march && c->naive) || !lin) {
         // raw-cost patch of this filterRect (the one-entry call table is rewritten when the rect changes; everything is ordered on the scratch's stream)
         const size_t rneed = (size_t)fr->w * fr->h;
         if (rneed > s->raw_cap || !s->d_rawcall) {
@@ -388,7 +474,25 @@ int les_hip_unary_one_scratch(les_hip_ctx* c, les_hip_scratch* s, int mode, cons
             s->raw_f = *fr;
         }
         const RawPatches rp{s->d_rawcall, s->d_raw_off, s->d_raw, 1, (int)std::min<size_t>(1024, (rneed + 4095) / 4096)};
-        rc = launch_march(c, static_cast<const MarchEntry*>(e->march), mode, e->d_jobs, e->ngroups, s->d_plane, s->d_tile, check, s->stream, &rp);
+        if (!c->naive) {
+            // (interpolation 0 / 2: the target rect of les_nan_spread_kernel)
+            if (!s->d_target) {
+                HIPCHECK(hipMalloc((void**)&s->d_target, sizeof(les::WtaJob)));
+                HIPCHECK(hipMalloc((void**)&s->d_zero, sizeof(long long)));
+                const long long zero = 0;
+                HIPCHECK(hipMemcpy(s->d_zero, &zero, sizeof zero, hipMemcpyHostToDevice));
+            }
+            const les::WtaJob tj{tr->x, tr->y, tr->w, tr->h};
+            HIPCHECK(hipStreamSynchronize(s->stream));
+            HIPCHECK(hipMemcpy(s->d_target, &tj, sizeof tj, hipMemcpyHostToDevice));
+        }
+        if (c->naive) rc = launch_march(c, static_cast<const MarchEntry*>(e->march), mode, e->d_jobs, e->ngroups, s->d_plane, s->d_tile, check, s->stream, &rp);
+        else if (e->march) rc = launch_interp_march(c, static_cast<const MarchEntry*>(e->march), mode, e->d_jobs, e->ngroups, rp, s->d_flag, e->d_sjobs, s->d_rjobs,
+                                                    c->interp == 2 ? e->nsjobs : 0, s->d_target, s->d_zero, tr->w, s->d_plane, s->d_tile, check, s->stream);
+        else {
+            rc = launch_strips(c, mode, e->d_jobs, e->njobs, s->d_plane, s->d_tile, check, s->stream);
+            if (!rc) rc = launch_nan_spread(c, mode, 1, s->d_rawcall, s->d_target, s->d_zero, tr->w, s->d_plane, nullptr, s->d_tile, check, s->stream);
+        }
     }
     else if (e->march) rc = launch_march(c, static_cast<const MarchEntry*>(e->march), mode, e->d_jobs, e->ngroups, s->d_plane, s->d_tile, check, s->stream);
     else rc = launch_strips(c, mode, e->d_jobs, e->njobs, s->d_plane, s->d_tile, check, s->stream);

@@ -118,6 +118,12 @@ int launch_bf(les_hip_ctx* c, int mode, const les::BfJob* d_jobs, int njobs, int
     if (njobs <= 0) return LES_HIP_OK;
     if (c->naive)
         hipLaunchKernelGGL(les::les_naive_raw_kernel, dim3(ncalls, chunks), dim3(256), 0, stream, c->geom, strip_view(c, mode), d_calls, d_planes, d_raw);
+    else if (c->interp == 0)
+        hipLaunchKernelGGL(les::les_interp_raw_kernel<0>, dim3(ncalls, chunks), dim3(256), 0, stream, c->geom, (const float*)c->v[mode].vol, d_calls, d_planes, d_raw,
+                           (unsigned*)nullptr, 0.0f);
+    else if (c->interp == 2)
+        hipLaunchKernelGGL(les::les_interp_raw_kernel<2>, dim3(ncalls, chunks), dim3(256), 0, stream, c->geom, (const float*)c->v[mode].vol, d_calls, d_planes, d_raw,
+                           (unsigned*)nullptr, 0.0f);
     else
         hipLaunchKernelGGL(les::les_bf_volume_raw_kernel, dim3(ncalls, chunks), dim3(256), 0, stream, c->geom, (const float*)c->v[mode].vol, d_calls, d_planes, d_raw);
     HIPCHECK(hipGetLastError());

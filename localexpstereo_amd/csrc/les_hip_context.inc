@@ -48,6 +48,11 @@ static int create_common(les_hip_ctx** out, const les_hip_params* params, const 
     c->filter = filter;
     c->R = gf ? p.windR / 2 : (filter == LES_HIP_FILTER_BILATERAL ? p.windR : 0);
     c->strip = strip;
+    if (gf && !naive)
+        for (int k = 0; k < 2; k++) {
+            const StripEntry* e = find_interp_strip(p.windR / 2, k == 0 ? 0 : 2);
+            c->istrip[k] = e && e->TW >= strip->TW ? e : nullptr;       // (the job tables are cut for c->strip's width)
+        }
     c->march = gf ? find_march(p.windR / 2) : nullptr;
     if (gf && !c->march && !(getenv("LES_HIP_KERNEL") && !strcmp(getenv("LES_HIP_KERNEL"), "strip")))
         note_fallback(c->fallback_seen, FB_RADIUS, "no march kernel for guided-filter radius %d (windR %d; instantiated: 2 .. 10)", p.windR / 2, p.windR);
@@ -174,6 +179,15 @@ int les_hip_refresh_volume(les_hip_ctx* c, int mode)
     const int rc = build_march_view(c, mode, nullptr);             // cost range -> fixed-point scales, tiled copy rebuilt; the guide's tables stay
     if (rc) return rc;
     HIPCHECK(hipStreamSynchronize(cur_stream(c)));
+    return LES_HIP_OK;
+}
+
+int les_hip_set_interpolation(les_hip_ctx* c, int none_lin_quad)
+{
+    if (!c) return fail(LES_HIP_ERR_ARG, "null context");
+    if (c->naive) return fail(LES_HIP_ERR_ARG, "the image-based energy has no cost volume to interpolate");
+    if (none_lin_quad < 0 || none_lin_quad > 2) return fail(LES_HIP_ERR_ARG, "interpolation %d (0: nearest, 1: linear, 2: quadratic)", none_lin_quad);
+    c->interp = none_lin_quad;
     return LES_HIP_OK;
 }
 

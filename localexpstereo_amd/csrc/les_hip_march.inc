@@ -181,14 +181,80 @@ int launch_march(les_hip_ctx* c, const MarchEntry* m, int mode, const les::Job* 
     return LES_HIP_OK;
 }
 
+// The strip kernel of the context's interpolation (les_hip_set_interpolation); null when that radius has none whose strips are at least as
+// wide as the job tables' (c->strip's)
+const StripEntry* strip_for(const les_hip_ctx* c) { return (c->naive || c->interp == 1) ? c->strip : c->istrip[c->interp == 0 ? 0 : 1]; }
+
 int launch_strips(les_hip_ctx* c, int mode, const les::Job* d_jobs, int njobs, const float4* d_planes, float* d_out, int check, hipStream_t stream)
 {
     if (njobs <= 0) return LES_HIP_OK;
     if (mode < 0 || mode > 1 || !c->v[mode].stats || (c->naive ? !c->v[1 - mode].feat : !c->v[mode].vol))
         return fail(LES_HIP_ERR_ARG, "view %d was not supplied at creation", mode);
+    const StripEntry* se = strip_for(c);
+    if (!se) return fail(LES_HIP_ERR_UNSUPPORTED, "no strip kernel for interpolation %d at guided-filter radius %d", c->interp, c->R);
     const les::View view = strip_view(c, mode);
-    hipLaunchKernelGGL(c->strip->fn, dim3(njobs), dim3(c->strip->NT), 0, stream, c->geom, view, d_jobs, d_planes, d_out, njobs, check);
+    hipLaunchKernelGGL(se->fn, dim3(njobs), dim3(se->NT), 0, stream, c->geom, view, d_jobs, d_planes, d_out, njobs, check);
     HIPCHECK(hipGetLastError());
+    return LES_HIP_OK;
+}
+
+// Interpolation 0 / 2 of a cost-volume context can run on the march kernel for view `mode` (the caller checks the batch's geometry)
+bool interp_march_ok(const les_hip_ctx* c, int mode)
+{
+    return !c->naive && c->interp != 1 && c->march && c->v[mode].march_ok && (c->interp == 0 || c->v[mode].march2_ok);
+}
+
+// After the strip kernel served calls at interpolation 0 / 2: NaN over the rest of the quadrant a NaN raw cost reaches in the reference's running
+// box sums (les_nan_spread_kernel; flags: only the flagged calls, null: every call).  calls: the filterRects, targets / out_off / stride: where
+// each call's target rect was written.
+int launch_nan_spread(les_hip_ctx* c, int mode, int n, const les::RawCall* calls, const les::WtaJob* targets, const long long* out_off, int stride,
+                      const float4* d_planes, const unsigned* flags, float* d_out, int check, hipStream_t stream)
+{
+    if (n <= 0) return LES_HIP_OK;
+    if (c->interp == 2)
+        hipLaunchKernelGGL(les::les_nan_spread_kernel<2>, dim3(n), dim3(256), 0, stream, c->geom, (const float*)c->v[mode].vol, calls, targets, out_off, stride,
+                           d_planes, flags, d_out, 2 * c->R, check);
+    else
+        hipLaunchKernelGGL(les::les_nan_spread_kernel<0>, dim3(n), dim3(256), 0, stream, c->geom, (const float*)c->v[mode].vol, calls, targets, out_off, stride,
+                           d_planes, flags, d_out, 2 * c->R, check);
+    HIPCHECK(hipGetLastError());
+    return LES_HIP_OK;
+}
+
+// Interpolation 0 / 2 on the march kernel: the raw-cost pre-pass fills the calls' patches, the march kernel filters them (role A's KIND 3).
+// Interpolation 2 also flags every call whose patch leaves the range the view was scaled for; a dependent strip launch recomputes exactly
+// those calls (its jobs of unflagged calls are emptied on the device and return at once), overwriting what the march kernel wrote for them.
+// d_flags (rp.n entries) and d_rjobs (nsjobs entries) are scratch of the caller; d_sjobs: the strip jobs of the same calls; targets, out_off,
+// stride: as for launch_nan_spread.
+int launch_interp_march(les_hip_ctx* c, const MarchEntry* m, int mode, const les::Job* d_mjobs, int ngroups, const RawPatches& rp,
+                        unsigned* d_flags, const les::Job* d_sjobs, les::Job* d_rjobs, int nsjobs, const les::WtaJob* targets, const long long* out_off,
+                        int stride, const float4* d_planes, float* d_out, int check, hipStream_t stream)
+{
+    const ViewData& v = c->v[mode];
+    const bool quad = c->interp == 2;
+    les::MarchView mv = quad ? v.mv2 : v.mv;
+    mv.vol = rp.raw; mv.raw_off = rp.off; mv.vol_t = nullptr;
+    if (quad) {
+        if (!c->istrip[1]) return fail(LES_HIP_ERR_UNSUPPORTED, "no strip kernel for interpolation 2 at guided-filter radius %d", c->R);
+        HIPCHECK(hipMemsetAsync(d_flags, 0, (size_t)rp.n * sizeof(unsigned), stream));
+        hipLaunchKernelGGL(les::les_interp_raw_kernel<2>, dim3(rp.n, rp.chunks), dim3(256), 0, stream, c->geom, (const float*)v.vol, rp.calls, d_planes,
+                           rp.raw, d_flags, v.lo2);
+    } else {
+        // (a finite volume -- the view's march_ok -- gives nearest-slice costs in [vmin, th_col]: nothing to flag)
+        hipLaunchKernelGGL(les::les_interp_raw_kernel<0>, dim3(rp.n, rp.chunks), dim3(256), 0, stream, c->geom, (const float*)v.vol, rp.calls, d_planes,
+                           rp.raw, (unsigned*)nullptr, -INFINITY);
+    }
+    HIPCHECK(hipGetLastError());
+    if (ngroups > 0) hipLaunchKernelGGL(m->fn, dim3(ngroups), dim3(m->NT), 0, stream, c->geom, mv, d_mjobs, d_planes, d_out, ngroups, check);
+    HIPCHECK(hipGetLastError());
+    if (quad && nsjobs > 0) {
+        hipLaunchKernelGGL(les::les_mask_jobs_kernel, dim3((nsjobs + 255) / 256), dim3(256), 0, stream, d_sjobs, d_rjobs, (const unsigned*)d_flags, nsjobs);
+        HIPCHECK(hipGetLastError());
+        const StripEntry* se = c->istrip[1];
+        hipLaunchKernelGGL(se->fn, dim3(nsjobs), dim3(se->NT), 0, stream, c->geom, strip_view(c, mode), (const les::Job*)d_rjobs, d_planes, d_out, nsjobs, check);
+        HIPCHECK(hipGetLastError());
+        return launch_nan_spread(c, mode, rp.n, rp.calls, targets, out_off, stride, d_planes, d_flags, d_out, check, stream);
+    }
     return LES_HIP_OK;
 }
 
@@ -202,6 +268,7 @@ int build_march_view(les_hip_ctx* c, int m, const double* d_hs)
     const size_t P = (size_t)c->p.H * c->p.W;
     const int W = c->p.W, H = c->p.H;
     v.march_ok = false;
+    v.march2_ok = false;
     // the kernel addresses image rows and statistics rows by 32-bit byte offsets (raw buffer access): images of 2^26 pixels or more stay on the strip kernel
     if ((unsigned long long)P * (4ull * les::kMarchStatWords) >= (1ull << 31)) {
         note_fallback(c->fallback_seen, FB_IMAGE_SIZE, "image of %d x %d pixels (32-bit row offsets reach 2^26 pixels)", W, H);
@@ -262,24 +329,41 @@ int build_march_view(les_hip_ctx* c, int m, const double* d_hs)
     memcpy(&dmax, &dbits, sizeof dmax);
     if (!(dmax > 0.0f) || !(dmax < INFINITY)) { note_fallback(c->fallback_seen, FB_GUIDE, "view %d: the inverse covariance of the guide is not positive and finite (largest diagonal entry %g)", m, (double)dmax); return LES_HIP_OK; }
     const int K = 2 * c->R + 1;
-    const double Ba = 0.5 * range * std::sqrt((double)dmax), Bb = range + 1.5 * Ba;
-    const double scale = 1073741824.0 / ((double)K * Bb * 1.25);    // horizontal box sums of the quantised a, b stay below 2^30
-    // centred fixed-point cost (les_march.h): count = rint(p sp) + c0, c0 an integer, so that [vmin, th] maps onto [-2^(PB-1), 2^(PB-1) - 1]
-    const int PB = les::march_pb(c->R);
-    const float spf = (float)((double)((1 << PB) - 1) / range);
-    const double c0 = std::rint(-(double)vmin * (double)spf) - (double)(1 << (PB - 1));
-    const double up = 1.0 / (double)spf;
-    les::MarchView mv;
-    mv.vol = v.vol; mv.ipk8 = v.ipk8; mv.mstats = v.mstats;
-    mv.sp = spf;
-    mv.pmagic = (float)(12582912.0 + c0);                           // 1.5 * 2^23 + c0: an integer below 2^24, exact
-    mv.poff = (float)(-c0 * up);
-    mv.kapS = (float)((double)(1 << les::kMarchSH) * up / 255.0 * scale);
-    mv.upS = (float)(up * scale);
-    mv.qscale = (float)((double)(1 << les::kMarchS2) / (255.0 * scale));
-    mv.kmu = (float)(1.0 / ((double)(1ll << les::kMarchMB) * 255.0));
-    mv.raw_off = nullptr;
-    mv.vol_t = nullptr;
+    // the constants of the march kernel for costs in [lo, th]
+    auto scaled_view = [&](float lo) {
+        const double range = (double)th - (double)lo;
+        const double Ba = 0.5 * range * std::sqrt((double)dmax), Bb = range + 1.5 * Ba;
+        const double scale = 1073741824.0 / ((double)K * Bb * 1.25);    // horizontal box sums of the quantised a, b stay below 2^30
+        // centred fixed-point cost (les_march.h): count = rint(p sp) + c0, c0 an integer, so that [lo, th] maps onto [-2^(PB-1), 2^(PB-1) - 1]
+        const int PB = les::march_pb(c->R);
+        const float spf = (float)((double)((1 << PB) - 1) / range);
+        const double c0 = std::rint(-(double)lo * (double)spf) - (double)(1 << (PB - 1));
+        const double up = 1.0 / (double)spf;
+        les::MarchView mv;
+        mv.vol = v.vol; mv.ipk8 = v.ipk8; mv.mstats = v.mstats;
+        mv.sp = spf;
+        mv.pmagic = (float)(12582912.0 + c0);                           // 1.5 * 2^23 + c0: an integer below 2^24, exact
+        mv.poff = (float)(-c0 * up);
+        mv.kapS = (float)((double)(1 << les::kMarchSH) * up / 255.0 * scale);
+        mv.upS = (float)(up * scale);
+        mv.qscale = (float)((double)(1 << les::kMarchS2) / (255.0 * scale));
+        mv.kmu = (float)(1.0 / ((double)(1ll << les::kMarchMB) * 255.0));
+        mv.raw_off = nullptr;
+        mv.vol_t = nullptr;
+        return mv;
+    };
+    les::MarchView mv = scaled_view(vmin);
+    if (!c->naive) {
+        // interpolation 2: the quadratic through three slices falls below their minimum by up to about 1/8 of their spread, and f32
+        // cancellation adds to that.  Half the linear range below vmin keeps the resolution within 1.5x of the linear view's; raw costs
+        // below it (and NaN: the end slices) flag their call for the strip kernel.
+        const float lo2 = (float)((double)vmin - 0.5 * range);
+        if ((double)th - (double)lo2 <= 8.0 * (double)th) {
+            v.mv2 = scaled_view(lo2);
+            v.lo2 = lo2;
+            v.march2_ok = true;
+        }
+    }
     // The tiled copy for the taps of planes that are steep along x (a second resident copy of the volume: 1.5 GB more at 1500 x 1000 x 256, of
     // 288 GB).  Optional: LES_HIP_TILED=0 turns it off, a failing allocation or too little free memory (below) leaves it out
     // -- such planes then gather from [D][H][W] as every other plane does (same values, more HBM traffic).

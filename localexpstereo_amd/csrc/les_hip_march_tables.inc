@@ -30,6 +30,24 @@ const StripEntry kNaiveStrips[] = {
     LES_NAIVE_ENTRY(5, 64, 16, 4, 2), LES_NAIVE_ENTRY(6, 64, 16, 4, 2), LES_NAIVE_ENTRY(7, 64, 16, 4, 2), LES_NAIVE_ENTRY(8, 64, 16, 4, 2),
     LES_NAIVE_ENTRY(9, 64, 16, 4, 2), LES_NAIVE_ENTRY(10, 64, 16, 4, 2), LES_NAIVE_ENTRY(12, 64, 16, 4, 2), LES_NAIVE_ENTRY(15, 96, 16, 6, 2),
 };
+// cost volume at interpolation 0 / 2 (setInterpolationMethod, les_hip_set_interpolation): the exact per-pixel gathers, the same
+// conservative configuration per radius.  They serve every fall-back of those modes and recompute the flagged calls of a march launch.
+#define LES_INTERP_ENTRY(R_, WA_, BY_, SEG_, MW_, SRC_) \
+    { R_, 0, les::StripCfg<R_, WA_, BY_, SEG_>::TW, les::StripCfg<R_, WA_, BY_, SEG_>::NT, les::les_strip_kernel<R_, WA_, BY_, SEG_, MW_, SRC_> }
+#define LES_INTERP_ENTRIES(SRC_) \
+    LES_INTERP_ENTRY(1, 64, 16, 4, 2, SRC_), LES_INTERP_ENTRY(2, 64, 16, 4, 2, SRC_), LES_INTERP_ENTRY(3, 64, 16, 4, 2, SRC_), \
+    LES_INTERP_ENTRY(4, 64, 16, 4, 2, SRC_), LES_INTERP_ENTRY(5, 64, 16, 4, 2, SRC_), LES_INTERP_ENTRY(6, 64, 16, 4, 2, SRC_), \
+    LES_INTERP_ENTRY(7, 64, 16, 4, 2, SRC_), LES_INTERP_ENTRY(8, 64, 16, 4, 2, SRC_), LES_INTERP_ENTRY(9, 64, 16, 4, 2, SRC_), \
+    LES_INTERP_ENTRY(10, 64, 16, 4, 2, SRC_), LES_INTERP_ENTRY(12, 64, 16, 4, 2, SRC_), LES_INTERP_ENTRY(15, 96, 16, 6, 2, SRC_)
+const StripEntry kNearestStrips[] = { LES_INTERP_ENTRIES(2) };
+const StripEntry kQuadraticStrips[] = { LES_INTERP_ENTRIES(3) };
+// interp 0: nearest, 2: quadratic
+const StripEntry* find_interp_strip(int R, int interp)
+{
+    for (const auto& e : (interp == 0 ? kNearestStrips : kQuadraticStrips))
+        if (e.R == R) return &e;
+    return nullptr;
+}
 const StripEntry* find_naive_strip(int R)
 {
     for (const auto& e : kNaiveStrips)

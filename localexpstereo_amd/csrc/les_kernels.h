@@ -131,6 +131,51 @@ __device__ __forceinline__ float gather_finish(const Geom& g, const GatherPrep& 
     return r.mode == 3 ? 0.0f : p;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// LES/CostVolumeEnergy.h:99-167: the other two values of setInterpolationMethod (0: nearest slice, 2: three-point quadratic).
+// The reference converts with (int) on a double, undefined in C++ for NaN, +-inf and out-of-range values; its only platform
+// (MSVC x86-64, cvttsd2si) returns INT_MIN for all of them, and that is the contract here.  v_cvt_i32_f64 alone would saturate and
+// map NaN to 0, so the range test is explicit.  cvt(t) + D0 wraps as 32-bit two's complement.
+// ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int cvt_i32_msvc(double t)
+{
+    return (t >= -2147483648.0 && t < 2147483648.0) ? (int)t : (int)0x80000000u;      // NaN fails both comparisons
+}
+__device__ __forceinline__ int add_wrap_i32(int a, int b) { return (int)((uint32_t)a + (uint32_t)b); }
+
+// One raw cost min(C, th_col) at pixel (gx, gy) for INTERP 0 or 2.  Mode 2 divides by zero at the end slices (k2 == 0, k2 == D - 1,
+// and D == 1) and returns NaN there, as the reference does; its value is not bounded below by the volume's minimum.
+template <int INTERP>
+__device__ __forceinline__ float gather_cost_interp(const Geom& g, const float* __restrict__ vol, float a, float b, float c, int gx, int gy)
+{
+    static_assert(INTERP == 0 || INTERP == 2, "interpolation 1 is gather_cost");
+    const size_t HW = (size_t)g.H * g.W;
+    const size_t px = (size_t)gy * g.W + gx;
+    const float d_base = b * (float)gy + c;
+    const float d = a * (float)gx + d_base;
+    const int k = add_wrap_i32(cvt_i32_msvc((double)d + 0.5), g.D0);           // the literal 0.5 is a double: the add is in double
+    const float e = INTERP == 0 ? d_base : d;                                     // what the reference tests for NaN / inf (:110, :134)
+    float C;
+    if (k < 0) C = vol[px];
+    else if (k >= g.D) C = vol[(size_t)(g.D - 1) * HW + px];
+    else if (e != e || fabsf(e) == INFINITY) C = LES_COST_INVALID;
+    else if (INTERP == 0) C = vol[(size_t)k * HW + px];
+    else {
+        const int k1 = k - 1 > 0 ? k - 1 : 0, k3 = k + 1 < g.D - 1 ? k + 1 : g.D - 1;
+        const float y1 = vol[(size_t)k1 * HW + px], y2 = vol[(size_t)k * HW + px], y3 = vol[(size_t)k3 * HW + px];
+        const float r1 = (float)k1, r2 = (float)k, r3 = (float)k3;
+        const float A = y1 / (r1 - r2) / (r1 - r3);
+        const float B = y2 / (r2 - r1) / (r2 - r3);
+        const float Cq = y3 / (r3 - r1) / (r3 - r2);
+        const float r = (A + B) + Cq;
+        const float p = -((A * (r2 + r3) + B * (r1 + r3)) + Cq * (r1 + r2));
+        const float q = ((A * r2) * r3 + (B * r1) * r3) + (Cq * r1) * r2;
+        const float dd = d + (float)g.D0;
+        C = ((r * dd) * dd + p * dd) + q;
+    }
+    return (g.th_col < C) ? g.th_col : C;       // std::min(C, th_col), NaN-propagating like the reference
+}
+
 // NaiveStereoEnergy raw cost, LES/StereoEnergy.h:702-742: the other view is sampled at x - sign * d on the same row with
 // the bilinear interpolation of cv::warpAffine (source coordinate rounded to 1/32 pixel, replicated border).
 struct NaivePrep {
@@ -328,7 +373,9 @@ __device__ unsigned long long les_dbg[12];
 #define LES_PHASE_END() ((void)0)
 #endif
 
-template <int R, int WA, int BY, int SEG, int MW, int SRC = 0>       // SRC 0: cost volume, 1: image-based matching cost
+// SRC 0: cost volume, 1: image-based matching cost, 2 / 3: cost volume at interpolation 0 / 2 (gather_cost_interp; jobs with an empty
+// target -- the unflagged calls of a recompute launch, les_mask_jobs_kernel -- return at once)
+template <int R, int WA, int BY, int SEG, int MW, int SRC = 0>
 __global__ void __launch_bounds__(4 * WA, MW)
 les_strip_kernel(Geom g, View view, const Job* __restrict__ jobs, const float4* __restrict__ planes,
                  float* __restrict__ out, int njobs, int check)
@@ -365,6 +412,7 @@ les_strip_kernel(Geom g, View view, const Job* __restrict__ jobs, const float4* 
     }
     if (job_id >= njobs) return;
     const Job job = jobs[job_id];
+    if constexpr (SRC >= 2) if (job.tw <= 0 || job.th <= 0) return;
     const float4 plane = planes[job.plane_idx];          // (a, b, c, v)
     const int tid = (int)threadIdx.x;
     const int Ttot = job.th + 4 * R;         // p-rows to march over
@@ -435,7 +483,7 @@ les_strip_kernel(Geom g, View view, const Job* __restrict__ jobs, const float4* 
         gr.rowpx = ((uint32_t)sy * (uint32_t)g.W) | ((t < Ttot && gy >= job.cy0 && gy < job.cy1) ? 0x80000000u : 0u);
         gr.d_base = plane.y * (float)sy + plane.z;
         s_grow[tid] = gr;
-        if constexpr (SRC == 1) s_gsy[tid] = sy;
+        if constexpr (SRC != 0) s_gsy[tid] = sy;
     };
     if (tid < BY) fill_row_tables(0);
     if (tid < TW + 4) s_rnx2[tid] = s_rtab[window_count(job.tx0 + tid, R, job.cx0, job.cx1)];
@@ -462,6 +510,22 @@ les_strip_kernel(Geom g, View view, const Job* __restrict__ jobs, const float4* 
                     const uint32_t ip = view.ipk10[px];
                     if (g_lane && i < BY) {
                         s_p[i][g_xi] = inside ? naive_finish(view, np, own, fa, fb) : 0.0f;
+                        s_ipk[i][g_xi] = ip;
+                    }
+                }
+            } else if constexpr (SRC >= 2) {
+                // interpolation 0 / 2: the exact per-pixel gather (one row per lane in flight, as for the image-based cost)
+#pragma unroll 1
+                for (int jp = 0; jp < GPASS; jp++) {
+                    const int i = jp * GRP + g_ri;
+                    const GRow gr = s_grow[i < BY ? i : BY - 1];
+                    const bool inside = g_lane && g_col_in && i < BY && (gr.rowpx >> 31);
+                    const int sy = s_gsy[i < BY ? i : BY - 1];
+                    const uint32_t px = (gr.rowpx & 0x7fffffffu) + (uint32_t)g_sx;
+                    const float p = inside ? gather_cost_interp<SRC == 2 ? 0 : 2>(g, view.vol, plane.x, plane.y, plane.z, g_sx, sy) : 0.0f;
+                    const uint32_t ip = view.ipk10[px];
+                    if (g_lane && i < BY) {
+                        s_p[i][g_xi] = p;
                         s_ipk[i][g_xi] = ip;
                     }
                 }
@@ -713,6 +777,39 @@ __global__ void les_naive_raw_kernel(Geom g, View view, const RawCall* __restric
     }
 }
 
+// Raw cost of a cost-volume context at interpolation 0 or 2 over whole filterRects, into the same per-call patches (the march kernel's
+// KIND 3 and the bilateral kernel read them).  flags (null: not wanted) gets a non-zero entry for every call whose patch holds a NaN
+// or a value below lo, the bottom of the range the march view was scaled for: those calls are recomputed by the strip kernel.
+template <int INTERP>
+__global__ void les_interp_raw_kernel(Geom g, const float* __restrict__ vol, const RawCall* __restrict__ calls, const float4* __restrict__ planes,
+                                      float* __restrict__ raw, unsigned* __restrict__ flags, float lo)
+{
+    const RawCall rc = calls[blockIdx.x];
+    const float4 plane = planes[blockIdx.x];
+    const long long area = (long long)rc.fw * rc.fh;
+    const long long per = (area + gridDim.y - 1) / gridDim.y;
+    const long long p0 = per * blockIdx.y, p1 = p0 + per < area ? p0 + per : area;
+    bool bad = false;
+    for (long long p = p0 + threadIdx.x; p < p1; p += blockDim.x) {
+        const int yy = (int)(p / rc.fw), xx = (int)(p - (long long)yy * rc.fw);
+        const float v = gather_cost_interp<INTERP>(g, vol, plane.x, plane.y, plane.z, rc.fx + xx, rc.fy + yy);
+        raw[rc.off + p] = v;
+        bad = bad || !(v >= lo);
+    }
+    if (flags && bad) atomicMax(&flags[blockIdx.x], 1u);
+}
+
+// The strip jobs of a recompute launch: job i keeps its target where its call is flagged and gets an empty one (the strip kernel's
+// SRC 2 / 3 instantiations return at once on it) elsewhere.  Same order as the source table.
+__global__ void les_mask_jobs_kernel(const Job* __restrict__ src, Job* __restrict__ dst, const unsigned* __restrict__ flags, int njobs)
+{
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= njobs) return;
+    Job j = src[i];
+    if (!flags[j.plane_idx]) { j.tw = 0; j.th = 0; }
+    dst[i] = j;
+}
+
 // One dword per lane streaming copy: the calibration pattern for the rocprofv3 FETCH_SIZE / WRITE_SIZE counters (the strip
 // kernel reads and writes dwords; MI355X_MICROARCH.md asks for a calibration on a known byte count in the same access width).
 __global__ void les_calib_copy_kernel(const float* __restrict__ src, float* __restrict__ dst, size_t n)
@@ -820,6 +917,59 @@ __global__ void les_xchg_unpack_kernel(const XchgRect* __restrict__ rects, const
         const size_t k = (size_t)(r.y + yy) * W + r.x + xx;
         labels[k] = sl[r.off + idx];
         cost[k] = sc[r.off + idx];
+    }
+}
+
+// The reference's guided filter sums its boxes with running sums (OpenCV's RowSum / ColumnSum, restated by the oracle's boxfilter): a NaN
+// raw cost at (xn, yn) of the filterRect, once added, stays in every later sum of its row and column sweep, so after the two box passes of
+// the filter (p -> a, b -> q) q is NaN at every (x, y) with x >= xn - 2R and y >= yn - 2R, not only inside the NaN's windows.  The strip
+// kernel sums windows; this pass, run after it, writes NaN over the rest of that quadrant of each call (where the label is valid under check).
+// One workgroup per call; flags (null: every call) selects the calls.  Columns in chunks of kNanChunk: the first NaN row of each column, then
+// its running minimum over the columns.
+constexpr int kNanChunk = 1024;
+template <int INTERP>
+__global__ void __launch_bounds__(256)
+les_nan_spread_kernel(Geom g, const float* __restrict__ vol, const RawCall* __restrict__ calls, const WtaJob* __restrict__ targets,
+                      const long long* __restrict__ out_off, int out_stride, const float4* __restrict__ planes, const unsigned* __restrict__ flags,
+                      float* __restrict__ out, int R2, int check)
+{
+    __shared__ int s_min[kNanChunk];
+    __shared__ int s_carry;
+    const int i = (int)blockIdx.x;
+    if (flags && !flags[i]) return;
+    const RawCall rc = calls[i];
+    const WtaJob t = targets[i];
+    if (t.w <= 0 || t.h <= 0 || rc.fw <= 0 || rc.fh <= 0) return;
+    const float4 pl = planes[i];
+    const int tx = t.x - rc.fx, ty = t.y - rc.fy;                      // the target in filterRect coordinates
+    const int ncols = min(rc.fw, tx + t.w + R2), nrows = min(rc.fh, ty + t.h + R2);
+    const long long area = (long long)t.w * t.h;
+    if (threadIdx.x == 0) s_carry = 0x7fffffff;
+    for (int c0 = 0; c0 < ncols; c0 += kNanChunk) {
+        __syncthreads();
+        for (int c = (int)threadIdx.x; c < kNanChunk; c += (int)blockDim.x) {
+            int m = 0x7fffffff;
+            if (c0 + c < ncols)
+                for (int r = 0; r < nrows; r++) {
+                    const float v = gather_cost_interp<INTERP>(g, vol, pl.x, pl.y, pl.z, rc.fx + c0 + c, rc.fy + r);
+                    if (v != v) { m = r; break; }
+                }
+            s_min[c] = m;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int run = s_carry;
+            for (int c = 0; c < kNanChunk && c0 + c < ncols; c++) { run = min(run, s_min[c]); s_min[c] = run; }
+            s_carry = run;
+        }
+        __syncthreads();
+        for (long long p = threadIdx.x; p < area; p += blockDim.x) {
+            const int yy = (int)(p / t.w), xx = (int)(p - (long long)yy * t.w);
+            const int cl = min(tx + xx + R2, ncols - 1);                // last column whose NaN reaches this pixel
+            if (cl < c0 || cl >= c0 + kNanChunk || s_min[cl - c0] > ty + yy + R2) continue;
+            if (check && !label_valid(g, pl.x, pl.y, pl.z, pl.w, t.x + xx, t.y + yy)) continue;
+            out[out_off[i] + (long long)yy * out_stride + xx] = __int_as_float(0x7fc00000);
+        }
     }
 }
 

@@ -95,6 +95,14 @@ public:
             fprintf(stderr, "HipCostVolumeEnergy: %s\n", les_hip_last_error());
     }
 
+    // CostVolumeEnergy::setInterpolationMethod (LES/CostVolumeEnergy.h:45-48): 0 nearest slice, 1 linear (the default), 2 quadratic.  Like the
+    // reference's setter it is not synchronised with evaluations running on other threads.
+    virtual void setInterpolationMethod(int none_lin_quad)
+    {
+        if (les_hip_set_interpolation(ctx_, none_lin_quad) != LES_HIP_OK)
+            throw std::invalid_argument(std::string("setInterpolationMethod: ") + les_hip_last_error());
+    }
+
     les_hip_ctx* handle() const { return ctx_; }
 
 private:
@@ -124,6 +132,12 @@ public:
     HipNaiveStereoEnergy(const uint8_t* imL, const uint8_t* imR, int width, int height, Parameters p, float MAX_DISPARITY,
                          float MIN_DISPARITY = 0, int device = 0)
         : HipCostVolumeEnergy(NaiveTag{}, imL, imR, width, height, std::move(p), MAX_DISPARITY, MIN_DISPARITY, device) {}
+
+    // NaiveStereoEnergy has no volume and no interpolation setting
+    void setInterpolationMethod(int) override
+    {
+        throw std::invalid_argument("setInterpolationMethod: the image-based energy has no cost volume");
+    }
 };
 
 }  // namespace les_host

@@ -277,17 +277,18 @@ def MidV2(data, iterations=5, pmIterations=2, doDual=False, smooth_weight=None, 
 
 
 def MidV3(data, volL, volR, iterations=5, pmIterations=2, doDual=False, smooth_weight=0.5, mc_threshold=0.5, filterRadious=20,
-          error_threshold=1.0, device="cuda", seed=1, lib=None, params=None, **kw):
+          error_threshold=1.0, device="cuda", seed=1, lib=None, params=None, interpolate=1, **kw):
     """MidV3 (LES/main.cpp:330-420): cost-volume energy (volumes ingested on the device), layers 1 % / 3 % / 9 % of the
     image width.  volL / volR: host arrays / memmaps [ndisp][H][W] (volR None: synthesised from the left one).  params: PARAMS_GF
-    (default) or PARAMS_BF: filter and eps; smooth_weight, mc_threshold and filterRadious override lambda_, th_col and windR (:351-353)."""
+    (default) or PARAMS_BF: filter and eps; smooth_weight, mc_threshold and filterRadious override lambda_, th_col and windR (:351-353).
+    interpolate: the energy's setInterpolationMethod (LES/CostVolumeEnergy.h:45-48) -- 0 nearest, 1 linear (default), 2 quadratic."""
     p = dict(PARAMS_GF if params is None else params)
     maxdisp = float(data["ndisp"] - 1)
     tl, tr = io.ingest_volumes(volL, volR, device=device, lib=lib)
     D, H, W = tl.shape
     e = api.HipCostVolumeEnergy(data["imL"], data["imR"], tl.data_ptr(), tr.data_ptr(), windR=filterRadious, eps=p["eps"],
                                 th_col=mc_threshold, max_disp=maxdisp, device=torch.device(device).index or 0, volumes_on_device=True,
-                                shape=(D, H, W), lib=lib, filter=p["filter"])
+                                shape=(D, H, W), lib=lib, filter=p["filter"], interpolate=interpolate)
     st = FastGCStereo(e, data["imL"], data["imR"], dict(p, lambda_=smooth_weight, windR=filterRadious, th_col=mc_threshold), device=device, seed=seed, **kw)
     st.setEvaluator(io.Evaluator(data["dispGT"], data["nonocc"], error_threshold), precision=-1.0)
     _layers(st, (int(W * 0.01), int(W * 0.03), int(W * 0.09)))
