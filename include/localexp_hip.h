@@ -111,6 +111,20 @@ int les_hip_create_filtered(les_hip_ctx** out, const les_hip_params* params, int
 /* les_hip_create_naive with a filter: replaces NaiveStereoEnergy::NaiveStereoEnergy for any filterName. */
 int les_hip_create_naive_filtered(les_hip_ctx** out, const les_hip_params* params, int filter, const uint8_t* imL, const uint8_t* imR,
                                   float alpha, float th_grad);
+/* ---- vertical disparity (Plane::v, LES/Plane.h:4-40): labels for pairs with imperfect rectification.
+ * The image-based energy (les_hip_create_naive*) samples the other view at (x - sign d(x, y), y + v) for every plane with v != 0
+ * (NaiveStereoEnergy, LES/StereoEnergy.h:704-729; -0.0 counts as 0) on every evaluation entry point, view, filter and check value; the
+ * cost-volume energy ignores v (LES/CostVolumeEnergy.h:64-98), as do the validity rule, the pairwise terms, disparities and post-processing.
+ * The two setters below only choose draws of v: with both at 0 (the default) every generator stream is the one of a context without them.
+ * replaces: the maxVDisp argument of FastGCStereo / NaiveStereoEnergy (MAX_VDISPARITY, PMStereoBase.h:37): les_hip_batch_propose(INIT)
+ * draws v uniformly in [-max_vdisp, max_vdisp] after the disparity (createRandomLabel, LES/StereoEnergy.h:120-129).  Allowed on both
+ * energies (only the image-based one reads v).  max_vdisp: finite, >= 0, else LES_HIP_ERR_ARG. */
+int les_hip_set_max_vdisparity(les_hip_ctx* ctx, float max_vdisp);
+/* replaces: RandomProposer(K, maxDisp, minDisp, maxVDisp) (LES/Proposer.h:100-148): les_hip_batch_propose(RANDOM) perturbs v within
+ * max_vdisp * 0.5^(m+1) of the source label's, clamped to [-max_vdisp, max_vdisp], drawn after the disparity; 0 keeps the source's v.
+ * EXPANSION keeps the source label's v; RANSAC proposes v = 0.  max_vdisp: finite, >= 0, else LES_HIP_ERR_ARG. */
+int les_hip_set_random_vdisparity(les_hip_ctx* ctx, float max_vdisp);
+
 void les_hip_destroy(les_hip_ctx* ctx);                 /* replaces: ~CostVolumeEnergy (:50-52)          */
 const char* les_hip_last_error(void);                   /* thread-local description of the last failure  */
 

@@ -19,7 +19,7 @@ PLANE_DT = np.dtype([("a", "<f4"), ("b", "<f4"), ("c", "<f4"), ("v", "<f4")])
 SYMBOLS = [
     "les_hip_create", "les_hip_create_naive", "les_hip_create_filtered", "les_hip_create_naive_filtered", "les_hip_destroy", "les_hip_last_error", "les_hip_set_stream", "les_hip_set_thread_stream", "les_hip_synchronize",
     "les_hip_unary_one", "les_hip_unary_one_scratch", "les_hip_scratch_create", "les_hip_scratch_destroy", "les_hip_unary_batch", "les_hip_batch_create", "les_hip_batch_destroy",
-    "les_hip_batch_num_jobs", "les_hip_batch_kernel_kind", "les_hip_batch_graph_nodes", "les_hip_batch_graph_offsets", "les_hip_batch_expansion_graph", "les_hip_batch_max_cell_nodes", "les_hip_batch_graph_solver_kind", "les_hip_refresh_volume", "les_hip_set_interpolation", "les_hip_batch_solve_graphs", "les_hip_batch_solve_graphs_counted", "les_hip_batch_solve_graphs_tiled", "les_hip_batch_solve_graphs_tiled_stats", "les_hip_batch_tiled_workspace_bytes", "les_hip_batch_apply_masks", "les_hip_batch_run", "les_hip_batch_set_units", "les_hip_batch_propose", "les_hip_batch_wta",
+    "les_hip_batch_num_jobs", "les_hip_batch_kernel_kind", "les_hip_batch_graph_nodes", "les_hip_batch_graph_offsets", "les_hip_batch_expansion_graph", "les_hip_batch_max_cell_nodes", "les_hip_batch_graph_solver_kind", "les_hip_refresh_volume", "les_hip_set_interpolation", "les_hip_set_max_vdisparity", "les_hip_set_random_vdisparity", "les_hip_batch_solve_graphs", "les_hip_batch_solve_graphs_counted", "les_hip_batch_solve_graphs_tiled", "les_hip_batch_solve_graphs_tiled_stats", "les_hip_batch_tiled_workspace_bytes", "les_hip_batch_apply_masks", "les_hip_batch_run", "les_hip_batch_set_units", "les_hip_batch_propose", "les_hip_batch_wta",
     "les_hip_wta_update", "les_hip_malloc", "les_hip_free",
     "les_hip_memcpy_h2d", "les_hip_memcpy_d2h", "les_hip_memset", "les_hip_get_stats", "les_hip_strip_width", "les_hip_tiled_volume_bytes",
     "les_hip_calib_copy", "les_hip_calib_copy_wide", "les_hip_exchange_create", "les_hip_exchange_destroy", "les_hip_exchange_slot_floats",
@@ -131,6 +131,8 @@ def load(path=None):
         "les_hip_batch_num_jobs": (ci, [vp]),
         "les_hip_batch_kernel_kind": (ci, [vp, vp, ci]),
         "les_hip_set_interpolation": (ci, [vp, ci]),
+        "les_hip_set_max_vdisparity": (ci, [vp, C.c_float]),
+        "les_hip_set_random_vdisparity": (ci, [vp, C.c_float]),
         "les_hip_batch_run": (ci, [vp, vp, ci, vp, ci, vp, ci]),
         "les_hip_batch_set_units": (ci, [vp, vp, vp]),
         "les_hip_batch_propose": (ci, [vp, vp, ci, ci, vp, vp, vp]),
@@ -405,9 +407,11 @@ class HipCostVolumeEnergy:
 
     @classmethod
     def naive(cls, imL, imR, windR=20, eps=1e-4, alpha=0.9, th_col=10.0, th_grad=2.0, max_disp=63.0, min_disp=0.0, device=0, lib=None,
-              filter="GF"):
+              filter="GF", max_vdisp=0.0):
         """Python mirror of NaiveStereoEnergy (LES/StereoEnergy.h:629-764; MiddV2 parameters LES/main.cpp:86-121):
-        image-based matching cost, no volume.  Every method of the volume-based operator works on it.  filter: as for the constructor."""
+        image-based matching cost, no volume.  Every method of the volume-based operator works on it.  filter: as for the constructor.
+        max_vdisp: MAX_VDISPARITY (PMStereoBase.h:37): the range [-max_vdisp, max_vdisp] of the vertical disparity Plane::v that
+        PROPOSE_INIT draws (createRandomLabel); the cost honours every plane's v whatever this value."""
         self = cls.__new__(cls)
         self.h = None
         self.filter = filter_kind(filter)
@@ -428,6 +432,9 @@ class HipCostVolumeEnergy:
                                                            C.c_float(alpha), C.c_float(th_grad)))
         self.h = h
         self.interpolate = 1      # (no volume: les_hip_set_interpolation refuses this context)
+        self.max_vdisp = self.random_vdisp = 0.0
+        if max_vdisp:
+            self.set_max_vdisparity(max_vdisp)
         return self
 
     def _chk(self, rc):
@@ -463,6 +470,17 @@ class HipCostVolumeEnergy:
         evaluation (prepared batches included).  Not for the image-based energy, and not while another thread evaluates on this context."""
         self._chk(self.L.les_hip_set_interpolation(self.h, int(none_lin_quad)))
         self.interpolate = int(none_lin_quad)
+
+    def set_max_vdisparity(self, max_vdisp):
+        """The energy's MAX_VDISPARITY: PROPOSE_INIT draws v in [-max_vdisp, max_vdisp] (0: no draw).  Only the image-based cost reads v."""
+        self._chk(self.L.les_hip_set_max_vdisparity(self.h, C.c_float(max_vdisp)))
+        self.max_vdisp = float(max_vdisp)
+
+    def set_random_vdisparity(self, max_vdisp):
+        """RandomProposer's maxVDisp (LES/Proposer.h:100-148): PROPOSE_RANDOM perturbs v within max_vdisp * 0.5^(m+1), clamped to
+        [-max_vdisp, max_vdisp]; 0 (the default) keeps the source label's v."""
+        self._chk(self.L.les_hip_set_random_vdisparity(self.h, C.c_float(max_vdisp)))
+        self.random_vdisp = float(max_vdisp)
 
     def refresh_volume(self, mode=0):
         """After the caller refilled the device-resident volume of `mode` in place: cost range / fixed-point scales / tiled copy re-derived."""

@@ -14,6 +14,7 @@
 #include "les_maxflow_tiled.h"
 #include "les_maxflow_cell.h"
 #include "les_bilateral.h"
+#include "les_vdisp.h"
 
 #include "../host/ResidualCut.h"      // the host cores' finisher of the tiled max-flow (plain C++: search trees / push-relabel on a residual graph)
 
@@ -100,6 +101,7 @@ struct ViewData {
 
 struct MtHost;
 namespace { void mt_host_free(MtHost* m); }
+namespace { struct VdispStrip; void vdisp_free(VdispStrip* v); }
 
 struct les_hip_ctx {
     les_hip_params p;
@@ -118,6 +120,9 @@ struct les_hip_ctx {
     float naive_alpha = 0;
     int naive = 0;                       // 1: raw cost from the feature images (les_hip_create_naive), no volume
     float th_color = 0, th_grad = 0;
+    // vertical disparity (Plane::v): the energy's MAX_VDISPARITY (les_hip_set_max_vdisparity: createRandomLabel, PROPOSE_INIT) and the
+    // RandomProposer's maxVDisp (les_hip_set_random_vdisparity: PROPOSE_RANDOM); 0: no draw, the RNG streams of a context without v
+    float max_vdisp = 0.0f, random_vdisp = 0.0f;
     // scratch reused by the non-prepared entry points and by batch_run
     float4* d_planes = nullptr; size_t planes_cap = 0;
     float* d_map = nullptr;                         // H*W floats
@@ -157,6 +162,8 @@ struct les_hip_batch {
     mutable long long* d_out_off = nullptr;      // float offset of each call's target corner in the output (les_nan_spread_kernel)
     mutable unsigned* d_flags[2] = {nullptr, nullptr};
     mutable les::Job* d_rjobs[2] = {nullptr, nullptr};
+    // image-based context on the strip kernel: the recompute of its calls with v != 0 (les_hip_vdisp.inc), built on the first such run
+    mutable VdispStrip* vd = nullptr;
     // bilateral / unfiltered context: tiles of calls that share their rects (les_hip_bilateral.inc); the raw-cost patches above serve it too
     les::BfJob* d_bfjobs = nullptr;
     int bf_np = 1;                       // most calls per tile (1: the one-plane instantiation of the kernel)
@@ -206,6 +213,9 @@ struct les_hip_scratch {
     float* d_raw = nullptr; size_t raw_cap = 0;
     les::RawCall* d_rawcall = nullptr; long long* d_raw_off = nullptr;
     les_hip_rect raw_f = {-1, -1, -1, -1};
+    // image-based energy on the strip kernel: the recompute of a call with v != 0 (les_hip_vdisp.inc) for the filterRect vd_f
+    VdispStrip* vd = nullptr;
+    les_hip_rect vd_f = {-1, -1, -1, -1}, vd_t = {-1, -1, -1, -1};
     // bilateral / unfiltered context: the tiles of the last rect pair
     les::BfJob* d_bfjobs = nullptr; size_t bf_cap = 0; int bf_njobs = 0;
     les_hip_rect bf_f = {-1, -1, -1, -1}, bf_t = {-1, -1, -1, -1};
@@ -241,6 +251,7 @@ inline hipStream_t cur_stream(const les_hip_ctx* c) { return (tl_stream_gen != 0
 
 float naive_alpha(const les_hip_ctx* c) { return c->naive_alpha; }
 
+#include "les_hip_vdisp.inc"             // the image-based cost with vertical disparity (Plane::v): pre-pass and strip-path recompute launches
 #include "les_hip_bilateral.inc"         // the bilateral / unfiltered aggregation: per-view set-up, weight table, tiles, launches
 
 }  // namespace

@@ -17,7 +17,7 @@ int les_hip_batch_create(les_hip_ctx* c, int n, const les_hip_rect* frs, const l
     les_hip_batch* b = new les_hip_batch();
     b->n = n; b->njobs = (int)jobs.size(); b->out_slabs = out_slabs; b->R = c->R; b->device = c->p.device;
     b->targets.assign(trs, trs + n);
-    if (!c->naive && c->filter == LES_HIP_FILTER_GF) b->filters.assign(frs, frs + n);     // (the raw-cost patch table of interpolation 0 / 2)
+    if (c->filter == LES_HIP_FILTER_GF) b->filters.assign(frs, frs + n);     // (the raw-cost patch table of interpolation 0 / 2; the vertical-disparity recompute)
     {
         int max_area = 1;
         for (int i = 0; i < n; i++) max_area = std::max(max_area, trs[i].w * trs[i].h);
@@ -112,6 +112,7 @@ void les_hip_batch_destroy(les_hip_batch* b)
     for (int m = 0; m < 2; m++) if (b->d_flags[m]) (void)hipFree(b->d_flags[m]);
     if (b->d_out_off) (void)hipFree(b->d_out_off);
     for (int m = 0; m < 2; m++) if (b->d_rjobs[m]) (void)hipFree(b->d_rjobs[m]);
+    vdisp_free(b->vd);
     if (b->d_units) (void)hipFree(b->d_units);
     if (b->d_targets) (void)hipFree(b->d_targets);
     if (b->d_graph_off) (void)hipFree(b->d_graph_off);
@@ -175,7 +176,7 @@ int les_hip_batch_propose(les_hip_ctx* c, const les_hip_batch* b, int kind, int 
         hipLaunchKernelGGL(les::les_expansion_kernel, dim3((n + 63) / 64), dim3(64), 0, cur_stream(c), b->d_units, lab, W, rng, pl, n);
         break;
     case LES_HIP_PROPOSE_RANDOM:
-        hipLaunchKernelGGL(les::les_random_kernel, dim3((n + 63) / 64), dim3(64), 0, cur_stream(c), b->d_units, lab, W, rng, pl, n, m, mind, maxd);
+        hipLaunchKernelGGL(les::les_random_kernel, dim3((n + 63) / 64), dim3(64), 0, cur_stream(c), b->d_units, lab, W, rng, pl, n, m, mind, maxd, c->random_vdisp);
         break;
     case LES_HIP_PROPOSE_RANSAC:
         // RansacProposer(K, MAX_SAM = 500, conf = 0.95), threshold 1.0 (LES/Proposer.h:265,305)
@@ -191,7 +192,7 @@ int les_hip_batch_propose(les_hip_ctx* c, const les_hip_batch* b, int kind, int 
         }
         break;
     case LES_HIP_PROPOSE_INIT:
-        hipLaunchKernelGGL(les::les_init_labels_kernel, dim3(n), dim3(64), 0, cur_stream(c), b->d_units, lab, W, rng, pl, mind, maxd);
+        hipLaunchKernelGGL(les::les_init_labels_kernel, dim3(n), dim3(64), 0, cur_stream(c), b->d_units, lab, W, rng, pl, mind, maxd, c->max_vdisp);
         break;
     default:
         return fail(LES_HIP_ERR_ARG, "unknown proposer kind %d", kind);
@@ -290,7 +291,7 @@ int les_hip_batch_run(les_hip_ctx* c, const les_hip_batch* b, int mode, const le
             if (!b->d_raw[mode]) HIPCHECK(hipMalloc((void**)&b->d_raw[mode], (size_t)std::max<long long>(b->raw_floats, 1) * sizeof(float)));
         }
         const RawPatches rp{b->d_rawcalls, b->d_raw_off, b->d_raw[mode], b->n, b->raw_chunks};
-        return launch_march(c, b->mentry, mode, b->d_mjobs, b->nmgroups, d_planes, out_dev, check, cur_stream(c), &rp);
+        return launch_naive_march(c, b->mentry, mode, b->d_mjobs, b->nmgroups, d_planes, out_dev, check, cur_stream(c), rp);
     }
     if (!c->naive && c->interp != 1) {
         {
@@ -302,7 +303,15 @@ int les_hip_batch_run(les_hip_ctx* c, const les_hip_batch* b, int mode, const le
         if (rc) return rc;
         return launch_nan_spread(c, mode, b->n, b->d_rawcalls, b->d_targets, b->d_out_off, c->p.W, d_planes, nullptr, out_dev, check, cur_stream(c));
     }
-    return launch_strips(c, mode, b->d_jobs, b->njobs, d_planes, out_dev, check, cur_stream(c));
+    int rc = launch_strips(c, mode, b->d_jobs, b->njobs, d_planes, out_dev, check, cur_stream(c));
+    if (rc || !c->naive) return rc;
+    // image-based context: the strip kernel gathers along one row; the calls with v != 0 are recomputed after it
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        if (!b->vd) rc = vdisp_build(c, b->n, b->filters.data(), b->targets.data(), &b->vd);
+        if (rc) return rc;
+    }
+    return launch_vdisp_strips(c, b->vd, mode, b->d_jobs, b->njobs, d_planes, out_dev, check, cur_stream(c));
 }
 
 int les_hip_unary_batch(les_hip_ctx* c, int mode, int n, const les_hip_rect* frs, const les_hip_rect* trs,
@@ -356,6 +365,7 @@ void les_hip_scratch_destroy(les_hip_scratch* s)
     if (s->d_target) (void)hipFree(s->d_target);
     if (s->d_zero) (void)hipFree(s->d_zero);
     if (s->d_rjobs) (void)hipFree(s->d_rjobs);
+    vdisp_free(s->vd);
     if (s->d_tile) (void)hipFree(s->d_tile);
     if (s->h_tile) (void)hipHostFree(s->h_tile);
     if (s->d_raw) (void)hipFree(s->d_raw);
@@ -486,7 +496,7 @@ int les_hip_unary_one_scratch(les_hip_ctx* c, les_hip_scratch* s, int mode, cons
             HIPCHECK(hipStreamSynchronize(s->stream));
             HIPCHECK(hipMemcpy(s->d_target, &tj, sizeof tj, hipMemcpyHostToDevice));
         }
-        if (c->naive) rc = launch_march(c, static_cast<const MarchEntry*>(e->march), mode, e->d_jobs, e->ngroups, s->d_plane, s->d_tile, check, s->stream, &rp);
+        if (c->naive) rc = launch_naive_march(c, static_cast<const MarchEntry*>(e->march), mode, e->d_jobs, e->ngroups, s->d_plane, s->d_tile, check, s->stream, rp);
         else if (e->march) rc = launch_interp_march(c, static_cast<const MarchEntry*>(e->march), mode, e->d_jobs, e->ngroups, rp, s->d_flag, e->d_sjobs, s->d_rjobs,
                                                     c->interp == 2 ? e->nsjobs : 0, s->d_target, s->d_zero, tr->w, s->d_plane, s->d_tile, check, s->stream);
         else {
@@ -495,7 +505,23 @@ int les_hip_unary_one_scratch(les_hip_ctx* c, les_hip_scratch* s, int mode, cons
         }
     }
     else if (e->march) rc = launch_march(c, static_cast<const MarchEntry*>(e->march), mode, e->d_jobs, e->ngroups, s->d_plane, s->d_tile, check, s->stream);
-    else rc = launch_strips(c, mode, e->d_jobs, e->njobs, s->d_plane, s->d_tile, check, s->stream);
+    else {
+        rc = launch_strips(c, mode, e->d_jobs, e->njobs, s->d_plane, s->d_tile, check, s->stream);
+        if (!rc && c->naive) {
+            // image-based context: a call with v != 0 is recomputed after the strip kernel (les_hip_vdisp.inc); the call table follows the rect
+            // pair, the stand-in volume (one slice) and the flag stay
+            if (!s->vd || memcmp(&s->vd_f, fr, sizeof *fr) || memcmp(&s->vd_t, tr, sizeof *tr)) {
+                VdispStrip* nv = nullptr;
+                HIPCHECK(hipStreamSynchronize(s->stream));
+                rc = vdisp_build(c, 1, fr, tr, &nv);
+                if (rc) return rc;
+                if (s->vd) for (int m = 0; m < 2; m++) { std::swap(nv->d_vol[m], s->vd->d_vol[m]); std::swap(nv->d_flags[m], s->vd->d_flags[m]); }
+                vdisp_free(s->vd);
+                s->vd = nv; s->vd_f = *fr; s->vd_t = *tr;
+            }
+            rc = launch_vdisp_strips(c, s->vd, mode, e->d_jobs, e->njobs, s->d_plane, s->d_tile, check, s->stream);
+        }
+    }
     if (rc) return rc;
     HIPCHECK(hipMemcpyAsync(s->h_tile, s->d_tile, need * sizeof(float), hipMemcpyDeviceToHost, s->stream));
     HIPCHECK(hipStreamSynchronize(s->stream));

@@ -117,7 +117,7 @@ int launch_bf(les_hip_ctx* c, int mode, const les::BfJob* d_jobs, int njobs, int
     if (rc) return rc;
     if (njobs <= 0) return LES_HIP_OK;
     if (c->naive)
-        hipLaunchKernelGGL(les::les_naive_raw_kernel, dim3(ncalls, chunks), dim3(256), 0, stream, c->geom, strip_view(c, mode), d_calls, d_planes, d_raw);
+        launch_naive_raw(c, mode, d_calls, ncalls, chunks, d_planes, d_raw, stream);          // (honours Plane::v: les_vdisp.h)
     else if (c->interp == 0)
         hipLaunchKernelGGL(les::les_interp_raw_kernel<0>, dim3(ncalls, chunks), dim3(256), 0, stream, c->geom, (const float*)c->v[mode].vol, d_calls, d_planes, d_raw,
                            (unsigned*)nullptr, 0.0f);

@@ -191,6 +191,22 @@ int les_hip_set_interpolation(les_hip_ctx* c, int none_lin_quad)
     return LES_HIP_OK;
 }
 
+int les_hip_set_max_vdisparity(les_hip_ctx* c, float max_vdisp)
+{
+    if (!c) return fail(LES_HIP_ERR_ARG, "null context");
+    if (!(max_vdisp >= 0.0f) || max_vdisp == INFINITY) return fail(LES_HIP_ERR_ARG, "MAX_VDISPARITY %g (a finite value >= 0)", (double)max_vdisp);
+    c->max_vdisp = max_vdisp;
+    return LES_HIP_OK;
+}
+
+int les_hip_set_random_vdisparity(les_hip_ctx* c, float max_vdisp)
+{
+    if (!c) return fail(LES_HIP_ERR_ARG, "null context");
+    if (!(max_vdisp >= 0.0f) || max_vdisp == INFINITY) return fail(LES_HIP_ERR_ARG, "maxVDisp %g (a finite value >= 0)", (double)max_vdisp);
+    c->random_vdisp = max_vdisp;
+    return LES_HIP_OK;
+}
+
 int les_hip_calib_copy(const float* d_src, float* d_dst, size_t n, int device, void* stream)
 {
     if (!d_src || !d_dst || n == 0) return fail(LES_HIP_ERR_ARG, "bad argument");

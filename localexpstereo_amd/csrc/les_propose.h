@@ -94,7 +94,7 @@ __global__ void les_expansion_kernel(const Rect4* __restrict__ units, const floa
 
 __global__ void les_random_kernel(const Rect4* __restrict__ units, const float4* __restrict__ labels, int W,
                                   uint64_t* __restrict__ rng, float4* __restrict__ planes, int n, int m,
-                                  float mind, float maxd)
+                                  float mind, float maxd, float maxv)
 {
     int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (i >= n) return;
@@ -110,6 +110,13 @@ __global__ void les_random_kernel(const Rect4* __restrict__ units, const float4*
     const float minz = fmaxf(mind, zs - dz);                          // :130
     const float maxz = fminf(maxd, zs + dz);                          // :131
     zs = r.uniform_float(minz, maxz);                                 // :132
+    float vs = in.w;                                                  // :134-141 (maxVDisp of RandomProposer's constructor, :100)
+    if (maxv != 0) {
+        const float dv = (float)((double)maxv * ldexp(1.0, -(m + 1)));   // MAX_VDISPARITY * pow(0.5f, m + 1): a double product
+        const float minv = fmaxf(-maxv, vs - dv);
+        const float maxv_ = fminf(maxv, vs + dv);
+        vs = r.uniform_float(minv, maxv_);
+    }
     const float nr = (float)ldexp(1.0, -m);                           // :142 randomNmax * pow(0.5f, m)
     float n0[3];
     plane_normal(in, n0);
@@ -120,13 +127,13 @@ __global__ void les_random_kernel(const Rect4* __restrict__ units, const float4*
     const double dd = (double)nv[0] * nv[0] + (double)nv[1] * nv[1] + (double)nv[2] * nv[2];
     const double inv = 1. / sqrt(dd);                                 // :145
     for (int c = 0; c < 3; c++) nv[c] = (float)(nv[c] * inv);
-    planes[i] = plane_create(nv[0], nv[1], nv[2], zs, (float)sx, (float)sy, in.w);   // :147
+    planes[i] = plane_create(nv[0], nv[1], nv[2], zs, (float)sx, (float)sy, vs);     // :147
     rng[i] = r.state;
 }
 
 // createRandomLabel + fill of the unit region (LES/FastGCStereo.h:105-109, LES/StereoEnergy.h:120-129)
 __global__ void les_init_labels_kernel(const Rect4* __restrict__ units, float4* __restrict__ labels, int W,
-                                       uint64_t* __restrict__ rng, float4* __restrict__ planes, float mind, float maxd)
+                                       uint64_t* __restrict__ rng, float4* __restrict__ planes, float mind, float maxd, float maxv)
 {
     const double PI = 3.1415926535897932384626433832795;
     const int i = (int)blockIdx.x;
@@ -137,9 +144,10 @@ __global__ void les_init_labels_kernel(const Rect4* __restrict__ units, float4* 
         int k = r.uniform_int(0, u.h * u.w);                          // selectRandomPixelInRect, LES/FastGCStereo.h:231-238
         int sx = u.x + k % u.w, sy = u.y + k / u.w;
         float zs = r.uniform_float(mind, maxd);                       // LES/StereoEnergy.h:122
+        const float vs = maxv != 0 ? r.uniform_float(-maxv, maxv) : 0.0f;   // :123, MAX_VDISPARITY of the energy
         double nn[3];
         random_unit_vector(r, PI / 3, nn);                            // :126
-        s_plane = plane_create((float)nn[0], (float)nn[1], (float)nn[2], zs, (float)sx, (float)sy, 0.0f);
+        s_plane = plane_create((float)nn[0], (float)nn[1], (float)nn[2], zs, (float)sx, (float)sy, vs);
         planes[i] = s_plane;
         rng[i] = r.state;
     }

@@ -54,8 +54,8 @@ protected:
     // image-based matching cost (HipNaiveStereoEnergy below)
     struct NaiveTag {};
     HipCostVolumeEnergy(NaiveTag, const uint8_t* imL, const uint8_t* imR, int width, int height, Parameters p, float MAX_DISPARITY,
-                        float MIN_DISPARITY, int device)
-        : StereoEnergy(width, height, std::move(p), MAX_DISPARITY, MIN_DISPARITY), ctx_(nullptr)
+                        float MIN_DISPARITY, float MAX_VDISPARITY, int device)
+        : StereoEnergy(width, height, std::move(p), MAX_DISPARITY, MIN_DISPARITY, MAX_VDISPARITY), ctx_(nullptr)
     {
         const int filter = filter_kind(params.filterName);
         les_hip_params hp;
@@ -65,6 +65,11 @@ protected:
         hp.device = device; hp.volumes_on_device = 0;
         if (les_hip_create_naive_filtered(&ctx_, &hp, filter, imL, imR, params.alpha, params.th_grad) != LES_HIP_OK)
             throw std::runtime_error(std::string("les_hip_create_naive_filtered: ") + les_hip_last_error());
+        if (les_hip_set_max_vdisparity(ctx_, MAX_VDISPARITY) != LES_HIP_OK) {
+            const std::string e = les_hip_last_error();
+            les_hip_destroy(ctx_);
+            throw std::invalid_argument("les_hip_set_max_vdisparity: " + e);
+        }
         setImages(imL, imR);
     }
 
@@ -129,9 +134,11 @@ private:
 // (LES/PMStereoBase.h:37, parameters LES/main.cpp:86-121): same operator, raw cost from the two images.
 class HipNaiveStereoEnergy : public HipCostVolumeEnergy {
 public:
+    // MAX_VDISPARITY: the range of Plane::v of the initial labels (NaiveStereoEnergy's MAX_VDISPARITY, LES/StereoEnergy.h:120-129); the
+    // cost samples row y + v for every plane (csrc/les_vdisp.h)
     HipNaiveStereoEnergy(const uint8_t* imL, const uint8_t* imR, int width, int height, Parameters p, float MAX_DISPARITY,
-                         float MIN_DISPARITY = 0, int device = 0)
-        : HipCostVolumeEnergy(NaiveTag{}, imL, imR, width, height, std::move(p), MAX_DISPARITY, MIN_DISPARITY, device) {}
+                         float MIN_DISPARITY = 0, int device = 0, float MAX_VDISPARITY = 0)
+        : HipCostVolumeEnergy(NaiveTag{}, imL, imR, width, height, std::move(p), MAX_DISPARITY, MIN_DISPARITY, MAX_VDISPARITY, device) {}
 
     // NaiveStereoEnergy has no volume and no interpolation setting
     void setInterpolationMethod(int) override

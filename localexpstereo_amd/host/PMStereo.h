@@ -33,8 +33,10 @@ struct ProposerSpec { int kind; int K; };   // kind: LES_HIP_PROPOSE_EXPANSION /
 
 class PMStereo {
 public:
-    PMStereo(int width, int height, Parameters params, float maxDisparity, float minDisparity = 0)
-        : width(width), height(height), params(params), MAX_DISPARITY(maxDisparity), MIN_DISPARITY(minDisparity),
+    // maxVDisparity: maxVDisp of the RANDOM proposals (RandomProposer(K, maxDisp, minDisp, maxVDisp), LES/Proposer.h:100); the range of
+    // the initial labels is the energy's MAX_VDISPARITY (createRandomLabel)
+    PMStereo(int width, int height, Parameters params, float maxDisparity, float minDisparity = 0, float maxVDisparity = 0)
+        : width(width), height(height), params(params), MAX_DISPARITY(maxDisparity), MIN_DISPARITY(minDisparity), MAX_VDISPARITY(maxVDisparity),
           layermng(width, height, params.windR)
     {
         for (int m = 0; m < 2; m++) {
@@ -178,6 +180,7 @@ public:
         const size_t P = (size_t)width * height;
         bool ok = true;
         auto chk = [&](int rc) { if (rc != LES_HIP_OK) { if (ok) fprintf(stderr, "PMStereo::runDevice: %s\n", les_hip_last_error()); ok = false; } };
+        chk(les_hip_set_random_vdisparity(ctx, MAX_VDISPARITY));        // the RANDOM proposals' maxVDisp, as makeHostProposer's
         // prepared geometry: one batch per (layer, disjoint set) + the init batch (unit +- windR -> unit)
         // Several ranks (one process per GPU): the cells of every disjoint set are dealt out in contiguous bands, rank r owns
         // cells [n r / world, n (r + 1) / world) of the set; volume, statistics and maps are replicated, and after a set's lock-steps the tiles
@@ -494,14 +497,14 @@ private:
     IProposer* makeHostProposer(const ProposerSpec& s) const
     {
         if (s.kind == LES_HIP_PROPOSE_EXPANSION) return new ExpansionProposer(s.K);
-        if (s.kind == LES_HIP_PROPOSE_RANDOM) return new RandomProposer(s.K, MAX_DISPARITY, MIN_DISPARITY);
+        if (s.kind == LES_HIP_PROPOSE_RANDOM) return new RandomProposer(s.K, MAX_DISPARITY, MIN_DISPARITY, MAX_VDISPARITY);
         if (s.kind == LES_HIP_PROPOSE_RANSAC) return new RansacProposer(s.K);                        // MAX_SAM 500, conf 0.95, LES/Proposer.h:265
         throw std::runtime_error("PMStereo: unknown proposer kind in the layer table");
     }
 
     const int width, height;
     const Parameters params;
-    const float MAX_DISPARITY, MIN_DISPARITY;
+    const float MAX_DISPARITY, MIN_DISPARITY, MAX_VDISPARITY;
     LayerManager layermng;
     std::vector<std::vector<ProposerSpec>> layerProposers;
     std::vector<std::vector<uint64_t>> rngStates;

@@ -55,8 +55,9 @@ public:
 
 class RandomProposer : public ExpansionProposer {                                     // LES/Proposer.h:84-153
 public:
-    RandomProposer(int K, float maxDisp, float minDisp = 0) : ExpansionProposer(K), MIN_DISPARITY(minDisp), MAX_DISPARITY(maxDisp) {}
-    IProposer* createInstance() override { return new RandomProposer(K, MAX_DISPARITY, MIN_DISPARITY); }
+    RandomProposer(int K, float maxDisp, float minDisp = 0, float maxVDisp = 0)
+        : ExpansionProposer(K), MIN_DISPARITY(minDisp), MAX_DISPARITY(maxDisp), MAX_VDISPARITY(maxVDisp) {}
+    IProposer* createInstance() override { return new RandomProposer(K, MAX_DISPARITY, MIN_DISPARITY, MAX_VDISPARITY); }
     Plane getNextProposal() override
     {
         const double PI = 3.1415926535897932384626433832795;
@@ -68,6 +69,12 @@ public:
         const float dz = width(m);
         const float minz = std::max(MIN_DISPARITY, zs - dz), maxz = std::min(MAX_DISPARITY, zs + dz);
         zs = rng->uniform(minz, maxz);
+        float vs = in.v;                                                              // :134-141
+        if (MAX_VDISPARITY != 0) {
+            const float dv = (float)((double)MAX_VDISPARITY * std::ldexp(1.0, -(m + 1)));   // MAX_VDISPARITY * pow(0.5f, m + 1) in double
+            const float minv = std::max(-MAX_VDISPARITY, vs - dv), maxv = std::min(+MAX_VDISPARITY, vs + dv);
+            vs = rng->uniform(minv, maxv);
+        }
         const float nr = (float)std::ldexp(1.0, -m);                                  // randomNmax (=1) * 0.5^m
         float n0[3];
         in.GetNormal(n0);
@@ -77,12 +84,12 @@ public:
         for (int c = 0; c < 3; c++) nv[c] = n0[c] + (float)u[c] * nr;
         const double inv = 1. / std::sqrt((double)nv[0] * nv[0] + (double)nv[1] * nv[1] + (double)nv[2] * nv[2]);
         for (int c = 0; c < 3; c++) nv[c] = (float)(nv[c] * inv);
-        return Plane::CreatePlane(nv[0], nv[1], nv[2], zs, float(s.x), float(s.y), in.v);
+        return Plane::CreatePlane(nv[0], nv[1], nv[2], zs, float(s.x), float(s.y), vs);
     }
     bool isContinued() override { return iter < K && !(width(outerIter + iter) < 0.1); }   // early stop, :149-152
 
 private:
-    const float MIN_DISPARITY, MAX_DISPARITY;
+    const float MIN_DISPARITY, MAX_DISPARITY, MAX_VDISPARITY;
     float width(int m) const { return (float)((double)(MAX_DISPARITY - MIN_DISPARITY) * std::ldexp(1.0, -(m + 1))); }
 };
 

@@ -29,8 +29,9 @@ public:
 
     Parameters params;
 
-    StereoEnergy(int width, int height, Parameters p, float MAX_DISPARITY, float MIN_DISPARITY = 0)
-        : params(std::move(p)), width(width), height(height), MAX_DISPARITY(MAX_DISPARITY), MIN_DISPARITY(MIN_DISPARITY) {}
+    StereoEnergy(int width, int height, Parameters p, float MAX_DISPARITY, float MIN_DISPARITY = 0, float MAX_VDISPARITY = 0)
+        : params(std::move(p)), width(width), height(height), MAX_DISPARITY(MAX_DISPARITY), MIN_DISPARITY(MIN_DISPARITY),
+          MAX_VDISPARITY(MAX_VDISPARITY) {}
     virtual ~StereoEnergy() {}
 
     // ---- pairwise terms (host side of the graph cut) ------------------------------------------------------
@@ -148,14 +149,15 @@ public:
                 && ((d = ds - a5 - b5) >= MIN_DISPARITY) && d <= MAX_DISPARITY);
     }
 
-    // LES/StereoEnergy.h:120-129 with LES/Utilities.hpp:254-261 (MAX_VDISPARITY == 0)
+    // LES/StereoEnergy.h:120-129 with LES/Utilities.hpp:254-261: v is drawn after z, only when MAX_VDISPARITY != 0
     Plane createRandomLabel(Point s, RNG& rng) const
     {
         const double PI = 3.1415926535897932384626433832795;
         const float zs = rng.uniform(MIN_DISPARITY, MAX_DISPARITY);
+        const float vs = MAX_VDISPARITY != 0 ? rng.uniform(-MAX_VDISPARITY, MAX_VDISPARITY) : 0.0f;
         const double theta = rng.uniform(0.0, PI / 3), phi = rng.uniform(0.0, PI * 2.0);
         const double cosT = std::cos(theta), sinT = std::sin(theta), cosP = std::cos(phi), sinP = std::sin(phi);
-        return Plane::CreatePlane((float)(sinT * cosP), (float)(sinT * sinP), (float)cosT, zs, (float)s.x, (float)s.y, 0.0f);
+        return Plane::CreatePlane((float)(sinT * cosP), (float)(sinT * sinP), (float)cosT, zs, (float)s.x, (float)s.y, vs);
     }
 
     // StereoEnergy::computePatchWeight (LES/StereoEnergy.h:251-257): exp(-|I(s) - I(t)|_1 / omega) on the float BGR image
@@ -197,10 +199,12 @@ public:
     int getHeight() const { return height; }
     float maxDisparity() const { return MAX_DISPARITY; }
     float minDisparity() const { return MIN_DISPARITY; }
+    float maxVDisparity() const { return MAX_VDISPARITY; }
 
 protected:
     const int width, height;
     const float MAX_DISPARITY, MIN_DISPARITY;
+    const float MAX_VDISPARITY;                                // range of Plane::v drawn by createRandomLabel (0: none)
     std::vector<float> I[2];                                   // BGR as float, H x W x 3
     std::vector<float> smoothnessCoeff[2][8];                  // H x W each
 };

@@ -80,10 +80,13 @@ class _Shard:
 
 
 class PMRunner:
-    def __init__(self, energy, layer_units, proposer_table, seed=1, rank=0, world=1, device="cuda", mode=0, group=None):
+    def __init__(self, energy, layer_units, proposer_table, seed=1, rank=0, world=1, device="cuda", mode=0, group=None, random_vdisp=None):
         """rank / world: this process's place among the ranks that share THIS view's cells; group: their torch.distributed process group
-        (None = the default group).  Two-view runs on several ranks give each view its own group (stereo.FastGCStereo.run)."""
+        (None = the default group).  Two-view runs on several ranks give each view its own group (stereo.FastGCStereo.run).
+        random_vdisp: maxVDisp of the RANDOM proposals (RandomProposer(K, maxDisp, minDisp, maxVDisp)); None leaves the energy's setting."""
         self.e, self.rank, self.world, self.mode, self.group = energy, rank, world, mode, group
+        if random_vdisp is not None:
+            energy.set_random_vdisparity(random_vdisp)
         self.device = torch.device(device)
         if self.device.type == "cuda":
             # the torch ops of this class (exchange index_copy_, label / mask copies) run on torch's current stream: bind the

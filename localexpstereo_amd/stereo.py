@@ -20,8 +20,9 @@ PARAMS_BF = dict(PARAMS_GF, lambda_=20.0, windR=20, eps=10.0, filter="BF")
 
 
 class FastGCStereo:
-    def __init__(self, energy, imL, imR, params, device="cuda", rank=0, world=1, seed=1, host_threads=0, device_cuts=None):
+    def __init__(self, energy, imL, imR, params, device="cuda", rank=0, world=1, seed=1, host_threads=0, device_cuts=None, random_vdisp=None):
         self.e, self.imL, self.imR, self.p = energy, imL, imR, dict(PARAMS_GF, **params)
+        self.random_vdisp = random_vdisp          # maxVDisp of the RANDOM proposals (pm.PMRunner); None: the energy's setting (0 by default)
         # Parameters::filterName: the energy aggregates with the filter it was built with; a params dict that names another one is a mistake
         if "filter" in params and api.filter_kind(params["filter"]) != getattr(energy, "filter", api.FILTER_GF):
             raise ValueError(f"params name filter {params['filter']!r}, the energy was built with filter kind {energy.filter}")
@@ -120,7 +121,7 @@ class FastGCStereo:
             view_root = {all_views[0]: 0, all_views[1]: n0}
             viewModes = (all_views[mine],)
         runners = {m: pm.PMRunner(self.e, self.units, self.table, seed=self.seed + 7919 * m, rank=view_rank, world=view_world,
-                                  device=self.device, mode=m, group=view_group) for m in viewModes}
+                                  device=self.device, mode=m, group=view_group, random_vdisp=self.random_vdisp) for m in viewModes}
         g = gc.GraphCut(self.imL, self.imR, lambda_=self.p["lambda_"], th_smooth=self.p["th_smooth"], omega=self.p["omega"],
                         epsilon=self.p["epsilon"]) if maxIteration > 0 else None
         for m in viewModes:
@@ -249,6 +250,11 @@ def disparities(labeling):
     return labeling[..., 0] * xs + labeling[..., 1] * ys + labeling[..., 2]
 
 
+def vertical_disparities(labeling):
+    """The v map of a labeling (H x W x 4 planes a, b, c, v): the vertical offset each pixel's label samples the other view at."""
+    return np.asarray(labeling)[..., 3].copy()
+
+
 def _layers(st, sizes):
     e, r, p = api.PROPOSE_EXPANSION, api.PROPOSE_RANSAC, api.PROPOSE_RANDOM
     st.addLayer(sizes[0], [(e, 1), (r, 1), (p, 7)])                    # LES/main.cpp:300-306 / :391-397
@@ -256,18 +262,22 @@ def _layers(st, sizes):
     st.addLayer(sizes[2], [(e, 2), (r, 1)])
 
 
-def MidV2(data, iterations=5, pmIterations=2, doDual=False, smooth_weight=None, filterRadious=20, device="cuda", seed=1, lib=None, params=None, **kw):
+def MidV2(data, iterations=5, pmIterations=2, doDual=False, smooth_weight=None, filterRadious=20, device="cuda", seed=1, lib=None, params=None,
+          vdisp=0.0, random_vdisp=0.0, **kw):
     """MidV2 (LES/main.cpp:270-328) on a data dict of io.load_data: image-based matching cost, layers 5/15/25, error
     threshold 0.5, disparities quantised to the ground-truth precision before evaluation.  params: PARAMS_GF (the reference's choice,
     default) or PARAMS_BF (or a dict with their keys): filter, eps, alpha, th_col, th_grad; smooth_weight (default: params' lambda_)
-    and filterRadious override lambda_ and windR as the reference's options do (:284-286)."""
+    and filterRadious override lambda_ and windR as the reference's options do (:284-286).
+    vdisp: the vertical-disparity range of the energy (MAX_VDISPARITY, :281): initial labels draw v in [-vdisp, vdisp].  As in main.cpp
+    the random proposer keeps range 0 (RandomProposer(7, maxdisp)); random_vdisp (opt-in, not in main.cpp) gives it its own maxVDisp."""
     p = dict(PARAMS_GF if params is None else params)
     lam = p["lambda_"] if smooth_weight is None else smooth_weight
     maxdisp = float(data["ndisp"] - 1)
     e = api.HipCostVolumeEnergy.naive(data["imL"], data["imR"], windR=filterRadious, eps=p["eps"], alpha=p["alpha"],
                                       th_col=p["th_col"], th_grad=p["th_grad"], max_disp=maxdisp,
-                                      device=torch.device(device).index or 0, lib=lib, filter=p["filter"])
-    st = FastGCStereo(e, data["imL"], data["imR"], dict(p, lambda_=lam, windR=filterRadious), device=device, seed=seed, **kw)
+                                      device=torch.device(device).index or 0, lib=lib, filter=p["filter"], max_vdisp=vdisp)
+    st = FastGCStereo(e, data["imL"], data["imR"], dict(p, lambda_=lam, windR=filterRadious), device=device, seed=seed,
+                      random_vdisp=random_vdisp, **kw)
     st.setEvaluator(io.Evaluator(data["dispGT"], data["nonocc"], 0.5), precision=data.get("gt_prec", -1.0))
     _layers(st, (5, 15, 25))
     lab, raw = st.run(iterations, (0, 1) if doDual else (0,), pmIterations)
