@@ -101,7 +101,50 @@ struct ViewData {
 
 struct MtHost;
 namespace { void mt_host_free(MtHost* m); }
-namespace { struct VdispStrip; void vdisp_free(VdispStrip* v); }
+
+namespace {
+
+// Everything a fixed list of (filterRect, targetRect) calls needs for its unary costs, built once by build_unary_tables
+// (les_hip_unary.inc) and immutable afterwards: the tables of every kernel that may serve the calls, since run_unary picks one at
+// run time (the context's interpolation, the view's march_ok).  Two output layouts: map / slab (les_hip_batch_create's out_slabs) and
+// compact (one call, row stride = target width, origin = target corner: the per-call operator's tile).  One device allocation.
+struct VdispGroup { int c0, c1, slices; };
+struct UnaryTables {
+    int n = 0;
+    void* d_mem = nullptr;                       // every device table below
+    const les::Job* d_jobs = nullptr; int njobs = 0;                   // strip kernel (guided filter)
+    // march kernel: groups of NJ jobs cut for mentry; march_ok: every target keeps 2R distance from the filterRect borders that are
+    // not image borders, so the kernel's bound on |a| holds (les_march.h)
+    const les::Job* d_mjobs = nullptr; int nmgroups = 0;
+    const MarchEntry* mentry = nullptr;
+    bool march_ok = false;
+    // raw-cost patches, one per call of its filterRect's size (interpolation 0 / 2, the image-based march kernel, bilateral / unfiltered)
+    const les::RawCall* d_rawcalls = nullptr; const long long* d_raw_off = nullptr;
+    long long raw_floats = 0; int raw_chunks = 1;
+    // where each call's target rect is written (les_nan_spread_kernel): the rect, the float offset of its corner, the row stride
+    const les::WtaJob* d_targets = nullptr; const long long* d_out_off = nullptr; int out_stride = 0;
+    const les::BfJob* d_bfjobs = nullptr; int nbfjobs = 0, bf_np = 1;    // bilateral / unfiltered tiles (bf_np: most calls per tile)
+    // image-based guided filter on the strip kernel: the calls' slices of the Plane::v stand-in volume (les_hip_vdisp.inc)
+    std::vector<VdispGroup> vd_groups;           // calls [c0, c1) in one pass over `slices` slices
+    const les::RawCall* d_vd_calls = nullptr;    // per call: its filterRect at its slice (offset slice * H * W + y * W + x)
+    const float4* d_vd_stand_in = nullptr;       // per call: (0, 0, slice, 0)
+    int vd_max_slices = 0, vd_chunks = 1;
+};
+
+// The device buffers a run of some UnaryTables writes, grow-only: raw-cost patches, per-call flags and masked strip jobs (interpolation 2,
+// the Plane::v recompute), the Plane::v stand-in volume.  A batch's workspace is shared by the host threads that run its two views (one
+// slot per view, grown under the context's lock); a scratch's is private to its caller (slot 0 for both views, no lock).
+struct UnaryWorkspace {
+    bool shared = false;
+    struct Slot {
+        float* raw = nullptr; size_t raw_cap = 0;
+        unsigned* flags = nullptr; size_t flags_cap = 0;
+        les::Job* rjobs = nullptr; size_t rjobs_cap = 0;
+        float* vol = nullptr; size_t vol_cap = 0;
+    } slot[2];
+};
+
+}  // namespace
 
 struct les_hip_ctx {
     les_hip_params p;
@@ -130,7 +173,7 @@ struct les_hip_ctx {
     float4* d_wta_planes = nullptr; size_t wta_planes_cap = 0;
     // smoothness-coefficient table of the pairwise terms, cached per (omega, epsilon)
     float* d_pw_tab = nullptr; float pw_omega = -1.f, pw_epsilon = -1.f;
-    std::mutex mu;                       // guards the lazily built tables when two host threads (the two views) share the context
+    std::mutex mu;                       // guards lazily built state (batch workspaces, scratch lists) when two host threads (the two views) share the context
     unsigned long long gen = 0;          // unique id of this context: thread-local bindings compare it, not the address (an address can be reused)
     std::vector<les_hip_scratch*> idle_scratch;  // hidden scratches whose owning thread has exited, ready for the next new thread
     bool maxflow_lds_ready = false;      // the per-device dynamic-LDS opt-in of les_maxflow_kernel has been made on this context's device
@@ -139,34 +182,12 @@ struct les_hip_ctx {
     std::vector<MtHost*> mt_idle; // host-mapped flag words + hand-over staging of the tiled max-flow: one per CONCURRENT caller, reused, freed with the context
 };
 
+// A prepared batch: the unary-cost tables of its calls (map / slab layout) and their workspace, run by run_unary (les_hip_unary.inc); the
+// cell geometry of the proposers, the WTA and the cuts
 struct les_hip_batch {
-    int n = 0, njobs = 0, out_slabs = 0, R = 0;
-    les::Job* d_jobs = nullptr;
-    // the same calls cut for the march kernel (groups of NJ jobs); march_ok: every target keeps 2R distance from clip borders
-    // that are not image borders, so the kernel's bound on |a| holds (les_march.h)
-    les::Job* d_mjobs = nullptr;
-    const MarchEntry* mentry = nullptr;  // the geometry the table was cut for
-    int nmgroups = 0;
-    bool march_ok = false;
-    // image-based energy on the march kernel: the calls' filterRects with the offsets of their raw-cost patches, and one patch
-    // buffer per view (allocated on the view's first run; two host threads may drive the two views of one batch)
-    les::RawCall* d_rawcalls = nullptr;
-    long long* d_raw_off = nullptr;
-    long long raw_floats = 0;
-    int raw_chunks = 1;
-    mutable float* d_raw[2] = {nullptr, nullptr};
-    // cost-volume context at interpolation 0 / 2 on the march kernel: the same patch tables, built on the first such run (ensure_interp_tables),
-    // per view a flag per call and the masked strip jobs of the recompute launch (interpolation 2)
-    std::vector<les_hip_rect> filters;
-    mutable bool interp_tables = false;
-    mutable long long* d_out_off = nullptr;      // float offset of each call's target corner in the output (les_nan_spread_kernel)
-    mutable unsigned* d_flags[2] = {nullptr, nullptr};
-    mutable les::Job* d_rjobs[2] = {nullptr, nullptr};
-    // image-based context on the strip kernel: the recompute of its calls with v != 0 (les_hip_vdisp.inc), built on the first such run
-    mutable VdispStrip* vd = nullptr;
-    // bilateral / unfiltered context: tiles of calls that share their rects (les_hip_bilateral.inc); the raw-cost patches above serve it too
-    les::BfJob* d_bfjobs = nullptr;
-    int bf_np = 1;                       // most calls per tile (1: the one-plane instantiation of the kernel)
+    int n = 0, R = 0;
+    UnaryTables tab;
+    mutable UnaryWorkspace ws;           // shared: two host threads may run the two views of one batch
     std::vector<les_hip_rect> targets;
     int device = 0;
     // cell geometry for the proposers / WTA
@@ -194,33 +215,19 @@ struct les_hip_batch {
 };
 
 // Caller-owned scratch of the one-call operator (the reference's `Reusable`, LES/StereoEnergy.h:616-623): its own stream, a
-// compact device tile for the target rect, pinned host staging, and the job tables of the (filterRect, targetRect) pairs it has
-// seen -- a cell visit calls the operator ~10 times with the same rects (LES/FastGCStereo.h:40-49).  Distinct scratch objects
-// may be used concurrently from distinct host threads on one context; nothing is allocated once a rect pair is known.
+// compact device tile for the target rect, pinned host staging, one workspace, and the compact-layout tables of the 16 (filterRect,
+// targetRect) pairs it has used last -- a cell visit calls the operator ~10 times with the same rects (LES/FastGCStereo.h:40-49).
+// Distinct scratch objects may be used concurrently from distinct host threads on one context; nothing is allocated, and the context's
+// lock is not taken, once a rect pair is known and the workspace has grown to it.
 struct les_hip_scratch {
     les_hip_ctx* c = nullptr;
     hipStream_t stream = nullptr;
     float* d_tile = nullptr; float* h_tile = nullptr; size_t tile_cap = 0;        // floats
     float4* d_plane = nullptr; float4* h_plane = nullptr;
-    struct Entry { les_hip_rect f, t; int want_march; const void* march; int njobs, ngroups; les::Job* d_jobs; unsigned long long stamp;
-                   les::Job* d_sjobs = nullptr; int nsjobs = 0; };     // (interpolation 2 on the march kernel: the strip jobs of the recompute launch)
-    // interpolation 2 on the march kernel: the call's flag and the masked strip jobs
-    unsigned* d_flag = nullptr;
-    // interpolation 0 / 2: the call's target rect and output offset (0: the compact tile) for les_nan_spread_kernel
-    les::WtaJob* d_target = nullptr; long long* d_zero = nullptr;
-    les::Job* d_rjobs = nullptr; size_t rjobs_cap = 0;
-    // image-based energy on the march kernel: raw-cost patch of the call's filterRect and its one-entry call table
-    float* d_raw = nullptr; size_t raw_cap = 0;
-    les::RawCall* d_rawcall = nullptr; long long* d_raw_off = nullptr;
-    les_hip_rect raw_f = {-1, -1, -1, -1};
-    // image-based energy on the strip kernel: the recompute of a call with v != 0 (les_hip_vdisp.inc) for the filterRect vd_f
-    VdispStrip* vd = nullptr;
-    les_hip_rect vd_f = {-1, -1, -1, -1}, vd_t = {-1, -1, -1, -1};
-    // bilateral / unfiltered context: the tiles of the last rect pair
-    les::BfJob* d_bfjobs = nullptr; size_t bf_cap = 0; int bf_njobs = 0;
-    les_hip_rect bf_f = {-1, -1, -1, -1}, bf_t = {-1, -1, -1, -1};
+    struct Entry { les_hip_rect f, t; UnaryTables tab; unsigned long long stamp; };
     std::vector<Entry> cache;
     unsigned long long clock = 0;
+    UnaryWorkspace ws;
 };
 
 namespace {
@@ -253,6 +260,7 @@ float naive_alpha(const les_hip_ctx* c) { return c->naive_alpha; }
 
 #include "les_hip_vdisp.inc"             // the image-based cost with vertical disparity (Plane::v): pre-pass and strip-path recompute launches
 #include "les_hip_bilateral.inc"         // the bilateral / unfiltered aggregation: per-view set-up, weight table, tiles, launches
+#include "les_hip_unary.inc"             // the unary-cost tables of a list of calls, their workspace, and the one router of batches and single calls
 
 }  // namespace
 

@@ -470,3 +470,109 @@ def case_naive_refuses(lib):
             assert e.L.les_hip_set_interpolation(e.h, m) == 1
     finally:
         e.close()
+
+
+# ------------------------------------------------------------------------------------------------ one call, three entry points
+# The per-call operator (les_hip_unary_one_scratch, les_hip_unary_one) and a one-call prepared batch (les_hip_batch_run) route the same
+# call through the same kernels: their target rects agree bit for bit, NaN sets included.
+PATH_CONTEXTS = [f"gf{windR}_interp{i}" for windR in (20, 30) for i in (0, 1, 2)] + [f"gf_nan_interp{i}" for i in (0, 1, 2)] + \
+                ["naive_gf20", "naive_gf30"] + [f"{f}_interp{i}" for f in ("bf", "none") for i in (0, 1, 2)] + ["naive_bf", "naive_none"]
+
+
+def path_context(lib, name):
+    """(energy, calls) of one context kind of PATH_CONTEXTS; calls: (filterRect, targetRect, plane), each run in both views."""
+    from tests import vdisp_cases as vc
+    imL, imR = load_cones_crop()
+    H, W = imL.shape[:2]
+    D = 16
+    if name.startswith("naive"):
+        filt, windR = {"naive_gf20": ("GF", 20), "naive_gf30": ("GF", 30), "naive_bf": ("BF", 5), "naive_none": ("", 0)}[name]
+        e = api.HipCostVolumeEnergy.naive(imL, imR, windR=windR, eps=10.0 if filt == "BF" else 1e-4, max_disp=31.0, lib=lib, filter=filt)
+        return e, [(fr, tr, pl) for _, fr, tr, pl in vc.mixed_calls(H, W)]
+    interp = int(name[-1])
+    if name.startswith("gf_nan"):
+        # an interior NaN in view 0 only: view 0 runs the strip kernel (+ the NaN spread at 0 / 2), view 1 the march kernel
+        e = api.HipCostVolumeEnergy(imL, imR, interior_nan_volume(H, W, D), synth.make_volume(D, H, W, 43), windR=20, max_disp=D - 1.0, lib=lib,
+                                    interpolate=interp)
+        pl = (0.0, 0.0, 3.0, 0.0)
+        return e, [((0, 0, W, H), (0, 0, W, H), pl), ((19, 22, 82, 74), (39, 42, 42, 34), pl), ((5, 4, 55, 50), (15, 14, 35, 30), pl)]
+    filt, windR = {"gf20": ("GF", 20), "gf30": ("GF", 30), "bf": ("BF", 5), "none": ("", 0)}[name.split("_")[0]]
+    e = api.HipCostVolumeEnergy(imL, imR, synth.make_volume(D, H, W, 42), synth.make_volume(D, H, W, 43), windR=windR,
+                                eps=10.0 if filt == "BF" else 1e-4, max_disp=D - 1.0, lib=lib, filter=filt, interpolate=interp)
+    calls = [(fr, tr, pl) for _, fr, tr, pl in gf_single_calls(H, W, D)]
+    calls += [((19, 22, 82, 74), (39, 42, 42, 34), (0.0, 0.0, 0.0, 0.0)), ((19, 22, 82, 74), (39, 42, 42, 34), (0.01, 0.0, float(D - 1), 0.0))]
+    return e, calls
+
+
+def one_call_three_ways(e, sc, fr, tr, pl, mode, check):
+    """The target rect of one call through les_hip_unary_one_scratch, les_hip_unary_one and a one-call prepared batch; asserts that
+    the three agree bit for bit and returns the first."""
+    H, W = e.H, e.W
+    x, y, w, h = tr
+    sub = (slice(y, y + h), slice(x, x + w))
+    outs = [e.ComputeUnaryPotentialScratch(sc, fr, tr, np.full((H, W), FILL, F32), pl, mode=mode, check=check)[sub],
+            e.ComputeUnaryPotential(fr, tr, np.full((H, W), FILL, F32), pl, mode=mode, check=check)[sub]]
+    b = api.Batch(e, [fr], [tr])
+    buf = api.DeviceBuffer(e, H * W * 4)
+    try:
+        buf.fill(0xFF)
+        b.run([pl], buf.ptr, mode=mode, check=check)
+        e.synchronize()
+        outs.append(buf.download((H, W), F32)[sub])
+    finally:
+        buf.free()
+        b.destroy()
+    for name, o in zip(("les_hip_unary_one", "one-call batch"), outs[1:]):
+        assert same_bits(outs[0], o), f"les_hip_unary_one_scratch and {name} differ: {fr} {tr} {pl} mode {mode} check {check}"
+    return outs[0]
+
+
+def case_one_call_paths_agree(lib, name):
+    """Every call of the context kind `name`, both views, check 0 / 1, through one scratch (its cached rect pairs are revisited with
+    the other view and the other check)."""
+    e, calls = path_context(lib, name)
+    sc = e.scratch()
+    try:
+        for check in (True, False):
+            for fr, tr, pl in calls:
+                for mode in (0, 1):
+                    one_call_three_ways(e, sc, fr, tr, pl, mode, check)
+    finally:
+        e.scratch_free(sc)
+        e.close()
+
+
+def case_scratch_cache(lib):
+    """One scratch through more than 16 rect pairs and back to the first (eviction); a cached pair after a change of interpolation; a
+    bilateral scratch alternating between two rect pairs."""
+    imL, imR = load_cones_crop()
+    H, W = imL.shape[:2]
+    D = 16
+    pl = (0.02, -0.01, 6.5, 0.0)
+    e = api.HipCostVolumeEnergy(imL, imR, synth.make_volume(D, H, W, 42), synth.make_volume(D, H, W, 43), windR=20, max_disp=D - 1.0, lib=lib)
+    sc = e.scratch()
+    try:
+        pairs = [((x, y, 44, 44), (x + 2 * (k % 3), y + 3, 20, 18)) for k, (y, x) in enumerate((y, x) for y in (0, 20, 40) for x in (0, 12, 24, 36, 48, 60))]
+        assert len(set(pairs)) > 16
+        first = [one_call_three_ways(e, sc, fr, tr, pl, 0, True) for fr, tr in pairs]
+        again = one_call_three_ways(e, sc, pairs[0][0], pairs[0][1], pl, 0, True)
+        assert same_bits(first[0], again), "the first rect pair gives other bits after its eviction"
+        fr, tr = (19, 22, 82, 74), (39, 42, 42, 34)
+        outs = []
+        for interp in (1, 0, 2, 1):
+            e.setInterpolationMethod(interp)
+            outs.append(one_call_three_ways(e, sc, fr, tr, pl, 1, True))
+        assert same_bits(outs[0], outs[3]) and not same_bits(outs[0], outs[1]), "the cached pair does not follow the interpolation"
+    finally:
+        e.scratch_free(sc)
+        e.close()
+    e = api.HipCostVolumeEnergy(imL, imR, synth.make_volume(D, H, W, 42), synth.make_volume(D, H, W, 43), windR=5, eps=10.0, max_disp=D - 1.0,
+                                lib=lib, filter="BF")
+    sc = e.scratch()
+    try:
+        pairs = [((0, 0, 60, 50), (10, 10, 30, 25)), ((40, 30, 70, 60), (50, 45, 40, 30))]
+        outs = [one_call_three_ways(e, sc, fr, tr, pl, k % 2, True) for k in range(3) for fr, tr in pairs]
+        assert same_bits(outs[0], outs[4]) and same_bits(outs[1], outs[5]), "a bilateral rect pair gives other bits on its second visit"
+    finally:
+        e.scratch_free(sc)
+        e.close()

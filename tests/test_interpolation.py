@@ -1,6 +1,7 @@
 """setInterpolationMethod (les_hip_set_interpolation): nearest-slice (0) and quadratic (2) raw costs on every device path, against the
-numpy restatement of LES/CostVolumeEnergy.h:99-167 fed through the oracle's guided filter or the bilateral restatement.  CPU simulator
-build (-m "not gpu") and MI355X (-m gpu).  Cases: tests/interp_cases.py."""
+numpy restatement of LES/CostVolumeEnergy.h:99-167 fed through the oracle's guided filter or the bilateral restatement; the per-call
+operator against a one-call batch, bit for bit, for every filter, energy and interpolation.  CPU simulator build (-m "not gpu") and
+MI355X (-m gpu).  Cases: tests/interp_cases.py."""
 import os
 import subprocess
 
@@ -83,6 +84,15 @@ def test_sim_mode_switching(sim_lib, oracle_mod):
     ic.case_naive_refuses(sim_lib)
 
 
+@pytest.mark.parametrize("name", ic.PATH_CONTEXTS)
+def test_sim_one_call_paths_agree(sim_lib, name):
+    ic.case_one_call_paths_agree(sim_lib, name)
+
+
+def test_sim_scratch_cache(sim_lib):
+    ic.case_scratch_cache(sim_lib)
+
+
 # ---------------------------------------------------------------- MI355X
 @pytest.mark.gpu
 @pytest.mark.parametrize("interp", [0, 2])
@@ -149,6 +159,13 @@ def test_gpu_mode_switching_and_refresh(oracle_mod):
         pr.close()
     ic.case_naive_refuses(None)
     ic.case_refresh_keeps_setting(None, "cuda")
+
+
+@pytest.mark.gpu
+def test_gpu_one_call_paths_agree():
+    for name in ic.PATH_CONTEXTS:
+        ic.case_one_call_paths_agree(None, name)
+    ic.case_scratch_cache(None)
 
 
 @pytest.mark.gpu
