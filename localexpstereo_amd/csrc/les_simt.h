@@ -50,11 +50,13 @@ __device__ inline T wave_sum_tree(T v)
 struct alignas(16) int4 { int x, y, z, w; };
 #define LES_MARCH_SCHED_FENCE() ((void)0)
 __device__ inline int readfirstlane_i32(int v) { return v; }
-// floor(x + 0.5), saturating (v_cvt_rpi_i32_f32)
+// floor(x + 0.5), saturating (v_cvt_rpi_i32_f32): exact round-half-up.  floorf(x + 0.5f) would round the sum to float first -- an odd
+// integer in [2^23, 2^24) plus 0.5 ties to the even integer above it -- and differ from the instruction by one there; x - floor(x) is exact.
 __device__ inline int cvt_rpi_i32(float x)
 {
     if (!(x == x)) return 0;
-    const float f = floorf(x + 0.5f);
+    float f = floorf(x);
+    if (x - f >= 0.5f) f += 1.0f;
     if (f >= 2147483648.0f) return 2147483647;
     if (f <= -2147483648.0f) return (int)0x80000000;
     return (int)f;
@@ -193,7 +195,8 @@ __device__ __forceinline__ int readfirstlane_i32(int v) { return __builtin_amdgc
 __device__ __forceinline__ int cvt_rpi_i32(float x)
 {
     if (!(x == x)) return 0;
-    const float f = floorf(x + 0.5f);
+    float f = floorf(x);                  // (exact round-half-up, as the simulator's definition above)
+    if (x - f >= 0.5f) f += 1.0f;
     if (f >= 2147483648.0f) return 2147483647;
     if (f <= -2147483648.0f) return (int)0x80000000;
     return (int)f;

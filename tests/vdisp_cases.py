@@ -178,11 +178,11 @@ def case_v0_is_the_oracle():
 
 # ------------------------------------------------------------------------------------------------ device
 class VPair:
-    """An image-based library context of filter `filter` plus the oracle (guided filter, validity) over the cones crop.  Duck-types
-    interp_cases.InterpPair so that its call / batch runners and comparison apply."""
+    """An image-based library context of filter `filter` plus the oracle (guided filter, validity) over the cones crop (or the pair
+    `ims`).  Duck-types interp_cases.InterpPair so that its call / batch runners and comparison apply."""
 
-    def __init__(self, lib, filter="GF", windR=20, sig2=10.0, max_disp=31.0):
-        self.imL, self.imR = load_cones_crop()
+    def __init__(self, lib, filter="GF", windR=20, sig2=10.0, max_disp=31.0, ims=None):
+        self.imL, self.imR = load_cones_crop() if ims is None else ims
         self.H, self.W = self.imL.shape[:2]
         self.D = int(max_disp) + 1
         self.filter = filter

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Randomised parity sweep: random image sizes, radii, (filterRect, targetRect) pairs and planes through the C ABI
-(`les_hip_unary_batch`, check on/off, both views) against the oracle.  Also random label maps through the device
-post-processing and the expansion-graph construction.  Exits non-zero on the first mismatch.
+(`les_hip_unary_batch`, check on/off, both views) against the oracle, and the same calls at a drawn interpolation 0 / 2 against
+tests/interp_cases.py's restatement.  Also random label maps through the device post-processing and the expansion-graph
+construction.  Exits non-zero on the first mismatch.
 
   python tools/fuzz_parity.py [--seconds 120] [--seed 0] [--lib PATH]     (default library: the HIP build)
 """
@@ -16,6 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from localexpstereo_amd import api, synth          # noqa: E402
 from oracle import oracle as om                     # noqa: E402
+from tests import interp_cases as ic                # noqa: E402
 from tests import parity_cases as pc                # noqa: E402
 
 RADII = [1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 15]
@@ -25,7 +27,7 @@ def one_case(rng, lib, stats):
     # half of the configurations are shaped for the fixed-point march kernel (radius 10, targets at least windR away from
     # filterRect borders that are not image borders -- LayerManager-like cells -- or whole-image slabs), the others roam freely
     march_shaped = rng.random() < 0.5
-    R = int(rng.choice([10, 10, 10, 10, 7, 4, 5, 6, 8, 9])) if march_shaped else int(rng.choice(RADII))      # radii with a march-kernel instantiation
+    R = int(rng.choice([10, 10, 10, 10, 7, 2, 3, 4, 5, 6, 8, 9])) if march_shaped else int(rng.choice(RADII))      # radii with a march-kernel instantiation
     windR = 2 * R + int(rng.integers(0, 2))                       # windR / 2 == R
     H, W = (int(rng.integers(30, 260)), int(rng.integers(30, 520))) if march_shaped else (int(rng.integers(8, 150)), int(rng.integers(8, 200)))
     D = int(rng.integers(2, 24))
@@ -91,6 +93,28 @@ def one_case(rng, lib, stats):
                     raise AssertionError(f"max err {err.max():.3e} (R={R} {W}x{H}x{D} eps={eps} th={th} mode={mode} check={check})")
                 stats["max_err"] = max(stats["max_err"], float(err.max() / max(1.0, th)))
     stats["calls"] += 4 * k
+    # the same calls at interpolation 0 / 2 (setInterpolationMethod) against tests/interp_cases.py's restatement (NaN is a legitimate output there)
+    interp = int(rng.choice([0, 1, 2]))
+    if interp != 1:
+        ip = ic.InterpPair(lib, imL, imR, volL, volR, interp, windR=windR, eps=eps, th_col=th, min_disp=mind)
+        try:
+            for mode in (0, 1):
+                for check in (True, False):
+                    got = ic.run_batch(ip, frs, trs, planes, mode, check)[0]
+                    ref, _, written = ic.expected_batch(ip, frs, trs, planes, mode, check)
+                    g, r = got[written[0]], ref[0][written[0]]
+                    assert np.array_equal(np.isnan(g), np.isnan(r)), f"NaN set at interpolation {interp}"
+                    m = ~np.isnan(r)
+                    assert np.array_equal(g[m] == np.float32(1e6), r[m] == np.float32(1e6)), f"sentinels at interpolation {interp}"
+                    v = m & (r != np.float32(1e6))
+                    if v.any():
+                        err = np.abs(g[v].astype(np.float64) - r[v])
+                        if not np.all(err <= 1e-4 * np.abs(r[v]) + 2e-6 * max(1.0, th)):
+                            raise AssertionError(f"interpolation {interp}: max err {err.max():.3e} (R={R} {W}x{H}x{D} eps={eps} th={th} mode={mode} check={check})")
+                        stats["max_err"] = max(stats["max_err"], float(err.max() / max(1.0, th)))
+        finally:
+            ip.close()
+        stats["interp_calls"] = stats.get("interp_calls", 0) + 4 * k
     # post-processing on random piecewise label maps (both views): labels must come out bit-identical
     if rng.random() < 0.35 and windR <= 31:
         def labels():
@@ -226,7 +250,7 @@ def main():
             print("FAILED case", cases, "rng state:", state["state"])
             raise
         cases += 1
-    print(f"fuzz OK: {cases} configurations, {stats['calls']} operator calls, {stats['post']} post-processing runs, "
+    print(f"fuzz OK: {cases} configurations, {stats['calls']} operator calls ({stats.get('interp_calls', 0)} more at interpolation 0 / 2), {stats['post']} post-processing runs, "
           f"{stats.get('graphs', 0)} expansion-graph lock-steps ({stats.get('cuts', 0)} of them also cut on the device, {stats.get('cuts_cell_kernel', 0)} by les_maxflow_cell.h and the rest by les_maxflow.h: {stats.get('cut_diff', 0)} of {stats.get('cut_nodes', 0)} nodes differ from the host cut; {stats.get('tiled_cuts', 0)} cut by the tiled solver, {stats.get('tiled_multi', 0)} of them with cells of several tiles: {stats.get('tiled_diff', 0)} of {stats.get('tiled_nodes', 0)} nodes differ), {stats.get('naive', 0)} image-based energies ({stats.get('naive_march', 0)} of them on the march kernel), {stats.get('march', 0)} configurations on the march kernel, "
           f"max abs err / max(1, th_col) = {stats['max_err']:.2e}, {time.time() - t0:.0f} s")
 
