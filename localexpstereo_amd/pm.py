@@ -11,10 +11,15 @@ volume, the guide statistics and the label/cost maps are replicated; nothing is 
 torch is plumbing here: device buffers and torch.distributed (backend "nccl" == RCCL on ROCm, "gloo" for
 the CPU tests that run against the simulator build of the same C ABI).
 """
+import os
+import time
+from collections import Counter
+from types import SimpleNamespace
+
 import numpy as np
 import torch
 
-from . import api
+from . import api, gc as lgc
 
 
 def layer_geometry(W, H, windR, unit):
@@ -74,7 +79,8 @@ class _Shard:
         self.planes = torch.zeros((max(1, self.n), 4), dtype=torch.float32, device=dev)
         self.graph_off = self.batch.graph_offsets()
         self.graph_nodes = self.batch.graph_nodes()
-        self.payload = None                      # device / pinned host buffers of the graph capacities, allocated on first use
+        self.max_cell_nodes = self.batch.max_cell_nodes
+        self.payload = self.payload_host = self.masks = self.masks_host = None      # views of the runner's staging buffers, cut on first use (_gc_buffers)
         # the plan of the set's tile exchange (C ABI: les_hip_exchange_*): every rank's target rects, this rank's slot layout
         self.xchg = api.Exchange(e, rank, [tgt[cells[bounds[r]:bounds[r + 1]]] for r in range(world)]) if world > 1 else None
 
@@ -99,7 +105,7 @@ class PMRunner:
         self.labels = torch.zeros((self.H, self.W, 4), dtype=torch.float32, device=self.device)
         self.cur = torch.zeros((self.H, self.W), dtype=torch.float32, device=self.device)
         self.prop = torch.zeros((self.H, self.W), dtype=torch.float32, device=self.device)
-        self.shards = []
+        self.shards, self.init = [], None
         for li, unit in enumerate(layer_units):
             units, shared, filt, sets = layer_geometry(self.W, self.H, windR, unit)
             seeds = seeds_for(len(units), seed + 1000 * li)
@@ -109,9 +115,23 @@ class PMRunner:
                 x1 = np.minimum(units["x"] + units["w"] + windR, self.W); y1 = np.minimum(units["y"] + units["h"] + windR, self.H)
                 fr = np.stack([x0, y0, x1 - x0, y1 - y0], 1).astype(np.int32).view(api.RECT_DT).reshape(-1)
                 self.init = _Shard(self, units, shared, fr, np.arange(len(units)), seeds_for(len(units), seed + 777), target_is_unit=True)
+        self.sets = [(li, sh) for li, layer in enumerate(self.shards) for sh in layer]      # every (layer, shard of a disjoint set), in the order they are visited
         self.bytes_exchanged = 0
         self.exchanges = 0                       # all-gathers issued
         self._xevents = []
+        self._xbuf = None                        # send / receive slots of the tile exchange: single-rank runs never exchange
+        # the two switches a caller may set between construction and begin_gc
+        self.device_cuts = None                  # None | True | False | "all" | "fine" | "none": see begin_gc, which replaces it by one of the three names
+        self.speculative_sets_on_cpu = False     # tests: take _gc_set_without_round_trips on the simulator too
+        # graph-cut state: set by begin_gc; the buffers are sized from all shards and allocated by the first lock-step that needs them
+        # (runs without graph-cut iterations, or with every cut on the device, never do)
+        self.gc, self.device_graph, self._gc_mode, self._prop_host, self._env = None, True, self.mode, None, None
+        self.gc_max_gap, self.gc_seconds, self.tiled_lockstep_ms = 0.0, Counter(), {}
+        self._gc_staging = self._gc_status = None      # _gc_buffers: graphs and masks of a lock-step, device + pinned host; _status: a word per cell
+        self._gc_tiled_ws = None                 # _cut_on_device: scratch of the tiled solver (runs without coarse layers have none)
+        self._gc_snap = self._gc_fail = None     # _gc_set_without_round_trips: roll-back copy of labels / costs, the failure word
+        self._joint_staging, self._joint = None, {}      # gc_iteration_joint (first runner only): staging for the cells of all views, set index -> record
+        self._dumped = dict(tiled=0, tiled_written=0, samples=0, worst=0.012)     # tooling dumps: lock-steps seen / files written / slowest host cut so far (s)
 
     # -- exchange: one all-gather of the updated tiles of a set (labels 16 B/px + cost 4 B/px).  Pack and unpack are kernels of the
     # library on the runner's stream; with the nccl backend the collective is enqueued on the same stream by torch, so nothing here
@@ -123,9 +143,8 @@ class PMRunner:
         x = sh.xchg
         if x.slot_floats == 0:
             return
-        if getattr(self, "_xbuf", None) is None or self._xbuf[0].numel() < x.slot_floats:
-            n = max(s_.xchg.slot_floats for layer in self.shards for s_ in layer) if self.shards else x.slot_floats
-            n = max(n, x.slot_floats, self.init.xchg.slot_floats if getattr(self, "init", None) is not None and self.init.xchg else 0)
+        if self._xbuf is None or self._xbuf[0].numel() < x.slot_floats:
+            n = max([x.slot_floats] + [s.xchg.slot_floats for s in [s_ for _, s_ in self.sets] + [self.init] if s.xchg])
             self._xbuf = (torch.zeros(n, dtype=torch.float32, device=self.device), torch.zeros(n * self.world, dtype=torch.float32, device=self.device))
         send, recv = self._xbuf[0][: x.slot_floats], self._xbuf[1][: x.slot_floats * self.world]
         ev = None
@@ -194,27 +213,36 @@ class PMRunner:
         if self.world > 1:
             pass        # every rank evaluates the whole map here (replicated state, nothing to exchange)
 
+    def _proposals(self, li, iteration):
+        """(kind, m) of every lock-step of a set of layer li, in the order of the proposer table.  The RandomProposer stops once its
+        perturbation is below 0.1 disparities (LES/Proposer.h:149-152)."""
+        for kind, K in self.table[li]:
+            for m in range(iteration, iteration + K):
+                if kind == api.PROPOSE_RANDOM and (self.maxd - self.mind) * 0.5 ** (m + 1) < 0.1:
+                    break
+                yield kind, m
+
+    def _propose(self, sh, kind, m):
+        """What every lock-step starts with: one proposal plane per cell of the shard and its unary costs (into self.prop)."""
+        sh.batch.propose(kind, self.labels.data_ptr(), sh.rng.data_ptr(), sh.planes.data_ptr(), m=m)
+        sh.batch.run(sh.planes.data_ptr(), self.prop.data_ptr(), mode=self.mode, check=True, planes_on_device=True)
+
     def iteration(self, iteration):
         """One PatchMatch iteration over all layers (LES/FastGCStereo.h:143-157 with doGC == false)."""
-        for li, layer in enumerate(self.shards):
-            for sh in layer:
-                if sh.n:
-                    for kind, K in self.table[li]:
-                        for it in range(K):
-                            m = iteration + it
-                            if kind == api.PROPOSE_RANDOM and (self.maxd - self.mind) * 0.5 ** (m + 1) < 0.1:      # LES/Proposer.h:149-152
-                                break
-                            sh.batch.propose(kind, self.labels.data_ptr(), sh.rng.data_ptr(), sh.planes.data_ptr(), m=m)
-                            sh.batch.run(sh.planes.data_ptr(), self.prop.data_ptr(), mode=self.mode, check=True, planes_on_device=True)
-                            sh.batch.wta(sh.planes.data_ptr(), self.cur.data_ptr(), self.prop.data_ptr(), self.labels.data_ptr())
-                if self.world == 1 or self.device.type != "cuda":
-                    self._sync()                     # (bounds the launch queue; with several ranks on GPUs the collective orders the stream itself)
-                self._exchange(sh)
+        for li, sh in self.sets:
+            for kind, m in self._proposals(li, iteration) if sh.n else ():
+                self._propose(sh, kind, m)
+                sh.batch.wta(sh.planes.data_ptr(), self.cur.data_ptr(), self.prop.data_ptr(), self.labels.data_ptr())
+            if self.world == 1 or self.device.type != "cuda":
+                self._sync()                     # (bounds the launch queue; with several ranks on GPUs the collective orders the stream itself)
+            self._exchange(sh)
 
     # -- graph-cut iterations (LES/FastGCStereo.h:171-185: the main loop, doGC == true) ----------------------------
     # Proposals and unary costs come from the GPU exactly as in iteration(); the winner-take-all update is replaced by
-    # the local expansion moves of the rank's own cells on the host cores (gc.GraphCut), and the fused labels go
-    # back to the device for the next proposals.  Cross-rank coherence is the same per-set all-gather.
+    # the local expansion moves of the rank's own cells, cut on the device or on the host cores (gc.py).  Cross-rank coherence is the same
+    # per-set all-gather.  One lock-step is: _propose, _graph, _cut (_cut_on_device, else _cut_on_host), _apply.  The cut steps take WHAT
+    # is cut as a record (batch, n, regions, graph_off, graph_nodes, max_cell_nodes, payload / masks on the device and pinned on the
+    # host): a _Shard, or the cells of two views as one batch (_joint_set).
     def begin_gc(self, graph_cut, mode=None, device_graph=True):
         """device_graph (default): the solution stays on the GPU -- pairwise terms / graph capacities of every move are
         computed there (les_hip_batch_expansion_graph), the host receives only the graphs, runs the max-flows and
@@ -223,11 +251,10 @@ class PMRunner:
         self.gc = graph_cut
         self.device_graph = device_graph
         # device_cuts: cells small enough for a workgroup's LDS (the finest layer) are also CUT on the GPU (les_hip_batch_solve_graphs),
-        # so neither their graphs nor their masks cross PCIe and the host cores only see the larger cells.  On by default on a GPU
-        # (the simulator build used by the CPU tests would spend minutes in it).
+        # so neither their graphs nor their masks cross PCIe and the host cores only see the larger cells.
         # "all" (default on a GPU): the larger cells as well, by the tiled solver (les_hip_batch_solve_graphs_tiled: graphs resident in device
         # memory, a workgroup per tile); "fine": only the cells that fit the LDS (rounds 2-4); "none": every cut on the host.
-        dc = getattr(self, "device_cuts", None)
+        dc = self.device_cuts
         if dc is None:
             dc = "all" if self.device.type == "cuda" else "none"     # (the simulator build used by the CPU tests would spend minutes in it)
         elif dc is True:
@@ -239,12 +266,16 @@ class PMRunner:
         self.device_cuts = dc
         self._gc_mode = self.mode if mode is None else mode
         self.sync_gc_state()
-        pin = (lambda t: t.pin_memory()) if self.device.type == "cuda" else (lambda t: t)
-        self._prop_host = pin(torch.empty((self.H, self.W), dtype=torch.float32))
+        self._prop_host = self._pin(torch.empty((self.H, self.W), dtype=torch.float32))
         self.gc_max_gap = 0.0
         self.tiled_lockstep_ms = {}              # layer -> [(ms, launches)] of every lock-step the tiled solver cut (per view: a runner is a view)
-        self.gc_seconds = {"device": 0.0, "host_cuts": 0.0, "h2d": 0.0}
+        self.gc_seconds = Counter({"device": 0.0, "host_cuts": 0.0, "h2d": 0.0})      # (the other keys appear once they count something)
         self.gc_seconds.update({f"host_cuts_layer{li}": 0.0 for li in range(len(self.shards))})
+        # the tooling's environment (what each variable does: _dump_host_cut, _dump_tiled, _gc_set_without_round_trips), read here and nowhere else
+        env = os.environ.get
+        self._env = SimpleNamespace(graphs=env("LES_DUMP_GRAPHS"), tiled=env("LES_DUMP_TILED"), every=env("LES_DUMP_EVERY"), full=env("LES_DUMP_FULL"),
+                                    max=int(env("LES_DUMP_MAX", "6")), this_view=env("LES_DUMP_VIEW", str(self.mode)) == str(self.mode),
+                                    per_lockstep=env("LES_GC_PER_LOCKSTEP_CHECK"))
 
     def sync_gc_state(self):
         """Copy the device solution into the host graph-cut context (for its energy queries / the host-construction path)."""
@@ -253,36 +284,162 @@ class PMRunner:
         self.gc.labels[m][...] = self.labels.cpu().numpy()
         self.gc.costs[m][...] = self.cur.cpu().numpy()
 
+    def _pin(self, t):
+        return t.pin_memory() if self.device.type == "cuda" else t
+
+    def _staging(self, nodes):
+        """Graph (5 floats per node) and mask (a byte per node) staging: device, pinned host, device, pinned host."""
+        return (torch.empty(nodes * 5, dtype=torch.float32, device=self.device), self._pin(torch.empty(nodes * 5, dtype=torch.float32)),
+                torch.empty(nodes, dtype=torch.uint8, device=self.device), self._pin(torch.zeros(nodes, dtype=torch.uint8)))
+
+    @staticmethod
+    def _stage(lk, staging):
+        """Gives a lock-step record its views of a staging allocation, cut to its node count."""
+        payload, payload_host, masks, masks_host = staging
+        n = max(1, lk.graph_nodes)
+        lk.payload, lk.payload_host, lk.masks, lk.masks_host = payload[: n * 5], payload_host[: n * 5], masks[:n], masks_host[:n]
+
     def _gc_buffers(self, sh):
         """Views of the runner-wide graph / mask staging buffers (one device + one pinned host allocation, sized for the
         largest lock-step) cut to this shard's node count."""
-        if getattr(self, "_gc_payload", None) is None:
-            pin = (lambda t: t.pin_memory()) if self.device.type == "cuda" else (lambda t: t)
-            n = max([1] + [s.graph_nodes for layer in self.shards for s in layer])
-            self._gc_payload = torch.empty(n * 5, dtype=torch.float32, device=self.device)
-            self._gc_payload_host = pin(torch.empty(n * 5, dtype=torch.float32))
-            self._gc_masks = torch.empty(n, dtype=torch.uint8, device=self.device)
-            self._gc_masks_host = pin(torch.zeros(n, dtype=torch.uint8))
+        if self._gc_staging is None:
+            self._gc_staging = self._staging(max([1] + [s.graph_nodes for _, s in self.sets]))
         if sh.payload is None:
-            n = max(1, sh.graph_nodes)
-            sh.payload, sh.payload_host = self._gc_payload[: n * 5], self._gc_payload_host[: n * 5]
-            sh.masks, sh.masks_host = self._gc_masks[:n], self._gc_masks_host[:n]
+            self._stage(sh, self._gc_staging)
 
-    def _dump_tiled(self, sh, m, iteration, li, ms, launches):
+    def _status(self, n):
+        """n of the runner's status words (int32 per cell, 0 = cut on the device): sized for its largest set; the joint batch of two views grows it."""
+        if self._gc_status is None or self._gc_status.numel() < n:
+            self._gc_status = torch.zeros(max([n] + [s.n for _, s in self.sets]), dtype=torch.int32, device=self.device)
+        return self._gc_status[:n]
+
+    def _graph(self, sh, payload_ptr):
+        """The expansion graphs of the shard's cells (current labels against the proposals of _propose) into device memory at payload_ptr."""
+        p = self.gc.params
+        sh.batch.expansion_graph(sh.planes.data_ptr(), self.labels.data_ptr(), self.cur.data_ptr(), self.prop.data_ptr(), payload_ptr, mode=self.mode,
+                                 lambda_=p["lambda_"], th_smooth=p["th_smooth"], omega=p["omega"], epsilon=p["epsilon"])
+
+    def _apply(self, sh, masks_ptr):
+        sh.batch.apply_masks(sh.planes.data_ptr(), masks_ptr, self.cur.data_ptr(), self.prop.data_ptr(), self.labels.data_ptr())
+
+    def _on_device(self, lk):
+        """Does the device try to cut this lock-step?"""
+        return bool(lk.n) and (self.device_cuts == "all" or (self.device_cuts == "fine" and lk.max_cell_nodes <= api.Batch.MAXFLOW_MAX_NODES))
+
+    def _cut_on_device(self, lk, li=None, iteration=None):
+        """Cuts the graphs at lk.payload into lk.masks: one workgroup per cell where every cell fits the LDS, else the tiled solver.  -> True: every
+        cell was cut (else the status words say which were not).  li, iteration: where the lock-step belongs, for the per-layer statistics of the
+        tiled solver and LES_DUMP_TILED (the joint form keeps neither)."""
+        st = self._status(lk.n)
+        if lk.max_cell_nodes <= api.Batch.MAXFLOW_MAX_NODES:
+            lk.batch.solve_graphs(lk.payload.data_ptr(), lk.masks.data_ptr(), st.data_ptr())
+            done = not bool(st.any().item())         # (the only synchronisation of the lock-step)
+        else:
+            need = lk.batch.tiled_workspace_bytes() + 256
+            if self._gc_tiled_ws is None or self._gc_tiled_ws.numel() < need:     # one scratch per runner (= per view and host thread), for its largest batch
+                own = [s.batch.tiled_workspace_bytes() + 256 for _, s in self.sets if s.n and s.max_cell_nodes > api.Batch.MAXFLOW_MAX_NODES]
+                self._gc_tiled_ws = torch.empty(max([need] + own), dtype=torch.uint8, device=self.device)
+            ws, sec = self._gc_tiled_ws, self.gc_seconds
+            wp = (ws.data_ptr() + 255) & ~255        # (the solver wants 256-byte alignment)
+            t0 = time.perf_counter()
+            nl = lk.batch.solve_graphs_tiled(lk.payload.data_ptr(), lk.masks.data_ptr(), st.data_ptr(), wp, ws.numel() - (wp - ws.data_ptr()))
+            sec["tiled_launches"] += nl
+            sec["tiled_locksteps"] += 1
+            if li is not None:
+                handed = lk.batch.tiled_stats        # cells the host cores finished from their residual graphs (hand-over)
+                sec["tiled_handed_cells"] += handed["handed_cells"]
+                sec["tiled_handed_locksteps"] += 1 if handed["handed_cells"] else 0
+                sec["tiled_handed_host_seconds"] += 1e-3 * handed["host_ms"]
+                sec[f"tiled_seconds_layer{li}"] += time.perf_counter() - t0
+                self.tiled_lockstep_ms.setdefault(li, []).append((1e3 * (time.perf_counter() - t0), nl))      # (wall of the solve call, launches enqueued)
+                self._dump_tiled(lk, iteration, li, 1e3 * (time.perf_counter() - t0), nl)
+            done = lk.batch.tiled_unsolved == 0      # (the call synchronised; it reports "cells that gave up" through a host-mapped word: no copy)
+        if done:
+            self.gc_seconds["cells_cut_on_device"] += lk.n
+        return done
+
+    def _cut_on_host(self, lk, nthreads, partial):
+        """Copies the graphs down, cuts them on the host cores, copies the masks up.  partial: when the device tried and gave up on only SOME
+        cells (their status word is non-zero), only those are cut again and the device's masks of the others stay.
+        -> (t1, t2): the clock before and after the cuts proper."""
+        self._sync()
+        lk.payload_host.copy_(lk.payload)
+        regions, offsets = lk.regions, lk.graph_off
+        failed = np.nonzero(self._status(lk.n).cpu().numpy())[0] if partial and self._on_device(lk) else ()
+        t1 = time.perf_counter()
+        if 0 < len(failed) < lk.n:
+            lk.masks_host.copy_(lk.masks)
+            regions, offsets = np.ascontiguousarray(regions[failed]), np.ascontiguousarray(offsets[failed])
+            self.gc_seconds["cells_recut_on_host"] += len(failed)
+        lgc.solve_prebuilt(regions, lk.payload_host.numpy(), offsets, lk.masks_host.numpy(), nthreads=nthreads)
+        t2 = time.perf_counter()
+        lk.masks.copy_(lk.masks_host)
+        return t1, t2
+
+    def _cut(self, lk, nthreads, partial, li=None, iteration=None):
+        """The cuts of a lock-step: on the device where device_cuts says so, on the host where not or when the device gave up.
+        -> (every cell cut on the device, t1, t2): the clock before and after the host's cuts."""
+        if self._on_device(lk) and self._cut_on_device(lk, li, iteration):
+            t = time.perf_counter()
+            return True, t, t
+        return (False,) + self._cut_on_host(lk, nthreads, partial)
+
+    def _moves_on_host_maps(self, sh, nthreads, check):
+        """The lock-step in the reference's shape (check=True or device_graph=False): the proposals' costs go to the host, gc.expansion_moves builds
+        and cuts the graphs there on the host-resident solution (with the reference's flow == energy self-check when `check`), and the fused maps
+        come back.  -> (t1, t2) as _cut_on_host."""
+        self._sync()
+        self._prop_host.copy_(self.prop)
+        planes = sh.planes[: sh.n].cpu().numpy()
+        t1 = time.perf_counter()
+        gap = self.gc.expansion_moves(sh.regions, planes, self._prop_host.numpy(), mode=self.mode, nthreads=nthreads, check=check)
+        self.gc_max_gap = max(self.gc_max_gap, gap)
+        t2 = time.perf_counter()
+        self.labels.copy_(torch.from_numpy(self.gc.labels[self.mode]))
+        self.cur.copy_(torch.from_numpy(self.gc.costs[self.mode]))
+        return t1, t2
+
+    def _book(self, li, t0, t1, t2):
+        """A lock-step's wall time: device work (and the way down) | the host cores' cuts | the way back up and the mask updates."""
+        self.gc_seconds["device"] += t1 - t0
+        self.gc_seconds["host_cuts"] += t2 - t1
+        self.gc_seconds[f"host_cuts_layer{li}"] += t2 - t1
+        self.gc_seconds["h2d"] += time.perf_counter() - t2
+
+    def _dump_tiled(self, sh, iteration, li, ms, launches):
         """Tooling (tools/tiled_cut_replay.py): LES_DUMP_TILED=dir LES_DUMP_EVERY=n [LES_DUMP_VIEW=v LES_DUMP_MAX=k] writes the graphs of every
         n-th lock-step the tiled solver cut (regions, node offsets, the 5-float payload) with its wall time and launch count."""
-        import os
-        d = os.environ.get("LES_DUMP_TILED")
-        if not d or os.environ.get("LES_DUMP_VIEW", str(m)) != str(m):
+        env, seen = self._env, self._dumped
+        if not env.tiled or not env.this_view:
             return
-        self._dump_tiled_count = getattr(self, "_dump_tiled_count", 0) + 1
-        every = int(os.environ.get("LES_DUMP_EVERY", "50"))
-        if self._dump_tiled_count % every or getattr(self, "_dump_tiled_done", 0) >= int(os.environ.get("LES_DUMP_MAX", "6")):
+        seen["tiled"] += 1
+        if seen["tiled"] % int(env.every or "50") or seen["tiled_written"] >= env.max:
             return
-        self._dump_tiled_done = getattr(self, "_dump_tiled_done", 0) + 1
-        nn = int(sh.graph_off[-1] + int(sh.regions[-1]["w"]) * int(sh.regions[-1]["h"]))
-        np.savez_compressed(os.path.join(d, f"tiled_view{m}_it{iteration}_layer{li}_{self._dump_tiled_count}.npz"), regions=sh.regions, offsets=sh.graph_off,
-                            payload=sh.payload[: nn * 5].cpu().numpy(), ms=ms, launches=launches, cells=sh.n)
+        seen["tiled_written"] += 1
+        np.savez_compressed(os.path.join(env.tiled, f"tiled_view{self.mode}_it{iteration}_layer{li}_{seen['tiled']}.npz"), regions=sh.regions, offsets=sh.graph_off,
+                            payload=sh.payload[: sh.graph_nodes * 5].cpu().numpy(), ms=ms, launches=launches, cells=sh.n)
+
+    def _dump_host_cut(self, sh, li, iteration, kind, it, on_dev, seconds):
+        """Tooling (tools/cut_replay.py, tools/tiled_cut_replay.py), LES_DUMP_GRAPHS=dir: a timing log of the lock-steps; with LES_DUMP_EVERY=n a sample of
+        ordinary ones (the first two cells, or with LES_DUMP_FULL all, of every n-th lock-step that was cut on the host); the graphs of the slowest
+        lock-step of the coarsest layer."""
+        env, seen, m = self._env, self._dumped, self.mode
+        if not env.graphs:
+            return
+        with open(os.path.join(env.graphs, f"cutlog_view{m}.txt"), "a") as f:
+            f.write(f"{iteration} {li} {kind} {it} {sh.n} {seconds:.6f}\n")
+        every = int(env.every or "0")
+        if every and not on_dev and env.this_view:
+            seen["samples"] += 1
+            if seen["samples"] % every == 0:
+                k2 = sh.n if env.full else min(2, sh.n)
+                nn = int(sh.graph_off[k2 - 1] + int(sh.regions[k2 - 1]["w"]) * int(sh.regions[k2 - 1]["h"]))
+                np.savez_compressed(os.path.join(env.graphs, f"sample_view{m}_it{iteration}_layer{li}_{seen['samples']}.npz"), regions=sh.regions[:k2],
+                                    offsets=sh.graph_off[:k2], payload=sh.payload_host.numpy()[: nn * 5].copy(), seconds=seconds, cells=sh.n)
+        if li == len(self.shards) - 1 and iteration >= 1 and seconds > seen["worst"]:
+            seen["worst"] = seconds
+            np.savez_compressed(os.path.join(env.graphs, f"graphs_view{m}_layer{li}.npz"), regions=sh.regions, offsets=sh.graph_off,
+                                payload=sh.payload_host.numpy()[: sh.graph_nodes * 5].copy(), seconds=seconds)
 
     def _gc_set_without_round_trips(self, sh, li, iteration):
         """All proposals of one disjoint set of the FINEST layer (cells that fit a workgroup's LDS: propose -> unary costs -> graph -> cut -> apply, nine
@@ -290,262 +447,106 @@ class PMRunner:
         end of the set (rounds 2-5 read a status word per lock-step: 720 synchronisations per view).  In the -- so far unobserved -- case that the word
         is not zero the set is rolled back (labels, costs, generator states were saved in device memory: 30 MB, microseconds) and the caller repeats it
         lock-step by lock-step with the host fall-back.  -> True: done."""
-        import os
-        import time
-        if self.device.type != "cuda" and not getattr(self, "speculative_sets_on_cpu", False):
+        if self.device.type != "cuda" and not self.speculative_sets_on_cpu:      # (the simulator would spend minutes in the cuts: only the test of this form)
             return False
-        if self.device_cuts not in ("all", "fine") or sh.batch.max_cell_nodes > api.Batch.MAXFLOW_MAX_NODES:
+        if self.device_cuts not in ("all", "fine") or sh.max_cell_nodes > api.Batch.MAXFLOW_MAX_NODES:
             return False
-        if os.environ.get("LES_DUMP_GRAPHS") or os.environ.get("LES_GC_PER_LOCKSTEP_CHECK"):
+        if self._env.graphs or self._env.per_lockstep:       # (LES_DUMP_GRAPHS logs, LES_GC_PER_LOCKSTEP_CHECK=1 checks every lock-step)
             return False
         t0 = time.perf_counter()
-        if getattr(self, "_gc_snap", None) is None:
+        if self._gc_snap is None:
             self._gc_snap = (torch.empty_like(self.labels), torch.empty_like(self.cur))
             self._gc_fail = torch.zeros(1, dtype=torch.int32, device=self.device)
-            nmax = max([1] + [s_.n for layer_ in self.shards for s_ in layer_])
-            if getattr(self, "_gc_status", None) is None:
-                self._gc_status = torch.zeros(nmax, dtype=torch.int32, device=self.device)
         self._gc_buffers(sh)
         self._gc_snap[0].copy_(self.labels)
         self._gc_snap[1].copy_(self.cur)
         rng0 = sh.rng.clone()
         self._gc_fail.zero_()
-        st = self._gc_status[: sh.n]
-        p, m = self.gc.params, self.mode
-        locksteps = 0
-        for kind, K in self.table[li]:
-            for it in range(K):
-                mm = iteration + it
-                if kind == api.PROPOSE_RANDOM and (self.maxd - self.mind) * 0.5 ** (mm + 1) < 0.1:
-                    break
-                sh.batch.propose(kind, self.labels.data_ptr(), sh.rng.data_ptr(), sh.planes.data_ptr(), m=mm)
-                sh.batch.run(sh.planes.data_ptr(), self.prop.data_ptr(), mode=m, check=True, planes_on_device=True)
-                sh.batch.expansion_graph(sh.planes.data_ptr(), self.labels.data_ptr(), self.cur.data_ptr(), self.prop.data_ptr(), sh.payload.data_ptr(), mode=m,
-                                         lambda_=p["lambda_"], th_smooth=p["th_smooth"], omega=p["omega"], epsilon=p["epsilon"])
-                sh.batch.solve_graphs(sh.payload.data_ptr(), sh.masks.data_ptr(), st.data_ptr(), unsolved_total_dev=self._gc_fail.data_ptr())
-                sh.batch.apply_masks(sh.planes.data_ptr(), sh.masks.data_ptr(), self.cur.data_ptr(), self.prop.data_ptr(), self.labels.data_ptr())
-                locksteps += 1
+        st, proposals = self._status(sh.n), list(self._proposals(li, iteration))
+        for kind, m in proposals:
+            self._propose(sh, kind, m)
+            self._graph(sh, sh.payload.data_ptr())
+            sh.batch.solve_graphs(sh.payload.data_ptr(), sh.masks.data_ptr(), st.data_ptr(), unsolved_total_dev=self._gc_fail.data_ptr())
+            self._apply(sh, sh.masks.data_ptr())
         failed = int(self._gc_fail.item())                 # the set's only synchronisation
         self.gc_seconds["device"] += time.perf_counter() - t0
         if failed:
             self.labels.copy_(self._gc_snap[0])
             self.cur.copy_(self._gc_snap[1])
             sh.rng.copy_(rng0)
-            self.gc_seconds["sets_rolled_back"] = self.gc_seconds.get("sets_rolled_back", 0) + 1
+            self.gc_seconds["sets_rolled_back"] += 1
             return False
-        self.gc_seconds["cells_cut_on_device"] = self.gc_seconds.get("cells_cut_on_device", 0) + sh.n * locksteps
-        self.gc_seconds["sets_without_round_trips"] = self.gc_seconds.get("sets_without_round_trips", 0) + 1
+        self.gc_seconds["cells_cut_on_device"] += sh.n * len(proposals)
+        self.gc_seconds["sets_without_round_trips"] += 1
         return True
 
     def gc_iteration(self, iteration, check=False, nthreads=0):
-        import os
-        import time
-        from . import gc as lgc
-        gc, m = self.gc, self.mode
-        host_path = check or not self.device_graph
-        if host_path:
+        """One graph-cut iteration of this view over all layers and sets."""
+        host_maps = check or not self.device_graph
+        if host_maps:
             self.sync_gc_state()
-            lab_host = torch.from_numpy(gc.labels[m])
-            cur_host = torch.from_numpy(gc.costs[m])
-        for li, layer in enumerate(self.shards):
-            for sh in layer:
-                if sh.n and not host_path and self._gc_set_without_round_trips(sh, li, iteration):
-                    if self.world > 1:
-                        self._exchange(sh)
-                    continue
-                if sh.n:
-                    for kind, K in self.table[li]:
-                        for it in range(K):
-                            mm = iteration + it
-                            if kind == api.PROPOSE_RANDOM and (self.maxd - self.mind) * 0.5 ** (mm + 1) < 0.1:
-                                break
-                            t0 = time.perf_counter()
-                            sh.batch.propose(kind, self.labels.data_ptr(), sh.rng.data_ptr(), sh.planes.data_ptr(), m=mm)
-                            sh.batch.run(sh.planes.data_ptr(), self.prop.data_ptr(), mode=m, check=True, planes_on_device=True)
-                            if host_path:
-                                self._sync()
-                                self._prop_host.copy_(self.prop)
-                                planes = sh.planes[: sh.n].cpu().numpy()
-                                t1 = time.perf_counter()
-                                gap = gc.expansion_moves(sh.regions, planes, self._prop_host.numpy(), mode=m, nthreads=nthreads, check=check)
-                                self.gc_max_gap = max(self.gc_max_gap, gap)
-                                t2 = time.perf_counter()
-                                self.labels.copy_(lab_host)
-                                self.cur.copy_(cur_host)
-                            else:
-                                self._gc_buffers(sh)
-                                p = gc.params
-                                sh.batch.expansion_graph(sh.planes.data_ptr(), self.labels.data_ptr(), self.cur.data_ptr(), self.prop.data_ptr(),
-                                                         sh.payload.data_ptr(), mode=m, lambda_=p["lambda_"], th_smooth=p["th_smooth"], omega=p["omega"],
-                                                         epsilon=p["epsilon"])
-                                on_dev = False
-                                small = sh.batch.max_cell_nodes <= api.Batch.MAXFLOW_MAX_NODES
-                                if sh.n and (self.device_cuts == "all" or (self.device_cuts == "fine" and small)):
-                                    if getattr(self, "_gc_status", None) is None:
-                                        nmax = max([1] + [s_.n for layer_ in self.shards for s_ in layer_])
-                                        self._gc_status = torch.zeros(nmax, dtype=torch.int32, device=self.device)
-                                    st = self._gc_status[: sh.n]
-                                    if small:
-                                        sh.batch.solve_graphs(sh.payload.data_ptr(), sh.masks.data_ptr(), st.data_ptr())
-                                    else:
-                                        if getattr(self, "_gc_tiled_ws", None) is None:      # one scratch per runner (= per view and host thread)
-                                            nb = max(s_.batch.tiled_workspace_bytes() for layer_ in self.shards for s_ in layer_
-                                                     if s_.n and s_.batch.max_cell_nodes > api.Batch.MAXFLOW_MAX_NODES)
-                                            self._gc_tiled_ws = torch.empty(nb + 256, dtype=torch.uint8, device=self.device)
-                                        ws = self._gc_tiled_ws
-                                        wp = (ws.data_ptr() + 255) & ~255
-                                        tl0 = time.perf_counter()
-                                        nl = sh.batch.solve_graphs_tiled(sh.payload.data_ptr(), sh.masks.data_ptr(), st.data_ptr(), wp, ws.numel() - (wp - ws.data_ptr()))
-                                        self.gc_seconds["tiled_launches"] = self.gc_seconds.get("tiled_launches", 0) + nl
-                                        self.gc_seconds["tiled_locksteps"] = self.gc_seconds.get("tiled_locksteps", 0) + 1
-                                        ts_ = sh.batch.tiled_stats                       # cells the host cores finished from their residual graphs (hand-over)
-                                        self.gc_seconds["tiled_handed_cells"] = self.gc_seconds.get("tiled_handed_cells", 0) + ts_["handed_cells"]
-                                        self.gc_seconds["tiled_handed_locksteps"] = self.gc_seconds.get("tiled_handed_locksteps", 0) + (1 if ts_["handed_cells"] else 0)
-                                        self.gc_seconds["tiled_handed_host_seconds"] = self.gc_seconds.get("tiled_handed_host_seconds", 0.0) + 1e-3 * ts_["host_ms"]
-                                        self.gc_seconds[f"tiled_seconds_layer{li}"] = self.gc_seconds.get(f"tiled_seconds_layer{li}", 0.0) + time.perf_counter() - tl0
-                                        self.tiled_lockstep_ms.setdefault(li, []).append((1e3 * (time.perf_counter() - tl0), nl))      # (wall of the solve call, launches enqueued)
-                                        self._dump_tiled(sh, m, iteration, li, 1e3 * (time.perf_counter() - tl0), nl)
-                                    # (the only synchronisation of the lock-step; the tiled solver reports "cells that gave up" through a host-mapped word: no copy)
-                                    on_dev = (sh.batch.tiled_unsolved == 0) if not small else not bool(st.any().item())
-                                    if on_dev:
-                                        self.gc_seconds["cells_cut_on_device"] = self.gc_seconds.get("cells_cut_on_device", 0) + sh.n
-                                if on_dev:
-                                    t1 = t2 = time.perf_counter()
-                                else:
-                                    self._sync()
-                                    sh.payload_host.copy_(sh.payload)
-                                    # only the cells the device gave up on are cut again (their status word is non-zero); the masks of the others stay
-                                    failed = None
-                                    if sh.n and self.device_cuts in ("all", "fine") and getattr(self, "_gc_status", None) is not None and (self.device_cuts == "all" or small):
-                                        bad = np.nonzero(self._gc_status[: sh.n].cpu().numpy())[0]
-                                        if 0 < len(bad) < sh.n:
-                                            failed = bad
-                                    t1 = time.perf_counter()
-                                    if failed is None:
-                                        lgc.solve_prebuilt(sh.regions, sh.payload_host.numpy(), sh.graph_off, sh.masks_host.numpy(), nthreads=nthreads)
-                                    else:
-                                        sh.masks_host.copy_(sh.masks)
-                                        lgc.solve_prebuilt(np.ascontiguousarray(sh.regions[failed]), sh.payload_host.numpy(), np.ascontiguousarray(sh.graph_off[failed]),
-                                                           sh.masks_host.numpy(), nthreads=nthreads)
-                                        self.gc_seconds["cells_recut_on_host"] = self.gc_seconds.get("cells_recut_on_host", 0) + len(failed)
-                                    t2 = time.perf_counter()
-                                dump = os.environ.get("LES_DUMP_GRAPHS")           # tooling: timing log of the lock-steps + the graphs of the slowest one of the coarsest layer
-                                if dump:
-                                    with open(os.path.join(dump, f"cutlog_view{m}.txt"), "a") as f:
-                                        f.write(f"{iteration} {li} {kind} {it} {sh.n} {t2 - t1:.6f}\n")
-                                every = int(os.environ.get("LES_DUMP_EVERY", "0")) if dump else 0   # tooling: a sample of ordinary lock-steps (first two cells of every N-th one that was cut on the host)
-                                if every and not on_dev and os.environ.get("LES_DUMP_VIEW", str(m)) == str(m):
-                                    self._dump_count = getattr(self, "_dump_count", 0) + 1
-                                    if self._dump_count % every == 0:
-                                        k2 = sh.n if os.environ.get("LES_DUMP_FULL") else min(2, sh.n)
-                                        nn = int(sh.graph_off[k2 - 1] + int(sh.regions[k2 - 1]["w"]) * int(sh.regions[k2 - 1]["h"]))
-                                        np.savez_compressed(os.path.join(dump, f"sample_view{m}_it{iteration}_layer{li}_{self._dump_count}.npz"), regions=sh.regions[:k2],
-                                                            offsets=sh.graph_off[:k2], payload=sh.payload_host.numpy()[: nn * 5].copy(), seconds=t2 - t1, cells=sh.n)
-                                if dump and li == len(self.shards) - 1 and iteration >= 1 and t2 - t1 > getattr(self, "_dump_worst", 0.012):
-                                    self._dump_worst = t2 - t1
-                                    nn = int(sh.graph_off[-1] + int(sh.regions[-1]["w"]) * int(sh.regions[-1]["h"]))
-                                    np.savez_compressed(os.path.join(dump, f"graphs_view{m}_layer{li}.npz"), regions=sh.regions, offsets=sh.graph_off,
-                                                        payload=sh.payload_host.numpy()[: nn * 5].copy(), seconds=t2 - t1)
-                                if not on_dev:
-                                    sh.masks.copy_(sh.masks_host)
-                                sh.batch.apply_masks(sh.planes.data_ptr(), sh.masks.data_ptr(), self.cur.data_ptr(), self.prop.data_ptr(), self.labels.data_ptr())
-                            t3 = time.perf_counter()
-                            self.gc_seconds["device"] += t1 - t0
-                            self.gc_seconds["host_cuts"] += t2 - t1
-                            self.gc_seconds[f"host_cuts_layer{li}"] += t2 - t1
-                            self.gc_seconds["h2d"] += t3 - t2
-                if self.world > 1:
-                    self._exchange(sh)
-                    if host_path:
-                        lab_host.copy_(self.labels)
-                        cur_host.copy_(self.cur)
+        for li, sh in self.sets:
+            per_lock_step = sh.n and (host_maps or not self._gc_set_without_round_trips(sh, li, iteration))
+            for kind, m in self._proposals(li, iteration) if per_lock_step else ():
+                t0 = time.perf_counter()
+                self._propose(sh, kind, m)
+                if host_maps:
+                    t1, t2 = self._moves_on_host_maps(sh, nthreads, check)
+                else:
+                    self._gc_buffers(sh)
+                    self._graph(sh, sh.payload.data_ptr())
+                    on_dev, t1, t2 = self._cut(sh, nthreads, True, li, iteration)      # (partial recut allowed)
+                    self._dump_host_cut(sh, li, iteration, kind, m - iteration, on_dev, t2 - t1)
+                    self._apply(sh, sh.masks.data_ptr())
+                self._book(li, t0, t1, t2)
+            if self.world > 1:
+                self._exchange(sh)
+                if host_maps:
+                    torch.from_numpy(self.gc.labels[self.mode]).copy_(self.labels)
+                    torch.from_numpy(self.gc.costs[self.mode]).copy_(self.cur)
         self._sync()
+
+    def _joint_set(self, runners, k):
+        """Set k of every view as ONE record for the cut steps: a joint batch (the views' target rects one after the other) has exactly the node
+        offsets of the concatenated payload, so the single-batch entry points serve it unchanged.  views: (runner, shard, first node) of
+        the views that have cells in the set."""
+        if self._joint_staging is None:
+            self._joint_staging = self._staging(max([1] + [sum(r.sets[i][1].graph_nodes for r in runners) for i in range(len(self.sets))]))
+        lk = self._joint.get(k)
+        if lk is None:
+            shs = [r.sets[k][1] for r in runners]
+            base = np.cumsum([0] + [sh.graph_nodes for sh in shs])
+            lk = self._joint[k] = SimpleNamespace(
+                n=sum(sh.n for sh in shs), batch=None, regions=np.concatenate([sh.regions for sh in shs]), graph_nodes=int(base[-1]),
+                graph_off=np.concatenate([sh.graph_off + int(b) for sh, b in zip(shs, base)]).astype(np.int64),
+                max_cell_nodes=max([0] + [sh.max_cell_nodes for sh in shs if sh.n]), views=[(r, sh, int(b)) for r, sh, b in zip(runners, shs, base) if sh.n])
+            self._stage(lk, self._joint_staging)
+        if lk.batch is None and self._on_device(lk):
+            lk.batch = api.Batch(self.e, np.concatenate([sh.batch_filter for _, sh, _ in lk.views]), lk.regions)
+            assert lk.batch.graph_nodes() == lk.graph_nodes and np.array_equal(lk.batch.graph_offsets(), lk.graph_off)
+        return lk
 
     @staticmethod
     def gc_iteration_joint(runners, iteration, nthreads=0):
         """Graph-cut iteration of SEVERAL views in lock-step (two-view runs, LES/FastGCStereo.h:172-185: the views are independent
-        until the post-processing).  Every lock-step evaluates the proposals of all views on the GPU, moves ONE payload to the host,
-        cuts the cells of all views in ONE OpenMP team (twice the cells per fork/join, and for the coarsest layer twice the
-        otherwise scarce parallelism) and applies the masks per view.  Same results as gc_iteration per view: the cuts of
-        different views touch disjoint state.  Single rank, device-built graphs."""
-        import time
-        from . import gc as lgc
+        until the post-processing).  Every lock-step evaluates the proposals of all views on the GPU and cuts the cells of all views at
+        once: ONE solve on the device, or ONE payload to the host and ONE OpenMP team (twice the cells per fork/join, and for the coarsest
+        layer twice the otherwise scarce parallelism); the masks are applied per view.  Same results as gc_iteration per view: the cuts of
+        different views touch disjoint state.  Single rank, device-built graphs.  The counters are booked on the first runner; when the device
+        gives up on some cells the whole lock-step is cut again on the host (gc_iteration: only those cells)."""
         r0 = runners[0]
         assert all(r.world == 1 and r.device_graph for r in runners)
-        p = r0.gc.params
-        if getattr(r0, "_joint", None) is None:
-            pin = (lambda t: t.pin_memory()) if r0.device.type == "cuda" else (lambda t: t)
-            n = max([1] + [sum(r.shards[li][si].graph_nodes for r in runners) for li in range(len(r0.shards)) for si in range(len(r0.shards[li]))])
-            r0._joint = dict(payload=torch.empty(n * 5, dtype=torch.float32, device=r0.device), payload_host=pin(torch.empty(n * 5, dtype=torch.float32)),
-                             masks=torch.empty(n, dtype=torch.uint8, device=r0.device), masks_host=pin(torch.zeros(n, dtype=torch.uint8)), batches={})
-        J = r0._joint
-        for li in range(len(r0.shards)):
-            for si in range(len(r0.shards[li])):
-                shs = [r.shards[li][si] for r in runners]
-                if not any(sh.n for sh in shs):
-                    continue
-                base = np.cumsum([0] + [sh.graph_nodes for sh in shs])
-                regions = np.concatenate([sh.regions for sh in shs])
-                offsets = np.concatenate([sh.graph_off + int(base[v]) for v, sh in enumerate(shs)]).astype(np.int64)
-                total = int(base[-1])
-                for kind, K in r0.table[li]:
-                    for it in range(K):
-                        mm = iteration + it
-                        if kind == api.PROPOSE_RANDOM and (r0.maxd - r0.mind) * 0.5 ** (mm + 1) < 0.1:
-                            break
-                        t0 = time.perf_counter()
-                        for v, (r, sh) in enumerate(zip(runners, shs)):
-                            if not sh.n:
-                                continue
-                            sh.batch.propose(kind, r.labels.data_ptr(), sh.rng.data_ptr(), sh.planes.data_ptr(), m=mm)
-                            sh.batch.run(sh.planes.data_ptr(), r.prop.data_ptr(), mode=r.mode, check=True, planes_on_device=True)
-                            sh.batch.expansion_graph(sh.planes.data_ptr(), r.labels.data_ptr(), r.cur.data_ptr(), r.prop.data_ptr(),
-                                                     J["payload"].data_ptr() + 20 * int(base[v]), mode=r.mode, lambda_=p["lambda_"], th_smooth=p["th_smooth"],
-                                                     omega=p["omega"], epsilon=p["epsilon"])
-                        # device cuts: ONE solve over the cells of all views -- a joint batch (the views' target rects one after the other) has
-                        # exactly the node offsets of the concatenated payload, so the single-batch entry points serve it unchanged
-                        on_dev = False
-                        ncell = sum(sh.n for sh in shs)
-                        small = max([0] + [sh.batch.max_cell_nodes for sh in shs if sh.n]) <= api.Batch.MAXFLOW_MAX_NODES
-                        if ncell and (r0.device_cuts == "all" or (r0.device_cuts == "fine" and small)):
-                            jb = J["batches"].get((li, si))
-                            if jb is None:
-                                fr = np.concatenate([sh.batch_filter for sh in shs])
-                                jb = J["batches"][(li, si)] = api.Batch(r0.e, fr, regions)
-                                assert jb.graph_nodes() == total and np.array_equal(jb.graph_offsets(), offsets)
-                            if J.get("status") is None or J["status"].numel() < ncell:
-                                J["status"] = torch.zeros(max(ncell, 1024), dtype=torch.int32, device=r0.device)
-                            st = J["status"][:ncell]
-                            if small:
-                                jb.solve_graphs(J["payload"].data_ptr(), J["masks"].data_ptr(), st.data_ptr())
-                            else:
-                                nb = jb.tiled_workspace_bytes()
-                                if J.get("ws") is None or J["ws"].numel() < nb + 256:
-                                    J["ws"] = torch.empty(nb + 256, dtype=torch.uint8, device=r0.device)
-                                wp = (J["ws"].data_ptr() + 255) & ~255
-                                nl = jb.solve_graphs_tiled(J["payload"].data_ptr(), J["masks"].data_ptr(), st.data_ptr(), wp, J["ws"].numel() - (wp - J["ws"].data_ptr()))
-                                r0.gc_seconds["tiled_launches"] = r0.gc_seconds.get("tiled_launches", 0) + nl
-                                r0.gc_seconds["tiled_locksteps"] = r0.gc_seconds.get("tiled_locksteps", 0) + 1
-                            on_dev = (jb.tiled_unsolved == 0) if not small else not bool(st.any().item())
-                            if on_dev:
-                                r0.gc_seconds["cells_cut_on_device"] = r0.gc_seconds.get("cells_cut_on_device", 0) + ncell
-                        if on_dev:
-                            t1 = t2 = time.perf_counter()
-                        else:
-                            r0._sync()
-                            J["payload_host"][: total * 5].copy_(J["payload"][: total * 5])
-                            t1 = time.perf_counter()
-                            lgc.solve_prebuilt(regions, J["payload_host"].numpy()[: total * 5], offsets, J["masks_host"].numpy()[:total], nthreads=nthreads)
-                            t2 = time.perf_counter()
-                            J["masks"][:total].copy_(J["masks_host"][:total])
-                        for v, (r, sh) in enumerate(zip(runners, shs)):
-                            if sh.n:
-                                sh.batch.apply_masks(sh.planes.data_ptr(), J["masks"].data_ptr() + int(base[v]), r.cur.data_ptr(), r.prop.data_ptr(), r.labels.data_ptr())
-                        t3 = time.perf_counter()
-                        r0.gc_seconds["device"] += t1 - t0
-                        r0.gc_seconds["host_cuts"] += t2 - t1
-                        r0.gc_seconds[f"host_cuts_layer{li}"] += t2 - t1
-                        r0.gc_seconds["h2d"] += t3 - t2
+        for k, (li, _) in enumerate(r0.sets):
+            lk = r0._joint_set(runners, k)
+            for kind, m in r0._proposals(li, iteration) if lk.n else ():
+                t0 = time.perf_counter()
+                for r, sh, base in lk.views:
+                    r._propose(sh, kind, m)
+                    r._graph(sh, lk.payload.data_ptr() + 20 * base)
+                _, t1, t2 = r0._cut(lk, nthreads, partial=False)
+                for r, sh, base in lk.views:
+                    r._apply(sh, lk.masks.data_ptr() + base)
+                r0._book(li, t0, t1, t2)
         r0._sync()
 
     def run(self, pm_iterations, iterations=0, graph_cut=None):
@@ -567,11 +568,10 @@ class PMRunner:
         return self.labels[..., 0] * xs + self.labels[..., 1] * ys + self.labels[..., 2]
 
     def close(self):
-        if getattr(self, "_joint", None) is not None:
-            for jb in self._joint["batches"].values():
-                jb.destroy()
-            self._joint = None
-        for sh in [s_ for layer in self.shards for s_ in layer] + [self.init]:
+        for lk in self._joint.values():
+            if lk.batch is not None:
+                lk.batch.destroy()
+        for sh in [s for _, s in self.sets] + [self.init]:
             sh.batch.destroy()
             if sh.xchg is not None:
                 sh.xchg.destroy()

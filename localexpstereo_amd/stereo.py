@@ -39,6 +39,7 @@ class FastGCStereo:
         # slow ones (7-8 s of the 10 s of cuts) and then sit on the critical path of every lock-step, so it is not the default.
         self.concurrent_views = world == 1 and int(np.asarray(imL).shape[0]) * int(np.asarray(imL).shape[1]) >= 500_000
         self.joint_views = False
+        self._swap_view_threads = False                 # tooling: start the right view's thread first
         if os.environ.get("LES_VIEWS"):                 # tooling: "joint" | "concurrent" | "serial" | "concurrent-swapped"
             v = os.environ["LES_VIEWS"]
             self.joint_views = v == "joint"
@@ -84,7 +85,7 @@ class FastGCStereo:
 
     def _evaluate_body(self, index, mode, runner, g, t0):
         disp = runner.disparities().cpu().numpy()
-        if g is not None and getattr(runner, "gc", None) is g:
+        if g is not None and runner.gc is g:
             runner.sync_gc_state()
             dc, sc = g.data_cost(mode), g.smoothness_cost(mode)
         else:
@@ -186,7 +187,7 @@ class FastGCStereo:
                                 one_view(m, it, per_view)
                         except BaseException as ex:          # re-raised in the caller's thread below
                             errors.append(ex)
-                    ths = [threading.Thread(target=guarded, args=(m,)) for m in (reversed(viewModes) if getattr(self, "_swap_view_threads", False) else viewModes)]
+                    ths = [threading.Thread(target=guarded, args=(m,)) for m in (reversed(viewModes) if self._swap_view_threads else viewModes)]
                     for th in ths:
                         th.start()
                     for th in ths:
@@ -232,7 +233,7 @@ class FastGCStereo:
         # per view and layer: how long the lock-steps cut by the tiled solver took (p50 / p90 / max ms, launches)
         self.tiled_lockstep_stats = {}
         for m, r in runners.items():
-            for li, rows in getattr(r, "tiled_lockstep_ms", {}).items():
+            for li, rows in r.tiled_lockstep_ms.items():
                 a = np.array(rows, np.float64)
                 self.tiled_lockstep_stats[f"view{m}_layer{li}"] = dict(locksteps=len(a), ms_p50=round(float(np.percentile(a[:, 0], 50)), 2), ms_p90=round(float(np.percentile(a[:, 0], 90)), 2),
                                                                        ms_max=round(float(a[:, 0].max()), 2), ms_sum=round(float(a[:, 0].sum()), 1), launches_p50=int(np.percentile(a[:, 1], 50)),

@@ -336,6 +336,14 @@ def test_sim_gc_sets_without_round_trips(sim_lib, oracle_mod, monkeypatch):
     assert done > 0 and rolled > 0
 
 
+def test_sim_two_views_joint_lock_steps(sim_lib, oracle_mod, monkeypatch):
+    """Both views advanced in lock-step by pm.PMRunner.gc_iteration_joint (one host team cuts the cells of both) == view after view, bytes equal."""
+    monkeypatch.setenv("LES_HIP_KERNEL", "strip")
+    from localexpstereo_amd import build
+    build.build_host_lib()
+    pc.case_joint_views(sim_lib, "cpu", units=(16,))
+
+
 def test_sim_ingest_files(sim_lib, oracle_mod, tmp_path):
     pc.case_ingest_files(sim_lib, "cpu", tmp_path)
 
