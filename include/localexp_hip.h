@@ -301,6 +301,45 @@ int les_hip_batch_solve_graphs_tiled_stats(les_hip_ctx* ctx, const les_hip_batch
 int les_hip_batch_apply_masks(les_hip_ctx* ctx, const les_hip_batch* batch, const les_hip_plane* d_planes, const unsigned char* d_masks,
                               float* d_cur, const float* d_prop, les_hip_plane* d_labels);
 
+/* ---- evaluation of the device-resident solution on the device (csrc/les_eval.h) ----
+ * replaces: Evaluator::evaluate's numbers (LES/Evaluator.h:113-187; its PNG dumps and windows are not part of this) with
+ * PMStereoBase::computeCurrentEnergy (LES/PMStereoBase.h:263-270) = cv::sum(currentCost) + StereoEnergy::computeSmoothnessCost
+ * (LES/StereoEnergy.h:165-203), Evaluator::quantize (:106-111) and the bad-pixel counts (:133-140), in one pass over the device label
+ * and cost maps of a view, without copying either to the host.
+ * An evaluator holds the ground truth and the non-occlusion mask (H x W floats / bytes on the host, uploaded once; both may be NULL: the
+ * four counts are then 0; a NULL mask with ground truth counts every pixel as non-occluded), the error threshold, the precision the
+ * disparities are quantised to (<= 0: none) and a device-resident log of max_rows rows.  One host thread at a time uses an evaluator;
+ * two views take two evaluators. */
+typedef struct les_hip_evaluator les_hip_evaluator;
+typedef struct les_hip_eval_row {
+    int index, mode;                     /* as given to les_hip_evaluate */
+    double data, smooth;                 /* sum of the cost map; sum of the forward pair terms inside the image */
+    long long good_valid, good_nonocc;   /* pixels with |d - gt| <= threshold among the valid (gt > 0 and finite) / the non-occluded ones */
+    long long n_valid, n_nonocc;
+} les_hip_eval_row;
+int les_hip_evaluator_create(les_hip_ctx* ctx, const float* gt_host, const unsigned char* nonocc_host, float error_threshold, float precision,
+                             int max_rows, les_hip_evaluator** out);
+void les_hip_evaluator_destroy(les_hip_evaluator* ev);
+/* Appends one row for the maps d_labels / d_cost of view `mode`.  ENQUEUE ONLY, on the calling thread's stream of the context
+ * (les_hip_set_thread_stream is honoured): no synchronisation and no allocation (the first call, and a call with another omega or epsilon
+ * than the context's last pairwise call, build the 766-entry coefficient table and synchronise once).  The row describes the maps as they
+ * are at this point of the stream.  Every f32 term is added in fp64 in an order that depends on (H, W) only: the same maps give the same
+ * bits on any stream, beside any other work.  A NaN term makes its sum NaN, as on the host.  A full log is an error, returned before
+ * anything is enqueued. */
+int les_hip_evaluate(les_hip_ctx* ctx, les_hip_evaluator* ev, int mode, const les_hip_plane* d_labels, const float* d_cost, float lambda,
+                     float th_smooth, float omega, float epsilon, int index);
+/* Synchronises the calling thread's stream and copies the rows written so far (*n of them; capacity = room in rows_host). */
+int les_hip_evaluator_rows(les_hip_ctx* ctx, les_hip_evaluator* ev, les_hip_eval_row* rows_host, int capacity, int* n);
+/* replaces (on the device): the energy side of the reference's flow == energy self-check (LES/FastGCStereo.h:561-594) -- for every cell i of
+ * the batch (its target rect = the shared region) the energy of the CURRENT maps that the move can change: the cost of every pixel of the
+ * region plus every forward pair term with at least one endpoint in the region and both in the image.  Called after
+ * les_hip_batch_apply_masks it is the energy of the fused labelling, which the cut's value (flow0 + flow) equals.  d_energy: n doubles on
+ * the device.  Enqueue only on the calling thread's stream, except that the first call per (batch, view) allocates the partial-sum slots (hipMalloc:
+ * an implicit synchronisation) and the first call, or one with another omega or epsilon than the context's last pairwise call, builds the coefficient
+ * table and synchronises once.  A cell's value is a function of its rect and the maps, not of the other cells of the call. */
+int les_hip_batch_region_energy(les_hip_ctx* ctx, const les_hip_batch* batch, int mode, const les_hip_plane* d_labels, const float* d_cost,
+                                float lambda, float th_smooth, float omega, float epsilon, double* d_energy);
+
 /* replaces: PMStereoBase::doConsistencyCheck (LES/PMStereoBase.h:111-144) -- left-right check of the disparities of two
  * device label maps (H x W planes each): fail = 255 where |d_other(x -/+ d) - d| > threshold, 128 where the pixel maps
  * outside the other view, 0 otherwise.  d_failL / d_failR: H x W bytes on the device. */

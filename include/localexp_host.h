@@ -77,6 +77,10 @@ int les_gc_build_graphs(les_gc_ctx* ctx, int mode, int n, const les_hip_rect* re
 /* StereoEnergy::computeSmoothnessCost (LES/StereoEnergy.h:165-203) and the data term (sum of the current costs,
  * LES/Evaluator.h:119-121) of the context's current solution. */
 double les_gc_smoothness_cost(les_gc_ctx* ctx, int mode);
+/* The energy side of the flow == energy self-check (LES/FastGCStereo.h:561-594) for the context's CURRENT solution: per region the unary costs of
+ * its pixels plus every forward pair term with an endpoint in it (fusedEnergy with no node taking a proposal).  energy: n doubles.  The host
+ * counterpart of les_hip_batch_region_energy. */
+int les_gc_region_energy(les_gc_ctx* ctx, int mode, int n, const les_hip_rect* regions, double* energy);
 double les_gc_data_cost(les_gc_ctx* ctx, int mode);
 
 #ifdef __cplusplus

@@ -24,6 +24,7 @@ SYMBOLS = [
     "les_hip_memcpy_h2d", "les_hip_memcpy_d2h", "les_hip_memset", "les_hip_get_stats", "les_hip_strip_width", "les_hip_tiled_volume_bytes",
     "les_hip_calib_copy", "les_hip_calib_copy_wide", "les_hip_exchange_create", "les_hip_exchange_destroy", "les_hip_exchange_slot_floats",
     "les_hip_exchange_pack", "les_hip_exchange_unpack", "les_hip_exchange_tiles", "les_hip_fill_out_of_view", "les_hip_convert_volume_l2r", "les_hip_consistency_check", "les_hip_post_process",
+    "les_hip_evaluator_create", "les_hip_evaluator_destroy", "les_hip_evaluate", "les_hip_evaluator_rows", "les_hip_batch_region_energy",
 ]
 
 
@@ -49,6 +50,12 @@ class LesHipError(RuntimeError):
 class TiledStats(C.Structure):
     """les_hip_tiled_stats (include/localexp_hip.h)."""
     _fields_ = [("launches", C.c_int), ("unsolved", C.c_int), ("handed_cells", C.c_int), ("handed_nodes", C.c_longlong), ("host_ms", C.c_double)]
+
+
+class EvalRow(C.Structure):
+    """les_hip_eval_row (include/localexp_hip.h)."""
+    _fields_ = [("index", C.c_int), ("mode", C.c_int), ("data", C.c_double), ("smooth", C.c_double), ("good_valid", C.c_longlong),
+                ("good_nonocc", C.c_longlong), ("n_valid", C.c_longlong), ("n_nonocc", C.c_longlong)]
 
 
 class Params(C.Structure):
@@ -148,6 +155,11 @@ def load(path=None):
         "les_hip_tiled_volume_bytes": (C.c_size_t, [vp, ci]),
         "les_hip_fill_out_of_view": (ci, [vp, ci, ci, ci, ci, ci, vp]),
         "les_hip_convert_volume_l2r": (ci, [vp, vp, ci, ci, ci, ci, vp]),
+        "les_hip_evaluator_create": (ci, [vp, vp, vp, C.c_float, C.c_float, ci, C.POINTER(vp)]),
+        "les_hip_evaluator_destroy": (None, [vp]),
+        "les_hip_evaluate": (ci, [vp, vp, ci, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, ci]),
+        "les_hip_evaluator_rows": (ci, [vp, vp, vp, ci, C.POINTER(ci)]),
+        "les_hip_batch_region_energy": (ci, [vp, vp, ci, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -362,9 +374,58 @@ class Batch:
         self.e._chk(self.e.L.les_hip_batch_apply_masks(self.e.h, self.h, C.c_void_p(int(planes_dev)), C.c_void_p(int(masks_dev)), C.c_void_p(int(cur_dev)),
                                                        C.c_void_p(int(prop_dev)), C.c_void_p(int(labels_dev))))
 
+    def region_energy(self, labels_dev, cost_dev, energy_dev, mode=0, lambda_=1.0, th_smooth=1.0, omega=10.0, epsilon=0.01):
+        """Per cell, the energy of the current maps that a move on the cell can change (fusedEnergy of host/ExpansionMove.h, LES/FastGCStereo.h:561-594):
+        the costs of its region + the forward pair terms with an endpoint in it.  energy_dev: n float64 on the device.  Enqueue only."""
+        self.e._chk(self.e.L.les_hip_batch_region_energy(self.e.h, self.h, mode, C.c_void_p(int(labels_dev)), C.c_void_p(int(cost_dev)), lambda_, th_smooth,
+                                                         omega, epsilon, C.c_void_p(int(energy_dev))))
+
     def destroy(self):
         if self.h:
             self.e.L.les_hip_batch_destroy(self.h)
+            self.h = None
+
+
+class DeviceEvaluator:
+    """Evaluator::evaluate's numbers (LES/Evaluator.h:113-187) computed on the device from a view's device maps (include/localexp_hip.h:
+    les_hip_evaluator_*).  evaluate() only enqueues; rows() synchronises and reads the log.  One host thread at a time; one object per view."""
+
+    def __init__(self, energy, dispGT=None, nonocc=None, error_threshold=0.5, precision=-1.0, max_rows=4096):
+        self.e = energy
+        gt = np.ascontiguousarray(dispGT, np.float32) if dispGT is not None else None
+        no = np.ascontiguousarray(np.asarray(nonocc, bool), np.uint8) if nonocc is not None else None
+        assert gt is None or gt.shape == (energy.H, energy.W)
+        assert no is None or no.shape == (energy.H, energy.W)
+        self.max_rows = int(max_rows)
+        self.has_gt = gt is not None
+        h = C.c_void_p()
+        self.h = None
+        energy._chk(energy.L.les_hip_evaluator_create(energy.h, _ptr(gt), _ptr(no), C.c_float(error_threshold), C.c_float(precision), self.max_rows, C.byref(h)))
+        self.h = h
+
+    def evaluate(self, labels_ptr, cost_ptr, mode=0, index=0, lambda_=1.0, th_smooth=1.0, omega=10.0, epsilon=0.01):
+        self.e._chk(self.e.L.les_hip_evaluate(self.e.h, self.h, mode, C.c_void_p(int(labels_ptr)), C.c_void_p(int(cost_ptr)), lambda_, th_smooth, omega, epsilon,
+                                              int(index)))
+
+    def rows(self):
+        """The rows enqueued so far, as dicts: index, mode, data, smooth, energy, the four counts, and all / nonocc computed from the counts as
+        io.Evaluator.evaluate does (present whenever the evaluator holds ground truth; NaN when no pixel is valid / non-occluded)."""
+        buf = (EvalRow * self.max_rows)()
+        n = C.c_int(0)
+        self.e._chk(self.e.L.les_hip_evaluator_rows(self.e.h, self.h, buf, self.max_rows, C.byref(n)))
+        out = []
+        for r in buf[: n.value]:
+            row = dict(index=r.index, mode=r.mode, data=r.data, smooth=r.smooth, energy=r.data + r.smooth, good_valid=r.good_valid, good_nonocc=r.good_nonocc,
+                       n_valid=r.n_valid, n_nonocc=r.n_nonocc)
+            if self.has_gt:          # (NaN where nothing counts, as io.Evaluator)
+                row["all"] = float(100.0 * (1.0 - np.int64(r.good_valid) / r.n_valid)) if r.n_valid else float("nan")
+                row["nonocc"] = float(100.0 * (1.0 - np.int64(r.good_nonocc) / r.n_nonocc)) if r.n_nonocc else float("nan")
+            out.append(row)
+        return out
+
+    def close(self):
+        if self.h:
+            self.e.L.les_hip_evaluator_destroy(self.h)
             self.h = None
 
 

@@ -10,6 +10,7 @@
 #include "les_propose.h"
 #include "les_post.h"
 #include "les_pairwise.h"
+#include "les_eval.h"
 #include "les_maxflow.h"
 #include "les_maxflow_tiled.h"
 #include "les_maxflow_cell.h"
@@ -212,6 +213,11 @@ struct les_hip_batch {
     mutable int* d_mf_list = nullptr;
     mutable int mf_list_key = -1;
     mutable int mf_count[3] = {0, 0, 0};
+    // region energy of the cells (les_hip_eval.inc): partial sums, cells * region_chunks doubles per view (two host threads may run the two views of one
+    // batch), built on first use (region_chunks -1: not yet)
+    mutable std::mutex re_mu;
+    mutable double* d_region_part[2] = {nullptr, nullptr};
+    mutable int region_chunks = -1;
 };
 
 // Caller-owned scratch of the one-call operator (the reference's `Reusable`, LES/StereoEnergy.h:616-623): its own stream, a
@@ -269,5 +275,6 @@ float naive_alpha(const les_hip_ctx* c) { return c->naive_alpha; }
 #include "les_hip_context.inc"
 #include "les_hip_batch.inc"
 #include "les_hip_cuts.inc"
+#include "les_hip_eval.inc"
 #include "les_hip_ingest_post.inc"
 #include "les_hip_exchange.inc"

@@ -57,6 +57,7 @@ void les_hip_batch_destroy(les_hip_batch* b)
     if (b->d_mt_tiles) (void)hipFree(b->d_mt_tiles);
     if (b->d_mt_tiles_per_cell) (void)hipFree(b->d_mt_tiles_per_cell);
     if (b->d_mf_list) (void)hipFree(b->d_mf_list);
+    for (double* q : b->d_region_part) if (q) (void)hipFree(q);
     if (b->rs.disp) (void)hipFree(b->rs.disp);
     if (b->rs.idx) (void)hipFree(b->rs.idx);
     if (b->rs.state) (void)hipFree(b->rs.state);

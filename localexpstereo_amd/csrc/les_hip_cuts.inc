@@ -61,6 +61,21 @@ int mt_host_stage(MtHost* m, long long nodes, int cells)
     if (rc) { m->cap_nodes = 0; m->cap_cells = 0; return rc; }
     return LES_HIP_OK;
 }
+// The context's smoothness-coefficient table for (omega, epsilon), rebuilt (and the calling thread's stream synchronised) only when they change:
+// initSmoothnessCoeff (LES/StereoEnergy.h:131-163), max(epsilon, exp(-|dI|_1 / omega)) in float.  Shared by the graph construction and the
+// evaluation kernels (les_hip_eval.inc).
+int pw_table(les_hip_ctx* c, float omega, float epsilon)
+{
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->pw_omega == omega && c->pw_epsilon == epsilon && c->d_pw_tab) return LES_HIP_OK;
+    std::vector<float> tab(766);
+    for (int k = 0; k < 766; k++) tab[k] = std::max(epsilon, std::exp(-(float)k / omega));
+    if (!c->d_pw_tab) HIPCHECK(hipMalloc((void**)&c->d_pw_tab, tab.size() * sizeof(float)));
+    HIPCHECK(hipMemcpyAsync(c->d_pw_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, cur_stream(c)));
+    HIPCHECK(hipStreamSynchronize(cur_stream(c)));
+    c->pw_omega = omega; c->pw_epsilon = epsilon;
+    return LES_HIP_OK;
+}
 struct MtHostLease {                       // returns the MtHost to the pool on every exit path
     les_hip_ctx* c; MtHost* m;
     ~MtHostLease() { if (m) mt_host_release(c, m); }
@@ -86,17 +101,8 @@ int les_hip_batch_expansion_graph(les_hip_ctx* c, const les_hip_batch* b, int mo
     if (mode < 0 || mode > 1 || !c->v[mode].ipk) return fail(LES_HIP_ERR_ARG, "view %d was not supplied at creation", mode);
     if (b->n == 0) return LES_HIP_OK;
     HIPCHECK(hipSetDevice(c->p.device));                     // the calling host thread may be new (one thread per view)
-    std::unique_lock<std::mutex> lk(c->mu);
-    if (c->pw_omega != omega || c->pw_epsilon != epsilon || !c->d_pw_tab) {
-        // initSmoothnessCoeff (LES/StereoEnergy.h:131-163): max(epsilon, exp(-|dI|_1 / omega)) in float
-        std::vector<float> tab(766);
-        for (int k = 0; k < 766; k++) tab[k] = std::max(epsilon, std::exp(-(float)k / omega));
-        if (!c->d_pw_tab) HIPCHECK(hipMalloc((void**)&c->d_pw_tab, tab.size() * sizeof(float)));
-        HIPCHECK(hipMemcpyAsync(c->d_pw_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, cur_stream(c)));
-        HIPCHECK(hipStreamSynchronize(cur_stream(c)));
-        c->pw_omega = omega; c->pw_epsilon = epsilon;
-    }
-    lk.unlock();
+    const int trc = pw_table(c, omega, epsilon);
+    if (trc) return trc;
     const les::PairwiseParams pp{c->p.H, c->p.W, lambda, th_smooth};
     const les::GraphCell* cells = reinterpret_cast<const les::GraphCell*>(b->d_targets);
     const long long* offs = b->d_graph_off;

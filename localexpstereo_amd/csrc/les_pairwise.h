@@ -26,13 +26,16 @@ struct PairwiseParams {
 
 // smoothness coefficient of pixel (x, y) towards neighbour k: max(epsilon, exp(-|dI|_1 / omega)) via the 766-entry table
 // (|dI|_1 of 8-bit colours is an integer), 0 for pairs that leave the image  (LES/StereoEnergy.h:131-163)
+// |dI|_1 of two packed guide pixels: the index into the table
+__device__ __forceinline__ int pw_absdiff(uint32_t a, uint32_t b)
+{
+    return abs((int)(a & 255) - (int)(b & 255)) + abs((int)((a >> 8) & 255) - (int)((b >> 8) & 255)) + abs((int)((a >> 16) & 255) - (int)((b >> 16) & 255));
+}
 __device__ __forceinline__ float pw_coeff(const uint32_t* __restrict__ ipk, const float* __restrict__ wtab, int W, int H, int x, int y, int dx, int dy)
 {
     const int xn = x + dx, yn = y + dy;
     if (xn < 0 || xn >= W || yn < 0 || yn >= H) return 0.0f;
-    const uint32_t a = ipk[(size_t)y * W + x], b = ipk[(size_t)yn * W + xn];
-    const int ad = abs((int)(a & 255) - (int)(b & 255)) + abs((int)((a >> 8) & 255) - (int)((b >> 8) & 255)) + abs((int)((a >> 16) & 255) - (int)((b >> 16) & 255));
-    return wtab[ad];
+    return wtab[pw_absdiff(ipk[(size_t)y * W + x], ipk[(size_t)yn * W + xn])];
 }
 // std::min(a, b) of the reference / host code: (b < a) ? b : a  -- NaN in `a` propagates, unlike fminf
 __device__ __forceinline__ float pw_min(float a, float b) { return (b < a) ? b : a; }

@@ -11,7 +11,7 @@ from . import api
 
 DEFAULT_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host", "liblocalexp_host.so")
 SYMBOLS = ["les_gc_create", "les_gc_destroy", "les_gc_last_error", "les_gc_labels", "les_gc_costs", "les_gc_expansion_moves",
-           "les_gc_expansion_moves_prebuilt", "les_gc_solve_prebuilt", "les_gc_solve_residual", "les_gc_build_graphs", "les_gc_smoothness_cost", "les_gc_data_cost"]
+           "les_gc_expansion_moves_prebuilt", "les_gc_solve_prebuilt", "les_gc_solve_residual", "les_gc_build_graphs", "les_gc_smoothness_cost", "les_gc_data_cost", "les_gc_region_energy"]
 _lib = None
 
 
@@ -37,6 +37,7 @@ def load(path=None):
         "les_gc_solve_residual": (ci, [ci, vp, vp, vp, vp, ci, ci, vp, vp]),
         "les_gc_smoothness_cost": (C.c_double, [vp, ci]),
         "les_gc_data_cost": (C.c_double, [vp, ci]),
+        "les_gc_region_energy": (ci, [vp, ci, ci, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -151,6 +152,14 @@ class GraphCut:
 
     def data_cost(self, mode=0):
         return self.L.les_gc_data_cost(self.h, mode)
+
+    def region_energy(self, regions, mode=0):
+        """Per region, the energy of the current solution that a move on it can change (fusedEnergy, LES/FastGCStereo.h:561-594)."""
+        regions = api._rects(regions)
+        out = np.zeros(len(regions), np.float64)
+        if self.L.les_gc_region_energy(self.h, mode, len(regions), api._ptr(regions), api._ptr(out)):
+            raise RuntimeError(self.L.les_gc_last_error().decode())
+        return out
 
     def energy(self, mode=0):
         return self.data_cost(mode) + self.smoothness_cost(mode)

@@ -259,6 +259,26 @@ int les_gc_build_graphs(les_gc_ctx* c, int mode, int n, const les_hip_rect* regi
     return 0;
 }
 
+int les_gc_region_energy(les_gc_ctx* c, int mode, int n, const les_hip_rect* regions, double* energy)
+{
+    if (!c || mode < 0 || mode > 1 || n < 0 || (n > 0 && (!regions || !energy))) return fail("les_gc_region_energy: bad argument");
+    if (!c->E->hasImages(mode)) return fail("les_gc_region_energy: view %d has no image", mode);
+    for (int i = 0; i < n; i++) {
+        const les_hip_rect& r = regions[i];
+        if (r.w < 0 || r.h < 0 || r.x < 0 || r.y < 0 || r.x + r.w > c->W || r.y + r.h > c->H) return fail("les_gc_region_energy: region %d outside the image", i);
+    }
+    const CostMap& cur = c->costs[mode];
+    for (int i = 0; i < n; i++) {
+        const Rect region(regions[i].x, regions[i].y, regions[i].w, regions[i].h);
+        energy[i] = 0.0;
+        if (region.width == 0 || region.height == 0) continue;
+        // no node takes a proposal: the fused labelling is the current one
+        const std::vector<uint8_t> none((size_t)region.width * region.height, 0);
+        energy[i] = fusedEnergy(*c->E, c->labels[mode], cur, cur, Plane(), region, none, mode);
+    }
+    return 0;
+}
+
 double les_gc_smoothness_cost(les_gc_ctx* c, int mode) { return (c && mode >= 0 && mode < 2 && c->E->hasImages(mode)) ? c->E->computeSmoothnessCost(c->labels[mode], mode) : 0.0; }
 
 double les_gc_data_cost(les_gc_ctx* c, int mode)

@@ -116,6 +116,12 @@ class PMRunner:
                 fr = np.stack([x0, y0, x1 - x0, y1 - y0], 1).astype(np.int32).view(api.RECT_DT).reshape(-1)
                 self.init = _Shard(self, units, shared, fr, np.arange(len(units)), seeds_for(len(units), seed + 777), target_is_unit=True)
         self.sets = [(li, sh) for li, layer in enumerate(self.shards) for sh in layer]      # every (layer, shard of a disjoint set), in the order they are visited
+        self.set_index = [k for layer in self.shards for k in range(len(layer))]            # ... and each one's number within its layer
+        # the reference's doInnerLoopLog (LES/FastGCStereo.h:20,65): None, or a record (evaluator = api.DeviceEvaluator, params = the pairwise
+        # parameters, meta = []) the driver sets: after every disjoint set one evaluation of this view's maps is ENQUEUED (no synchronisation; the
+        # driver reads the evaluator's rows once at the end) and (iteration, layer, set) is appended to meta.  inner_iteration: the row index the
+        # driver gives the iteration that is running.
+        self.inner_log, self.inner_iteration = None, 0
         self.bytes_exchanged = 0
         self.exchanges = 0                       # all-gathers issued
         self._xevents = []
@@ -129,6 +135,7 @@ class PMRunner:
         self.gc_max_gap, self.gc_seconds, self.tiled_lockstep_ms = 0.0, Counter(), {}
         self._gc_staging = self._gc_status = None      # _gc_buffers: graphs and masks of a lock-step, device + pinned host; _status: a word per cell
         self._gc_tiled_ws = None                 # _cut_on_device: scratch of the tiled solver (runs without coarse layers have none)
+        self._gc_check = None                    # _checked_moves: region energies before / after and flows of a lock-step's cells
         self._gc_snap = self._gc_fail = None     # _gc_set_without_round_trips: roll-back copy of labels / costs, the failure word
         self._joint_staging, self._joint = None, {}      # gc_iteration_joint (first runner only): staging for the cells of all views, set index -> record
         self._dumped = dict(tiled=0, tiled_written=0, samples=0, worst=0.012)     # tooling dumps: lock-steps seen / files written / slowest host cut so far (s)
@@ -178,6 +185,26 @@ class PMRunner:
 
     def _sync(self):
         self.e.synchronize()
+
+    def _log_set(self, i):
+        """Inner-loop log: one device evaluation after set i of self.sets, enqueued on the runner's stream."""
+        if self.inner_log is None:
+            return
+        lg = self.inner_log
+        lg.evaluator.evaluate(self.labels.data_ptr(), self.cur.data_ptr(), mode=self.mode, index=len(lg.meta), **lg.params)
+        lg.meta.append((self.inner_iteration, self.sets[i][0], self.set_index[i]))
+
+    def energy(self, params):
+        """PMStereoBase::computeCurrentEnergy (LES/PMStereoBase.h:263-270) of this view's device maps, computed on the device: (data, smooth) =
+        (sum of the current costs, sum of the forward smoothness terms).  params: lambda_, th_smooth, omega, epsilon.  Synchronises."""
+        ev = api.DeviceEvaluator(self.e, max_rows=1)
+        try:
+            ev.evaluate(self.labels.data_ptr(), self.cur.data_ptr(), mode=self.mode, index=0, lambda_=params["lambda_"], th_smooth=params["th_smooth"],
+                        omega=params["omega"], epsilon=params["epsilon"])
+            row = ev.rows()[0]
+        finally:
+            ev.close()
+        return row["data"], row["smooth"]
 
     def init_labels(self):
         """initCurrentFast (LES/FastGCStereo.h:94-115): random label per layer-0 cell + its unit-region cost."""
@@ -229,13 +256,14 @@ class PMRunner:
 
     def iteration(self, iteration):
         """One PatchMatch iteration over all layers (LES/FastGCStereo.h:143-157 with doGC == false)."""
-        for li, sh in self.sets:
+        for i, (li, sh) in enumerate(self.sets):
             for kind, m in self._proposals(li, iteration) if sh.n else ():
                 self._propose(sh, kind, m)
                 sh.batch.wta(sh.planes.data_ptr(), self.cur.data_ptr(), self.prop.data_ptr(), self.labels.data_ptr())
             if self.world == 1 or self.device.type != "cuda":
                 self._sync()                     # (bounds the launch queue; with several ranks on GPUs the collective orders the stream itself)
             self._exchange(sh)
+            self._log_set(i)
 
     # -- graph-cut iterations (LES/FastGCStereo.h:171-185: the main loop, doGC == true) ----------------------------
     # Proposals and unary costs come from the GPU exactly as in iteration(); the winner-take-all update is replaced by
@@ -326,13 +354,15 @@ class PMRunner:
         """Does the device try to cut this lock-step?"""
         return bool(lk.n) and (self.device_cuts == "all" or (self.device_cuts == "fine" and lk.max_cell_nodes <= api.Batch.MAXFLOW_MAX_NODES))
 
-    def _cut_on_device(self, lk, li=None, iteration=None):
+    def _cut_on_device(self, lk, li=None, iteration=None, flows=None):
         """Cuts the graphs at lk.payload into lk.masks: one workgroup per cell where every cell fits the LDS, else the tiled solver.  -> True: every
         cell was cut (else the status words say which were not).  li, iteration: where the lock-step belongs, for the per-layer statistics of the
-        tiled solver and LES_DUMP_TILED (the joint form keeps neither)."""
+        tiled solver and LES_DUMP_TILED (the joint form keeps neither).  flows: a float64 device tensor that receives every cell's flow through
+        its n-links (the device self-check), or None."""
         st = self._status(lk.n)
+        fp = flows.data_ptr() if flows is not None else None
         if lk.max_cell_nodes <= api.Batch.MAXFLOW_MAX_NODES:
-            lk.batch.solve_graphs(lk.payload.data_ptr(), lk.masks.data_ptr(), st.data_ptr())
+            lk.batch.solve_graphs(lk.payload.data_ptr(), lk.masks.data_ptr(), st.data_ptr(), flows_dev=fp)
             done = not bool(st.any().item())         # (the only synchronisation of the lock-step)
         else:
             need = lk.batch.tiled_workspace_bytes() + 256
@@ -342,7 +372,7 @@ class PMRunner:
             ws, sec = self._gc_tiled_ws, self.gc_seconds
             wp = (ws.data_ptr() + 255) & ~255        # (the solver wants 256-byte alignment)
             t0 = time.perf_counter()
-            nl = lk.batch.solve_graphs_tiled(lk.payload.data_ptr(), lk.masks.data_ptr(), st.data_ptr(), wp, ws.numel() - (wp - ws.data_ptr()))
+            nl = lk.batch.solve_graphs_tiled(lk.payload.data_ptr(), lk.masks.data_ptr(), st.data_ptr(), wp, ws.numel() - (wp - ws.data_ptr()), flows_dev=fp)
             sec["tiled_launches"] += nl
             sec["tiled_locksteps"] += 1
             if li is not None:
@@ -358,9 +388,10 @@ class PMRunner:
             self.gc_seconds["cells_cut_on_device"] += lk.n
         return done
 
-    def _cut_on_host(self, lk, nthreads, partial):
+    def _cut_on_host(self, lk, nthreads, partial, flows=None):
         """Copies the graphs down, cuts them on the host cores, copies the masks up.  partial: when the device tried and gave up on only SOME
-        cells (their status word is non-zero), only those are cut again and the device's masks of the others stay.
+        cells (their status word is non-zero), only those are cut again and the device's masks of the others stay.  flows: as _cut_on_device
+        (the cells cut here get the host solver's flow).
         -> (t1, t2): the clock before and after the cuts proper."""
         self._sync()
         lk.payload_host.copy_(lk.payload)
@@ -371,24 +402,32 @@ class PMRunner:
             lk.masks_host.copy_(lk.masks)
             regions, offsets = np.ascontiguousarray(regions[failed]), np.ascontiguousarray(offsets[failed])
             self.gc_seconds["cells_recut_on_host"] += len(failed)
-        lgc.solve_prebuilt(regions, lk.payload_host.numpy(), offsets, lk.masks_host.numpy(), nthreads=nthreads)
+        fh = np.zeros(len(regions), np.float64) if flows is not None else None
+        lgc.solve_prebuilt(regions, lk.payload_host.numpy(), offsets, lk.masks_host.numpy(), nthreads=nthreads, flows_out=fh)
         t2 = time.perf_counter()
         lk.masks.copy_(lk.masks_host)
+        if flows is not None:
+            fd = torch.from_numpy(fh).to(self.device)
+            if len(regions) < lk.n:
+                flows[torch.from_numpy(np.asarray(failed, np.int64)).to(self.device)] = fd
+            else:
+                flows[: lk.n] = fd
         return t1, t2
 
-    def _cut(self, lk, nthreads, partial, li=None, iteration=None):
+    def _cut(self, lk, nthreads, partial, li=None, iteration=None, flows=None):
         """The cuts of a lock-step: on the device where device_cuts says so, on the host where not or when the device gave up.
         -> (every cell cut on the device, t1, t2): the clock before and after the host's cuts."""
-        if self._on_device(lk) and self._cut_on_device(lk, li, iteration):
+        if self._on_device(lk) and self._cut_on_device(lk, li, iteration, flows):
             t = time.perf_counter()
             return True, t, t
-        return (False,) + self._cut_on_host(lk, nthreads, partial)
+        return (False,) + self._cut_on_host(lk, nthreads, partial, flows)
 
     def _moves_on_host_maps(self, sh, nthreads, check):
         """The lock-step in the reference's shape (check=True or device_graph=False): the proposals' costs go to the host, gc.expansion_moves builds
         and cuts the graphs there on the host-resident solution (with the reference's flow == energy self-check when `check`), and the fused maps
         come back.  -> (t1, t2) as _cut_on_host."""
         self._sync()
+        self.gc_seconds["host_graph_locksteps"] += 1
         self._prop_host.copy_(self.prop)
         planes = sh.planes[: sh.n].cpu().numpy()
         t1 = time.perf_counter()
@@ -397,6 +436,55 @@ class PMRunner:
         t2 = time.perf_counter()
         self.labels.copy_(torch.from_numpy(self.gc.labels[self.mode]))
         self.cur.copy_(torch.from_numpy(self.gc.costs[self.mode]))
+        return t1, t2
+
+    def _region_energy(self, sh, out):
+        p = self.gc.params
+        sh.batch.region_energy(self.labels.data_ptr(), self.cur.data_ptr(), out.data_ptr(), mode=self.mode, lambda_=p["lambda_"], th_smooth=p["th_smooth"],
+                               omega=p["omega"], epsilon=p["epsilon"])
+
+    def _checked_moves(self, sh, li, iteration, nthreads):
+        """One lock-step on the device path with the reference's flow == energy self-check (LES/FastGCStereo.h:561-594) kept on the device: the graphs
+        with their t-link flow, the cuts with their flow values, the energy of every cell's region before and after the masks are applied
+        (les_hip_batch_region_energy).  Per cell gap = |flow0 + flow - E_after| / max(1, |E_after|), the host route's formula (host/les_gc.cpp);
+        gc_max_gap is the largest; gc_seconds["moves_raised"] counts the cells whose move raised the energy by more than 1e-5 max(1, |E_after|).
+        Cells the device hands to the host solver are checked with that solver's flow.  A diagnostic mode: it synchronises.
+        gc_seconds["own_max_gap_<solver>"] keeps every device solver's own worst gap, gc_seconds["locksteps_checked_<solver>"] how many lock-steps
+        each one cut (cell_kernel, lds_1024, lds_512: the most general one-workgroup kernel of the lock-step; tiled).  -> (t1, t2) as _cut_on_host."""
+        p, n, sec = self.gc.params, sh.n, self.gc_seconds
+        if self._gc_check is None or self._gc_check.shape[1] < n:
+            self._gc_check = torch.zeros((3, max([n] + [s.n for _, s in self.sets])), dtype=torch.float64, device=self.device)
+        e_before, e_after, flows = (self._gc_check[k, :n] for k in range(3))
+        self._region_energy(sh, e_before)
+        flow0 = sh.batch.expansion_graph(sh.planes.data_ptr(), self.labels.data_ptr(), self.cur.data_ptr(), self.prop.data_ptr(), sh.payload.data_ptr(),
+                                         mode=self.mode, lambda_=p["lambda_"], th_smooth=p["th_smooth"], omega=p["omega"], epsilon=p["epsilon"], want_flow0=True)
+        _, t1, t2 = self._cut(sh, nthreads, True, li, iteration, flows=flows)
+        self._apply(sh, sh.masks.data_ptr())
+        self._region_energy(sh, e_after)
+        self._sync()
+        eb, ea, fl = (t.cpu().numpy() for t in (e_before, e_after, flows))
+        scale = np.maximum(1.0, np.abs(ea))
+        gap = np.abs(flow0 + fl - ea) / scale
+        if self._on_device(sh):
+            # the device solvers push float residuals: next to the 1e6 terminals of invalid labels a push rounds at 0.06, and the tiled solver adds its
+            # flow in fixed-point units, so a solver's own flow VALUE can be coarser than 1e-5 although its mask is a minimum cut.  Where it is, the
+            # lock-step is checked against the host solver's flow on the same graphs (the value of a minimum cut does not depend on who computes
+            # it); the solver's own worst gap is kept per kind.
+            kind = "tiled" if sh.max_cell_nodes > api.Batch.MAXFLOW_MAX_NODES else ("cell_kernel", "lds_1024", "lds_512")[max(0, sh.batch.graph_solver_kind)]
+            sec[f"own_max_gap_{kind}"] = max(sec[f"own_max_gap_{kind}"], float(np.max(np.where(np.isnan(gap), np.inf, gap))) if n else 0.0)
+            sec[f"locksteps_checked_{kind}"] += 1
+            if not np.all(gap <= 1e-5):
+                th = time.perf_counter()
+                sh.payload_host.copy_(sh.payload)
+                fh, scratch = np.zeros(n, np.float64), np.zeros(max(1, sh.graph_nodes), np.uint8)
+                lgc.solve_prebuilt(sh.regions, sh.payload_host.numpy(), sh.graph_off, scratch, nthreads=nthreads, flows_out=fh)
+                gap = np.abs(flow0 + fh - ea) / scale
+                sec["locksteps_checked_with_host_flow"] += 1
+                sec["check_host_flow_seconds"] += time.perf_counter() - th      # (the check's own re-solve, not a cut of the run: host_cuts stays 0)
+        worst = float(np.max(np.where(np.isnan(gap), np.inf, gap))) if n else 0.0
+        self.gc_max_gap = max(self.gc_max_gap, worst)
+        sec["moves_raised"] += int(np.count_nonzero(ea > eb + 1e-5 * scale))
+        sec["cells_checked_on_device"] += n
         return t1, t2
 
     def _book(self, li, t0, t1, t2):
@@ -482,16 +570,22 @@ class PMRunner:
 
     def gc_iteration(self, iteration, check=False, nthreads=0):
         """One graph-cut iteration of this view over all layers and sets."""
-        host_maps = check or not self.device_graph
+        device_check = check == "device"         # the self-check on the device path (_checked_moves); True: the reference's shape, on the host
+        if device_check and not self.device_graph:
+            raise ValueError('check="device" needs device-built graphs (begin_gc(device_graph=True))')
+        host_maps = (bool(check) and not device_check) or not self.device_graph
         if host_maps:
             self.sync_gc_state()
-        for li, sh in self.sets:
-            per_lock_step = sh.n and (host_maps or not self._gc_set_without_round_trips(sh, li, iteration))
+        for i, (li, sh) in enumerate(self.sets):
+            per_lock_step = sh.n and (host_maps or device_check or not self._gc_set_without_round_trips(sh, li, iteration))
             for kind, m in self._proposals(li, iteration) if per_lock_step else ():
                 t0 = time.perf_counter()
                 self._propose(sh, kind, m)
                 if host_maps:
-                    t1, t2 = self._moves_on_host_maps(sh, nthreads, check)
+                    t1, t2 = self._moves_on_host_maps(sh, nthreads, bool(check))
+                elif device_check:
+                    self._gc_buffers(sh)
+                    t1, t2 = self._checked_moves(sh, li, iteration, nthreads)
                 else:
                     self._gc_buffers(sh)
                     self._graph(sh, sh.payload.data_ptr())
@@ -504,6 +598,7 @@ class PMRunner:
                 if host_maps:
                     torch.from_numpy(self.gc.labels[self.mode]).copy_(self.labels)
                     torch.from_numpy(self.gc.costs[self.mode]).copy_(self.cur)
+            self._log_set(i)
         self._sync()
 
     def _joint_set(self, runners, k):
@@ -547,6 +642,8 @@ class PMRunner:
                 for r, sh, base in lk.views:
                     r._apply(sh, lk.masks.data_ptr() + base)
                 r0._book(li, t0, t1, t2)
+            for r in runners:
+                r._log_set(k)
         r0._sync()
 
     def run(self, pm_iterations, iterations=0, graph_cut=None):

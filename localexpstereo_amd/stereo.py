@@ -7,6 +7,7 @@ Evaluator -> numpy (io.py).  One process per GPU: pass rank/world to shard the c
 """
 import os
 import time
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -20,7 +21,8 @@ PARAMS_BF = dict(PARAMS_GF, lambda_=20.0, windR=20, eps=10.0, filter="BF")
 
 
 class FastGCStereo:
-    def __init__(self, energy, imL, imR, params, device="cuda", rank=0, world=1, seed=1, host_threads=0, device_cuts=None, random_vdisp=None):
+    def __init__(self, energy, imL, imR, params, device="cuda", rank=0, world=1, seed=1, host_threads=0, device_cuts=None, random_vdisp=None,
+                 evaluate_on_device=False, inner_loop_log=False, check_flow_energy=False):
         self.e, self.imL, self.imR, self.p = energy, imL, imR, dict(PARAMS_GF, **params)
         self.random_vdisp = random_vdisp          # maxVDisp of the RANDOM proposals (pm.PMRunner); None: the energy's setting (0 by default)
         # Parameters::filterName: the energy aggregates with the filter it was built with; a params dict that names another one is a mistake
@@ -29,8 +31,23 @@ class FastGCStereo:
         self.device, self.rank, self.world, self.seed = device, rank, world, seed
         self.units, self.table = [], []
         self.evaluator = None
+        self._dev_eval, self._inner = None, {}      # run(): the device evaluators of the log rows / per view of the inner-loop log
         self.log = []
-        self.check_flow_energy = False
+        # the reference's flow == energy self-check (LES/FastGCStereo.h:561-594).  True: the iteration moves to the host route (host maps, host graph
+        # construction, host cuts: what the reference does).  "device": it stays on the device path -- device graphs, device cuts, the region energies of
+        # les_hip_batch_region_energy before and after every lock-step (pm.PMRunner._checked_moves); gc_max_gap is the largest relative
+        # |flow - energy|, gc_moves_raised the number of cells whose move raised the energy.  A diagnostic mode (it synchronises every lock-step).
+        self.check_flow_energy = check_flow_energy
+        self.gc_moves_raised = 0
+        # Opt-in: every row of the log from les_hip_evaluate (csrc/les_eval.h) instead of the host route (copy the disparities down, copy labels
+        # and costs into the host graph-cut context, sum there): no copy of a map, no host sum, and `smooth` is a number in every row
+        # (the host route has no context before the graph-cut iterations and logs NaN there).
+        self.evaluate_on_device = bool(evaluate_on_device)
+        # Opt-in, the reference's doInnerLoopLog (LES/FastGCStereo.h:20,65): one row per view after every disjoint set of every layer, in
+        # PatchMatch and graph-cut iterations, enqueued without a synchronisation and read once at the end of run() into self.inner_log
+        # (iteration, layer, set, mode, data, smooth, energy, all, nonocc; no time: nothing synchronised).  Implies device evaluation.
+        self.inner_loop_log = bool(inner_loop_log)
+        self.inner_log = []
         # two-view runs: graph-cut iterations of the two views in parallel host threads.  Pays when the host cuts dominate
         # (1436 x 992: 14.2 -> 11.3 s); on small images the shared stream's synchronisations cost more (cones: 2.3 -> 3.1 s)
         # (never with several ranks: the per-set all-gathers of the two views would be issued from two threads in an order
@@ -83,7 +100,19 @@ class FastGCStereo:
         finally:
             self.eval_seconds += time.perf_counter() - te
 
+    def _pairwise(self):
+        return dict(lambda_=float(self.p["lambda_"]), th_smooth=float(self.p["th_smooth"]), omega=float(self.p["omega"]), epsilon=float(self.p["epsilon"]))
+
     def _evaluate_body(self, index, mode, runner, g, t0):
+        if self._dev_eval is not None:
+            ev = self._dev_eval[mode]
+            ev.evaluate(runner.labels.data_ptr(), runner.cur.data_ptr(), mode=mode, index=index, **self._pairwise())
+            r = ev.rows()[-1]
+            row = dict(index=index, time=time.perf_counter() - t0 - self.eval_seconds, energy=r["data"] + r["smooth"], data=r["data"], smooth=r["smooth"])
+            if self.evaluator is not None:
+                row["all"], row["nonocc"] = r["all"], r["nonocc"]
+            self.log.append(row)
+            return
         disp = runner.disparities().cpu().numpy()
         if g is not None and runner.gc is g:
             runner.sync_gc_state()
@@ -102,6 +131,16 @@ class FastGCStereo:
         """FastGCStereo::run (LES/FastGCStereo.h:133-227).  Returns (labeling, rawlabeling) of the left view as
         H x W x 4 float arrays (the raw one is the labelling before the two-view post-processing).  `labeling`: optional
         start labelling (the reference's `labeling` argument; every view starts from it, as in the reference)."""
+        try:
+            return self._run(maxIteration, viewModes, pmInit, labeling)
+        finally:                 # the device evaluators of the run, also when it raised
+            for ev in list((self._dev_eval or {}).values()) + [lg.evaluator for lg in self._inner.values()]:
+                ev.close()
+            self._dev_eval, self._inner = None, {}
+
+    def _run(self, maxIteration, viewModes, pmInit, labeling):
+        if self.inner_loop_log and self.world > 1:
+            raise ValueError("inner_loop_log is a single-rank log: with several ranks a rank holds only its band of a set's cells until the exchange")
         t0 = time.perf_counter()
         self.eval_seconds = 0.0
         # Several ranks and two views: the views are independent until the post-processing (LES/FastGCStereo.h:172-185), so the ranks are
@@ -123,6 +162,18 @@ class FastGCStereo:
             viewModes = (all_views[mine],)
         runners = {m: pm.PMRunner(self.e, self.units, self.table, seed=self.seed + 7919 * m, rank=view_rank, world=view_world,
                                   device=self.device, mode=m, group=view_group, random_vdisp=self.random_vdisp) for m in viewModes}
+        # device evaluation: one evaluator for the rows of the log (the left view's, as the host route's), one per view for the inner-loop log
+        # (the ground truth is the left view's: the right view's rows carry the energy only)
+        self._dev_eval, self.inner_log, inner = None, [], self._inner
+        ev_args = {} if self.evaluator is None else dict(dispGT=self.evaluator.gt, nonocc=self.evaluator.nonocc, error_threshold=self.evaluator.threshold,
+                                                         precision=self.precision)
+        if self.evaluate_on_device or self.inner_loop_log:
+            self._dev_eval = {0: api.DeviceEvaluator(self.e, max_rows=maxIteration + pmInit + 3, **ev_args)}
+        if self.inner_loop_log:
+            for m in viewModes:
+                r = runners[m]
+                ev = api.DeviceEvaluator(self.e, max_rows=max(1, len(r.sets) * (maxIteration + pmInit)), **(ev_args if m == 0 else {}))
+                inner[m] = r.inner_log = SimpleNamespace(evaluator=ev, params=self._pairwise(), meta=[])
         g = gc.GraphCut(self.imL, self.imR, lambda_=self.p["lambda_"], th_smooth=self.p["th_smooth"], omega=self.p["omega"],
                         epsilon=self.p["epsilon"]) if maxIteration > 0 else None
         for m in viewModes:
@@ -137,9 +188,10 @@ class FastGCStereo:
         self.init_seconds = time.perf_counter() - t0 - self.eval_seconds
         for it in range(pmInit):
             for m in viewModes:
+                runners[m].inner_iteration = it + 1
                 runners[m].iteration(it)
                 self._evaluate(it + 1, m, runners[m], None, t0)
-        self.gc_max_gap, self.gc_seconds = 0.0, {}
+        self.gc_max_gap, self.gc_seconds, self.gc_moves_raised = 0.0, {}, 0
         if maxIteration > 0:
             for m in viewModes:
                 if self.device_cuts is not None:
@@ -153,6 +205,8 @@ class FastGCStereo:
                     torch.cuda.set_device(dev.index if dev.index is not None else main_device)   # current device is per host thread
                 runners[m].gc_iteration(it, check=self.check_flow_energy, nthreads=self.host_threads if nthreads is None else nthreads)
             for it in range(maxIteration):
+                for m in viewModes:
+                    runners[m].inner_iteration = it + 1 + pmInit
                 if len(viewModes) == 2 and self.joint_views and self.world == 1 and not self.check_flow_energy:
                     # the two views are independent until the post-processing (LES/FastGCStereo.h:172-185)
                     pm.PMRunner.gc_iteration_joint([runners[m] for m in viewModes], it, nthreads=self.host_threads)
@@ -201,8 +255,9 @@ class FastGCStereo:
                     self._evaluate(it + 1 + pmInit, m, runners[m], g, t0)
             for m in viewModes:
                 self.gc_max_gap = max(self.gc_max_gap, runners[m].gc_max_gap)
-                for k, v in runners[m].gc_seconds.items():
-                    self.gc_seconds[k] = self.gc_seconds.get(k, 0.0) + v
+                self.gc_moves_raised += int(runners[m].gc_seconds.get("moves_raised", 0))
+                for k, v in runners[m].gc_seconds.items():      # sums over the views; a worst gap is the worst of the views
+                    self.gc_seconds[k] = max(self.gc_seconds.get(k, 0.0), v) if k.startswith("own_max_gap_") else self.gc_seconds.get(k, 0.0) + v
         if view_root:
             # the view groups meet: every rank receives both final label maps (16 B/px each) from the first rank of each group
             import torch.distributed as dist
@@ -238,6 +293,11 @@ class FastGCStereo:
                 self.tiled_lockstep_stats[f"view{m}_layer{li}"] = dict(locksteps=len(a), ms_p50=round(float(np.percentile(a[:, 0], 50)), 2), ms_p90=round(float(np.percentile(a[:, 0], 90)), 2),
                                                                        ms_max=round(float(a[:, 0].max()), 2), ms_sum=round(float(a[:, 0].sum()), 1), launches_p50=int(np.percentile(a[:, 1], 50)),
                                                                        launches_max=int(a[:, 1].max()))
+        # the inner-loop log: read once, here (each view's rows were enqueued on the stream that ran its sets)
+        for m, lg in inner.items():
+            for (iteration, li, k), r in zip(lg.meta, lg.evaluator.rows()):
+                self.inner_log.append(dict(iteration=iteration, layer=li, set=k, mode=m, data=r["data"], smooth=r["smooth"], energy=r["data"] + r["smooth"],
+                                           all=r.get("all"), nonocc=r.get("nonocc")))
         for r in runners.values():
             r.close()
         if g is not None:
