@@ -191,6 +191,23 @@ int les_hip_batch_kernel_kind(const les_hip_ctx* ctx, const les_hip_batch* b, in
 int les_hip_batch_run(les_hip_ctx* ctx, const les_hip_batch* b, int mode, const les_hip_plane* planes,
                       int planes_on_device, float* out_dev, int check);
 
+/* ---- the unary costs of a whole label map in one dense device pass (csrc/les_dense.h)
+ * replaces: the warm-start branch of FastGCStereo::initCurrentFast (LES/FastGCStereo.h:116-130): for every pixel p = (x, y) of `region`
+ * (NULL: the whole image)
+ *     d_cost[y * W + x] = ComputeUnaryPotential(filterRect = (p +- windR) clipped to the image, targetRect = (x, y, 1, 1), d_labels[y * W + x])
+ * (check != 0; ComputeUnaryPotentialWithoutCheck for check == 0) -- what les_hip_unary_batch returns for those region.w x region.h calls, on
+ * every kind of context (both energies, Plane::v, every filter, the interpolation set at call time, min_disparity, the 1e6 sentinel, NaN results
+ * where the quadratic read gives NaN).  Pixels outside `region` are not written.  d_labels, d_cost: H * W elements in DEVICE memory.  One
+ * launch of a kernel whose unit of work is a pixel with its own plane: a workgroup per tile of pixels, the tile's guide statistics and guide
+ * in LDS, a wave per pixel.  Asynchronous on the calling thread's stream (les_hip_set_thread_stream); it stages through nothing the context
+ * owns, so two host threads with their own streams may call it concurrently on one context.  LES_HIP_ERR_ARG for a view without data, a
+ * region outside the image or null pointers; an empty region is a no-op. */
+int les_hip_unary_labels(les_hip_ctx* ctx, int mode, const les_hip_rect* region, const les_hip_plane* d_labels, float* d_cost, int check);
+/* Diagnostic: 1 = the dense kernel serves this context and view (every context this build can create: the kernel is instantiated for each
+ * guided-filter radius the strip tables serve -- 1 .. 10, 12, 15 -- and takes the radius of the bilateral / unfiltered aggregation at run
+ * time), 0 = one job per pixel on the strip kernel (no build does that today), -1 = bad argument. */
+int les_hip_unary_labels_kind(const les_hip_ctx* ctx, int mode);
+
 /* ---- hypothesis generation for the cells of a prepared batch (one proposal per cell per call) ----
  * replaces: IProposer::startIterations/getNextProposal as driven by LES/FastGCStereo.h:41-48, for
  * ExpansionProposer (LES/Proposer.h:62-79), RandomProposer (:120-152, `m` = outerIter + iter) and

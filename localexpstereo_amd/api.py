@@ -25,6 +25,7 @@ SYMBOLS = [
     "les_hip_calib_copy", "les_hip_calib_copy_wide", "les_hip_exchange_create", "les_hip_exchange_destroy", "les_hip_exchange_slot_floats",
     "les_hip_exchange_pack", "les_hip_exchange_unpack", "les_hip_exchange_tiles", "les_hip_fill_out_of_view", "les_hip_convert_volume_l2r", "les_hip_consistency_check", "les_hip_post_process",
     "les_hip_evaluator_create", "les_hip_evaluator_destroy", "les_hip_evaluate", "les_hip_evaluator_rows", "les_hip_batch_region_energy",
+    "les_hip_unary_labels", "les_hip_unary_labels_kind",
 ]
 
 
@@ -160,6 +161,8 @@ def load(path=None):
         "les_hip_evaluate": (ci, [vp, vp, ci, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, ci]),
         "les_hip_evaluator_rows": (ci, [vp, vp, vp, ci, C.POINTER(ci)]),
         "les_hip_batch_region_energy": (ci, [vp, vp, ci, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, vp]),
+        "les_hip_unary_labels": (ci, [vp, ci, vp, vp, vp, ci]),
+        "les_hip_unary_labels_kind": (ci, [vp, ci]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -594,6 +597,17 @@ class HipCostVolumeEnergy:
         assert len(frs) == len(trs) == len(pls)
         self._chk(self.L.les_hip_unary_batch(self.h, mode, len(frs), _ptr(frs), _ptr(trs), _ptr(pls), _ptr(costs_map), int(check)))
         return costs_map
+
+    def unary_labels(self, labels_ptr, cost_ptr, mode=0, region=None, check=True):
+        """les_hip_unary_labels: the unary cost of every pixel's own label (the warm-start branch of initCurrentFast, LES/FastGCStereo.h:116-130)
+        in one dense device pass.  labels_ptr / cost_ptr: device addresses of the H x W plane map and the H x W float map; region: (x, y, w, h),
+        None = the whole image; pixels outside it are not written.  Enqueue only (the calling thread's stream)."""
+        rg = _rects([region]) if region is not None else None
+        self._chk(self.L.les_hip_unary_labels(self.h, mode, _ptr(rg), C.c_void_p(int(labels_ptr)), C.c_void_p(int(cost_ptr)), int(check)))
+
+    def unary_labels_kind(self, mode=0):
+        """1: the dense kernel (csrc/les_dense.h) serves unary_labels on this context and view, 0: one job per pixel, -1: bad argument."""
+        return int(self.L.les_hip_unary_labels_kind(self.h, mode))
 
     # -- dual-view post-processing (LES/PMStereoBase.h:111-256) on device label maps -----------------
     def consistency_check(self, labelsL_dev, labelsR_dev, failL_dev, failR_dev, threshold=1.5):

@@ -16,6 +16,7 @@
 #include "les_maxflow_cell.h"
 #include "les_bilateral.h"
 #include "les_vdisp.h"
+#include "les_dense.h"
 
 #include "../host/ResidualCut.h"      // the host cores' finisher of the tiled max-flow (plain C++: search trees / push-relabel on a residual graph)
 
@@ -278,3 +279,4 @@ float naive_alpha(const les_hip_ctx* c) { return c->naive_alpha; }
 #include "les_hip_eval.inc"
 #include "les_hip_ingest_post.inc"
 #include "les_hip_exchange.inc"
+#include "les_hip_dense.inc"

@@ -100,6 +100,30 @@ public:
             fprintf(stderr, "HipCostVolumeEnergy: %s\n", les_hip_last_error());
     }
 
+    // The unary cost of every pixel's own label (the warm-start branch of FastGCStereo::initCurrentFast, LES/FastGCStereo.h:116-130): for
+    // every pixel p of `region` (the whole image by default), cost_map(p) = ComputeUnaryPotential((p +- windR) & image, (p, 1 x 1), labels(p)),
+    // in one dense device pass (les_hip_unary_labels).  labels, cost_map: width * height elements in HOST memory; pixels outside the region
+    // keep what cost_map held.  Returns false (and reports on stderr) when the library refuses the call.
+    bool ComputeUnaryPotentialOfLabels(const Plane* labels, float* cost_map, int mode = 0, bool check = true, const Rect* region = nullptr) const
+    {
+        static_assert(sizeof(Plane) == sizeof(les_hip_plane), "ABI layout");
+        const size_t P = (size_t)width * height;
+        les_hip_plane* d_lab = nullptr;
+        float* d_cost = nullptr;
+        bool ok = les_hip_malloc(ctx_, (void**)&d_lab, P * sizeof(les_hip_plane)) == LES_HIP_OK && les_hip_malloc(ctx_, (void**)&d_cost, P * sizeof(float)) == LES_HIP_OK;
+        ok = ok && les_hip_memcpy_h2d(ctx_, d_lab, labels, P * sizeof(les_hip_plane)) == LES_HIP_OK && les_hip_memcpy_h2d(ctx_, d_cost, cost_map, P * sizeof(float)) == LES_HIP_OK;
+        if (ok) {
+            les_hip_rect r{0, 0, width, height};
+            if (region) r = les_hip_rect{region->x, region->y, region->width, region->height};
+            ok = les_hip_unary_labels(ctx_, mode, &r, d_lab, d_cost, check ? 1 : 0) == LES_HIP_OK;
+        }
+        ok = ok && les_hip_memcpy_d2h(ctx_, cost_map, d_cost, P * sizeof(float)) == LES_HIP_OK;
+        if (!ok) fprintf(stderr, "HipCostVolumeEnergy: %s\n", les_hip_last_error());
+        if (d_lab) les_hip_free(ctx_, d_lab);
+        if (d_cost) les_hip_free(ctx_, d_cost);
+        return ok;
+    }
+
     // CostVolumeEnergy::setInterpolationMethod (LES/CostVolumeEnergy.h:45-48): 0 nearest slice, 1 linear (the default), 2 quadratic.  Like the
     // reference's setter it is not synchronised with evaluations running on other threads.
     virtual void setInterpolationMethod(int none_lin_quad)

@@ -89,6 +89,24 @@ public:
         }
     }
 
+    // The warm-start branch of initCurrentFast (LES/FastGCStereo.h:116-130): start from a given labelling; the cost of every pixel is the
+    // unary cost of its own label with a 1 x 1 target and the filter region pixel +- windR -- one operator call per pixel, as the reference.
+    void initCurrentFast(int mode, const LabelMap& labeling)
+    {
+        CostMap& cost = currentCost_[mode];
+        currentLabeling_[mode] = labeling;
+        const Rect image(0, 0, width, height);
+        const int R = params.windR;
+#pragma omp parallel for schedule(dynamic, 8)
+        for (int y = 0; y < height; y++) {
+            StereoEnergy::Reusable tmp;
+            for (int x = 0; x < width; x++) {
+                const Rect filterRegion = Rect(x - R, y - R, 2 * R + 1, 2 * R + 1) & image;
+                stereoEnergy->ComputeUnaryPotential(filterRegion, Rect(x, y, 1, 1), cost.view(filterRegion), width, labeling.at(y, x), tmp, mode);
+            }
+        }
+    }
+
     // fuse `label` into the current solution over `sharedRegion` given its unary costs in proposalCost
     // (LES/FastGCStereo.h:52-63)
     void fuseProposal(const Plane& label, const Rect& sharedRegion, CostView proposalCost, int mode, bool doGC)
@@ -158,9 +176,13 @@ public:
 
     // FastGCStereo::run (LES/FastGCStereo.h:133-199): pmInit winner-take-all iterations, then maxIteration
     // graph-cut iterations (the iteration counter restarts, so the random search widths do too)
-    void run(int pmInit, const std::vector<int>& viewModes = {0}, int maxIteration = 0)
+    // labeling (optional): every view starts from it (the reference's `labeling` argument, LES/FastGCStereo.h:133,137) instead of random labels
+    void run(int pmInit, const std::vector<int>& viewModes = {0}, int maxIteration = 0, const LabelMap* labeling = nullptr)
     {
-        for (int mode : viewModes) initCurrentFast(mode);
+        for (int mode : viewModes) {
+            if (labeling) initCurrentFast(mode, *labeling);
+            else initCurrentFast(mode);
+        }
         for (int iteration = 0; iteration < pmInit; iteration++)
             for (int mode : viewModes)
                 for (int li = 0; li < (int)layermng.layers.size(); li++) localExpansionMovesForLayer(li, mode, iteration, false);
@@ -172,10 +194,12 @@ public:
     // ---------------------------------------------------------------------------------------------
     // Device-resident driver (needs a HipCostVolumeEnergy)
     // ---------------------------------------------------------------------------------------------
-    bool runDevice(int pmInit, const std::vector<int>& viewModes = {0}, double* seconds = nullptr, int maxIteration = 0)
+    // labeling (optional): every view starts from it -- its costs come from one dense device pass (les_hip_unary_labels)
+    bool runDevice(int pmInit, const std::vector<int>& viewModes = {0}, double* seconds = nullptr, int maxIteration = 0, const LabelMap* labeling = nullptr)
     {
         auto* hip = dynamic_cast<HipCostVolumeEnergy*>(stereoEnergy.get());
         if (!hip) return false;
+        if (labeling && (labeling->rows != height || labeling->cols != width)) { fprintf(stderr, "PMStereo::runDevice: the start labelling is not %d x %d\n", width, height); return false; }
         les_hip_ctx* ctx = hip->handle();
         const size_t P = (size_t)width * height;
         bool ok = true;
@@ -261,11 +285,17 @@ public:
             // initCurrentFast on the device: random label per layer-0 cell, cost of its unit region
             chk(les_hip_memset(ctx, d_labels, 0, P * sizeof(les_hip_plane)));
             chk(les_hip_memset(ctx, d_cur, 0, P * sizeof(float)));
-            if (init.n > 0) {
-                chk(les_hip_batch_propose(ctx, init.b, LES_HIP_PROPOSE_INIT, 0, d_labels, init.rng, init.planes));
-                chk(les_hip_batch_run(ctx, init.b, mode, init.planes, 1, d_cur, 1));
+            if (labeling) {
+                // the warm-start branch (LES/FastGCStereo.h:116-130): every rank evaluates the whole map (replicated state, nothing to exchange)
+                chk(les_hip_memcpy_h2d(ctx, d_labels, labeling->data.data(), P * sizeof(les_hip_plane)));
+                chk(les_hip_unary_labels(ctx, mode, nullptr, d_labels, d_cur, 1));
+            } else {
+                if (init.n > 0) {
+                    chk(les_hip_batch_propose(ctx, init.b, LES_HIP_PROPOSE_INIT, 0, d_labels, init.rng, init.planes));
+                    chk(les_hip_batch_run(ctx, init.b, mode, init.planes, 1, d_cur, 1));
+                }
+                exchange(init, d_labels, d_cur);
             }
-            exchange(init, d_labels, d_cur);
             for (int iteration = 0; iteration < pmInit && ok; iteration++)
                 for (size_t li = 0; li < batches.size(); li++)
                     for (SetBatch& sb : batches[li]) {

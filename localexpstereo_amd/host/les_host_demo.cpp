@@ -230,6 +230,44 @@ static int cmd_run(int argc, char** argv)
         les_hip_free(c, d_lab); les_hip_free(c, d_rng); les_hip_free(c, d_pl);
         les_hip_batch_destroy(b);
     }
+    // (f) warm start: a device run resumed from the labelling of a previous device run.  Its costs come from one dense pass over the label
+    //     map (les_hip_unary_labels), so with no further iteration the labels are the previous run's and the data term is that run's.
+    {
+        auto mk = [&]() {
+            auto st = build(7);
+            st->addLayer(std::max(2, int(W * 0.04)), {{LES_HIP_PROPOSE_EXPANSION, 1}, {LES_HIP_PROPOSE_RANSAC, 1}, {LES_HIP_PROPOSE_RANDOM, 7}});
+            st->addLayer(std::max(4, int(W * 0.12)), {{LES_HIP_PROPOSE_EXPANSION, 2}, {LES_HIP_PROPOSE_RANSAC, 1}});
+            return st;
+        };
+        auto a = mk();
+        double sec = 0, sec2 = 0;
+        if (!a->runDevice(1, {0}, &sec)) { printf("FAIL: runDevice\n"); return 1; }
+        auto b = mk();
+        if (!b->runDevice(0, {0}, &sec2, 0, &a->currentLabeling_[0])) { printf("FAIL: runDevice (warm start)\n"); return 1; }
+        size_t diff = 0;
+        for (size_t i = 0; i < a->currentLabeling_[0].data.size(); i++) diff += !(a->currentLabeling_[0].data[i] == b->currentLabeling_[0].data[i]);
+        const double ea = a->totalCost(0), eb = b->totalCost(0);
+        printf("warm start: data term of the first run %.4f, of the run resumed from its labelling %.4f, %zu label differences  (%.3f s)\n", ea, eb, diff, sec2);
+        // each cost map is within 2e-6 per pixel of the exact one (costs in [0, th_col])
+        if (diff || !(std::fabs(ea - eb) <= 2.0 * 2e-6 * (double)W * H)) { printf("FAIL: the resumed run does not carry the first run's solution\n"); fail = 1; }
+        // the same labelling through the operator's label-map form and through the reference's shape (PMStereo::run: one operator call per pixel)
+        std::vector<float> dense((size_t)W * H, 0.f);
+        const auto& hip = static_cast<const HipCostVolumeEnergy&>(b->getEnergyInstance());
+        const bool okd = hip.ComputeUnaryPotentialOfLabels(a->currentLabeling_[0].data.data(), dense.data(), 0);
+        size_t bits = 0;
+        for (size_t i = 0; i < dense.size(); i++) bits += memcmp(&dense[i], &b->currentCost_[0].data[i], 4) != 0;
+        auto c = mk();
+        c->run(0, {0}, 0, &a->currentLabeling_[0]);
+        double worst = 0;
+        size_t sent = 0;
+        for (size_t i = 0; i < dense.size(); i++) {
+            const float p = c->currentCost_[0].data[i], q = dense[i];
+            if ((p == 1e6f) != (q == 1e6f)) sent++;
+            else worst = std::max(worst, (double)std::fabs(p - q));
+        }
+        printf("warm start: label-map operator vs the device run %zu cost differences; vs one operator call per pixel: max |diff| %.2e, %zu sentinel differences\n", bits, worst, sent);
+        if (!okd || bits || sent || !(worst <= 2.0 * 2e-6)) { printf("FAIL: the label-map operator disagrees\n"); fail = 1; }
+    }
     printf(fail ? "les_host_demo: FAILED\n" : "les_host_demo: OK\n");
     return fail;
 }

@@ -218,27 +218,18 @@ class PMRunner:
     def init_from_labels(self, labels, rows_per_launch=64):
         """The warm-start branch of initCurrentFast (LES/FastGCStereo.h:116-130, "very slow" on the CPU): start from a
         given H x W x 4 label map; the current cost of every pixel is the unary cost of its own label, evaluated with
-        a 1 x 1 target and the filter region pixel +- windR -- one job per pixel, `rows_per_launch` image rows per launch."""
+        a 1 x 1 target and the filter region pixel +- windR -- one dense device pass (les_hip_unary_labels).
+        rows_per_launch: accepted for callers of the former per-band launches, ignored."""
         lab = torch.as_tensor(np.ascontiguousarray(labels, np.float32)).to(self.device)
         assert tuple(lab.shape) == (self.H, self.W, 4)
         self.labels.copy_(lab)
-        R, W, H = self.e.params.windR, self.W, self.H
-        xs = np.arange(W, dtype=np.int32)
-        x0, x1 = np.maximum(xs - R, 0), np.minimum(xs + R + 1, W)
-        for ya in range(0, H, rows_per_launch):
-            yb = min(H, ya + rows_per_launch)
-            ys = np.arange(ya, yb, dtype=np.int32)
-            y0, y1 = np.maximum(ys - R, 0), np.minimum(ys + R + 1, H)
-            fr = np.stack([np.broadcast_to(x0, (yb - ya, W)), np.broadcast_to(y0[:, None], (yb - ya, W)),
-                           np.broadcast_to(x1 - x0, (yb - ya, W)), np.broadcast_to((y1 - y0)[:, None], (yb - ya, W))], -1).reshape(-1, 4)
-            tr = np.stack([np.broadcast_to(xs, (yb - ya, W)), np.broadcast_to(ys[:, None], (yb - ya, W)),
-                           np.ones((yb - ya, W), np.int32), np.ones((yb - ya, W), np.int32)], -1).reshape(-1, 4)
-            b = api.Batch(self.e, np.ascontiguousarray(fr, np.int32), np.ascontiguousarray(tr, np.int32))
-            b.run(self.labels[ya:yb].data_ptr(), self.cur.data_ptr(), mode=self.mode, check=True, planes_on_device=True)
-            self._sync()
-            b.destroy()
-        if self.world > 1:
-            pass        # every rank evaluates the whole map here (replicated state, nothing to exchange)
+        self.recost()             # (every rank evaluates the whole map: replicated state, nothing to exchange)
+
+    def recost(self):
+        """Re-evaluate the cost map from the label map (after the labels were changed behind the optimiser's back, e.g. by the
+        post-processing): cur[p] = unary cost of labels[p].  Synchronises."""
+        self.e.unary_labels(self.labels.data_ptr(), self.cur.data_ptr(), mode=self.mode, check=True)
+        self._sync()
 
     def _proposals(self, li, iteration):
         """(kind, m) of every lock-step of a set of layer li, in the order of the proposer table.  The RandomProposer stops once its

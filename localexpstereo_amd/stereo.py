@@ -22,8 +22,13 @@ PARAMS_BF = dict(PARAMS_GF, lambda_=20.0, windR=20, eps=10.0, filter="BF")
 
 class FastGCStereo:
     def __init__(self, energy, imL, imR, params, device="cuda", rank=0, world=1, seed=1, host_threads=0, device_cuts=None, random_vdisp=None,
-                 evaluate_on_device=False, inner_loop_log=False, check_flow_energy=False):
+                 evaluate_on_device=False, inner_loop_log=False, check_flow_energy=False, recost_after_post=False):
         self.e, self.imL, self.imR, self.p = energy, imL, imR, dict(PARAMS_GF, **params)
+        # Opt-in: after postProcess (two-view runs) every view's cost map is re-evaluated from its final labels (pm.PMRunner.recost: one dense
+        # pass), so the last row's `data` belongs to the labels it is logged with.  Off (the default, the reference's behaviour,
+        # LES/FastGCStereo.h:205-206): that row reports the data term of the labels before the left-right check, fill and weighted median.
+        self.recost_after_post = bool(recost_after_post)
+        self.raw_labelings = {}                   # run(): view -> its H x W x 4 labelling before the post-processing (what a later run resumes from)
         self.random_vdisp = random_vdisp          # maxVDisp of the RANDOM proposals (pm.PMRunner); None: the energy's setting (0 by default)
         # Parameters::filterName: the energy aggregates with the filter it was built with; a params dict that names another one is a mistake
         if "filter" in params and api.filter_kind(params["filter"]) != getattr(energy, "filter", api.FILTER_GF):
@@ -130,7 +135,9 @@ class FastGCStereo:
     def run(self, maxIteration, viewModes=(0,), pmInit=0, labeling=None):
         """FastGCStereo::run (LES/FastGCStereo.h:133-227).  Returns (labeling, rawlabeling) of the left view as
         H x W x 4 float arrays (the raw one is the labelling before the two-view post-processing).  `labeling`: optional
-        start labelling (the reference's `labeling` argument; every view starts from it, as in the reference)."""
+        start labelling (the reference's `labeling` argument; every view starts from it, as in the reference), or a dict {view: H x W x 4
+        map} that gives each view of a two-view run its own (self.raw_labelings of an earlier run resumes it).  The costs of a start labelling
+        come from one dense device pass per view (pm.PMRunner.init_from_labels)."""
         try:
             return self._run(maxIteration, viewModes, pmInit, labeling)
         finally:                 # the device evaluators of the run, also when it raised
@@ -180,7 +187,9 @@ class FastGCStereo:
             if labeling is None:
                 runners[m].init_labels()
             else:
-                runners[m].init_from_labels(labeling)          # warm start from a given labelling (LES/FastGCStereo.h:116-130)
+                if isinstance(labeling, dict) and m not in labeling:
+                    raise ValueError(f"labeling has no map for view {m} (views given: {sorted(labeling)})")
+                runners[m].init_from_labels(labeling[m] if isinstance(labeling, dict) else labeling)     # warm start (LES/FastGCStereo.h:116-130)
             self._evaluate(0, m, runners[m], None, t0)
         # the reference starts its clock HERE -- START_TIMER after initCurrentFast and the first evaluation (LES/FastGCStereo.h:135-141),
         # with the layers (addLayer, LES/main.cpp:395-397) and the energy built before run() -- `seconds` below keeps counting from the top
@@ -273,9 +282,13 @@ class FastGCStereo:
                     dist.broadcast(final[m], src=view_root[m])
         else:
             final = {m: runners[m].labels for m in all_views}
-        raw = final[0].cpu().numpy().copy() if 0 in final else None
+        self.raw_labelings = {m: final[m].cpu().numpy().copy() for m in all_views}
+        raw = self.raw_labelings.get(0)
         if len(all_views) == 2:
             self.e.post_process(final[0].data_ptr(), final[1].data_ptr(), 1.5, self.p["omega"])     # (left, right) whatever the order of viewModes; LES/FastGCStereo.h:202
+            if self.recost_after_post:
+                for m in runners:
+                    runners[m].recost()
             if 0 in runners:
                 self._evaluate(maxIteration + 1 + pmInit, 0, runners[0], None, t0)
             # (the rows of the log belong to the ranks of the left view's group)
