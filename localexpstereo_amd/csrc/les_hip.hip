@@ -78,7 +78,7 @@ void note_fallback(std::atomic<unsigned>& seen, FallbackReason r, const char* fm
 
 #include "les_hip_march_tables.inc"      // which kernel instantiations exist (radius -> geometry): part of what bench.py hashes as "the kernel sources"
 
-struct ViewData {
+struct ViewData {                        // (its device buffers are freed by the list in ~les_hip_ctx below: a new one needs an entry there)
     float* vol = nullptr;
     bool own_vol = false;
     float4* stats = nullptr;
@@ -101,6 +101,8 @@ struct ViewData {
 
 }  // namespace
 
+#include "les_hip_mem.h"                 // DevBuf / PinnedBuf: the owner of every allocation below (and what stays raw, and why)
+
 struct MtHost;
 namespace { void mt_host_free(MtHost* m); }
 
@@ -113,7 +115,7 @@ namespace {
 struct VdispGroup { int c0, c1, slices; };
 struct UnaryTables {
     int n = 0;
-    void* d_mem = nullptr;                       // every device table below
+    DevBuf<char> mem;                            // every device table below
     const les::Job* d_jobs = nullptr; int njobs = 0;                   // strip kernel (guided filter)
     // march kernel: groups of NJ jobs cut for mentry; march_ok: every target keeps 2R distance from the filterRect borders that are
     // not image borders, so the kernel's bound on |a| holds (les_march.h)
@@ -139,10 +141,10 @@ struct UnaryTables {
 struct UnaryWorkspace {
     bool shared = false;
     struct Slot {
-        float* raw = nullptr; size_t raw_cap = 0;
-        unsigned* flags = nullptr; size_t flags_cap = 0;
-        les::Job* rjobs = nullptr; size_t rjobs_cap = 0;
-        float* vol = nullptr; size_t vol_cap = 0;
+        DevBuf<float> raw;
+        DevBuf<unsigned> flags;
+        DevBuf<les::Job> rjobs;
+        DevBuf<float> vol;
     } slot[2];
 };
 
@@ -152,7 +154,7 @@ struct les_hip_ctx {
     les_hip_params p;
     int filter = LES_HIP_FILTER_GF;      // aggregation (les_hip_create_filtered); the bilateral / unfiltered ones run les_hip_bilateral.inc
     int R;                               // its radius: windR / 2 (guided filter), windR (bilateral), 0 (unfiltered)
-    float* d_bf_tab = nullptr;           // bilateral / unfiltered: the weight table exp(-|dI|_1 / sig2), 766 floats
+    DevBuf<float> d_bf_tab;              // bilateral / unfiltered: the weight table exp(-|dI|_1 / sig2), 766 floats
     const StripEntry* strip;
     const StripEntry* istrip[2] = {nullptr, nullptr};   // cost-volume guided filter at interpolation 0 / 2 (find_interp_strip)
     int interp = 1;                      // setInterpolationMethod (les_hip_set_interpolation): 0 nearest, 1 linear, 2 quadratic
@@ -169,12 +171,12 @@ struct les_hip_ctx {
     // RandomProposer's maxVDisp (les_hip_set_random_vdisparity: PROPOSE_RANDOM); 0: no draw, the RNG streams of a context without v
     float max_vdisp = 0.0f, random_vdisp = 0.0f;
     // scratch reused by the non-prepared entry points and by batch_run
-    float4* d_planes = nullptr; size_t planes_cap = 0;
-    float* d_map = nullptr;                         // H*W floats
-    les::WtaJob* d_wta = nullptr; size_t wta_cap = 0;
-    float4* d_wta_planes = nullptr; size_t wta_planes_cap = 0;
+    float4* d_planes = nullptr; size_t planes_cap = 0;      // (raw: grown by ensure_planes of les_hip_march.inc)
+    DevBuf<float> d_map;                            // H*W floats
+    DevBuf<les::WtaJob> d_wta;
+    DevBuf<float4> d_wta_planes;
     // smoothness-coefficient table of the pairwise terms, cached per (omega, epsilon)
-    float* d_pw_tab = nullptr; float pw_omega = -1.f, pw_epsilon = -1.f;
+    DevBuf<float> d_pw_tab; float pw_omega = -1.f, pw_epsilon = -1.f;
     std::mutex mu;                       // guards lazily built state (batch workspaces, scratch lists) when two host threads (the two views) share the context
     unsigned long long gen = 0;          // unique id of this context: thread-local bindings compare it, not the address (an address can be reused)
     std::vector<les_hip_scratch*> idle_scratch;  // hidden scratches whose owning thread has exited, ready for the next new thread
@@ -182,6 +184,16 @@ struct les_hip_ctx {
     bool maxflow_tiled_lds_ready = false;   // ... and of les_maxflow_tiled_kernel
     std::vector<les_hip_scratch*> own_scratch;   // scratch objects created behind les_hip_unary_one (one per calling thread), freed with the context
     std::vector<MtHost*> mt_idle; // host-mapped flag words + hand-over staging of the tiled max-flow: one per CONCURRENT caller, reused, freed with the context
+    // what stays raw (les_hip_mem.h): the views' buffers and d_planes; every other table frees itself
+    ~les_hip_ctx()
+    {
+        for (ViewData& w : v) {
+            if (w.own_vol && w.vol) (void)hipFree(w.vol);    // (not own_vol: the caller's device volume)
+            for (void* q : {(void*)w.stats, (void*)w.ipk, (void*)w.ipk10, (void*)w.feat, (void*)w.ipk8, (void*)w.mstats, (void*)w.vol_t})
+                if (q) (void)hipFree(q);
+        }
+        if (d_planes) (void)hipFree(d_planes);
+    }
 };
 
 // A prepared batch: the unary-cost tables of its calls (map / slab layout) and their workspace, run by run_unary (les_hip_unary.inc); the
@@ -193,31 +205,33 @@ struct les_hip_batch {
     std::vector<les_hip_rect> targets;
     int device = 0;
     // cell geometry for the proposers / WTA
-    les::Rect4* d_units = nullptr;
-    les::WtaJob* d_targets = nullptr;
-    les::RansacScratch rs = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr};   // RANSAC proposer scratch
+    DevBuf<les::Rect4> d_units;
+    DevBuf<les::WtaJob> d_targets;
+    // RANSAC proposer scratch: the owners, and the kernels' argument filled from them (les_hip_batch_set_units)
+    DevBuf<float> rs_disp; DevBuf<int> rs_idx, rs_noi, rs_no; DevBuf<uint64_t> rs_state; DevBuf<float> rs_refit; DevBuf<les::RansacCell> rs_cell;
+    les::RansacScratch rs = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr};
     int wta_chunks = 1;                  // blocks per target rect in the WTA kernel
     int graph_chunks = 1;                // ... in the graph-construction kernel: about one node per thread (its loads are dependent: occupancy hides them)
     // expansion-graph payload layout (les_hip_batch_expansion_graph): node offset of every target, total node count
     std::vector<long long> graph_off;
     long long graph_nodes = 0;
-    long long* d_graph_off = nullptr;
-    double* d_flow0 = nullptr;           // n * graph_chunks partial sums
+    DevBuf<long long> d_graph_off;
+    DevBuf<double> d_flow0;              // n * graph_chunks partial sums
     // tiled device max-flow (les_maxflow_tiled.h): the cells cut into tiles, built on first use (two host threads -- the two views -- may share a batch)
     mutable std::mutex mt_mu;
-    mutable les::MtTile* d_mt_tiles = nullptr;
-    mutable int* d_mt_tiles_per_cell = nullptr;
+    mutable DevBuf<les::MtTile> d_mt_tiles;
+    mutable DevBuf<int> d_mt_tiles_per_cell;
     mutable int mt_ntiles = -1;          // -1: not built yet
     // one-workgroup device max-flow: the cells grouped by the kernel that cuts them (les_hip_cuts.inc), built on first use per value of
     // LES_HIP_MAXFLOW_CELL_KERNEL (mf_list_key; -1: not built yet)
     mutable std::mutex mf_mu;
-    mutable int* d_mf_list = nullptr;
+    mutable DevBuf<int> d_mf_list;
     mutable int mf_list_key = -1;
     mutable int mf_count[3] = {0, 0, 0};
     // region energy of the cells (les_hip_eval.inc): partial sums, cells * region_chunks doubles per view (two host threads may run the two views of one
     // batch), built on first use (region_chunks -1: not yet)
     mutable std::mutex re_mu;
-    mutable double* d_region_part[2] = {nullptr, nullptr};
+    mutable DevBuf<double> d_region_part[2];
     mutable int region_chunks = -1;
 };
 
@@ -229,8 +243,8 @@ struct les_hip_batch {
 struct les_hip_scratch {
     les_hip_ctx* c = nullptr;
     hipStream_t stream = nullptr;
-    float* d_tile = nullptr; float* h_tile = nullptr; size_t tile_cap = 0;        // floats
-    float4* d_plane = nullptr; float4* h_plane = nullptr;
+    DevBuf<float> d_tile; PinnedBuf<float> h_tile;         // grown together
+    DevBuf<float4> d_plane; PinnedBuf<float4> h_plane;
     struct Entry { les_hip_rect f, t; UnaryTables tab; unsigned long long stamp; };
     std::vector<Entry> cache;
     unsigned long long clock = 0;

@@ -29,14 +29,14 @@ int les_hip_batch_create(les_hip_ctx* c, int n, const les_hip_rect* frs, const l
     if (n > 0) {
         static_assert(sizeof(les::WtaJob) == sizeof(les_hip_rect), "rect layout");
         static_assert(sizeof(les::GraphCell) == sizeof(les_hip_rect), "rect layout");
-        if (hipMalloc((void**)&b->d_graph_off, (size_t)n * sizeof(long long)) != hipSuccess ||
-            hipMemcpy(b->d_graph_off, b->graph_off.data(), (size_t)n * sizeof(long long), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMalloc((void**)&b->d_flow0, (size_t)n * b->graph_chunks * sizeof(double)) != hipSuccess) {
+        if (b->d_graph_off.alloc((size_t)n) ||
+            hipMemcpy(b->d_graph_off.p, b->graph_off.data(), (size_t)n * sizeof(long long), hipMemcpyHostToDevice) != hipSuccess ||
+            b->d_flow0.alloc((size_t)n * b->graph_chunks)) {
             les_hip_batch_destroy(b);
             return fail(LES_HIP_ERR_DEVICE, "upload of the graph offset table failed");
         }
-        if (hipMalloc((void**)&b->d_targets, (size_t)n * sizeof(les::WtaJob)) != hipSuccess ||
-            hipMemcpy(b->d_targets, trs, (size_t)n * sizeof(les::WtaJob), hipMemcpyHostToDevice) != hipSuccess) {
+        if (b->d_targets.alloc((size_t)n) ||
+            hipMemcpy(b->d_targets.p, trs, (size_t)n * sizeof(les::WtaJob), hipMemcpyHostToDevice) != hipSuccess) {
             les_hip_batch_destroy(b);
             return fail(LES_HIP_ERR_DEVICE, "upload of the target table failed");
         }
@@ -47,24 +47,6 @@ int les_hip_batch_create(les_hip_ctx* c, int n, const les_hip_rect* frs, const l
 
 void les_hip_batch_destroy(les_hip_batch* b)
 {
-    if (!b) return;
-    free_unary_tables(b->tab);
-    free_workspace(b->ws);
-    if (b->d_units) (void)hipFree(b->d_units);
-    if (b->d_targets) (void)hipFree(b->d_targets);
-    if (b->d_graph_off) (void)hipFree(b->d_graph_off);
-    if (b->d_flow0) (void)hipFree(b->d_flow0);
-    if (b->d_mt_tiles) (void)hipFree(b->d_mt_tiles);
-    if (b->d_mt_tiles_per_cell) (void)hipFree(b->d_mt_tiles_per_cell);
-    if (b->d_mf_list) (void)hipFree(b->d_mf_list);
-    for (double* q : b->d_region_part) if (q) (void)hipFree(q);
-    if (b->rs.disp) (void)hipFree(b->rs.disp);
-    if (b->rs.idx) (void)hipFree(b->rs.idx);
-    if (b->rs.state) (void)hipFree(b->rs.state);
-    if (b->rs.noi) (void)hipFree(b->rs.noi);
-    if (b->rs.no) (void)hipFree(b->rs.no);
-    if (b->rs.refit) (void)hipFree(b->rs.refit);
-    if (b->rs.cell) (void)hipFree(b->rs.cell);
     delete b;
 }
 
@@ -80,22 +62,22 @@ int les_hip_batch_set_units(les_hip_ctx* c, les_hip_batch* b, const les_hip_rect
     }
     if (b->n == 0) return LES_HIP_OK;
     static_assert(sizeof(les::Rect4) == sizeof(les_hip_rect), "rect layout");
-    if (!b->d_units) HIPCHECK(hipMalloc((void**)&b->d_units, (size_t)b->n * sizeof(les::Rect4)));
-    HIPCHECK(hipMemcpy(b->d_units, units, (size_t)b->n * sizeof(les::Rect4), hipMemcpyHostToDevice));
-    if (!b->rs.idx) {
-        const size_t n = (size_t)b->n, S = kRansacMaxSam;
-        HIPCHECK(hipMalloc((void**)&b->rs.idx, n * S * 3 * sizeof(int)));
-        HIPCHECK(hipMalloc((void**)&b->rs.state, n * (S + 1) * sizeof(uint64_t)));
-        HIPCHECK(hipMalloc((void**)&b->rs.noi, n * S * sizeof(int)));
-        HIPCHECK(hipMalloc((void**)&b->rs.no, n * S * sizeof(int)));
-        HIPCHECK(hipMalloc((void**)&b->rs.refit, n * S * 3 * sizeof(float)));
-        HIPCHECK(hipMalloc((void**)&b->rs.cell, n * sizeof(les::RansacCell)));
-    }
-    if (b->rs.disp) HIPCHECK(hipFree(b->rs.disp));
-    b->rs.disp = nullptr;
-    b->rs.stride = maxlen;
-    HIPCHECK(hipMalloc((void**)&b->rs.disp, (size_t)b->n * maxlen * sizeof(float)));
-    return LES_HIP_OK;
+    int rc = b->d_units.grow((size_t)b->n, 0, cur_stream(c));
+    if (rc) return rc;
+    HIPCHECK(hipMemcpy(b->d_units.p, units, (size_t)b->n * sizeof(les::Rect4), hipMemcpyHostToDevice));
+    // (sized by b->n, which is fixed: allocated by the first call; the snapshot follows the largest unit seen)
+    const size_t n = (size_t)b->n, S = kRansacMaxSam;
+    hipStream_t st = cur_stream(c);
+    rc = b->rs_idx.grow(n * S * 3, 0, st);
+    if (!rc) rc = b->rs_state.grow(n * (S + 1), 0, st);
+    if (!rc) rc = b->rs_noi.grow(n * S, 0, st);
+    if (!rc) rc = b->rs_no.grow(n * S, 0, st);
+    if (!rc) rc = b->rs_refit.grow(n * S * 3, 0, st);
+    if (!rc) rc = b->rs_cell.grow(n, 0, st);
+    if (!rc) rc = b->rs_disp.grow(n * maxlen, 0, st);
+    // (after a failure too: a grow that failed has freed its old buffer, which must not stay in the kernels' argument)
+    b->rs = les::RansacScratch{b->rs_disp.p, b->rs_idx.p, b->rs_state.p, b->rs_noi.p, b->rs_no.p, b->rs_refit.p, maxlen, b->rs_cell.p};
+    return rc;
 }
 
 int les_hip_batch_propose(les_hip_ctx* c, const les_hip_batch* b, int kind, int m, les_hip_plane* labels, uint64_t* rng,
@@ -104,33 +86,33 @@ int les_hip_batch_propose(les_hip_ctx* c, const les_hip_batch* b, int kind, int 
     if (c) (void)hipSetDevice(c->p.device);                 // HIP's current device is per host thread
     if (!c || !b || !labels || !rng || !planes) return fail(LES_HIP_ERR_ARG, "null argument");
     if (b->n == 0) return LES_HIP_OK;
-    if (!b->d_units) return fail(LES_HIP_ERR_ARG, "les_hip_batch_set_units was not called for this batch");
+    if (!b->d_units.p) return fail(LES_HIP_ERR_ARG, "les_hip_batch_set_units was not called for this batch");
     float4* lab = reinterpret_cast<float4*>(labels);
     float4* pl = reinterpret_cast<float4*>(planes);
     const int n = b->n, W = c->p.W;
     const float mind = c->p.min_disparity, maxd = c->p.max_disparity;
     switch (kind) {
     case LES_HIP_PROPOSE_EXPANSION:
-        hipLaunchKernelGGL(les::les_expansion_kernel, dim3((n + 63) / 64), dim3(64), 0, cur_stream(c), b->d_units, lab, W, rng, pl, n);
+        hipLaunchKernelGGL(les::les_expansion_kernel, dim3((n + 63) / 64), dim3(64), 0, cur_stream(c), b->d_units.p, lab, W, rng, pl, n);
         break;
     case LES_HIP_PROPOSE_RANDOM:
-        hipLaunchKernelGGL(les::les_random_kernel, dim3((n + 63) / 64), dim3(64), 0, cur_stream(c), b->d_units, lab, W, rng, pl, n, m, mind, maxd, c->random_vdisp);
+        hipLaunchKernelGGL(les::les_random_kernel, dim3((n + 63) / 64), dim3(64), 0, cur_stream(c), b->d_units.p, lab, W, rng, pl, n, m, mind, maxd, c->random_vdisp);
         break;
     case LES_HIP_PROPOSE_RANSAC:
         // RansacProposer(K, MAX_SAM = 500, conf = 0.95), threshold 1.0 (LES/Proposer.h:265,305)
-        hipLaunchKernelGGL(les::les_ransac_snapshot_kernel, dim3(n), dim3(256), 0, cur_stream(c), b->d_units, lab, W, b->rs);
+        hipLaunchKernelGGL(les::les_ransac_snapshot_kernel, dim3(n), dim3(256), 0, cur_stream(c), b->d_units.p, lab, W, b->rs);
         // the reference's adaptive schedule (:193, :229-236): candidates in chunks, a cell whose loop has ended ignores the later launches
         // (no host round trip: the launches of dead chunks return at once)
-        hipLaunchKernelGGL(les::les_ransac_begin_kernel, dim3((n + 63) / 64), dim3(64), 0, cur_stream(c), b->d_units, rng, b->rs, n, kRansacMaxSam, kRansacChunkEnds[0]);
+        hipLaunchKernelGGL(les::les_ransac_begin_kernel, dim3((n + 63) / 64), dim3(64), 0, cur_stream(c), b->d_units.p, rng, b->rs, n, kRansacMaxSam, kRansacChunkEnds[0]);
         for (int k = 0, j0 = 0; k < kRansacChunks; k++) {
             const int j1 = kRansacChunkEnds[k], j2 = k + 1 < kRansacChunks ? kRansacChunkEnds[k + 1] : kRansacMaxSam;
-            hipLaunchKernelGGL(les::les_ransac_eval_kernel, dim3(n, (j1 - j0 + les::kRansacCandPerBlock - 1) / les::kRansacCandPerBlock), dim3(64 * les::kRansacCandPerBlock), 0, cur_stream(c), b->d_units, b->rs, kRansacMaxSam, 1.0f, j0, j1);
-            hipLaunchKernelGGL(les::les_ransac_walk_kernel, dim3((n + 63) / 64), dim3(64), 0, cur_stream(c), b->d_units, rng, pl, b->rs, n, kRansacMaxSam, 0.95f, j0, j1, j2);
+            hipLaunchKernelGGL(les::les_ransac_eval_kernel, dim3(n, (j1 - j0 + les::kRansacCandPerBlock - 1) / les::kRansacCandPerBlock), dim3(64 * les::kRansacCandPerBlock), 0, cur_stream(c), b->d_units.p, b->rs, kRansacMaxSam, 1.0f, j0, j1);
+            hipLaunchKernelGGL(les::les_ransac_walk_kernel, dim3((n + 63) / 64), dim3(64), 0, cur_stream(c), b->d_units.p, rng, pl, b->rs, n, kRansacMaxSam, 0.95f, j0, j1, j2);
             j0 = j1;
         }
         break;
     case LES_HIP_PROPOSE_INIT:
-        hipLaunchKernelGGL(les::les_init_labels_kernel, dim3(n), dim3(64), 0, cur_stream(c), b->d_units, lab, W, rng, pl, mind, maxd, c->max_vdisp);
+        hipLaunchKernelGGL(les::les_init_labels_kernel, dim3(n), dim3(64), 0, cur_stream(c), b->d_units.p, lab, W, rng, pl, mind, maxd, c->max_vdisp);
         break;
     default:
         return fail(LES_HIP_ERR_ARG, "unknown proposer kind %d", kind);
@@ -145,8 +127,8 @@ int les_hip_batch_wta(les_hip_ctx* c, const les_hip_batch* b, const les_hip_plan
     if (c) (void)hipSetDevice(c->p.device);                 // HIP's current device is per host thread
     if (!c || !b || !planes || !cur || !prop || !labels) return fail(LES_HIP_ERR_ARG, "null argument");
     if (b->n == 0) return LES_HIP_OK;
-    if (!b->d_targets) return fail(LES_HIP_ERR_ARG, "batch has no target table");
-    hipLaunchKernelGGL(les::les_wta_kernel, dim3(b->n, b->wta_chunks), dim3(256), 0, cur_stream(c), b->d_targets, reinterpret_cast<const float4*>(planes),
+    if (!b->d_targets.p) return fail(LES_HIP_ERR_ARG, "batch has no target table");
+    hipLaunchKernelGGL(les::les_wta_kernel, dim3(b->n, b->wta_chunks), dim3(256), 0, cur_stream(c), b->d_targets.p, reinterpret_cast<const float4*>(planes),
                        cur, prop, reinterpret_cast<float4*>(labels), c->p.W);
     HIPCHECK(hipGetLastError());
     return LES_HIP_OK;
@@ -184,14 +166,14 @@ int les_hip_unary_batch(les_hip_ctx* c, int mode, int n, const les_hip_rect* frs
     les_hip_batch* b = nullptr;
     int rc = les_hip_batch_create(c, n, frs, trs, 0, &b);
     if (rc) return rc;
-    rc = les_hip_batch_run(c, b, mode, planes, 0, c->d_map, check);
+    rc = les_hip_batch_run(c, b, mode, planes, 0, c->d_map.p, check);
     if (rc == LES_HIP_OK) {
         // copy back only the target rects (the reference writes nothing else, LES/CostVolumeEnergy.h:169-171)
         for (int i = 0; i < n && rc == LES_HIP_OK; i++) {
             const les_hip_rect& t = trs[i];
             if (t.w <= 0 || t.h <= 0) continue;
             size_t off = (size_t)t.y * c->p.W + t.x;
-            hipError_t e = hipMemcpy2DAsync(cost_map + off, (size_t)c->p.W * sizeof(float), c->d_map + off, (size_t)c->p.W * sizeof(float),
+            hipError_t e = hipMemcpy2DAsync(cost_map + off, (size_t)c->p.W * sizeof(float), c->d_map.p + off, (size_t)c->p.W * sizeof(float),
                                             (size_t)t.w * sizeof(float), (size_t)t.h, hipMemcpyDeviceToHost, cur_stream(c));
             if (e != hipSuccess) rc = fail(LES_HIP_ERR_DEVICE, "hipMemcpy2DAsync failed: %s", hipGetErrorString(e));
         }
@@ -208,8 +190,7 @@ int les_hip_scratch_create(les_hip_ctx* c, les_hip_scratch** out)
     HIPCHECK(hipSetDevice(c->p.device));
     les_hip_scratch* s = new les_hip_scratch();
     s->c = c;
-    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc((void**)&s->d_plane, sizeof(float4)) != hipSuccess || hipHostMalloc((void**)&s->h_plane, sizeof(float4), hipHostMallocDefault) != hipSuccess) {
+    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess || s->d_plane.alloc(1) || s->h_plane.alloc(1)) {
         les_hip_scratch_destroy(s);
         return fail(LES_HIP_ERR_DEVICE, "scratch allocation failed");
     }
@@ -221,13 +202,7 @@ void les_hip_scratch_destroy(les_hip_scratch* s)
 {
     if (!s) return;
     if (s->c) (void)hipSetDevice(s->c->p.device);
-    if (s->stream) { (void)hipStreamSynchronize(s->stream); (void)hipStreamDestroy(s->stream); }
-    for (auto& e : s->cache) free_unary_tables(e.tab);
-    free_workspace(s->ws);
-    if (s->d_tile) (void)hipFree(s->d_tile);
-    if (s->h_tile) (void)hipHostFree(s->h_tile);
-    if (s->d_plane) (void)hipFree(s->d_plane);
-    if (s->h_plane) (void)hipHostFree(s->h_plane);
+    if (s->stream) { (void)hipStreamSynchronize(s->stream); (void)hipStreamDestroy(s->stream); }      // drained before the buffers go
     delete s;
 }
 
@@ -250,37 +225,27 @@ int les_hip_unary_one_scratch(les_hip_ctx* c, les_hip_scratch* s, int mode, cons
         if (s->cache.size() >= 16) {                     // evict the least recently used pair
             size_t k = 0;
             for (size_t i = 1; i < s->cache.size(); i++) if (s->cache[i].stamp < s->cache[k].stamp) k = i;
-            HIPCHECK(hipStreamSynchronize(s->stream));
-            free_unary_tables(s->cache[k].tab);
+            HIPCHECK(hipStreamSynchronize(s->stream));      // (launches in flight may still read its tables, which go with the entry)
             s->cache.erase(s->cache.begin() + (long)k);
         }
         UnaryTables tab;
         rc = build_unary_tables(c, 1, fr, tr, 0, true, tab);
-        if (rc) { free_unary_tables(tab); return rc; }
+        if (rc) return rc;
         s->cache.push_back(les_hip_scratch::Entry{*fr, *tr, std::move(tab), 0});
         e = &s->cache.back();
     }
     e->stamp = ++s->clock;
     const size_t need = (size_t)tr->w * tr->h;
-    if (need > s->tile_cap) {
-        HIPCHECK(hipStreamSynchronize(s->stream));
-        if (s->d_tile) HIPCHECK(hipFree(s->d_tile));
-        if (s->h_tile) HIPCHECK(hipHostFree(s->h_tile));
-        s->d_tile = nullptr; s->h_tile = nullptr; s->tile_cap = 0;
-        const size_t cap = std::max(need, (size_t)256 * 256);
-        HIPCHECK(hipMalloc((void**)&s->d_tile, cap * sizeof(float)));
-        HIPCHECK(hipHostMalloc((void**)&s->h_tile, cap * sizeof(float), hipHostMallocDefault));
-        s->tile_cap = cap;
-    }
-    *s->h_plane = make_float4(plane->a, plane->b, plane->c, plane->v);
-    HIPCHECK(hipMemcpyAsync(s->d_plane, s->h_plane, sizeof(float4), hipMemcpyHostToDevice, s->stream));
-    rc = run_unary(c, e->tab, s->ws, mode, s->d_plane, s->d_tile, check, s->stream);
+    if ((rc = s->d_tile.grow(need, (size_t)256 * 256, s->stream)) || (rc = s->h_tile.grow(need, (size_t)256 * 256, s->stream))) return rc;
+    *s->h_plane.p = make_float4(plane->a, plane->b, plane->c, plane->v);
+    HIPCHECK(hipMemcpyAsync(s->d_plane.p, s->h_plane.p, sizeof(float4), hipMemcpyHostToDevice, s->stream));
+    rc = run_unary(c, e->tab, s->ws, mode, s->d_plane.p, s->d_tile.p, check, s->stream);
     if (rc) return rc;
-    HIPCHECK(hipMemcpyAsync(s->h_tile, s->d_tile, need * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    HIPCHECK(hipMemcpyAsync(s->h_tile.p, s->d_tile.p, need * sizeof(float), hipMemcpyDeviceToHost, s->stream));
     HIPCHECK(hipStreamSynchronize(s->stream));
     // costs(targetRect - filterRect.tl()), LES/CostVolumeEnergy.h:169
     float* dst = costs + (size_t)(tr->y - fr->y) * row_stride + (tr->x - fr->x);
-    for (int y = 0; y < tr->h; y++) memcpy(dst + (size_t)y * row_stride, s->h_tile + (size_t)y * tr->w, (size_t)tr->w * sizeof(float));
+    for (int y = 0; y < tr->h; y++) memcpy(dst + (size_t)y * row_stride, s->h_tile.p + (size_t)y * tr->w, (size_t)tr->w * sizeof(float));
     return LES_HIP_OK;
 }
 
@@ -322,29 +287,20 @@ int les_hip_wta_update(les_hip_ctx* c, int n, const les_hip_rect* rects, const l
     for (int i = 0; i < n; i++)
         if (rects[i].x < 0 || rects[i].y < 0 || rects[i].w < 0 || rects[i].h < 0 || rects[i].x + rects[i].w > c->p.W || rects[i].y + rects[i].h > c->p.H)
             return fail(LES_HIP_ERR_ARG, "rect outside the image");
-    if ((size_t)n > c->wta_cap) {
-        if (c->d_wta) HIPCHECK(hipFree(c->d_wta));
-        c->d_wta = nullptr; c->wta_cap = 0;
-        HIPCHECK(hipMalloc((void**)&c->d_wta, std::max<size_t>(n, 1024) * sizeof(les::WtaJob)));
-        c->wta_cap = std::max<size_t>(n, 1024);
-    }
+    int rc = c->d_wta.grow((size_t)n, 1024, cur_stream(c));
+    if (rc) return rc;
     static_assert(sizeof(les::WtaJob) == sizeof(les_hip_rect), "rect layout");
-    HIPCHECK(hipMemcpyAsync(c->d_wta, rects, (size_t)n * sizeof(les::WtaJob), hipMemcpyHostToDevice, cur_stream(c)));
+    HIPCHECK(hipMemcpyAsync(c->d_wta.p, rects, (size_t)n * sizeof(les::WtaJob), hipMemcpyHostToDevice, cur_stream(c)));
     const float4* d_planes = reinterpret_cast<const float4*>(planes);
     if (!planes_on_device) {
-        if ((size_t)n > c->wta_planes_cap) {
-            if (c->d_wta_planes) HIPCHECK(hipFree(c->d_wta_planes));
-            c->d_wta_planes = nullptr; c->wta_planes_cap = 0;
-            HIPCHECK(hipMalloc((void**)&c->d_wta_planes, std::max<size_t>(n, 1024) * sizeof(float4)));
-            c->wta_planes_cap = std::max<size_t>(n, 1024);
-        }
-        HIPCHECK(hipMemcpyAsync(c->d_wta_planes, planes, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, cur_stream(c)));
-        d_planes = c->d_wta_planes;
+        if ((rc = c->d_wta_planes.grow((size_t)n, 1024, cur_stream(c)))) return rc;
+        HIPCHECK(hipMemcpyAsync(c->d_wta_planes.p, planes, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, cur_stream(c)));
+        d_planes = c->d_wta_planes.p;
     }
     int max_area = 1;
     for (int i = 0; i < n; i++) max_area = std::max(max_area, rects[i].w * rects[i].h);
     const int chunks = std::min(32, std::max(1, (max_area + 4095) / 4096));
-    hipLaunchKernelGGL(les::les_wta_kernel, dim3(n, chunks), dim3(256), 0, cur_stream(c), c->d_wta, d_planes, cur, prop,
+    hipLaunchKernelGGL(les::les_wta_kernel, dim3(n, chunks), dim3(256), 0, cur_stream(c), c->d_wta.p, d_planes, cur, prop,
                        reinterpret_cast<float4*>(labels), c->p.W);
     HIPCHECK(hipGetLastError());
     return LES_HIP_OK;

@@ -18,9 +18,11 @@ int build_bf_view(les_hip_ctx* c, int m, const uint8_t* im, const float* vol)
         }
     }
     if (!im) return LES_HIP_OK;
-    uint8_t* d_img = nullptr;
-    HIPCHECK(hipMalloc((void**)&d_img, P * 3));
-    HIPCHECK(hipMemcpy(d_img, im, P * 3, hipMemcpyHostToDevice));
+    DevBuf<uint8_t> img;                  // freed on every return below
+    const int rc = img.alloc(P * 3);
+    if (rc) return rc;
+    const uint8_t* d_img = img.p;
+    HIPCHECK(hipMemcpy(img.p, im, P * 3, hipMemcpyHostToDevice));
     HIPCHECK(hipMalloc((void**)&v.ipk, P * sizeof(uint32_t)));
     HIPCHECK(hipMalloc((void**)&v.ipk10, P * sizeof(uint32_t)));
     if (c->naive) {
@@ -30,7 +32,6 @@ int build_bf_view(les_hip_ctx* c, int m, const uint8_t* im, const float* vol)
     hipLaunchKernelGGL(les::les_pack_guide_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, cur_stream(c), d_img, v.ipk, v.ipk10, (int)P);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(cur_stream(c)));
-    HIPCHECK(hipFree(d_img));
     return LES_HIP_OK;
 }
 
@@ -41,8 +42,9 @@ int build_bf_table(les_hip_ctx* c)
     std::vector<float> tab(les::kBfTabSize);
     const double sig2 = c->filter == LES_HIP_FILTER_BILATERAL ? c->p.eps : 1.0;
     for (int s = 0; s < les::kBfTabSize; s++) tab[s] = (float)std::exp(-(double)s / sig2);
-    HIPCHECK(hipMalloc((void**)&c->d_bf_tab, tab.size() * sizeof(float)));
-    HIPCHECK(hipMemcpy(c->d_bf_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    const int rc = c->d_bf_tab.alloc(tab.size());
+    if (rc) return rc;
+    HIPCHECK(hipMemcpy(c->d_bf_tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
     return LES_HIP_OK;
 }
 
@@ -118,10 +120,10 @@ int launch_bf(les_hip_ctx* c, int mode, const les::BfJob* d_jobs, int njobs, int
     HIPCHECK(hipGetLastError());
     if (np > 1)
         hipLaunchKernelGGL(les::les_bf_kernel<les::BF_NPMAX>, dim3(njobs), dim3(les::BF_NT), 0, stream, c->geom, (const uint32_t*)c->v[mode].ipk,
-                           (const float*)c->d_bf_tab, d_jobs, d_calls, d_planes, (const float*)d_raw, d_out, c->R, njobs, check);
+                           (const float*)c->d_bf_tab.p, d_jobs, d_calls, d_planes, (const float*)d_raw, d_out, c->R, njobs, check);
     else
         hipLaunchKernelGGL(les::les_bf_kernel<1>, dim3(njobs), dim3(les::BF_NT), 0, stream, c->geom, (const uint32_t*)c->v[mode].ipk,
-                           (const float*)c->d_bf_tab, d_jobs, d_calls, d_planes, (const float*)d_raw, d_out, c->R, njobs, check);
+                           (const float*)c->d_bf_tab.p, d_jobs, d_calls, d_planes, (const float*)d_raw, d_out, c->R, njobs, check);
     HIPCHECK(hipGetLastError());
     return LES_HIP_OK;
 }

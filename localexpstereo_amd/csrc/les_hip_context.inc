@@ -83,7 +83,7 @@ static int create_common(les_hip_ctx** out, const les_hip_params* params, const 
         int rc = build_bf_table(c);
         if (rc) { les_hip_destroy(c); return rc; }
     }
-    if (hipMalloc((void**)&c->d_map, (size_t)p.H * p.W * sizeof(float)) != hipSuccess) {
+    if (c->d_map.alloc((size_t)p.H * p.W)) {
         les_hip_destroy(c);
         return fail(LES_HIP_ERR_DEVICE, "hipMalloc of the scratch cost map failed");
     }
@@ -123,27 +123,11 @@ void les_hip_destroy(les_hip_ctx* c)
         std::lock_guard<std::mutex> lk(g_live_mu);
         g_live.erase(std::remove_if(g_live.begin(), g_live.end(), [c](const std::pair<unsigned long long, les_hip_ctx*>& e) { return e.second == c; }), g_live.end());
     }
-    for (int m = 0; m < 2; m++) {
-        if (c->v[m].own_vol && c->v[m].vol) (void)hipFree(c->v[m].vol);
-        if (c->v[m].stats) (void)hipFree(c->v[m].stats);
-        if (c->v[m].ipk) (void)hipFree(c->v[m].ipk);
-        if (c->v[m].ipk10) (void)hipFree(c->v[m].ipk10);
-        if (c->v[m].feat) (void)hipFree(c->v[m].feat);
-        if (c->v[m].ipk8) (void)hipFree(c->v[m].ipk8);
-        if (c->v[m].mstats) (void)hipFree(c->v[m].mstats);
-        if (c->v[m].vol_t) (void)hipFree(c->v[m].vol_t);
-    }
     for (les_hip_scratch* sc : c->own_scratch) les_hip_scratch_destroy(sc);
     c->own_scratch.clear();
     for (MtHost* m : c->mt_idle) mt_host_free(m);
     c->mt_idle.clear();
-    if (c->d_planes) (void)hipFree(c->d_planes);
-    if (c->d_map) (void)hipFree(c->d_map);
-    if (c->d_wta) (void)hipFree(c->d_wta);
-    if (c->d_wta_planes) (void)hipFree(c->d_wta_planes);
-    if (c->d_pw_tab) (void)hipFree(c->d_pw_tab);
-    if (c->d_bf_tab) (void)hipFree(c->d_bf_tab);
-    delete c;
+    delete c;                                                   // the views' buffers and every owned table
 }
 
 int les_hip_set_stream(les_hip_ctx* c, void* s)

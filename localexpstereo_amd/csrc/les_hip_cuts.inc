@@ -4,8 +4,9 @@
 // staging of the hand-over (les_maxflow_tiled.h: residual graphs out, masks and flow values back).  A context keeps a pool of them: a call
 // takes one, returns it at the end; they are freed with the context (round 5 kept two words per host THREAD for ever).
 struct MtHost {
-    int* h_flags = nullptr; int* d_flags = nullptr;                    // [0] cells finished, [1] of them: gave up, [2] cells handed over, [3] their nodes
-    char* h_stage = nullptr; char* d_stage = nullptr;                  // rc8 [cap_nodes][8] floats | ex [cap_nodes] floats | masks [cap_nodes] bytes | list [cap_cells] | flows [cap_cells]
+    // (h_*: the pinned owners; d_*: the addresses the device reaches them at)
+    PinnedBuf<int> h_flags; int* d_flags = nullptr;                    // [0] cells finished, [1] of them: gave up, [2] cells handed over, [3] their nodes
+    PinnedBuf<char> h_stage; char* d_stage = nullptr;                  // rc8 [cap_nodes][8] floats | ex [cap_nodes] floats | masks [cap_nodes] bytes | list [cap_cells] | flows [cap_cells]
     long long cap_nodes = 0;
     int cap_cells = 0;
     size_t off_ex() const { return (size_t)cap_nodes * 32; }
@@ -15,24 +16,12 @@ struct MtHost {
     size_t bytes() const { return off_flows() + (size_t)cap_cells * sizeof(double); }
 };
 namespace {
-void mt_host_free(MtHost* m)
-{
-    if (!m) return;
-    if (m->h_flags) (void)hipHostFree(m->h_flags);
-    if (m->h_stage) (void)hipHostFree(m->h_stage);
-    delete m;
-}
-int mt_host_map(void** h, void** d, size_t bytes)
-{
+void mt_host_free(MtHost* m) { delete m; }                 // (les_hip_destroy sees MtHost only declared)
 #if defined(LES_SIM)
-    HIPCHECK(hipHostMalloc(h, bytes, 0));
-    *d = *h;
+constexpr unsigned kMtHostFlags = 0;
 #else
-    HIPCHECK(hipHostMalloc(h, bytes, hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHECK(hipHostGetDevicePointer(d, *h, 0));
+constexpr unsigned kMtHostFlags = hipHostMallocMapped | hipHostMallocCoherent;
 #endif
-    return LES_HIP_OK;
-}
 int mt_host_acquire(les_hip_ctx* c, MtHost** out)
 {
     {
@@ -40,7 +29,8 @@ int mt_host_acquire(les_hip_ctx* c, MtHost** out)
         if (!c->mt_idle.empty()) { *out = c->mt_idle.back(); c->mt_idle.pop_back(); return LES_HIP_OK; }
     }
     MtHost* m = new MtHost();
-    const int rc = mt_host_map((void**)&m->h_flags, (void**)&m->d_flags, 64);
+    int rc = m->h_flags.alloc(16, kMtHostFlags);
+    if (!rc) rc = m->h_flags.dev(&m->d_flags);
     if (rc) { delete m; return rc; }
     *out = m;
     return LES_HIP_OK;
@@ -51,14 +41,14 @@ void mt_host_release(les_hip_ctx* c, MtHost* m)
     c->mt_idle.push_back(m);
 }
 // staging for `nodes` graph nodes (37 bytes each) of `cells` cells, grown on demand
-int mt_host_stage(MtHost* m, long long nodes, int cells)
+int mt_host_stage(MtHost* m, long long nodes, int cells, hipStream_t stream)
 {
     if (m->cap_nodes >= nodes && m->cap_cells >= cells) return LES_HIP_OK;
-    if (m->h_stage) { (void)hipHostFree(m->h_stage); m->h_stage = nullptr; }
     m->cap_nodes = std::max(m->cap_nodes, (nodes + 4095) & ~4095ll);
     m->cap_cells = std::max(m->cap_cells, (cells + 15) & ~15);
-    const int rc = mt_host_map((void**)&m->h_stage, (void**)&m->d_stage, m->bytes());
-    if (rc) { m->cap_nodes = 0; m->cap_cells = 0; return rc; }
+    int rc = m->h_stage.grow(m->bytes(), 0, stream, kMtHostFlags);      // (bytes() has grown: always a new buffer)
+    if (!rc) rc = m->h_stage.dev(&m->d_stage);
+    if (rc) { m->h_stage.reset(); m->cap_nodes = 0; m->cap_cells = 0; return rc; }
     return LES_HIP_OK;
 }
 // The context's smoothness-coefficient table for (omega, epsilon), rebuilt (and the calling thread's stream synchronised) only when they change:
@@ -67,11 +57,14 @@ int mt_host_stage(MtHost* m, long long nodes, int cells)
 int pw_table(les_hip_ctx* c, float omega, float epsilon)
 {
     std::lock_guard<std::mutex> lk(c->mu);
-    if (c->pw_omega == omega && c->pw_epsilon == epsilon && c->d_pw_tab) return LES_HIP_OK;
+    if (c->pw_omega == omega && c->pw_epsilon == epsilon && c->d_pw_tab.p) return LES_HIP_OK;
     std::vector<float> tab(766);
     for (int k = 0; k < 766; k++) tab[k] = std::max(epsilon, std::exp(-(float)k / omega));
-    if (!c->d_pw_tab) HIPCHECK(hipMalloc((void**)&c->d_pw_tab, tab.size() * sizeof(float)));
-    HIPCHECK(hipMemcpyAsync(c->d_pw_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, cur_stream(c)));
+    if (!c->d_pw_tab.p) {
+        const int rc = c->d_pw_tab.alloc(tab.size());
+        if (rc) return rc;
+    }
+    HIPCHECK(hipMemcpyAsync(c->d_pw_tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, cur_stream(c)));
     HIPCHECK(hipStreamSynchronize(cur_stream(c)));
     c->pw_omega = omega; c->pw_epsilon = epsilon;
     return LES_HIP_OK;
@@ -104,18 +97,18 @@ int les_hip_batch_expansion_graph(les_hip_ctx* c, const les_hip_batch* b, int mo
     const int trc = pw_table(c, omega, epsilon);
     if (trc) return trc;
     const les::PairwiseParams pp{c->p.H, c->p.W, lambda, th_smooth};
-    const les::GraphCell* cells = reinterpret_cast<const les::GraphCell*>(b->d_targets);
-    const long long* offs = b->d_graph_off;
+    const les::GraphCell* cells = reinterpret_cast<const les::GraphCell*>(b->d_targets.p);
+    const long long* offs = b->d_graph_off.p;
     const float4 *pl = reinterpret_cast<const float4*>(d_planes), *lab = reinterpret_cast<const float4*>(d_labels);
     const uint32_t* ipk = c->v[mode].ipk;
-    const float* wtab = c->d_pw_tab;
-    double* flow0 = b->d_flow0;
+    const float* wtab = c->d_pw_tab.p;
+    double* flow0 = b->d_flow0.p;
     hipLaunchKernelGGL(les::les_expansion_graph_kernel, dim3(b->n, b->graph_chunks), dim3(256), 0, cur_stream(c), cells, offs, pl, lab, d_cur, d_prop, ipk, wtab,
                        pp, d_payload, flow0);
     HIPCHECK(hipGetLastError());
     if (flow0_host) {
         std::vector<double> part((size_t)b->n * b->graph_chunks);
-        HIPCHECK(hipMemcpyAsync(part.data(), b->d_flow0, part.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream(c)));
+        HIPCHECK(hipMemcpyAsync(part.data(), b->d_flow0.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream(c)));
         HIPCHECK(hipStreamSynchronize(cur_stream(c)));
         for (int i = 0; i < b->n; i++) {
             double s = 0;
@@ -162,11 +155,9 @@ int mf_build_lists(const les_hip_batch* b, bool cell_kernel)
     for (int k = 0; k < 3; k++)
         for (int i = 0; i < b->n; i++)
             if (mf_cell_kind(b->targets[i], cell_kernel) == k) { list.push_back(i); count[k]++; }
-    if (!b->d_mf_list && hipMalloc((void**)&b->d_mf_list, std::max<size_t>(1, list.size()) * sizeof(int)) != hipSuccess) {
-        b->d_mf_list = nullptr;
+    if (!b->d_mf_list.p && b->d_mf_list.alloc(std::max<size_t>(1, list.size())))
         return fail(LES_HIP_ERR_DEVICE, "les_hip_batch_solve_graphs: cell list allocation failed");
-    }
-    if (!list.empty() && hipMemcpy(b->d_mf_list, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+    if (!list.empty() && hipMemcpy(b->d_mf_list.p, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
         return fail(LES_HIP_ERR_DEVICE, "les_hip_batch_solve_graphs: cell list upload failed");
     std::copy(count, count + 3, b->mf_count);
     b->mf_list_key = key;
@@ -219,7 +210,7 @@ int les_hip_batch_solve_graphs_counted(les_hip_ctx* c, const les_hip_batch* b, c
         }
     }
 #endif
-    const les::GraphCellMf* cells = reinterpret_cast<const les::GraphCellMf*>(b->d_targets);
+    const les::GraphCellMf* cells = reinterpret_cast<const les::GraphCellMf*>(b->d_targets.p);
     int max_iter = les::kMfMaxIter;
     if (const char* ev = getenv("LES_HIP_MAXFLOW_MAX_ITER")) max_iter = std::max(0, atoi(ev));      // tests of the callers' host fall-back
     int round_iters = 16;                                   // (8 ... 64 measured on whole runs: flat within 3 %, tools/lab/ab_cell_kernel.sh)
@@ -238,7 +229,7 @@ int les_hip_batch_solve_graphs_counted(les_hip_ctx* c, const les_hip_batch* b, c
         const int rc = mf_build_lists(b, cell_kernel);
         if (rc) return rc;
         std::copy(b->mf_count, b->mf_count + 3, count);
-        lists[0] = b->d_mf_list; lists[1] = lists[0] + count[0]; lists[2] = lists[1] + count[1];
+        lists[0] = b->d_mf_list.p; lists[1] = lists[0] + count[0]; lists[2] = lists[1] + count[1];
     }
     for (const les_hip_rect& t : b->targets) {
         const int k = uniform ? kind : mf_cell_kind(t, cell_kernel);
@@ -250,13 +241,13 @@ int les_hip_batch_solve_graphs_counted(les_hip_ctx* c, const les_hip_batch* b, c
         const int np = (int)((std::max<long long>(group_max[k], 1) + 7) / 8) * 8;
         const size_t lds = les::mf_lds_bytes(np);
         if (k == 0)
-            hipLaunchKernelGGL(les::les_maxflow_cell_kernel, dim3(count[k]), dim3(les::kMcThreads), les::kMcLdsBytes, cur_stream(c), cells, b->d_graph_off, d_payload, max_iter,
+            hipLaunchKernelGGL(les::les_maxflow_cell_kernel, dim3(count[k]), dim3(les::kMcThreads), les::kMcLdsBytes, cur_stream(c), cells, b->d_graph_off.p, d_payload, max_iter,
                                round_iters, d_masks, d_status, d_flows, d_unsolved_total, lists[k]);
         else if (k == 1)
-            hipLaunchKernelGGL((les::les_maxflow_kernel<2, 1024>), dim3(count[k]), dim3(1024), lds, cur_stream(c), cells, b->d_graph_off, d_payload, np, max_iter, d_masks, d_status,
+            hipLaunchKernelGGL((les::les_maxflow_kernel<2, 1024>), dim3(count[k]), dim3(1024), lds, cur_stream(c), cells, b->d_graph_off.p, d_payload, np, max_iter, d_masks, d_status,
                                d_flows, d_unsolved_total, lists[k]);
         else
-            hipLaunchKernelGGL((les::les_maxflow_kernel<5, 512>), dim3(count[k]), dim3(512), lds, cur_stream(c), cells, b->d_graph_off, d_payload, np, max_iter, d_masks, d_status,
+            hipLaunchKernelGGL((les::les_maxflow_kernel<5, 512>), dim3(count[k]), dim3(512), lds, cur_stream(c), cells, b->d_graph_off.p, d_payload, np, max_iter, d_masks, d_status,
                                d_flows, d_unsolved_total, lists[k]);
         HIPCHECK(hipGetLastError());
     }
@@ -300,18 +291,14 @@ int mt_build_tiles(const les_hip_batch* b)
                 per_cell[i]++;
             }
     }
-    les::MtTile* d_t = nullptr;
-    int* d_p = nullptr;
-    if (hipMalloc((void**)&d_t, std::max<size_t>(1, tiles.size()) * sizeof(les::MtTile)) != hipSuccess ||
-        hipMalloc((void**)&d_p, per_cell.size() * sizeof(int)) != hipSuccess ||
-        (tiles.size() && hipMemcpy(d_t, tiles.data(), tiles.size() * sizeof(les::MtTile), hipMemcpyHostToDevice) != hipSuccess) ||
-        hipMemcpy(d_p, per_cell.data(), per_cell.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-        if (d_t) (void)hipFree(d_t);
-        if (d_p) (void)hipFree(d_p);
+    DevBuf<les::MtTile> d_t;
+    DevBuf<int> d_p;
+    if (d_t.alloc(std::max<size_t>(1, tiles.size())) || d_p.alloc(per_cell.size()) ||
+        (tiles.size() && hipMemcpy(d_t.p, tiles.data(), tiles.size() * sizeof(les::MtTile), hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemcpy(d_p.p, per_cell.data(), per_cell.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
         return fail(LES_HIP_ERR_DEVICE, "les_hip_batch_solve_graphs_tiled: tile table allocation failed");
-    }
-    b->d_mt_tiles = d_t;
-    b->d_mt_tiles_per_cell = d_p;
+    b->d_mt_tiles = std::move(d_t);
+    b->d_mt_tiles_per_cell = std::move(d_p);
     b->mt_ntiles = (int)tiles.size();
     return LES_HIP_OK;
 }
@@ -368,10 +355,10 @@ int les_hip_batch_solve_graphs_tiled_stats(les_hip_ctx* c, const les_hip_batch* 
 #endif
     hipStream_t st = cur_stream(c);
     les::MtArgs a;
-    a.cells = reinterpret_cast<const les::GraphCellMf*>(b->d_targets);
-    a.offsets = b->d_graph_off;
+    a.cells = reinterpret_cast<const les::GraphCellMf*>(b->d_targets.p);
+    a.offsets = b->d_graph_off.p;
     a.payload = d_payload;
-    a.tiles = b->d_mt_tiles;
+    a.tiles = b->d_mt_tiles.p;
     a.ws = reinterpret_cast<char*>(d_workspace);
     a.nodes = b->graph_nodes;
     a.ncells = b->n;
@@ -390,10 +377,10 @@ int les_hip_batch_solve_graphs_tiled_stats(les_hip_ctx* c, const les_hip_batch* 
     rc = mt_host_acquire(c, &lease.m);
     if (rc) return rc;
     MtHost& hf = *lease.m;
-    volatile int* flags = hf.h_flags;
+    volatile int* flags = hf.h_flags.p;
     for (int i = 0; i < 6; i++) flags[i] = 0;   // (nothing in flight writes them: the previous user of this MtHost has synchronised)
     a.host_flags = hf.d_flags;
-    hipLaunchKernelGGL(les::les_maxflow_tiled_init_kernel, dim3((b->n + 255) / 256), dim3(256), 0, st, a.ws, a.nodes, a.ncells, b->d_mt_tiles_per_cell, d_status, d_flows, a.host_flags);
+    hipLaunchKernelGGL(les::les_maxflow_tiled_init_kernel, dim3((b->n + 255) / 256), dim3(256), 0, st, a.ws, a.nodes, a.ncells, b->d_mt_tiles_per_cell.p, d_status, d_flows, a.host_flags);
     HIPCHECK(hipGetLastError());
     if (b->mt_ntiles == 0) {                                // every target rect is empty: the init kernel has closed all cells
         HIPCHECK(hipStreamSynchronize(st));
@@ -433,14 +420,14 @@ int les_hip_batch_solve_graphs_tiled_stats(les_hip_ctx* c, const les_hip_batch* 
         if (done + handed >= b->n) break;
         if (hand && total >= hand_after && (total >= hand_late_after || smallest <= hand_cell_nodes)) {
             les::MtHandArgs ha;
-            ha.tiles = b->d_mt_tiles; ha.ws = a.ws; ha.nodes = a.nodes; ha.ncells = a.ncells; ha.cells = a.cells;
+            ha.tiles = b->d_mt_tiles.p; ha.ws = a.ws; ha.nodes = a.nodes; ha.ncells = a.ncells; ha.cells = a.cells;
             ha.hand_after = hand_after; ha.late_after = hand_late_after; ha.cell_nodes = hand_cell_nodes;
             ha.masks = d_masks; ha.status = d_status; ha.flows = d_flows; ha.host_flags = hf.d_flags;
             // the staging holds what the collect kernel selects; when it reports more than fits, it has parked nothing: grow the staging, collect again
             // (nothing has run in between, the selection is the same)
             for (int attempt = 0;; attempt++) {
                 if (attempt == 0 && hf.cap_nodes == 0) {
-                    rc = mt_host_stage(&hf, std::min<long long>(b->graph_nodes, 140000), std::min(b->n, 16));
+                    rc = mt_host_stage(&hf, std::min<long long>(b->graph_nodes, 140000), std::min(b->n, 16), st);
                     if (rc) return rc;
                 }
                 ha.cap_nodes = hf.cap_nodes; ha.cap_cells = hf.cap_cells;
@@ -456,7 +443,7 @@ int les_hip_batch_solve_graphs_tiled_stats(les_hip_ctx* c, const les_hip_batch* 
                 const int want_cells = flags[4], want_nodes = flags[5];
                 if (flags[2] > 0 || want_cells == 0) break;
                 if (attempt > 0) return fail(LES_HIP_ERR_DEVICE, "les_hip_batch_solve_graphs_tiled: hand-over staging of %lld nodes refused %d cells of %d nodes", hf.cap_nodes, want_cells, want_nodes);
-                rc = mt_host_stage(&hf, want_nodes, want_cells);
+                rc = mt_host_stage(&hf, want_nodes, want_cells, st);
                 if (rc) return rc;
             }
             const int now = flags[2];
@@ -464,11 +451,11 @@ int les_hip_batch_solve_graphs_tiled_stats(les_hip_ctx* c, const les_hip_batch* 
                 handed += now;
                 handed_nodes += flags[3];
                 const auto h0 = std::chrono::steady_clock::now();
-                const float* h_rc8 = reinterpret_cast<const float*>(hf.h_stage);
-                const float* h_ex = reinterpret_cast<const float*>(hf.h_stage + hf.off_ex());
-                uint8_t* h_masks = reinterpret_cast<uint8_t*>(hf.h_stage + hf.off_masks());
-                const les::MtHandCell* list = reinterpret_cast<const les::MtHandCell*>(hf.h_stage + hf.off_list());
-                double* hflows = reinterpret_cast<double*>(hf.h_stage + hf.off_flows());
+                const float* h_rc8 = reinterpret_cast<const float*>(hf.h_stage.p);
+                const float* h_ex = reinterpret_cast<const float*>(hf.h_stage.p + hf.off_ex());
+                uint8_t* h_masks = reinterpret_cast<uint8_t*>(hf.h_stage.p + hf.off_masks());
+                const les::MtHandCell* list = reinterpret_cast<const les::MtHandCell*>(hf.h_stage.p + hf.off_list());
+                double* hflows = reinterpret_cast<double*>(hf.h_stage.p + hf.off_flows());
                 const std::vector<les_hip_rect>& tg = b->targets;
                 const char* sev = getenv("LES_HIP_MAXFLOW_HANDOVER_SOLVER");      // 1 (default): FIFO push-relabel; 0: search trees with the push-relabel continuation (measured slower on what is handed over: tools/residual_probe.py)
                 const int solver = sev ? atoi(sev) : 1;
@@ -526,8 +513,8 @@ int les_hip_batch_apply_masks(les_hip_ctx* c, const les_hip_batch* b, const les_
     if (c) (void)hipSetDevice(c->p.device);                 // HIP's current device is per host thread
     if (!c || !b || !d_planes || !d_masks || !d_cur || !d_prop || !d_labels) return fail(LES_HIP_ERR_ARG, "null argument");
     if (b->n == 0) return LES_HIP_OK;
-    const les::GraphCell* cells = reinterpret_cast<const les::GraphCell*>(b->d_targets);
-    const long long* offs = b->d_graph_off;
+    const les::GraphCell* cells = reinterpret_cast<const les::GraphCell*>(b->d_targets.p);
+    const long long* offs = b->d_graph_off.p;
     const float4* pl = reinterpret_cast<const float4*>(d_planes);
     float4* lab = reinterpret_cast<float4*>(d_labels);
     hipLaunchKernelGGL(les::les_apply_masks_kernel, dim3(b->n, b->wta_chunks), dim3(256), 0, cur_stream(c), cells, offs, pl, d_masks, d_cur, d_prop, lab, c->p.W);

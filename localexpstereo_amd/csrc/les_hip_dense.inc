@@ -67,7 +67,7 @@ int les_hip_unary_labels(les_hip_ctx* c, int mode, const les_hip_rect* region, c
     } else {
         const les::DenseArgs a{r.x, r.y, r.w, r.h, c->R, check};      // (c->R: windR of the bilateral filter, 0 without aggregation)
         const long long tiles = (long long)((r.w + les::DENSE_BF_T - 1) / les::DENSE_BF_T) * ((r.h + les::DENSE_BF_T - 1) / les::DENSE_BF_T);
-        hipLaunchKernelGGL(kDenseDirect[src], dim3((unsigned)tiles), dim3(64 * les::DENSE_BF_NW), 0, cur_stream(c), c->geom, view, a, (const float*)c->d_bf_tab,
+        hipLaunchKernelGGL(kDenseDirect[src], dim3((unsigned)tiles), dim3(64 * les::DENSE_BF_NW), 0, cur_stream(c), c->geom, view, a, (const float*)c->d_bf_tab.p,
                            labels, d_cost);
     }
     HIPCHECK(hipGetLastError());

@@ -2,12 +2,12 @@
 // solution on the device (les_eval.h) -- the progress log of the Evaluator and the region energies of the flow == energy self-check
 struct les_hip_evaluator {
     les_hip_ctx* c = nullptr;
-    float* d_gt = nullptr;               // H * W floats, or null: no ground truth
-    uint8_t* d_nonocc = nullptr;         // H * W bytes, or null: every pixel counts as non-occluded
+    DevBuf<float> d_gt;                  // H * W floats, or empty: no ground truth
+    DevBuf<uint8_t> d_nonocc;            // H * W bytes, or empty: every pixel counts as non-occluded
     float threshold = 0.5f, precision = -1.0f;
     int max_rows = 0, rows = 0;          // rows: enqueued so far (host count; the device has written them once its stream has run)
-    les::EvalRecord* d_log = nullptr;
-    les::EvalPartial* d_part = nullptr;  // one slot per tile of les_eval_kernel
+    DevBuf<les::EvalRecord> d_log;
+    DevBuf<les::EvalPartial> d_part;     // one slot per tile of les_eval_kernel
     dim3 grid;
 };
 
@@ -28,12 +28,11 @@ int les_hip_evaluator_create(les_hip_ctx* c, const float* gt_host, const unsigne
     ev->threshold = error_threshold; ev->precision = precision; ev->max_rows = max_rows;
     ev->grid = dim3((unsigned)((c->p.W + les::kEvTW - 1) / les::kEvTW), (unsigned)((c->p.H + les::kEvTH - 1) / les::kEvTH));
     const size_t P = (size_t)c->p.H * c->p.W, slots = (size_t)ev->grid.x * ev->grid.y;
-    bool ok = hipMalloc((void**)&ev->d_log, (size_t)max_rows * sizeof(les::EvalRecord)) == hipSuccess &&
-              hipMalloc((void**)&ev->d_part, slots * sizeof(les::EvalPartial)) == hipSuccess;
-    if (ok && gt_host) ok = hipMalloc((void**)&ev->d_gt, P * sizeof(float)) == hipSuccess && hipMemcpy(ev->d_gt, gt_host, P * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && nonocc_host) ok = hipMalloc((void**)&ev->d_nonocc, P) == hipSuccess && hipMemcpy(ev->d_nonocc, nonocc_host, P, hipMemcpyHostToDevice) == hipSuccess;
+    bool ok = !ev->d_log.alloc((size_t)max_rows) && !ev->d_part.alloc(slots);
+    if (ok && gt_host) ok = !ev->d_gt.alloc(P) && hipMemcpy(ev->d_gt.p, gt_host, P * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && nonocc_host) ok = !ev->d_nonocc.alloc(P) && hipMemcpy(ev->d_nonocc.p, nonocc_host, P, hipMemcpyHostToDevice) == hipSuccess;
     if (!ok) {
-        les_hip_evaluator_destroy(ev);
+        delete ev;
         return fail(LES_HIP_ERR_DEVICE, "les_hip_evaluator_create: device allocation or upload failed");
     }
     *out = ev;
@@ -42,11 +41,6 @@ int les_hip_evaluator_create(les_hip_ctx* c, const float* gt_host, const unsigne
 
 void les_hip_evaluator_destroy(les_hip_evaluator* ev)
 {
-    if (!ev) return;
-    if (ev->d_gt) (void)hipFree(ev->d_gt);
-    if (ev->d_nonocc) (void)hipFree(ev->d_nonocc);
-    if (ev->d_log) (void)hipFree(ev->d_log);
-    if (ev->d_part) (void)hipFree(ev->d_part);
     delete ev;
 }
 
@@ -63,10 +57,10 @@ int les_hip_evaluate(les_hip_ctx* c, les_hip_evaluator* ev, int mode, const les_
     const les::EvalParams p{c->p.H, c->p.W, lambda, th_smooth, ev->threshold, ev->precision};
     const float4* lab = reinterpret_cast<const float4*>(d_labels);
     const uint32_t* ipk = c->v[mode].ipk;
-    const float *wtab = c->d_pw_tab, *gt = ev->d_gt;
-    const uint8_t* nonocc = ev->d_nonocc;
-    les::EvalPartial* part = ev->d_part;
-    les::EvalRecord* row = ev->d_log + ev->rows;
+    const float *wtab = c->d_pw_tab.p, *gt = ev->d_gt.p;
+    const uint8_t* nonocc = ev->d_nonocc.p;
+    les::EvalPartial* part = ev->d_part.p;
+    les::EvalRecord* row = ev->d_log.p + ev->rows;
     const int nslots = (int)(ev->grid.x * ev->grid.y);
     hipLaunchKernelGGL(les::les_eval_kernel, ev->grid, dim3(256), 0, cur_stream(c), lab, d_cost, ipk, wtab, gt, nonocc, p, part);
     hipLaunchKernelGGL(les::les_eval_finish_kernel, dim3(1), dim3(256), 0, cur_stream(c), part, nslots, index, mode, row);
@@ -83,7 +77,7 @@ int les_hip_evaluator_rows(les_hip_ctx* c, les_hip_evaluator* ev, les_hip_eval_r
     if (ev->rows == 0) return LES_HIP_OK;
     if (!rows_host || capacity < ev->rows) return fail(LES_HIP_ERR_ARG, "les_hip_evaluator_rows: room for %d rows, %d written", rows_host ? capacity : 0, ev->rows);
     HIPCHECK(hipSetDevice(c->p.device));
-    HIPCHECK(hipMemcpyAsync(rows_host, ev->d_log, (size_t)ev->rows * sizeof(les::EvalRecord), hipMemcpyDeviceToHost, cur_stream(c)));
+    HIPCHECK(hipMemcpyAsync(rows_host, ev->d_log.p, (size_t)ev->rows * sizeof(les::EvalRecord), hipMemcpyDeviceToHost, cur_stream(c)));
     HIPCHECK(hipStreamSynchronize(cur_stream(c)));
     return LES_HIP_OK;
 }
@@ -104,14 +98,17 @@ int les_hip_batch_region_energy(les_hip_ctx* c, const les_hip_batch* b, int mode
             for (const les_hip_rect& t : b->targets) most = std::max(most, (long long)(std::max(0, t.w) + 2) * (std::max(0, t.h) + 2));
             b->region_chunks = (int)((most + les::kRegChunk - 1) / les::kRegChunk);
         }
-        if (!b->d_region_part[mode]) HIPCHECK(hipMalloc((void**)&b->d_region_part[mode], (size_t)b->n * b->region_chunks * sizeof(double)));
+        if (!b->d_region_part[mode].p) {
+            const int rc = b->d_region_part[mode].alloc((size_t)b->n * b->region_chunks);
+            if (rc) return rc;
+        }
     }
     const les::PairwiseParams pp{c->p.H, c->p.W, lambda, th_smooth};
-    const les::GraphCell* cells = reinterpret_cast<const les::GraphCell*>(b->d_targets);
+    const les::GraphCell* cells = reinterpret_cast<const les::GraphCell*>(b->d_targets.p);
     const float4* lab = reinterpret_cast<const float4*>(d_labels);
     const uint32_t* ipk = c->v[mode].ipk;
-    const float* wtab = c->d_pw_tab;
-    double* part = b->d_region_part[mode];
+    const float* wtab = c->d_pw_tab.p;
+    double* part = b->d_region_part[mode].p;
     const int n = b->n, chunks = b->region_chunks, W = c->p.W, H = c->p.H;
     hipLaunchKernelGGL(les::les_region_energy_kernel, dim3(n, chunks), dim3(256), 0, cur_stream(c), cells, lab, d_cost, ipk, wtab, pp, part);
     hipLaunchKernelGGL(les::les_region_energy_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, cur_stream(c), cells, n, W, H, (const double*)part, chunks, d_energy);

@@ -6,8 +6,8 @@ extern "C" {
 struct les_hip_exchange {
     les_hip_ctx* c = nullptr;
     int rank = 0, world = 1, nrects = 0, own_first = 0, own_n = 0, lmax = 0, max_px = 0;
-    les::XchgRect* d_rects = nullptr;
-    float* d_send = nullptr; float* d_recv = nullptr;       // buffers of les_hip_exchange_tiles, allocated on its first call
+    DevBuf<les::XchgRect> d_rects;
+    DevBuf<float> d_send, d_recv;                           // buffers of les_hip_exchange_tiles, allocated on its first call
 };
 
 namespace {
@@ -59,8 +59,8 @@ int les_hip_exchange_create(les_hip_ctx* c, int rank, int world, int n, const le
     x->c = c; x->rank = rank; x->world = world; x->nrects = n; x->own_first = first[rank]; x->own_n = first[rank + 1] - first[rank];
     x->lmax = (int)lmax; x->max_px = max_px;
     if (n > 0) {
-        if (hipMalloc((void**)&x->d_rects, (size_t)n * sizeof(les::XchgRect)) != hipSuccess ||
-            hipMemcpy(x->d_rects, tab.data(), (size_t)n * sizeof(les::XchgRect), hipMemcpyHostToDevice) != hipSuccess) {
+        if (x->d_rects.alloc((size_t)n) ||
+            hipMemcpy(x->d_rects.p, tab.data(), (size_t)n * sizeof(les::XchgRect), hipMemcpyHostToDevice) != hipSuccess) {
             les_hip_exchange_destroy(x);
             return fail(LES_HIP_ERR_DEVICE, "les_hip_exchange_create: upload of the rect table failed");
         }
@@ -73,9 +73,6 @@ void les_hip_exchange_destroy(les_hip_exchange* x)
 {
     if (!x) return;
     if (x->c) (void)hipSetDevice(x->c->p.device);
-    if (x->d_rects) (void)hipFree(x->d_rects);
-    if (x->d_send) (void)hipFree(x->d_send);
-    if (x->d_recv) (void)hipFree(x->d_recv);
     delete x;
 }
 
@@ -85,7 +82,7 @@ int les_hip_exchange_pack(les_hip_ctx* c, const les_hip_exchange* x, const les_h
 {
     if (!c || !x || x->c != c || !d_labels || !d_cost || !d_slot) return fail(LES_HIP_ERR_ARG, "les_hip_exchange_pack: bad argument");
     if (x->own_n <= 0) return LES_HIP_OK;
-    hipLaunchKernelGGL(les::les_xchg_pack_kernel, dim3(x->own_n, xchg_chunks(x->max_px)), dim3(256), 0, cur_stream(c), x->d_rects, x->own_first,
+    hipLaunchKernelGGL(les::les_xchg_pack_kernel, dim3(x->own_n, xchg_chunks(x->max_px)), dim3(256), 0, cur_stream(c), x->d_rects.p, x->own_first,
                        reinterpret_cast<const float4*>(d_labels), d_cost, d_slot, x->lmax, c->p.W);
     HIPCHECK(hipGetLastError());
     return LES_HIP_OK;
@@ -95,7 +92,7 @@ int les_hip_exchange_unpack(les_hip_ctx* c, const les_hip_exchange* x, const flo
 {
     if (!c || !x || x->c != c || !d_labels || !d_cost || !d_recv) return fail(LES_HIP_ERR_ARG, "les_hip_exchange_unpack: bad argument");
     if (x->nrects <= 0 || x->world == 1) return LES_HIP_OK;
-    hipLaunchKernelGGL(les::les_xchg_unpack_kernel, dim3(x->nrects, xchg_chunks(x->max_px)), dim3(256), 0, cur_stream(c), x->d_rects, d_recv,
+    hipLaunchKernelGGL(les::les_xchg_unpack_kernel, dim3(x->nrects, xchg_chunks(x->max_px)), dim3(256), 0, cur_stream(c), x->d_rects.p, d_recv,
                        reinterpret_cast<float4*>(d_labels), d_cost, x->lmax, c->p.W, x->rank);
     HIPCHECK(hipGetLastError());
     return LES_HIP_OK;
@@ -110,17 +107,17 @@ int les_hip_exchange_tiles(les_hip_ctx* c, les_hip_exchange* x, void* nccl_comm,
     if (!allgather) return fail(LES_HIP_ERR_DEVICE, "les_hip_exchange_tiles: librccl.so (ncclAllGather) not found");
     const size_t slot = (size_t)5 * x->lmax;
     if (slot == 0) return LES_HIP_OK;
-    if (!x->d_send) {
+    int rc = LES_HIP_OK;
+    if (!x->d_send.p || !x->d_recv.p) {                         // the first call (or the one after a failed first call)
         HIPCHECK(hipSetDevice(c->p.device));
-        HIPCHECK(hipMalloc((void**)&x->d_send, slot * sizeof(float)));
-        HIPCHECK(hipMalloc((void**)&x->d_recv, slot * sizeof(float) * (size_t)x->world));
+        if ((rc = x->d_send.alloc(slot)) || (rc = x->d_recv.alloc(slot * (size_t)x->world))) return rc;
     }
     // pack -> all-gather -> unpack, all enqueued on the calling thread's stream: no host synchronisation anywhere
-    int rc = les_hip_exchange_pack(c, x, d_labels, d_cost, x->d_send);
+    rc = les_hip_exchange_pack(c, x, d_labels, d_cost, x->d_send.p);
     if (rc) return rc;
-    const int nrc = allgather(x->d_send, x->d_recv, slot, 7 /* ncclFloat32 */, nccl_comm, cur_stream(c));
+    const int nrc = allgather(x->d_send.p, x->d_recv.p, slot, 7 /* ncclFloat32 */, nccl_comm, cur_stream(c));
     if (nrc != 0) return fail(LES_HIP_ERR_DEVICE, "les_hip_exchange_tiles: ncclAllGather failed with ncclResult_t %d", nrc);
-    return les_hip_exchange_unpack(c, x, x->d_recv, d_labels, d_cost);
+    return les_hip_exchange_unpack(c, x, x->d_recv.p, d_labels, d_cost);
 }
 
 }  // extern "C"

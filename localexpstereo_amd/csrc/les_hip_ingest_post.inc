@@ -21,32 +21,21 @@ int les_hip_convert_volume_l2r(const float* src, float* dst, int D, int H, int W
 
 // ---- dual-view post-processing (LES/PMStereoBase.h:111-256)
 namespace {
-struct PostScratch {
-    float* disp[2] = {nullptr, nullptr};
-    uint8_t *fail = nullptr, *failb = nullptr, *fail2 = nullptr;
-    float4* copy = nullptr;
-    float* wtab = nullptr;
-    PostScratch() = default;
-    PostScratch(const PostScratch&) = delete;              // launches must capture the raw pointers, not this owner
-    PostScratch& operator=(const PostScratch&) = delete;
-    ~PostScratch()
-    {
-        for (float* d : disp) if (d) (void)hipFree(d);
-        if (fail) (void)hipFree(fail);
-        if (failb) (void)hipFree(failb);
-        if (fail2) (void)hipFree(fail2);
-        if (copy) (void)hipFree(copy);
-        if (wtab) (void)hipFree(wtab);
-    }
+struct PostScratch {                                       // (launches take the raw pointers, never the owners)
+    DevBuf<float> disp[2];
+    DevBuf<uint8_t> fail, failb, fail2;
+    DevBuf<float4> copy;
+    DevBuf<float> wtab;
 };
 int post_disparities(les_hip_ctx* c, PostScratch& ps, const les_hip_plane* const labels[2])
 {
     const int H = c->p.H, W = c->p.W;
     const size_t P = (size_t)H * W;
     for (int m = 0; m < 2; m++) {
-        if (!ps.disp[m]) HIPCHECK(hipMalloc((void**)&ps.disp[m], P * sizeof(float)));
+        const int rc = ps.disp[m].alloc(P);
+        if (rc) return rc;
         const float4* lab = (const float4*)labels[m];
-        float* disp = ps.disp[m];
+        float* disp = ps.disp[m].p;
         hipLaunchKernelGGL(les::les_disparity_kernel, dim3((W + 255) / 256, H), dim3(256), 0, cur_stream(c), lab, disp, H, W);
     }
     HIPCHECK(hipGetLastError());
@@ -66,7 +55,7 @@ int les_hip_consistency_check(les_hip_ctx* c, const les_hip_plane* d_labelsL, co
     if (rc) return rc;
     unsigned char* out[2] = {d_failL, d_failR};
     for (int m = 0; m < 2; m++) {
-        const float *d_self = ps.disp[m], *d_other = ps.disp[1 - m];
+        const float *d_self = ps.disp[m].p, *d_other = ps.disp[1 - m].p;
         unsigned char* o = out[m];
         const float sign = m ? -1.0f : 1.0f;
         hipLaunchKernelGGL(les::les_lr_check_kernel, dim3((W + 255) / 256, H), dim3(256), 0, cur_stream(c), d_self, d_other, o, H, W, sign, threshold);
@@ -89,26 +78,23 @@ int les_hip_post_process(les_hip_ctx* c, les_hip_plane* d_labelsL, les_hip_plane
     les_hip_plane* labels[2] = {d_labelsL, d_labelsR};
     int rc = post_disparities(c, ps, labels);
     if (rc) return rc;
-    HIPCHECK(hipMalloc((void**)&ps.fail, P));
-    HIPCHECK(hipMalloc((void**)&ps.failb, 2 * P));
-    HIPCHECK(hipMalloc((void**)&ps.fail2, P));
-    HIPCHECK(hipMalloc((void**)&ps.copy, P * sizeof(float4)));
+    if ((rc = ps.fail.alloc(P)) || (rc = ps.failb.alloc(2 * P)) || (rc = ps.fail2.alloc(P)) || (rc = ps.copy.alloc(P))) return rc;
     {
         // computePatchWeight (LES/StereoEnergy.h:251-257): exp(-|dI|_1 / omega) in float; |dI|_1 of 8-bit colours is an integer
         std::vector<float> tab(766);
         for (int k = 0; k < 766; k++) tab[k] = std::exp(-(float)k / omega);
-        HIPCHECK(hipMalloc((void**)&ps.wtab, tab.size() * sizeof(float)));
-        HIPCHECK(hipMemcpyAsync(ps.wtab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, cur_stream(c)));
+        if ((rc = ps.wtab.alloc(tab.size()))) return rc;
+        HIPCHECK(hipMemcpyAsync(ps.wtab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, cur_stream(c)));
         HIPCHECK(hipStreamSynchronize(cur_stream(c)));
     }
     const dim3 g((W + 255) / 256, H), b(256);
     // both fail masks come from the labels before any of them is modified (LES/PMStereoBase.h:158-164)
-    uint8_t *failm = ps.fail, *fail2 = ps.fail2;
-    const float* wtab = ps.wtab;
-    float4* copy = ps.copy;
+    uint8_t *failm = ps.fail.p, *fail2 = ps.fail2.p;
+    const float* wtab = ps.wtab.p;
+    float4* copy = ps.copy.p;
     for (int m = 0; m < 2; m++) {
-        const float *d_self = ps.disp[m], *d_other = ps.disp[1 - m];
-        uint8_t* failb = ps.failb + m * P;
+        const float *d_self = ps.disp[m].p, *d_other = ps.disp[1 - m].p;
+        uint8_t* failb = ps.failb.p + m * P;
         float4* lab = (float4*)labels[m];
         const float sign = m ? -1.0f : 1.0f;
         hipLaunchKernelGGL(les::les_lr_check_kernel, g, b, 0, cur_stream(c), d_self, d_other, failm, H, W, sign, threshold);
@@ -116,10 +102,10 @@ int les_hip_post_process(les_hip_ctx* c, les_hip_plane* d_labelsL, les_hip_plane
         hipLaunchKernelGGL(les::les_nn_fill_kernel, g, b, 0, cur_stream(c), failb, fail2, lab, H, W);
     }
     for (int m = 0; m < 2; m++) {
-        HIPCHECK(hipMemcpyAsync(ps.copy, labels[m], P * sizeof(float4), hipMemcpyDeviceToDevice, cur_stream(c)));
+        HIPCHECK(hipMemcpyAsync(ps.copy.p, labels[m], P * sizeof(float4), hipMemcpyDeviceToDevice, cur_stream(c)));
         const dim3 gp(W, H);
         const int area = (2 * windR + 1) * (2 * windR + 1);
-        const uint8_t* failb = ps.failb + m * P;
+        const uint8_t* failb = ps.failb.p + m * P;
         float4* lab = (float4*)labels[m];
         const uint32_t* ipk = c->v[m].ipk;
         if (area <= 256)

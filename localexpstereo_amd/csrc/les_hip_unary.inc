@@ -3,12 +3,6 @@
 // (les_hip_unary_one_scratch); run_unary is the one router both run through, and unary_kind the one place that decides which kernel serves
 // a run.  The launches themselves are les_hip_march.inc's, les_hip_vdisp.inc's and les_hip_bilateral.inc's.
 
-void free_unary_tables(UnaryTables& t)
-{
-    if (t.d_mem) (void)hipFree(t.d_mem);
-    t = UnaryTables();
-}
-
 // compact: one call, its outputs in a tile of its target rect's size (row stride = target width, origin = target corner); otherwise map /
 // slab coordinates (out_slabs as for les_hip_batch_create)
 int build_unary_tables(les_hip_ctx* c, int n, const les_hip_rect* frs, const les_hip_rect* trs, int out_slabs, bool compact, UnaryTables& t)
@@ -76,9 +70,10 @@ int build_unary_tables(les_hip_ctx* c, int n, const les_hip_rect* frs, const les
     const size_t o_jobs = put(jobs), o_mjobs = put(mjobs), o_calls = put(calls), o_raw_off = put(raw_off), o_targets = put(targets),
                  o_out_off = put(out_off), o_bfjobs = put(bfjobs), o_vd_calls = put(vd_calls), o_vd_stand = put(vd_stand);
     if (blob.empty()) return LES_HIP_OK;
-    HIPCHECK(hipMalloc(&t.d_mem, blob.size()));
-    HIPCHECK(hipMemcpy(t.d_mem, blob.data(), blob.size(), hipMemcpyHostToDevice));
-    auto at = [&](size_t off) -> const void* { return off == SIZE_MAX ? nullptr : static_cast<const char*>(t.d_mem) + off; };
+    int rc = t.mem.alloc(blob.size());
+    if (rc) return rc;
+    HIPCHECK(hipMemcpy(t.mem.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
+    auto at = [&](size_t off) -> const void* { return off == SIZE_MAX ? nullptr : t.mem.p + off; };
     t.d_jobs = static_cast<const les::Job*>(at(o_jobs));
     t.d_mjobs = static_cast<const les::Job*>(at(o_mjobs));
     t.d_rawcalls = static_cast<const les::RawCall*>(at(o_calls));
@@ -88,31 +83,6 @@ int build_unary_tables(les_hip_ctx* c, int n, const les_hip_rect* frs, const les
     t.d_bfjobs = static_cast<const les::BfJob*>(at(o_bfjobs));
     t.d_vd_calls = static_cast<const les::RawCall*>(at(o_vd_calls));
     t.d_vd_stand_in = static_cast<const float4*>(at(o_vd_stand));
-    return LES_HIP_OK;
-}
-
-void free_workspace(UnaryWorkspace& w)
-{
-    for (auto& s : w.slot) {
-        if (s.raw) (void)hipFree(s.raw);
-        if (s.flags) (void)hipFree(s.flags);
-        if (s.rjobs) (void)hipFree(s.rjobs);
-        if (s.vol) (void)hipFree(s.vol);
-        s = UnaryWorkspace::Slot();
-    }
-}
-
-template <class T> int grow(T*& p, size_t& cap, size_t need, size_t at_least, hipStream_t stream)
-{
-    if (need <= cap) return LES_HIP_OK;
-    if (p) {
-        HIPCHECK(hipStreamSynchronize(stream));             // (launches in flight may still read the old buffer)
-        HIPCHECK(hipFree(p));
-    }
-    p = nullptr; cap = 0;
-    const size_t n = std::max(need, at_least);
-    HIPCHECK(hipMalloc((void**)&p, n * sizeof(T)));
-    cap = n;
     return LES_HIP_OK;
 }
 
@@ -142,25 +112,25 @@ int run_unary(les_hip_ctx* c, const UnaryTables& t, UnaryWorkspace& w, int mode,
         if (w.shared) lk.lock();
         // (a batch's tables are fixed: exact sizes; a scratch's change with its rect pairs: room for the usual ones at once)
         const size_t min_raw = w.shared ? 1 : 256 * 256, min_jobs = w.shared ? 1 : 64;
-        if (patches) rc = grow(s.raw, s.raw_cap, (size_t)std::max<long long>(t.raw_floats, 1), min_raw, stream);
-        if (!rc && masked) rc = grow(s.flags, s.flags_cap, (size_t)std::max(t.n, 1), 1, stream);
-        if (!rc && masked) rc = grow(s.rjobs, s.rjobs_cap, (size_t)std::max(t.njobs, 1), min_jobs, stream);
-        if (!rc && vdisp) rc = grow(s.vol, s.vol_cap, std::max<size_t>((size_t)t.vd_max_slices * c->p.H * c->p.W, 1), 1, stream);
+        if (patches) rc = s.raw.grow((size_t)std::max<long long>(t.raw_floats, 1), min_raw, stream);
+        if (!rc && masked) rc = s.flags.grow((size_t)std::max(t.n, 1), 1, stream);
+        if (!rc && masked) rc = s.rjobs.grow((size_t)std::max(t.njobs, 1), min_jobs, stream);
+        if (!rc && vdisp) rc = s.vol.grow(std::max<size_t>((size_t)t.vd_max_slices * c->p.H * c->p.W, 1), 1, stream);
         if (rc) return rc;
     }
-    const RawPatches rp{t.d_rawcalls, t.d_raw_off, s.raw, t.n, t.raw_chunks};
-    if (kind == 2) return launch_bf(c, mode, t.d_bfjobs, t.nbfjobs, t.bf_np, t.d_rawcalls, t.n, t.raw_chunks, s.raw, d_planes, d_out, check, stream);
+    const RawPatches rp{t.d_rawcalls, t.d_raw_off, s.raw.p, t.n, t.raw_chunks};
+    if (kind == 2) return launch_bf(c, mode, t.d_bfjobs, t.nbfjobs, t.bf_np, t.d_rawcalls, t.n, t.raw_chunks, s.raw.p, d_planes, d_out, check, stream);
     if (kind == 1) {
         if (c->naive) return launch_naive_march(c, t.mentry, mode, t.d_mjobs, t.nmgroups, d_planes, d_out, check, stream, rp);
         if (c->interp == 1) return launch_march(c, t.mentry, mode, t.d_mjobs, t.nmgroups, d_planes, d_out, check, stream);
-        return launch_interp_march(c, t.mentry, mode, t.d_mjobs, t.nmgroups, rp, s.flags, t.d_jobs, s.rjobs, t.njobs, t.d_targets, t.d_out_off,
+        return launch_interp_march(c, t.mentry, mode, t.d_mjobs, t.nmgroups, rp, s.flags.p, t.d_jobs, s.rjobs.p, t.njobs, t.d_targets, t.d_out_off,
                                    t.out_stride, d_planes, d_out, check, stream);
     }
     if (!c->naive && c->interp != 1 && t.march_ok && interp_march_ok(c, mode))
         note_fallback(c->fallback_seen, FB_PATCHES, "the raw-cost patches of one batch at interpolation %d exceed 4 GB", c->interp);
     rc = launch_strips(c, mode, t.d_jobs, t.njobs, d_planes, d_out, check, stream);
     if (rc) return rc;
-    if (vdisp) return launch_vdisp_strips(c, t, s.vol, s.flags, s.rjobs, mode, d_planes, d_out, check, stream);
+    if (vdisp) return launch_vdisp_strips(c, t, s.vol.p, s.flags.p, s.rjobs.p, mode, d_planes, d_out, check, stream);
     if (!c->naive && c->interp != 1)
         return launch_nan_spread(c, mode, t.n, t.d_rawcalls, t.d_targets, t.d_out_off, t.out_stride, d_planes, nullptr, d_out, check, stream);
     return LES_HIP_OK;

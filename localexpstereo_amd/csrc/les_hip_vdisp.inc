@@ -87,14 +87,17 @@ int launch_vdisp_strips(les_hip_ctx* c, const UnaryTables& t, float* vol, unsign
     g.D0 = 0; g.th_col = INFINITY;                  // slice k of the stand-in volume holds raw costs as they are
     les::View view = strip_view(c, mode);
     view.vol = vol;
+    const les::RawCall* vd_calls = t.d_vd_calls;      // (launches take raw pointers, not t: les_hip_mem.h)
+    const les::Job* jobs = t.d_jobs;
+    const float4* stand_in = t.d_vd_stand_in;
     for (const auto& gr : t.vd_groups) {
         if (gr.c1 <= gr.c0 || gr.slices <= 0) continue;
         g.D = gr.slices;
         if (t.vd_groups.size() > 1) HIPCHECK(hipMemsetAsync(flags, 0, (size_t)t.n * sizeof(unsigned), stream));
         hipLaunchKernelGGL(les::les_naive_raw_v_kernel, dim3(gr.c1 - gr.c0, t.vd_chunks), dim3(256), 0, stream, c->geom, strip_view(c, mode),
-                           t.d_vd_calls + gr.c0, d_planes + gr.c0, vol, c->p.W, 1, flags + gr.c0);
-        hipLaunchKernelGGL(les::les_mask_jobs_kernel, dim3((njobs + 255) / 256), dim3(256), 0, stream, t.d_jobs, rjobs, (const unsigned*)flags, njobs);
-        hipLaunchKernelGGL(se->fn, dim3(njobs), dim3(se->NT), 0, stream, g, view, (const les::Job*)rjobs, t.d_vd_stand_in, d_out, njobs, 0);
+                           vd_calls + gr.c0, d_planes + gr.c0, vol, c->p.W, 1, flags + gr.c0);
+        hipLaunchKernelGGL(les::les_mask_jobs_kernel, dim3((njobs + 255) / 256), dim3(256), 0, stream, jobs, rjobs, (const unsigned*)flags, njobs);
+        hipLaunchKernelGGL(se->fn, dim3(njobs), dim3(se->NT), 0, stream, g, view, (const les::Job*)rjobs, stand_in, d_out, njobs, 0);
         if (check)
             hipLaunchKernelGGL(les::les_vdisp_check_kernel, dim3(njobs), dim3(256), 0, stream, c->geom, (const les::Job*)rjobs, d_planes, d_out, njobs);
         HIPCHECK(hipGetLastError());
