@@ -253,6 +253,20 @@ int les_hip_batch_expansion_graph(les_hip_ctx* ctx, const les_hip_batch* batch, 
                                   const les_hip_plane* d_labels, const float* d_cur, const float* d_prop, float lambda, float th_smooth,
                                   float omega, float epsilon, float* d_payload, double* flow0_host);
 
+/* replaces (on the device): the graph construction of FastGCStereo::fusionMoveBK (LES/FastGCStereo.h:241-363) with
+ * StereoEnergy::computeSmoothnessTermsFusion (LES/StereoEnergy.h:331-394) -- the move that fuses the current label map d_labels with a
+ * second map d_labels1 (H x W planes, device; not the same buffer), pixel by pixel, where the expansion move tries one plane per cell.  Same
+ * cells, payload layout, node order and flow0 as les_hip_batch_expansion_graph, so every solver below (and les_gc_solve_prebuilt) cuts the
+ * graphs unchanged; mask 255 = the pixel takes d_labels1's label.  d_cur / d_prop: the unary costs of d_labels / of d_labels1 at every pixel
+ * (les_hip_unary_labels gives the latter in one dense pass).  Definition and operation order: csrc/les_fusion.h.  Unlike the reference,
+ * which drops cost11 (:255, right only for a one-plane proposal), the term of "both take" enters the graph; a pair that is not submodular
+ * (c10 + c01 < c11 + c00) gets arc capacity 0, so the cut minimises an upper bound of the energy that is exact at "all keep" and "all
+ * take": the move never raises the energy.  With d_labels1 constant over every cell the payload is that of the expansion graph, bit for bit.
+ * d_nonsubmodular (n ints on the device, may be NULL): the truncated pairs per cell; zeroed and counted on the calling thread's stream. */
+int les_hip_batch_fusion_graph(les_hip_ctx* ctx, const les_hip_batch* batch, int mode, const les_hip_plane* d_labels1,
+                               const les_hip_plane* d_labels, const float* d_cur, const float* d_prop, float lambda, float th_smooth,
+                               float omega, float epsilon, float* d_payload, double* flow0_host, int* d_nonsubmodular);
+
 /* replaces (on the device, for cells of at most LES_HIP_MAXFLOW_MAX_NODES nodes): the max-flow and the segment read-out of
  * FastGCStereo::expansionMoveBK -- graph.maxflow(); graph.what_segment(i) == SOURCE (LES/FastGCStereo.h:553-559) -- on the
  * payload of les_hip_batch_expansion_graph, for all cells of the batch, one workgroup per cell with the whole graph on chip
@@ -317,6 +331,11 @@ int les_hip_batch_solve_graphs_tiled_stats(les_hip_ctx* ctx, const les_hip_batch
  * byte per graph node in the payload order of les_hip_batch_expansion_graph (non-zero = the node takes the proposal). */
 int les_hip_batch_apply_masks(les_hip_ctx* ctx, const les_hip_batch* batch, const les_hip_plane* d_planes, const unsigned char* d_masks,
                               float* d_cur, const float* d_prop, les_hip_plane* d_labels);
+
+/* replaces: the same mask updates after a fusion move (LES/FastGCStereo.h:61-62 with the label map of fusionMoveBK, :253, in the place of
+ * the one plane): where the mask is non-zero, d_cur <- d_prop and d_labels <- d_labels1 (H x W planes, device; not the same buffer). */
+int les_hip_batch_apply_masks_labels(les_hip_ctx* ctx, const les_hip_batch* batch, const les_hip_plane* d_labels1, const unsigned char* d_masks,
+                                     float* d_cur, const float* d_prop, les_hip_plane* d_labels);
 
 /* ---- evaluation of the device-resident solution on the device (csrc/les_eval.h) ----
  * replaces: Evaluator::evaluate's numbers (LES/Evaluator.h:113-187; its PNG dumps and windows are not part of this) with

@@ -19,7 +19,7 @@ PLANE_DT = np.dtype([("a", "<f4"), ("b", "<f4"), ("c", "<f4"), ("v", "<f4")])
 SYMBOLS = [
     "les_hip_create", "les_hip_create_naive", "les_hip_create_filtered", "les_hip_create_naive_filtered", "les_hip_destroy", "les_hip_last_error", "les_hip_set_stream", "les_hip_set_thread_stream", "les_hip_synchronize",
     "les_hip_unary_one", "les_hip_unary_one_scratch", "les_hip_scratch_create", "les_hip_scratch_destroy", "les_hip_unary_batch", "les_hip_batch_create", "les_hip_batch_destroy",
-    "les_hip_batch_num_jobs", "les_hip_batch_kernel_kind", "les_hip_batch_graph_nodes", "les_hip_batch_graph_offsets", "les_hip_batch_expansion_graph", "les_hip_batch_max_cell_nodes", "les_hip_batch_graph_solver_kind", "les_hip_refresh_volume", "les_hip_set_interpolation", "les_hip_set_max_vdisparity", "les_hip_set_random_vdisparity", "les_hip_batch_solve_graphs", "les_hip_batch_solve_graphs_counted", "les_hip_batch_solve_graphs_tiled", "les_hip_batch_solve_graphs_tiled_stats", "les_hip_batch_tiled_workspace_bytes", "les_hip_batch_apply_masks", "les_hip_batch_run", "les_hip_batch_set_units", "les_hip_batch_propose", "les_hip_batch_wta",
+    "les_hip_batch_num_jobs", "les_hip_batch_kernel_kind", "les_hip_batch_graph_nodes", "les_hip_batch_graph_offsets", "les_hip_batch_expansion_graph", "les_hip_batch_fusion_graph", "les_hip_batch_max_cell_nodes", "les_hip_batch_graph_solver_kind", "les_hip_refresh_volume", "les_hip_set_interpolation", "les_hip_set_max_vdisparity", "les_hip_set_random_vdisparity", "les_hip_batch_solve_graphs", "les_hip_batch_solve_graphs_counted", "les_hip_batch_solve_graphs_tiled", "les_hip_batch_solve_graphs_tiled_stats", "les_hip_batch_tiled_workspace_bytes", "les_hip_batch_apply_masks", "les_hip_batch_apply_masks_labels", "les_hip_batch_run", "les_hip_batch_set_units", "les_hip_batch_propose", "les_hip_batch_wta",
     "les_hip_wta_update", "les_hip_malloc", "les_hip_free",
     "les_hip_memcpy_h2d", "les_hip_memcpy_d2h", "les_hip_memset", "les_hip_get_stats", "les_hip_strip_width", "les_hip_tiled_volume_bytes",
     "les_hip_calib_copy", "les_hip_calib_copy_wide", "les_hip_exchange_create", "les_hip_exchange_destroy", "les_hip_exchange_slot_floats",
@@ -103,6 +103,8 @@ def load(path=None):
         "les_hip_batch_graph_offsets": (ci, [vp, vp]),
         "les_hip_batch_expansion_graph": (ci, [vp, vp, ci, vp, vp, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp]),
         "les_hip_batch_apply_masks": (ci, [vp, vp, vp, vp, vp, vp, vp]),
+        "les_hip_batch_fusion_graph": (ci, [vp, vp, ci, vp, vp, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp, vp]),
+        "les_hip_batch_apply_masks_labels": (ci, [vp, vp, vp, vp, vp, vp, vp]),
         "les_hip_batch_max_cell_nodes": (C.c_longlong, [vp]),
         "les_hip_batch_graph_solver_kind": (ci, [vp]),
         "les_hip_refresh_volume": (ci, [vp, ci]),
@@ -335,6 +337,19 @@ class Batch:
                                                            C.c_void_p(int(payload_dev)), _ptr(f0)))
         return f0
 
+    def fusion_graph(self, labels1_dev, labels_dev, cur_dev, prop_dev, payload_dev, mode=0, lambda_=1.0, th_smooth=1.0, omega=10.0, epsilon=0.01,
+                     want_flow0=False, nonsubmodular_dev=None):
+        """Graph capacities of one lock-step of FUSION moves (LES/FastGCStereo.h:241-363; definition: csrc/les_fusion.h): the current map labels_dev
+        against the second map labels1_dev, whose per-pixel unary costs are cur_dev / prop_dev.  Payload as expansion_graph; a mask byte of 255 means
+        the pixel takes labels1's label.  nonsubmodular_dev: n int32 on the device that receive every cell's count of truncated (non-submodular)
+        pairs, or None.  Returns the per-cell t-link flow when want_flow0."""
+        f0 = np.zeros(self.n, np.float64) if want_flow0 else None
+        self.e._chk(self.e.L.les_hip_batch_fusion_graph(self.e.h, self.h, mode, C.c_void_p(int(labels1_dev)), C.c_void_p(int(labels_dev)),
+                                                        C.c_void_p(int(cur_dev)), C.c_void_p(int(prop_dev)), lambda_, th_smooth, omega, epsilon,
+                                                        C.c_void_p(int(payload_dev)), _ptr(f0),
+                                                        C.c_void_p(int(nonsubmodular_dev)) if nonsubmodular_dev else None))
+        return f0
+
     MAXFLOW_MAX_NODES = 2304          # LES_HIP_MAXFLOW_MAX_NODES
 
     @property
@@ -376,6 +391,11 @@ class Batch:
         """Mask updates of a lock-step on the device (LES/FastGCStereo.h:61-62); masks in graph-node order."""
         self.e._chk(self.e.L.les_hip_batch_apply_masks(self.e.h, self.h, C.c_void_p(int(planes_dev)), C.c_void_p(int(masks_dev)), C.c_void_p(int(cur_dev)),
                                                        C.c_void_p(int(prop_dev)), C.c_void_p(int(labels_dev))))
+
+    def apply_masks_labels(self, labels1_dev, masks_dev, cur_dev, prop_dev, labels_dev):
+        """Mask updates of a lock-step of fusion moves: where the mask is non-zero the pixel takes labels1's label and prop's cost."""
+        self.e._chk(self.e.L.les_hip_batch_apply_masks_labels(self.e.h, self.h, C.c_void_p(int(labels1_dev)), C.c_void_p(int(masks_dev)), C.c_void_p(int(cur_dev)),
+                                                              C.c_void_p(int(prop_dev)), C.c_void_p(int(labels_dev))))
 
     def region_energy(self, labels_dev, cost_dev, energy_dev, mode=0, lambda_=1.0, th_smooth=1.0, omega=10.0, epsilon=0.01):
         """Per cell, the energy of the current maps that a move on the cell can change (fusedEnergy of host/ExpansionMove.h, LES/FastGCStereo.h:561-594):

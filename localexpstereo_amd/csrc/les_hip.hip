@@ -10,6 +10,7 @@
 #include "les_propose.h"
 #include "les_post.h"
 #include "les_pairwise.h"
+#include "les_fusion.h"
 #include "les_eval.h"
 #include "les_maxflow.h"
 #include "les_maxflow_tiled.h"

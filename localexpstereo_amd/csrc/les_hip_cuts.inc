@@ -1,4 +1,4 @@
-// les_hip_cuts.inc -- part of the single translation unit les_hip.hip (included there; not compiled on its own): the expansion moves on the device -- graph capacities, the LDS max-flow, the tiled max-flow with its hand-over to the host cores, mask application
+// les_hip_cuts.inc -- part of the single translation unit les_hip.hip (included there; not compiled on its own): the expansion and fusion moves on the device -- graph capacities, the LDS max-flow, the tiled max-flow with its hand-over to the host cores, mask application
 // Host side of one tiled solve in flight: the host-mapped words the kernels report through (pinned, fine-grained: the kernel adds to them with
 // system-scope atomics, the host reads them after synchronising its stream -- the progress check of a lock-step costs no copy) and the pinned
 // staging of the hand-over (les_maxflow_tiled.h: residual graphs out, masks and flow values back).  A context keeps a pool of them: a call
@@ -105,6 +105,40 @@ int les_hip_batch_expansion_graph(les_hip_ctx* c, const les_hip_batch* b, int mo
     double* flow0 = b->d_flow0.p;
     hipLaunchKernelGGL(les::les_expansion_graph_kernel, dim3(b->n, b->graph_chunks), dim3(256), 0, cur_stream(c), cells, offs, pl, lab, d_cur, d_prop, ipk, wtab,
                        pp, d_payload, flow0);
+    HIPCHECK(hipGetLastError());
+    if (flow0_host) {
+        std::vector<double> part((size_t)b->n * b->graph_chunks);
+        HIPCHECK(hipMemcpyAsync(part.data(), b->d_flow0.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream(c)));
+        HIPCHECK(hipStreamSynchronize(cur_stream(c)));
+        for (int i = 0; i < b->n; i++) {
+            double s = 0;
+            for (int k = 0; k < b->graph_chunks; k++) s += part[(size_t)i * b->graph_chunks + k];
+            flow0_host[i] = s;
+        }
+    }
+    return LES_HIP_OK;
+}
+
+int les_hip_batch_fusion_graph(les_hip_ctx* c, const les_hip_batch* b, int mode, const les_hip_plane* d_labels1, const les_hip_plane* d_labels,
+                               const float* d_cur, const float* d_prop, float lambda, float th_smooth, float omega, float epsilon,
+                               float* d_payload, double* flow0_host, int* d_nonsubmodular)
+{
+    if (!c || !b || !d_labels1 || !d_labels || !d_cur || !d_prop || !d_payload) return fail(LES_HIP_ERR_ARG, "null argument");
+    if (mode < 0 || mode > 1 || !c->v[mode].ipk) return fail(LES_HIP_ERR_ARG, "view %d was not supplied at creation", mode);
+    if (b->n == 0) return LES_HIP_OK;
+    HIPCHECK(hipSetDevice(c->p.device));                     // the calling host thread may be new (one thread per view)
+    const int trc = pw_table(c, omega, epsilon);
+    if (trc) return trc;
+    const les::PairwiseParams pp{c->p.H, c->p.W, lambda, th_smooth};
+    const les::GraphCell* cells = reinterpret_cast<const les::GraphCell*>(b->d_targets.p);
+    const long long* offs = b->d_graph_off.p;
+    const float4 *lab1 = reinterpret_cast<const float4*>(d_labels1), *lab = reinterpret_cast<const float4*>(d_labels);
+    const uint32_t* ipk = c->v[mode].ipk;
+    const float* wtab = c->d_pw_tab.p;
+    double* flow0 = b->d_flow0.p;
+    if (d_nonsubmodular) HIPCHECK(hipMemsetAsync(d_nonsubmodular, 0, (size_t)b->n * sizeof(int), cur_stream(c)));
+    hipLaunchKernelGGL(les::les_fusion_graph_kernel, dim3(b->n, b->graph_chunks), dim3(256), 0, cur_stream(c), cells, offs, lab1, lab, d_cur, d_prop, ipk, wtab,
+                       pp, d_payload, flow0, d_nonsubmodular);
     HIPCHECK(hipGetLastError());
     if (flow0_host) {
         std::vector<double> part((size_t)b->n * b->graph_chunks);
@@ -518,6 +552,21 @@ int les_hip_batch_apply_masks(les_hip_ctx* c, const les_hip_batch* b, const les_
     const float4* pl = reinterpret_cast<const float4*>(d_planes);
     float4* lab = reinterpret_cast<float4*>(d_labels);
     hipLaunchKernelGGL(les::les_apply_masks_kernel, dim3(b->n, b->wta_chunks), dim3(256), 0, cur_stream(c), cells, offs, pl, d_masks, d_cur, d_prop, lab, c->p.W);
+    HIPCHECK(hipGetLastError());
+    return LES_HIP_OK;
+}
+
+int les_hip_batch_apply_masks_labels(les_hip_ctx* c, const les_hip_batch* b, const les_hip_plane* d_labels1, const unsigned char* d_masks, float* d_cur,
+                                     const float* d_prop, les_hip_plane* d_labels)
+{
+    if (c) (void)hipSetDevice(c->p.device);                 // HIP's current device is per host thread
+    if (!c || !b || !d_labels1 || !d_masks || !d_cur || !d_prop || !d_labels) return fail(LES_HIP_ERR_ARG, "null argument");
+    if (b->n == 0) return LES_HIP_OK;
+    const les::GraphCell* cells = reinterpret_cast<const les::GraphCell*>(b->d_targets.p);
+    const float4* lab1 = reinterpret_cast<const float4*>(d_labels1);
+    float4* lab = reinterpret_cast<float4*>(d_labels);
+    hipLaunchKernelGGL(les::les_apply_masks_labels_kernel, dim3(b->n, b->wta_chunks), dim3(256), 0, cur_stream(c), cells, b->d_graph_off.p, lab1, d_masks, d_cur, d_prop,
+                       lab, c->p.W);
     HIPCHECK(hipGetLastError());
     return LES_HIP_OK;
 }

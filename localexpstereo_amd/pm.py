@@ -592,6 +592,54 @@ class PMRunner:
             self._log_set(i)
         self._sync()
 
+    # -- fusion moves (LES/FastGCStereo.h:241-410; definition and the deviation from the reference: csrc/les_fusion.h) -----------------
+    def fuse(self, labels_b, layers=None, nthreads=0):
+        """Fuses the current solution with a second labelling `labels_b` (H x W x 4) by graph cuts: after begin_gc, for every disjoint set of the
+        chosen layers (None = all; else the layer indices) one lock-step of fusion moves -- the graphs of the set's cells from the two label maps
+        (les_hip_batch_fusion_graph), the cuts of the graph-cut iterations (_cut: the device solvers chosen per cell, the host where device_cuts says
+        so or the device gave up), the masks applied from the label map (les_hip_batch_apply_masks_labels), a row of the inner-loop log.  The unary
+        cost of b's label at a pixel does not depend on the current map: ONE dense pass (les_hip_unary_labels) into self.prop serves the whole call.
+        A move never raises the energy (up to the float rounding of the capacities); every pixel ends with its own label of the current map or of b.
+        -> dict: cells moved, pixels_taken (mask bytes set, summed over the sets: a pixel counts in every set whose cut gives it to b, also when it
+        carries b's label already), nonsubmodular_pairs truncated, pairs built, seconds (the whole call, synchronised), dense_seconds (the dense pass,
+        synchronised).
+        Single rank: world > 1 raises NotImplementedError (the sets' tiles would have to be exchanged after every set)."""
+        if self.world > 1:
+            raise NotImplementedError("PMRunner.fuse is single-rank: multi-rank fusion is not implemented")
+        if self.gc is None:
+            raise RuntimeError("PMRunner.fuse needs begin_gc(graph_cut) first")
+        t0 = time.perf_counter()
+        lab = torch.as_tensor(np.ascontiguousarray(labels_b, np.float32)).to(self.device)
+        assert tuple(lab.shape) == (self.H, self.W, 4)
+        self.e.unary_labels(lab.data_ptr(), self.prop.data_ptr(), mode=self.mode, check=True)
+        self._sync()
+        dense = time.perf_counter() - t0
+        p = self.gc.params
+        counts = torch.zeros(max([1] + [sh.n for _, sh in self.sets]), dtype=torch.int32, device=self.device)
+        taken = torch.zeros((), dtype=torch.int64, device=self.device)
+        truncated = torch.zeros((), dtype=torch.int64, device=self.device)
+        cells = pairs = 0
+        for i, (li, sh) in enumerate(self.sets):
+            if layers is not None and li not in layers:
+                continue
+            if sh.n:
+                ts = time.perf_counter()
+                self._gc_buffers(sh)
+                sh.batch.fusion_graph(lab.data_ptr(), self.labels.data_ptr(), self.cur.data_ptr(), self.prop.data_ptr(), sh.payload.data_ptr(), mode=self.mode,
+                                      lambda_=p["lambda_"], th_smooth=p["th_smooth"], omega=p["omega"], epsilon=p["epsilon"], nonsubmodular_dev=counts.data_ptr())
+                _, t1, t2 = self._cut(sh, nthreads, True, li)
+                sh.batch.apply_masks_labels(lab.data_ptr(), sh.masks.data_ptr(), self.cur.data_ptr(), self.prop.data_ptr(), self.labels.data_ptr())
+                taken += (sh.masks[: sh.graph_nodes] != 0).sum()
+                truncated += counts[: sh.n].sum()
+                cells += sh.n
+                w, h = sh.regions["w"].astype(np.int64), sh.regions["h"].astype(np.int64)
+                pairs += int(((w - 1) * h + w * (h - 1) + 2 * (w - 1) * (h - 1)).sum())
+                self._book(li, ts, t1, t2)
+            self._log_set(i)
+        self._sync()
+        return dict(cells=cells, pixels_taken=int(taken.item()), nonsubmodular_pairs=int(truncated.item()), pairs=pairs,
+                    seconds=time.perf_counter() - t0, dense_seconds=dense)
+
     def _joint_set(self, runners, k):
         """Set k of every view as ONE record for the cut steps: a joint batch (the views' target rects one after the other) has exactly the node
         offsets of the concatenated payload, so the single-batch entry points serve it unchanged.  views: (runner, shard, first node) of

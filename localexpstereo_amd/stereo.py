@@ -145,6 +145,53 @@ class FastGCStereo:
                 ev.close()
             self._dev_eval, self._inner = None, {}
 
+    def fuse(self, labeling, others, viewMode=0, layers=None):
+        """Fusion moves (FastGCStereo::fusionMoveBK, LES/FastGCStereo.h:241-410, which no mode of the reference reaches): starts from `labeling`
+        (H x W x 4) by the route of run(..., labeling=) -- the costs of its labels from one dense device pass -- and fuses each map of `others` into it in
+        turn, over every disjoint set of the layers added by addLayer (layers: their indices, None = all), by graph cuts on the device
+        (pm.PMRunner.fuse).  A pixel of the result carries its label of `labeling` or of one of `others`; no map raises the energy.  With an evaluator
+        set, self.log gets one row for the start and one after each map (device evaluation when evaluate_on_device); self.fuse_stats: the runner's
+        report per map.  Single rank.  -> the fused labelling, H x W x 4."""
+        if self.world > 1:
+            raise NotImplementedError("FastGCStereo.fuse is single-rank: multi-rank fusion is not implemented")
+        t0 = time.perf_counter()
+        self.eval_seconds, self.log, self.fuse_stats = 0.0, [], []
+        m = int(viewMode)
+        runner = pm.PMRunner(self.e, self.units, self.table, seed=self.seed + 7919 * m, device=self.device, mode=m, random_vdisp=self.random_vdisp)
+        g = gc.GraphCut(self.imL, self.imR, lambda_=self.p["lambda_"], th_smooth=self.p["th_smooth"], omega=self.p["omega"], epsilon=self.p["epsilon"])
+        ev_args = {} if self.evaluator is None else dict(dispGT=self.evaluator.gt, nonocc=self.evaluator.nonocc, error_threshold=self.evaluator.threshold,
+                                                         precision=self.precision)
+        try:
+            if self.evaluate_on_device:
+                self._dev_eval = {m: api.DeviceEvaluator(self.e, max_rows=len(others) + 1, **ev_args)}
+            runner.init_from_labels(labeling)                # warm start (LES/FastGCStereo.h:116-130)
+            if self.device_cuts is not None:
+                runner.device_cuts = self.device_cuts
+            runner.begin_gc(g, mode=m)
+            if self.evaluator is not None:
+                self._evaluate_row(0, m, runner, g, t0)
+            for k, other in enumerate(others):
+                self.fuse_stats.append(runner.fuse(other, layers=layers, nthreads=self.host_threads))
+                if self.evaluator is not None:
+                    self._evaluate_row(k + 1, m, runner, g, t0)
+            runner._sync()
+            return runner.labels.cpu().numpy().copy()
+        finally:
+            for ev in (self._dev_eval or {}).values():
+                ev.close()
+            self._dev_eval = None
+            runner.close()
+            g.close()
+
+    def _evaluate_row(self, index, mode, runner, g, t0):
+        """_evaluate for the view that fuse() works on (the rows of run() are the left view's)."""
+        runner._sync()
+        te = time.perf_counter()
+        try:
+            self._evaluate_body(index, mode, runner, g, t0)
+        finally:
+            self.eval_seconds += time.perf_counter() - te
+
     def _run(self, maxIteration, viewModes, pmInit, labeling):
         if self.inner_loop_log and self.world > 1:
             raise ValueError("inner_loop_log is a single-rank log: with several ranks a rank holds only its band of a set's cells until the exchange")
