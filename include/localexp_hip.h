@@ -238,6 +238,29 @@ int les_hip_wta_update(les_hip_ctx* ctx, int n, const les_hip_rect* rects, const
 int les_hip_fill_out_of_view(float* vol_dev, int D, int H, int W, int mode, int device, void* hip_stream);
 int les_hip_convert_volume_l2r(const float* src_dev, float* dst_dev, int D, int H, int W, int device, void* hip_stream);
 
+/* ---- matching-cost volumes from the stereo pair (csrc/les_costvol.h holds the definition) ----
+ * replaces: the external MC-CNN step whose output the reference loads as im0.acrt / im1.acrt (LES/main.cpp:353-357): the classic AD-Census
+ * cost instead -- cost = ta[sum_c |I_c - J_c|] + tc[popcount(census_I ^ census_J)] in [0, 1), 9 x 7 census of the integer grey value,
+ * ta[s] = 0.5 (1 - exp(-(s / 3) / lambda_ad)), tc[h] = 0.5 (1 - exp(-h / lambda_census)); Mei et al. use lambda_ad = 10, lambda_census = 30.
+ * Images are H x W x 3 u8 (BGR) in DEVICE memory; every index clamps to the image.  Context-free, like the volume preparation above.
+ * LES_HIP_ERR_ARG for null pointers, non-positive sizes, a mode outside 0 / 1 and a lambda that is not positive and finite; nothing is
+ * written on a refused call. */
+/* the two tables (766 and 63 floats, HOST memory) the builder uses: double arithmetic, rounded once to float */
+int les_hip_costvol_tables(float lambda_ad, float lambda_census, float* ad766_host, float* census63_host);
+/* the census signatures of one image: d_sig[y * W + x], bit k = neighbour k (row-major over dy = -3..3, dx = -4..4 without the centre,
+ * coordinates clamped) is darker than the centre.  Asynchronous on hip_stream. */
+int les_hip_census(const uint8_t* d_bgr, unsigned long long* d_sig, int H, int W, int device, void* hip_stream);
+/* the float [D][H][W] volume of one view: slice k is disparity d = k + d0 (d0: the energy's min_disparity);
+ * mode 0 = left view's volume (partner column clamp(x - d)), 1 = right view's (clamp(x + d)).  Every entry is written, out-of-view
+ * ones through the clamped column: les_hip_fill_out_of_view comes after it, as after a loaded volume.  The call owns its scratch (both
+ * views' signatures and packed colours, the tables) and SYNCHRONISES hip_stream before it returns.  Volumes of 2^32 or more floats:
+ * LES_HIP_ERR_UNSUPPORTED.  LES_HIP_COSTVOL_NT=1 / 0 selects non-temporal / plain stores (default: non-temporal; the two measure alike). */
+int les_hip_build_cost_volume(const uint8_t* d_imL, const uint8_t* d_imR, float* d_vol, int D, int H, int W, int mode, int d0, float lambda_ad,
+                              float lambda_census, int device, void* hip_stream);
+/* diagnostics: with LES_HIP_COSTVOL_TIMING=1 in the environment les_hip_build_cost_volume brackets its launches with events; this returns the
+ * device milliseconds of the calling thread's last build -- the two census launches, the volume kernel (tools/costvol_timing.py). */
+int les_hip_costvol_last_times(float* census_ms, float* volume_ms);
+
 /* replaces (on the device): the pairwise side of FastGCStereo::expansionMoveBK's graph construction
  * (LES/FastGCStereo.h:425-551) with StereoEnergy::initSmoothnessCoeff / computeSmoothnessTerm /
  * computeSmoothnessTermsExpansion (LES/StereoEnergy.h:131-163, 225-230, 398-453): for every cell i of the batch (its

@@ -26,10 +26,12 @@ SYMBOLS = [
     "les_hip_exchange_pack", "les_hip_exchange_unpack", "les_hip_exchange_tiles", "les_hip_fill_out_of_view", "les_hip_convert_volume_l2r", "les_hip_consistency_check", "les_hip_post_process",
     "les_hip_evaluator_create", "les_hip_evaluator_destroy", "les_hip_evaluate", "les_hip_evaluator_rows", "les_hip_batch_region_energy",
     "les_hip_unary_labels", "les_hip_unary_labels_kind",
+    "les_hip_costvol_tables", "les_hip_census", "les_hip_build_cost_volume", "les_hip_costvol_last_times",
 ]
 
 
 PROPOSE_EXPANSION, PROPOSE_RANDOM, PROPOSE_RANSAC, PROPOSE_INIT = 0, 1, 2, 3
+LES_HIP_OK, LES_HIP_ERR_ARG, LES_HIP_ERR_DEVICE, LES_HIP_ERR_UNSUPPORTED = 0, 1, 2, 3        # the return codes of include/localexp_hip.h
 
 # Parameters::filterName (LES/StereoEnergy.h:25) -> les_hip_create_filtered's filter.  The reference's CostVolumeEnergy knows the bilateral
 # filter as "BL" and NaiveStereoEnergy as "BF" (CostVolumeEnergy given "BF" dereferences a null filter): both names select it for both energies.
@@ -165,6 +167,10 @@ def load(path=None):
         "les_hip_batch_region_energy": (ci, [vp, vp, ci, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, vp]),
         "les_hip_unary_labels": (ci, [vp, ci, vp, vp, vp, ci]),
         "les_hip_unary_labels_kind": (ci, [vp, ci]),
+        "les_hip_costvol_tables": (ci, [C.c_float, C.c_float, vp, vp]),
+        "les_hip_census": (ci, [vp, vp, ci, ci, ci, vp]),
+        "les_hip_build_cost_volume": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, C.c_float, C.c_float, ci, vp]),
+        "les_hip_costvol_last_times": (ci, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -210,6 +216,35 @@ def convert_volume_l2r(src_dev_ptr, dst_dev_ptr, D, H, W, device=0, stream=0, li
     rc = L.les_hip_convert_volume_l2r(C.c_void_p(int(src_dev_ptr)), C.c_void_p(int(dst_dev_ptr)), D, H, W, device, C.c_void_p(int(stream)))
     if rc:
         raise LesHipError(L.les_hip_last_error().decode())
+
+
+def _chk_lib(L, rc):
+    if rc:
+        raise LesHipError(f"liblocalexp_hip error {rc}: {L.les_hip_last_error().decode()}")
+
+
+def costvol_tables(lambda_ad=10.0, lambda_census=30.0, lib=None):
+    """The two tables of the AD-Census cost (csrc/les_costvol.h) as build_cost_volume uses them: ta[0..765] indexed by the summed absolute
+    colour difference, tc[0..62] by the Hamming distance of the census signatures."""
+    L = load(lib)
+    ta, tc = np.empty(766, np.float32), np.empty(63, np.float32)
+    _chk_lib(L, L.les_hip_costvol_tables(lambda_ad, lambda_census, _ptr(ta), _ptr(tc)))
+    return ta, tc
+
+
+def census(bgr_dev_ptr, sig_dev_ptr, H, W, device=0, stream=0, lib=None):
+    """9 x 7 census signatures (uint64 per pixel) of a device H x W x 3 u8 BGR image.  Enqueue only."""
+    L = load(lib)
+    _chk_lib(L, L.les_hip_census(C.c_void_p(int(bgr_dev_ptr)), C.c_void_p(int(sig_dev_ptr)), H, W, device, C.c_void_p(int(stream))))
+
+
+def build_cost_volume(imL_dev_ptr, imR_dev_ptr, vol_dev_ptr, D, H, W, mode, d0=0, lambda_ad=10.0, lambda_census=30.0, device=0, stream=0, lib=None):
+    """The AD-Census matching-cost volume of one view (mode 0 left, 1 right) from the two device images into the device float [D][H][W]
+    volume; slice k is disparity k + d0.  What the reference reads from an external MC-CNN run (LES/main.cpp:353-357).  Every entry is
+    written (out-of-view ones through the clamped column): fill_out_of_view comes after it.  Synchronises the stream."""
+    L = load(lib)
+    _chk_lib(L, L.les_hip_build_cost_volume(C.c_void_p(int(imL_dev_ptr)), C.c_void_p(int(imR_dev_ptr)), C.c_void_p(int(vol_dev_ptr)), D, H, W, mode, d0,
+                                            lambda_ad, lambda_census, device, C.c_void_p(int(stream))))
 
 
 class DeviceBuffer:

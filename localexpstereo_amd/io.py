@@ -106,6 +106,33 @@ def ingest_volumes(volL, volR=None, device="cuda", lib=None):
     return tl, tr
 
 
+def build_volumes(imL, imR, ndisp, device="cuda", lib=None, lambda_ad=10.0, lambda_census=30.0, d0=0):
+    """Both views' matching-cost volumes made on the device from the stereo pair alone: the AD-Census cost of csrc/les_costvol.h in the
+    place of the MC-CNN volumes the reference loads (LES/main.cpp:353-357).  imL / imR: H x W x 3 u8 (BGR) host arrays.  Each view is built
+    directly (mode 0 / mode 1; slice k is disparity k + d0), then filled like a loaded volume (fillOutOfView, :358 / :365).  Returns two
+    torch device tensors [ndisp][H][W], as ingest_volumes does."""
+    import torch
+    dev = torch.device(device)
+    idx = dev.index or 0 if dev.type == "cuda" else 0
+    imL, imR = np.ascontiguousarray(imL, np.uint8), np.ascontiguousarray(imR, np.uint8)
+    if imL.ndim != 3 or imL.shape[2] != 3 or imL.shape != imR.shape:
+        raise ValueError(f"two H x W x 3 images of one shape expected, got {imL.shape} and {imR.shape}")
+    H, W = imL.shape[:2]
+    D = int(ndisp)
+    tiL, tiR = torch.from_numpy(imL.copy()).to(dev), torch.from_numpy(imR.copy()).to(dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
+    out = []
+    for mode in (0, 1):
+        t = torch.empty((D, H, W), dtype=torch.float32, device=dev)
+        api.build_cost_volume(tiL.data_ptr(), tiR.data_ptr(), t.data_ptr(), D, H, W, mode, d0=int(d0), lambda_ad=lambda_ad, lambda_census=lambda_census,
+                              device=idx, stream=stream, lib=lib)
+        api.fill_out_of_view(t.data_ptr(), D, H, W, mode, device=idx, stream=stream, lib=lib)
+        out.append(t)
+    if dev.type == "cuda":
+        torch.cuda.synchronize(dev)
+    return out[0], out[1]
+
+
 # ------------------------------------------------------------------------------------------------
 # data-set folders
 # ------------------------------------------------------------------------------------------------

@@ -407,15 +407,22 @@ def MidV2(data, iterations=5, pmIterations=2, doDual=False, smooth_weight=None, 
     return st, lab, raw
 
 
-def MidV3(data, volL, volR, iterations=5, pmIterations=2, doDual=False, smooth_weight=0.5, mc_threshold=0.5, filterRadious=20,
-          error_threshold=1.0, device="cuda", seed=1, lib=None, params=None, interpolate=1, **kw):
+def MidV3(data, volL=None, volR=None, iterations=5, pmIterations=2, doDual=False, smooth_weight=0.5, mc_threshold=0.5, filterRadious=20,
+          error_threshold=1.0, device="cuda", seed=1, lib=None, params=None, interpolate=1, lambda_ad=10.0, lambda_census=30.0, **kw):
     """MidV3 (LES/main.cpp:330-420): cost-volume energy (volumes ingested on the device), layers 1 % / 3 % / 9 % of the
     image width.  volL / volR: host arrays / memmaps [ndisp][H][W] (volR None: synthesised from the left one).  params: PARAMS_GF
     (default) or PARAMS_BF: filter and eps; smooth_weight, mc_threshold and filterRadious override lambda_, th_col and windR (:351-353).
-    interpolate: the energy's setInterpolationMethod (LES/CostVolumeEnergy.h:45-48) -- 0 nearest, 1 linear (default), 2 quadratic."""
+    interpolate: the energy's setInterpolationMethod (LES/CostVolumeEnergy.h:45-48) -- 0 nearest, 1 linear (default), 2 quadratic.
+    volL None: no volume files -- both views' AD-Census volumes (io.build_volumes; lambda_ad, lambda_census) are built on the device from
+    data["imL"], data["imR"] and data["ndisp"]."""
     p = dict(PARAMS_GF if params is None else params)
     maxdisp = float(data["ndisp"] - 1)
-    tl, tr = io.ingest_volumes(volL, volR, device=device, lib=lib)
+    if volL is None:
+        if volR is not None:
+            raise ValueError("volR without volL")
+        tl, tr = io.build_volumes(data["imL"], data["imR"], data["ndisp"], device=device, lib=lib, lambda_ad=lambda_ad, lambda_census=lambda_census)
+    else:
+        tl, tr = io.ingest_volumes(volL, volR, device=device, lib=lib)
     D, H, W = tl.shape
     e = api.HipCostVolumeEnergy(data["imL"], data["imR"], tl.data_ptr(), tr.data_ptr(), windR=filterRadious, eps=p["eps"],
                                 th_col=mc_threshold, max_disp=maxdisp, device=torch.device(device).index or 0, volumes_on_device=True,
