@@ -405,6 +405,19 @@ int les_hip_batch_region_energy(les_hip_ctx* ctx, const les_hip_batch* batch, in
 int les_hip_consistency_check(les_hip_ctx* ctx, const les_hip_plane* d_labelsL, const les_hip_plane* d_labelsR, float threshold,
                               unsigned char* d_failL, unsigned char* d_failR);
 
+/* ---- cross-view fusion: a label map of one view expressed in the other view's coordinates (csrc/les_crossview.h holds the definition) ----
+ * No reference counterpart: the reference's two views meet only in the post-processing (LES/FastGCStereo.h:172-203); this is PatchMatch Stereo's
+ * "view propagation".  d_src: the H x W planes of view src_mode (0 left, 1 right); every source pixel (xs, y) with disparity d lands on column
+ * floor(xs -/+ d + 0.5) of row y of the other view, its plane rewritten for that view: (a, b, c) / (1 -/+ a), v negated.  The largest d wins a
+ * target pixel (then the largest xs); planes with 1 -/+ a < 0.125, non-finite components or a landing column outside the image are not
+ * proposed.  d_out: target pixels with a winner get its plane, the others d_fallback's plane bit for bit; d_hit (H x W bytes, may be NULL):
+ * 1 / 0.  The result is a function of the inputs only.  d_out may be d_fallback (each target pixel is read and written by one thread), NOT
+ * d_src (LES_HIP_ERR_ARG).  The output is a second labelling for les_hip_batch_fusion_graph.
+ * Enqueue only, on the calling thread's stream (les_hip_set_thread_stream is honoured): no allocation, no synchronisation; one launch, one
+ * workgroup per row.  Rows wider than 8192 pixels: LES_HIP_ERR_UNSUPPORTED, nothing is launched. */
+int les_hip_warp_labels(les_hip_ctx* ctx, int src_mode, const les_hip_plane* d_src, const les_hip_plane* d_fallback, les_hip_plane* d_out,
+                        unsigned char* d_hit /* may be NULL */);
+
 /* replaces: PMStereoBase::postProcess (LES/PMStereoBase.h:146-256), called by FastGCStereo::run for two-view runs
  * (LES/FastGCStereo.h:199-203, threshold 1.5): consistency check, horizontal fill of the failed pixels from the nearest
  * consistent neighbours (smaller disparity wins), then the colour-weighted median of the labels over the

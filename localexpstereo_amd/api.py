@@ -27,6 +27,7 @@ SYMBOLS = [
     "les_hip_evaluator_create", "les_hip_evaluator_destroy", "les_hip_evaluate", "les_hip_evaluator_rows", "les_hip_batch_region_energy",
     "les_hip_unary_labels", "les_hip_unary_labels_kind",
     "les_hip_costvol_tables", "les_hip_census", "les_hip_build_cost_volume", "les_hip_costvol_last_times",
+    "les_hip_warp_labels",
 ]
 
 
@@ -171,6 +172,7 @@ def load(path=None):
         "les_hip_census": (ci, [vp, vp, ci, ci, ci, vp]),
         "les_hip_build_cost_volume": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, C.c_float, C.c_float, ci, vp]),
         "les_hip_costvol_last_times": (ci, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+        "les_hip_warp_labels": (ci, [vp, ci, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -245,6 +247,14 @@ def build_cost_volume(imL_dev_ptr, imR_dev_ptr, vol_dev_ptr, D, H, W, mode, d0=0
     L = load(lib)
     _chk_lib(L, L.les_hip_build_cost_volume(C.c_void_p(int(imL_dev_ptr)), C.c_void_p(int(imR_dev_ptr)), C.c_void_p(int(vol_dev_ptr)), D, H, W, mode, d0,
                                             lambda_ad, lambda_census, device, C.c_void_p(int(stream))))
+
+
+WARP_MAX_WIDTH = 8192          # kWarpMaxW of csrc/les_crossview.h (the one source; tests/crossview_cases.py: case_width_limit holds this copy to it)
+
+
+def warp_labels(energy, src_mode, src_ptr, fallback_ptr, out_ptr, hit_ptr=None):
+    """les_hip_warp_labels on the context of `energy` (a HipCostVolumeEnergy): see HipCostVolumeEnergy.warp_labels."""
+    energy.warp_labels(src_mode, src_ptr, fallback_ptr, out_ptr, hit_ptr)
 
 
 class DeviceBuffer:
@@ -686,6 +696,15 @@ class HipCostVolumeEnergy:
             for b in bufs:
                 b.free()
         return out
+
+    # -- cross-view fusion (csrc/les_crossview.h; no reference counterpart) -----------------------------
+    def warp_labels(self, src_mode, src_ptr, fallback_ptr, out_ptr, hit_ptr=None):
+        """les_hip_warp_labels: the device label map src_ptr of view src_mode (0 left, 1 right) expressed in the other view's coordinates into
+        out_ptr (H x W planes; may be fallback_ptr, not src_ptr): a target pixel some source pixel lands on gets that pixel's plane rewritten for
+        the target view (the largest disparity wins), every other one fallback_ptr's plane.  hit_ptr: H x W bytes (1 = warped, 0 = fallback) or
+        None.  Enqueue only (the calling thread's stream).  Rows wider than WARP_MAX_WIDTH raise (error 3)."""
+        self._chk(self.L.les_hip_warp_labels(self.h, int(src_mode), C.c_void_p(int(src_ptr)), C.c_void_p(int(fallback_ptr)), C.c_void_p(int(out_ptr)),
+                                             C.c_void_p(int(hit_ptr)) if hit_ptr else None))
 
     def wta_update(self, rects, planes, cur_cost_dev, prop_cost_dev, labels_dev, planes_on_device=False):
         rects = _rects(rects)

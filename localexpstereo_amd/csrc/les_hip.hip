@@ -19,6 +19,7 @@
 #include "les_vdisp.h"
 #include "les_dense.h"
 #include "les_costvol.h"
+#include "les_crossview.h"
 
 #include "../host/ResidualCut.h"      // the host cores' finisher of the tiled max-flow (plain C++: search trees / push-relabel on a residual graph)
 
@@ -297,3 +298,4 @@ float naive_alpha(const les_hip_ctx* c) { return c->naive_alpha; }
 #include "les_hip_exchange.inc"
 #include "les_hip_dense.inc"
 #include "les_hip_costvol.inc"
+#include "les_hip_crossview.inc"

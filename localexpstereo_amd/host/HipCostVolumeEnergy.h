@@ -124,6 +124,28 @@ public:
         return ok;
     }
 
+    // Cross-view fusion's warp (les_hip_warp_labels, csrc/les_crossview.h; no reference counterpart): the label map `src` of view src_mode (0 left,
+    // 1 right) expressed in the other view's coordinates into `out`; target pixels no source pixel lands on keep `fallback`'s plane.  hit (may be
+    // null): 1 where a source pixel landed.  All maps: width * height elements in HOST memory; out may be fallback.  Returns false (and reports
+    // on stderr) when the library refuses the call (rows wider than 8192 pixels).
+    bool warpLabels(int src_mode, const Plane* src, const Plane* fallback, Plane* out, unsigned char* hit = nullptr) const
+    {
+        static_assert(sizeof(Plane) == sizeof(les_hip_plane), "ABI layout");
+        const size_t P = (size_t)width * height, B = P * sizeof(les_hip_plane);
+        les_hip_plane *d_src = nullptr, *d_out = nullptr;
+        unsigned char* d_hit = nullptr;
+        bool ok = les_hip_malloc(ctx_, (void**)&d_src, B) == LES_HIP_OK && les_hip_malloc(ctx_, (void**)&d_out, B) == LES_HIP_OK &&
+                  (!hit || les_hip_malloc(ctx_, (void**)&d_hit, P) == LES_HIP_OK);
+        ok = ok && les_hip_memcpy_h2d(ctx_, d_src, src, B) == LES_HIP_OK && les_hip_memcpy_h2d(ctx_, d_out, fallback, B) == LES_HIP_OK;
+        ok = ok && les_hip_warp_labels(ctx_, src_mode, d_src, d_out, d_out, d_hit) == LES_HIP_OK && les_hip_synchronize(ctx_) == LES_HIP_OK;
+        ok = ok && les_hip_memcpy_d2h(ctx_, out, d_out, B) == LES_HIP_OK && (!hit || les_hip_memcpy_d2h(ctx_, hit, d_hit, P) == LES_HIP_OK);
+        if (!ok) fprintf(stderr, "HipCostVolumeEnergy: %s\n", les_hip_last_error());
+        if (d_src) les_hip_free(ctx_, d_src);
+        if (d_out) les_hip_free(ctx_, d_out);
+        if (d_hit) les_hip_free(ctx_, d_hit);
+        return ok;
+    }
+
     // CostVolumeEnergy::setInterpolationMethod (LES/CostVolumeEnergy.h:45-48): 0 nearest slice, 1 linear (the default), 2 quadratic.  Like the
     // reference's setter it is not synchronised with evaluations running on other threads.
     virtual void setInterpolationMethod(int none_lin_quad)

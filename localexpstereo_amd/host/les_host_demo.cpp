@@ -267,6 +267,21 @@ static int cmd_run(int argc, char** argv)
         }
         printf("warm start: label-map operator vs the device run %zu cost differences; vs one operator call per pixel: max |diff| %.2e, %zu sentinel differences\n", bits, worst, sent);
         if (!okd || bits || sent || !(worst <= 2.0 * 2e-6)) { printf("FAIL: the label-map operator disagrees\n"); fail = 1; }
+        // cross-view fusion's warp through the adapter: a fronto-parallel left-view map at disparity 3 lands three columns to the left with v
+        // negated; the three rightmost columns keep the fallback
+        const size_t P = (size_t)W * H;
+        std::vector<Plane> wsrc(P, Plane(0.f, 0.f, 3.f, 0.5f)), wfb(P, Plane(0.125f, -0.25f, 7.f, 0.f)), wout(P);
+        std::vector<unsigned char> whit(P, 9);
+        const bool okw = hip.warpLabels(0, wsrc.data(), wfb.data(), wout.data(), whit.data());
+        size_t wbad = 0;
+        for (int y = 0; y < H; y++)
+            for (int x = 0; x < W; x++) {
+                const bool in = x + 3 < W;
+                const Plane want = in ? Plane(0.f, 0.f, 3.f, -0.5f) : wfb[(size_t)y * W + x];
+                wbad += memcmp(&wout[(size_t)y * W + x], &want, sizeof(Plane)) != 0 || whit[(size_t)y * W + x] != (in ? 1 : 0);
+            }
+        printf("warpLabels: %zu of %zu pixels differ from the expected map\n", wbad, P);
+        if (!okw || wbad) { printf("FAIL: warpLabels\n"); fail = 1; }
     }
     printf(fail ? "les_host_demo: FAILED\n" : "les_host_demo: OK\n");
     return fail;

@@ -594,7 +594,8 @@ class PMRunner:
 
     # -- fusion moves (LES/FastGCStereo.h:241-410; definition and the deviation from the reference: csrc/les_fusion.h) -----------------
     def fuse(self, labels_b, layers=None, nthreads=0):
-        """Fuses the current solution with a second labelling `labels_b` (H x W x 4) by graph cuts: after begin_gc, for every disjoint set of the
+        """Fuses the current solution with a second labelling `labels_b` (H x W x 4; a host array, or a float32 tensor on the runner's device, which is
+        read in place and must stay unchanged during the call) by graph cuts: after begin_gc, for every disjoint set of the
         chosen layers (None = all; else the layer indices) one lock-step of fusion moves -- the graphs of the set's cells from the two label maps
         (les_hip_batch_fusion_graph), the cuts of the graph-cut iterations (_cut: the device solvers chosen per cell, the host where device_cuts says
         so or the device gave up), the masks applied from the label map (les_hip_batch_apply_masks_labels), a row of the inner-loop log.  The unary
@@ -609,7 +610,11 @@ class PMRunner:
         if self.gc is None:
             raise RuntimeError("PMRunner.fuse needs begin_gc(graph_cut) first")
         t0 = time.perf_counter()
-        lab = torch.as_tensor(np.ascontiguousarray(labels_b, np.float32)).to(self.device)
+        if (torch.is_tensor(labels_b) and labels_b.device == self.labels.device and labels_b.dtype == torch.float32 and labels_b.is_contiguous()
+                and labels_b.data_ptr() != self.labels.data_ptr()):
+            lab = labels_b                       # a device map (stereo.FastGCStereo's cross-view step: the other view's warped labels) is used as is
+        else:                                    # (any other array or tensor: converted through numpy, as before)
+            lab = torch.as_tensor(np.ascontiguousarray(labels_b, np.float32)).to(self.device)
         assert tuple(lab.shape) == (self.H, self.W, 4)
         self.e.unary_labels(lab.data_ptr(), self.prop.data_ptr(), mode=self.mode, check=True)
         self._sync()

@@ -22,8 +22,16 @@ PARAMS_BF = dict(PARAMS_GF, lambda_=20.0, windR=20, eps=10.0, filter="BF")
 
 class FastGCStereo:
     def __init__(self, energy, imL, imR, params, device="cuda", rank=0, world=1, seed=1, host_threads=0, device_cuts=None, random_vdisp=None,
-                 evaluate_on_device=False, inner_loop_log=False, check_flow_energy=False, recost_after_post=False):
+                 evaluate_on_device=False, inner_loop_log=False, check_flow_energy=False, recost_after_post=False, cross_view=0):
         self.e, self.imL, self.imR, self.p = energy, imL, imR, dict(PARAMS_GF, **params)
+        # Opt-in, no reference counterpart (the reference's views meet only in the post-processing): n > 0 -- in a two-view run, after every n-th
+        # graph-cut iteration and after the last one, each view fuses the other view's solution, warped into its own coordinates on the device
+        # (les_hip_warp_labels, csrc/les_crossview.h), into its own by fusion moves (pm.PMRunner.fuse).  0 (the default): nothing changes.
+        self.cross_view = int(cross_view)
+        if self.cross_view < 0:
+            raise ValueError(f"cross_view {cross_view}: 0 (off) or the number of graph-cut iterations between two cross-view steps")
+        self.cross_stats = {}                     # cross_fuse(): view -> the runner's fuse report + hit_pixels, energy_before, energy_after
+        self.cross_view_stats = []                # run(): one dict(iteration=, views={view: report + hit_pixels}) per cross-view step
         # Opt-in: after postProcess (two-view runs) every view's cost map is re-evaluated from its final labels (pm.PMRunner.recost: one dense
         # pass), so the last row's `data` belongs to the labels it is logged with.  Off (the default, the reference's behaviour,
         # LES/FastGCStereo.h:205-206): that row reports the data term of the labels before the left-right check, fill and weighted median.
@@ -183,6 +191,51 @@ class FastGCStereo:
             runner.close()
             g.close()
 
+    def _cross_view_step(self, runners, layers=None):
+        """One cross-view step on two runners that are ready to cut (begin_gc): both label maps are snapshotted on the device, then each view fuses
+        the OTHER view's snapshot, warped into its coordinates with its own snapshot as the fallback, into its solution.  Both warps read the
+        snapshots, so the order of the views does not matter.  The labels make no host round trip.  -> {view: fuse report + hit_pixels}"""
+        snap = {m: runners[m].labels.clone() for m in (0, 1)}
+        out = {}
+        for m in (0, 1):
+            warped = torch.empty_like(snap[m])
+            hit = torch.empty((self.e.H, self.e.W), dtype=torch.uint8, device=warped.device)
+            self.e.warp_labels(1 - m, snap[1 - m].data_ptr(), snap[m].data_ptr(), warped.data_ptr(), hit.data_ptr())
+            out[m] = runners[m].fuse(warped, layers=layers, nthreads=self.host_threads)
+            out[m]["hit_pixels"] = int(hit.sum())
+        return out
+
+    def cross_fuse(self, labelings, layers=None):
+        """Cross-view fusion of two finished views (no reference counterpart; csrc/les_crossview.h): labelings = {0: L, 1: R}, both H x W x 4.
+        Each view starts from its map by the route of fuse() and fuses the other view's map, warped into its coordinates, into it:
+            L' = fuse(L, [warp(R -> view 0, fallback L)])        R' = fuse(R, [warp(L -> view 1, fallback R)])
+        over every disjoint set of the layers added by addLayer (layers: their indices, None = all).  Both warps are taken from the input maps.  A
+        pixel of L' carries its label of L or of the warped map; no view's energy rises.  self.cross_stats: per view the runner's fuse report plus
+        hit_pixels (target pixels some source pixel landed on) and energy_before / energy_after.  Single rank.  -> {0: L', 1: R'}"""
+        if self.world > 1:
+            raise NotImplementedError("FastGCStereo.cross_fuse is single-rank: multi-rank cross-view fusion is not implemented")
+        if sorted(labelings) != [0, 1]:
+            raise ValueError(f"cross_fuse takes the maps of both views, {{0: L, 1: R}} (views given: {sorted(labelings)})")
+        runners = {m: pm.PMRunner(self.e, self.units, self.table, seed=self.seed + 7919 * m, device=self.device, mode=m, random_vdisp=self.random_vdisp)
+                   for m in (0, 1)}
+        g = gc.GraphCut(self.imL, self.imR, lambda_=self.p["lambda_"], th_smooth=self.p["th_smooth"], omega=self.p["omega"], epsilon=self.p["epsilon"])
+        try:
+            before = {}
+            for m in (0, 1):
+                runners[m].init_from_labels(labelings[m])
+                if self.device_cuts is not None:
+                    runners[m].device_cuts = self.device_cuts
+                runners[m].begin_gc(g, mode=m)
+                before[m] = sum(runners[m].energy(self._pairwise()))
+            self.cross_stats = self._cross_view_step(runners, layers)
+            for m in (0, 1):
+                self.cross_stats[m].update(energy_before=before[m], energy_after=sum(runners[m].energy(self._pairwise())))
+            return {m: runners[m].labels.cpu().numpy().copy() for m in (0, 1)}
+        finally:
+            for r in runners.values():
+                r.close()
+            g.close()
+
     def _evaluate_row(self, index, mode, runner, g, t0):
         """_evaluate for the view that fuse() works on (the rows of run() are the left view's)."""
         runner._sync()
@@ -195,6 +248,14 @@ class FastGCStereo:
     def _run(self, maxIteration, viewModes, pmInit, labeling):
         if self.inner_loop_log and self.world > 1:
             raise ValueError("inner_loop_log is a single-rank log: with several ranks a rank holds only its band of a set's cells until the exchange")
+        if self.cross_view > 0:
+            if self.world > 1:
+                raise NotImplementedError("cross_view is single-rank: multi-rank cross-view fusion is not implemented")
+            if sorted(viewModes) != [0, 1]:
+                raise ValueError("cross_view needs a two-view run (viewModes (0, 1)): there is no other view to fuse with")
+        # graph-cut iterations (counted from 1) that end with a cross-view step: every cross_view-th one and the last one
+        cross_after = {it + 1 for it in range(maxIteration) if (it + 1) % self.cross_view == 0 or it + 1 == maxIteration} if self.cross_view > 0 else set()
+        self.cross_view_stats = []
         t0 = time.perf_counter()
         self.eval_seconds = 0.0
         # Several ranks and two views: the views are independent until the post-processing (LES/FastGCStereo.h:172-185), so the ranks are
@@ -226,7 +287,7 @@ class FastGCStereo:
         if self.inner_loop_log:
             for m in viewModes:
                 r = runners[m]
-                ev = api.DeviceEvaluator(self.e, max_rows=max(1, len(r.sets) * (maxIteration + pmInit)), **(ev_args if m == 0 else {}))
+                ev = api.DeviceEvaluator(self.e, max_rows=max(1, len(r.sets) * (maxIteration + pmInit + len(cross_after))), **(ev_args if m == 0 else {}))
                 inner[m] = r.inner_log = SimpleNamespace(evaluator=ev, params=self._pairwise(), meta=[])
         g = gc.GraphCut(self.imL, self.imR, lambda_=self.p["lambda_"], th_smooth=self.p["th_smooth"], omega=self.p["omega"],
                         epsilon=self.p["epsilon"]) if maxIteration > 0 else None
@@ -307,6 +368,10 @@ class FastGCStereo:
                 else:
                     for m in viewModes:
                         one_view(m, it)
+                if it + 1 in cross_after:
+                    # whichever schedule cut the iteration: both views are at rest here, on the driver's thread and stream (the fusion's sets
+                    # add their rows to the inner-loop log under this iteration, after the rows of its cuts)
+                    self.cross_view_stats.append(dict(iteration=it + 1, views=self._cross_view_step(runners)))
                 for m in viewModes:
                     self._evaluate(it + 1 + pmInit, m, runners[m], g, t0)
             for m in viewModes:
@@ -390,7 +455,8 @@ def MidV2(data, iterations=5, pmIterations=2, doDual=False, smooth_weight=None, 
     default) or PARAMS_BF (or a dict with their keys): filter, eps, alpha, th_col, th_grad; smooth_weight (default: params' lambda_)
     and filterRadious override lambda_ and windR as the reference's options do (:284-286).
     vdisp: the vertical-disparity range of the energy (MAX_VDISPARITY, :281): initial labels draw v in [-vdisp, vdisp].  As in main.cpp
-    the random proposer keeps range 0 (RandomProposer(7, maxdisp)); random_vdisp (opt-in, not in main.cpp) gives it its own maxVDisp."""
+    the random proposer keeps range 0 (RandomProposer(7, maxdisp)); random_vdisp (opt-in, not in main.cpp) gives it its own maxVDisp.
+    Further keywords go to FastGCStereo (cross_view=n with doDual: cross-view fusion after every n-th graph-cut iteration)."""
     p = dict(PARAMS_GF if params is None else params)
     lam = p["lambda_"] if smooth_weight is None else smooth_weight
     maxdisp = float(data["ndisp"] - 1)
@@ -414,7 +480,8 @@ def MidV3(data, volL=None, volR=None, iterations=5, pmIterations=2, doDual=False
     (default) or PARAMS_BF: filter and eps; smooth_weight, mc_threshold and filterRadious override lambda_, th_col and windR (:351-353).
     interpolate: the energy's setInterpolationMethod (LES/CostVolumeEnergy.h:45-48) -- 0 nearest, 1 linear (default), 2 quadratic.
     volL None: no volume files -- both views' AD-Census volumes (io.build_volumes; lambda_ad, lambda_census) are built on the device from
-    data["imL"], data["imR"] and data["ndisp"]."""
+    data["imL"], data["imR"] and data["ndisp"].  Further keywords go to FastGCStereo (cross_view=n with doDual: cross-view fusion after every
+    n-th graph-cut iteration)."""
     p = dict(PARAMS_GF if params is None else params)
     maxdisp = float(data["ndisp"] - 1)
     if volL is None:
