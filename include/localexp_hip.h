@@ -418,6 +418,34 @@ int les_hip_consistency_check(les_hip_ctx* ctx, const les_hip_plane* d_labelsL, 
 int les_hip_warp_labels(les_hip_ctx* ctx, int src_mode, const les_hip_plane* d_src, const les_hip_plane* d_fallback, les_hip_plane* d_out,
                         unsigned char* d_hit /* may be NULL */);
 
+/* ---- winner-take-all labels of the aggregated cost volume (csrc/les_wtavol.h holds the definition) ----
+ * No reference counterpart: the reference starts every run from one random plane per finest-layer cell (initCurrentFast,
+ * LES/FastGCStereo.h:94-115) and never reads a whole aggregated volume.  This is cost-volume filtering's read-out of the H1 workload (the slabs
+ * of K fronto-parallel planes, les_hip_batch_create with out_slabs = 1): per pixel the slab k* of least cost -- the comparison is c < best from
+ * best = +inf, so NaN and +inf never win and of equal costs the lowest disparity wins -- refined by the parabola through the costs of slabs
+ * k* - 1, k*, k* + 1 (off = 0.5 (cm - cp) / ((cm - c0) + (cp - c0)) when 0 < k* < K - 1, cm and cp are finite and the denominator is positive,
+ * else 0; |off| <= 0.5).  Label (0, 0, (k* + off) + min_disparity, 0), cost c0; a pixel without a winner gets (0, 0, min_disparity, 0) and +inf.
+ *
+ * The reduction streams: les_hip_slab_argmin consumes one chunk of n slabs ([n][H][W] floats on the device; slab i is slab k_first + i of the
+ * volume) and updates d_state (les_hip_slab_argmin_state_bytes(H, W) bytes on the device, 16-byte aligned, opaque; k_first == 0 initialises it, so
+ * it needs no clearing); the chunks of one volume are fed in order, each slab once.  les_hip_slab_argmin_finish turns the state after K slabs
+ * into d_labels (H x W planes) and d_cost (H x W floats); subpixel == 0: off = 0 everywhere.  How the K slabs are cut into chunks changes no bit
+ * of the outputs.  Both are enqueue only, on the calling thread's stream (les_hip_set_thread_stream is honoured): no allocation, no
+ * synchronisation; calls on distinct states may come from distinct host threads. */
+size_t les_hip_slab_argmin_state_bytes(int H, int W);
+int les_hip_slab_argmin(les_hip_ctx* ctx, const float* d_slabs, int n, int k_first, void* d_state);
+int les_hip_slab_argmin_finish(les_hip_ctx* ctx, const void* d_state, int K, int subpixel, les_hip_plane* d_labels, float* d_cost);
+/* The whole operation for view `mode`: K = int(max_disparity - min_disparity) + 1 planes (0, 0, min_disparity + k, 0) with filterRect =
+ * targetRect = the image and check = 0 run through the batch path (the kernel les_hip_batch_kernel_kind reports for such a batch: any context,
+ * any filter, the interpolation that is set), `chunk` planes per launch (chunk <= 0: 32; clamped to K) into a slab workspace the context owns;
+ * each chunk is reduced as it lands, then the state is finished into d_labels / d_cost.  Every label is a valid one (its disparity lies in
+ * [min_disparity, min_disparity + K - 1]).  A view that was not supplied at creation, or a null output: LES_HIP_ERR_ARG.
+ * Asynchronous on the calling thread's stream, except that the first call on a context -- and one with a larger chunk, or after the disparity
+ * range changed -- allocates (planes, one prepared batch per chunk length, chunk x H x W floats of slabs, the state: hipMalloc and table uploads
+ * synchronise).  The workspace is one per context: ONE host thread at a time may call this on a context (the two views one after the other);
+ * other entry points may run beside it on other threads. */
+int les_hip_wta_labels(les_hip_ctx* ctx, int mode, int chunk, int subpixel, les_hip_plane* d_labels, float* d_cost);
+
 /* replaces: PMStereoBase::postProcess (LES/PMStereoBase.h:146-256), called by FastGCStereo::run for two-view runs
  * (LES/FastGCStereo.h:199-203, threshold 1.5): consistency check, horizontal fill of the failed pixels from the nearest
  * consistent neighbours (smaller disparity wins), then the colour-weighted median of the labels over the

@@ -28,6 +28,7 @@ SYMBOLS = [
     "les_hip_unary_labels", "les_hip_unary_labels_kind",
     "les_hip_costvol_tables", "les_hip_census", "les_hip_build_cost_volume", "les_hip_costvol_last_times",
     "les_hip_warp_labels",
+    "les_hip_slab_argmin_state_bytes", "les_hip_slab_argmin", "les_hip_slab_argmin_finish", "les_hip_wta_labels",
 ]
 
 
@@ -173,6 +174,10 @@ def load(path=None):
         "les_hip_build_cost_volume": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, C.c_float, C.c_float, ci, vp]),
         "les_hip_costvol_last_times": (ci, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
         "les_hip_warp_labels": (ci, [vp, ci, vp, vp, vp, vp]),
+        "les_hip_slab_argmin_state_bytes": (C.c_size_t, [ci, ci]),
+        "les_hip_slab_argmin": (ci, [vp, vp, ci, ci, vp]),
+        "les_hip_slab_argmin_finish": (ci, [vp, vp, ci, ci, vp, vp]),
+        "les_hip_wta_labels": (ci, [vp, ci, ci, ci, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -705,6 +710,46 @@ class HipCostVolumeEnergy:
         None.  Enqueue only (the calling thread's stream).  Rows wider than WARP_MAX_WIDTH raise (error 3)."""
         self._chk(self.L.les_hip_warp_labels(self.h, int(src_mode), C.c_void_p(int(src_ptr)), C.c_void_p(int(fallback_ptr)), C.c_void_p(int(out_ptr)),
                                              C.c_void_p(int(hit_ptr)) if hit_ptr else None))
+
+    # -- winner-take-all labels of the aggregated cost volume (csrc/les_wtavol.h; no reference counterpart) ---------------
+    @property
+    def num_fronto_planes(self):
+        """K of wta_labels: int(max_disparity - min_disparity) + 1."""
+        return int(np.float32(self.params.max_disparity) - np.float32(self.params.min_disparity)) + 1
+
+    def slab_argmin_state_bytes(self):
+        """Bytes of the per-pixel state of slab_argmin for this context's image (16-byte aligned device memory, opaque)."""
+        return int(self.L.les_hip_slab_argmin_state_bytes(self.H, self.W))
+
+    def slab_argmin(self, slabs_ptr, n, k_first, state_ptr):
+        """les_hip_slab_argmin: the running arg-min over one chunk of n slabs ([n][H][W] floats on the device, slab i = slab k_first + i of the
+        volume) into the state; k_first == 0 initialises it.  Enqueue only."""
+        self._chk(self.L.les_hip_slab_argmin(self.h, C.c_void_p(int(slabs_ptr)) if slabs_ptr else None, int(n), int(k_first),
+                                             C.c_void_p(int(state_ptr)) if state_ptr else None))
+
+    def slab_argmin_finish(self, state_ptr, K, labels_ptr, cost_ptr, subpixel=True):
+        """les_hip_slab_argmin_finish: the state after K slabs -> the H x W plane map (0, 0, k* + off + min_disp, 0) and the H x W cost map."""
+        self._chk(self.L.les_hip_slab_argmin_finish(self.h, C.c_void_p(int(state_ptr)) if state_ptr else None, int(K), int(bool(subpixel)),
+                                                    C.c_void_p(int(labels_ptr)) if labels_ptr else None, C.c_void_p(int(cost_ptr)) if cost_ptr else None))
+
+    def wta_labels(self, mode=0, chunk=0, subpixel=True, labels_ptr=None, cost_ptr=None, device=None):
+        """les_hip_wta_labels: the winner-take-all label map of view `mode` -- per pixel the fronto-parallel plane of least aggregated cost among
+        the num_fronto_planes planes at min_disp + k, refined to sub-pixel by the parabola through its neighbours' costs -- and its costs; the
+        planes run through the batch path `chunk` at a time (0: the library's default) and each chunk is reduced as it lands.  Asynchronous on
+        the calling thread's stream once the context's workspace exists.  With labels_ptr and cost_ptr (device addresses of the H x W x 4 and
+        H x W float maps) it writes there and returns None; with neither it returns (labels, cost) as new torch tensors on `device` (None:
+        this context's GPU; the simulator build takes "cpu")."""
+        if (labels_ptr is None) != (cost_ptr is None):
+            raise ValueError("wta_labels: give both labels_ptr and cost_ptr, or neither")
+        out = None
+        if labels_ptr is None:
+            import torch
+            dev = torch.device(device if device is not None else f"cuda:{self.params.device}")
+            out = (torch.empty((self.H, self.W, 4), dtype=torch.float32, device=dev), torch.empty((self.H, self.W), dtype=torch.float32, device=dev))
+            labels_ptr, cost_ptr = out[0].data_ptr(), out[1].data_ptr()
+        self._chk(self.L.les_hip_wta_labels(self.h, int(mode), int(chunk), int(bool(subpixel)), C.c_void_p(int(labels_ptr)) if labels_ptr else None,
+                                            C.c_void_p(int(cost_ptr)) if cost_ptr else None))
+        return out
 
     def wta_update(self, rects, planes, cur_cost_dev, prop_cost_dev, labels_dev, planes_on_device=False):
         rects = _rects(rects)

@@ -20,6 +20,7 @@
 #include "les_dense.h"
 #include "les_costvol.h"
 #include "les_crossview.h"
+#include "les_wtavol.h"
 
 #include "../host/ResidualCut.h"      // the host cores' finisher of the tiled max-flow (plain C++: search trees / push-relabel on a residual graph)
 
@@ -108,6 +109,8 @@ struct ViewData {                        // (its device buffers are freed by the
 
 struct MtHost;
 namespace { void mt_host_free(MtHost* m); }
+struct WtaVol;
+namespace { void wtavol_free(WtaVol* w); }
 
 namespace {
 
@@ -186,6 +189,7 @@ struct les_hip_ctx {
     bool maxflow_lds_ready = false;      // the per-device dynamic-LDS opt-in of les_maxflow_kernel has been made on this context's device
     bool maxflow_tiled_lds_ready = false;   // ... and of les_maxflow_tiled_kernel
     std::vector<les_hip_scratch*> own_scratch;   // scratch objects created behind les_hip_unary_one (one per calling thread), freed with the context
+    WtaVol* wtavol = nullptr;            // les_hip_wta_labels' planes, batches, slab workspace and state (les_hip_wtavol.inc), built on first use, freed by les_hip_destroy
     std::vector<MtHost*> mt_idle; // host-mapped flag words + hand-over staging of the tiled max-flow: one per CONCURRENT caller, reused, freed with the context
     // what stays raw (les_hip_mem.h): the views' buffers and d_planes; every other table frees itself
     ~les_hip_ctx()
@@ -299,3 +303,4 @@ float naive_alpha(const les_hip_ctx* c) { return c->naive_alpha; }
 #include "les_hip_dense.inc"
 #include "les_hip_costvol.inc"
 #include "les_hip_crossview.inc"
+#include "les_hip_wtavol.inc"

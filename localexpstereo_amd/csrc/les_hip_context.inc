@@ -127,6 +127,8 @@ void les_hip_destroy(les_hip_ctx* c)
     c->own_scratch.clear();
     for (MtHost* m : c->mt_idle) mt_host_free(m);
     c->mt_idle.clear();
+    wtavol_free(c->wtavol);                                     // (its batches go before the context they were prepared on)
+    c->wtavol = nullptr;
     delete c;                                                   // the views' buffers and every owned table
 }
 

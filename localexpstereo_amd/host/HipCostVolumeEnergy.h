@@ -146,6 +146,26 @@ public:
         return ok;
     }
 
+    // Winner-take-all labels of the aggregated cost volume (les_hip_wta_labels, csrc/les_wtavol.h; no reference counterpart): per pixel of view
+    // `mode` the fronto-parallel plane (0, 0, d, 0) of least aggregated cost among the disparities min ... max of the energy, refined to sub-pixel
+    // by the parabola through its neighbours' costs when `subpixel`; cost (may be null): that least cost.  A start for run() (its `labeling`
+    // argument) or a second labelling for a fusion move.  labels, cost: width * height elements in HOST memory; chunk: planes per launch (0: the
+    // library's choice).  Returns false (and reports on stderr) when the library refuses the call (a view without data).
+    bool wtaLabels(Plane* labels, float* cost = nullptr, int mode = 0, bool subpixel = true, int chunk = 0) const
+    {
+        static_assert(sizeof(Plane) == sizeof(les_hip_plane), "ABI layout");
+        const size_t P = (size_t)width * height;
+        les_hip_plane* d_lab = nullptr;
+        float* d_cost = nullptr;
+        bool ok = les_hip_malloc(ctx_, (void**)&d_lab, P * sizeof(les_hip_plane)) == LES_HIP_OK && les_hip_malloc(ctx_, (void**)&d_cost, P * sizeof(float)) == LES_HIP_OK;
+        ok = ok && les_hip_wta_labels(ctx_, mode, chunk, subpixel ? 1 : 0, d_lab, d_cost) == LES_HIP_OK && les_hip_synchronize(ctx_) == LES_HIP_OK;
+        ok = ok && les_hip_memcpy_d2h(ctx_, labels, d_lab, P * sizeof(les_hip_plane)) == LES_HIP_OK && (!cost || les_hip_memcpy_d2h(ctx_, cost, d_cost, P * sizeof(float)) == LES_HIP_OK);
+        if (!ok) fprintf(stderr, "HipCostVolumeEnergy: %s\n", les_hip_last_error());
+        if (d_lab) les_hip_free(ctx_, d_lab);
+        if (d_cost) les_hip_free(ctx_, d_cost);
+        return ok;
+    }
+
     // CostVolumeEnergy::setInterpolationMethod (LES/CostVolumeEnergy.h:45-48): 0 nearest slice, 1 linear (the default), 2 quadratic.  Like the
     // reference's setter it is not synchronised with evaluations running on other threads.
     virtual void setInterpolationMethod(int none_lin_quad)

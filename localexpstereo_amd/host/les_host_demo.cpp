@@ -8,6 +8,7 @@
 //                                              and checks that both reduce the energy and reach the
 //                                              ground truth (needs an MI355X)
 #include <dlfcn.h>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <atomic>
@@ -282,6 +283,15 @@ static int cmd_run(int argc, char** argv)
             }
         printf("warpLabels: %zu of %zu pixels differ from the expected map\n", wbad, P);
         if (!okw || wbad) { printf("FAIL: warpLabels\n"); fail = 1; }
+        // the winner-take-all map of the filtered volume through the adapter: fronto-parallel planes, chunking does not change a bit
+        std::vector<Plane> wta(P), wta2(P);
+        std::vector<float> wcost(P);
+        const bool okt = hip.wtaLabels(wta.data(), wcost.data(), 0) && hip.wtaLabels(wta2.data(), nullptr, 0, true, 3);
+        size_t tbad = 0;
+        for (size_t i = 0; i < P; i++)
+            tbad += !(wta[i].a == 0.f && wta[i].b == 0.f && wta[i].v == 0.f && std::isfinite(wta[i].c) && std::isfinite(wcost[i])) || memcmp(&wta[i], &wta2[i], sizeof(Plane)) != 0;
+        printf("wtaLabels: %zu of %zu pixels are not a finite fronto-parallel plane or depend on the chunking\n", tbad, P);
+        if (!okt || tbad) { printf("FAIL: wtaLabels\n"); fail = 1; }
     }
     printf(fail ? "les_host_demo: FAILED\n" : "les_host_demo: OK\n");
     return fail;

@@ -217,10 +217,13 @@ class PMRunner:
 
     def init_from_labels(self, labels, rows_per_launch=64):
         """The warm-start branch of initCurrentFast (LES/FastGCStereo.h:116-130, "very slow" on the CPU): start from a
-        given H x W x 4 label map; the current cost of every pixel is the unary cost of its own label, evaluated with
+        given H x W x 4 label map (a host array, or a float32 tensor on the runner's device); the current cost of every pixel is the unary cost of its own label, evaluated with
         a 1 x 1 target and the filter region pixel +- windR -- one dense device pass (les_hip_unary_labels).
         rows_per_launch: accepted for callers of the former per-band launches, ignored."""
-        lab = torch.as_tensor(np.ascontiguousarray(labels, np.float32)).to(self.device)
+        if torch.is_tensor(labels) and labels.device == self.labels.device and labels.dtype == torch.float32:
+            lab = labels                         # a device map (stereo.FastGCStereo's labeling="wta") is copied on the device
+        else:
+            lab = torch.as_tensor(np.ascontiguousarray(labels, np.float32)).to(self.device)
         assert tuple(lab.shape) == (self.H, self.W, 4)
         self.labels.copy_(lab)
         self.recost()             # (every rank evaluates the whole map: replicated state, nothing to exchange)

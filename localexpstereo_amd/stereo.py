@@ -144,8 +144,9 @@ class FastGCStereo:
         """FastGCStereo::run (LES/FastGCStereo.h:133-227).  Returns (labeling, rawlabeling) of the left view as
         H x W x 4 float arrays (the raw one is the labelling before the two-view post-processing).  `labeling`: optional
         start labelling (the reference's `labeling` argument; every view starts from it, as in the reference), or a dict {view: H x W x 4
-        map} that gives each view of a two-view run its own (self.raw_labelings of an earlier run resumes it).  The costs of a start labelling
-        come from one dense device pass per view (pm.PMRunner.init_from_labels)."""
+        map} that gives each view of a two-view run its own (self.raw_labelings of an earlier run resumes it), or the string "wta": each view starts
+        from the winner-take-all map of its own filtered cost volume (les_hip_wta_labels, csrc/les_wtavol.h; the map stays on the device; single
+        rank).  The costs of a start labelling come from one dense device pass per view (pm.PMRunner.init_from_labels)."""
         try:
             return self._run(maxIteration, viewModes, pmInit, labeling)
         finally:                 # the device evaluators of the run, also when it raised
@@ -236,6 +237,60 @@ class FastGCStereo:
                 r.close()
             g.close()
 
+    def wta(self, viewModes=(0,), post_process=True, subpixel=True):
+        """Cost-volume filtering without a graph cut (no reference counterpart; csrc/les_wtavol.h): every view of viewModes gets the winner-take-all
+        map of its filtered cost volume -- per pixel the fronto-parallel plane of least aggregated cost, refined to sub-pixel when `subpixel`
+        (les_hip_wta_labels: the H1 workload and a streaming arg-min over its slabs, a few milliseconds).  With an evaluator set, self.log gets one
+        row per view (index = mode = the view; energy, data, smooth; all / nonocc for the left view, whose ground truth the evaluator holds), made
+        from the maps before any post-processing, through the device evaluator when evaluate_on_device (the host route has no pairwise sum without
+        a graph-cut context: smooth is NaN there, as in run() before the first cut).  With two views and post_process, the left-right check, fill
+        and weighted median of run() follow (threshold 1.5, the run's omega).  Sets self.raw_labelings.  Single rank.
+        -> (labeling, rawlabeling) of the left view as run() does (None without the left view)."""
+        if self.world > 1:
+            raise NotImplementedError("FastGCStereo.wta is single-rank: the multi-rank form is not implemented")
+        views = tuple(int(m) for m in viewModes)
+        t0 = time.perf_counter()
+        self.eval_seconds, self.log = 0.0, []
+        maps = {m: self.e.wta_labels(mode=m, subpixel=subpixel, device=self.device) for m in views}
+        self.e.synchronize()
+        self.raw_labelings = {m: maps[m][0].cpu().numpy().copy() for m in views}
+        if self.evaluator is not None:
+            for m in views:
+                te = time.perf_counter()
+                self.log.append(self._wta_row(m, maps[m][0], maps[m][1], t0))
+                self.eval_seconds += time.perf_counter() - te
+        if len(views) == 2 and post_process:
+            self.e.post_process(maps[0][0].data_ptr(), maps[1][0].data_ptr(), 1.5, self.p["omega"])
+            self.e.synchronize()
+        lab = maps[0][0].cpu().numpy().copy() if 0 in maps else None
+        self.seconds = time.perf_counter() - t0 - self.eval_seconds
+        return lab, self.raw_labelings.get(0)
+
+    def _wta_row(self, m, labels, cost, t0):
+        """The Evaluator row of a view's device maps (wta(): there is no runner)."""
+        row = dict(index=m, mode=m, time=time.perf_counter() - t0 - self.eval_seconds)
+        rates = m == 0                      # (the ground truth is the left view's)
+        if self.evaluate_on_device:
+            ev_args = dict(dispGT=self.evaluator.gt, nonocc=self.evaluator.nonocc, error_threshold=self.evaluator.threshold, precision=self.precision) if rates else {}
+            ev = api.DeviceEvaluator(self.e, max_rows=1, **ev_args)
+            try:
+                ev.evaluate(labels.data_ptr(), cost.data_ptr(), mode=m, index=m, **self._pairwise())
+                r = ev.rows()[0]
+            finally:
+                ev.close()
+            row.update(energy=r["data"] + r["smooth"], data=r["data"], smooth=r["smooth"])
+            if rates:
+                row["all"], row["nonocc"] = r["all"], r["nonocc"]
+            return row
+        dc = float(cost.sum(dtype=torch.float64))
+        row.update(energy=dc, data=dc, smooth=float("nan"))
+        if rates:
+            d = disparities(labels.cpu().numpy())
+            if self.precision > 0:                                         # Evaluator::quantize, LES/Evaluator.h:106-111
+                d = (np.rint(d / np.float32(self.precision)) * np.float32(self.precision)).astype(np.float32)
+            row["all"], row["nonocc"] = self.evaluator.evaluate(d)
+        return row
+
     def _evaluate_row(self, index, mode, runner, g, t0):
         """_evaluate for the view that fuse() works on (the rows of run() are the left view's)."""
         runner._sync()
@@ -246,6 +301,11 @@ class FastGCStereo:
             self.eval_seconds += time.perf_counter() - te
 
     def _run(self, maxIteration, viewModes, pmInit, labeling):
+        if isinstance(labeling, str):
+            if labeling != "wta":
+                raise ValueError(f"labeling {labeling!r}: a label map, a dict of them, or \"wta\"")
+            if self.world > 1:
+                raise NotImplementedError("labeling=\"wta\" is single-rank: the multi-rank start is not implemented")
         if self.inner_loop_log and self.world > 1:
             raise ValueError("inner_loop_log is a single-rank log: with several ranks a rank holds only its band of a set's cells until the exchange")
         if self.cross_view > 0:
@@ -294,6 +354,8 @@ class FastGCStereo:
         for m in viewModes:
             if labeling is None:
                 runners[m].init_labels()
+            elif isinstance(labeling, str):
+                runners[m].init_from_labels(self.e.wta_labels(mode=m, device=self.device)[0])
             else:
                 if isinstance(labeling, dict) and m not in labeling:
                     raise ValueError(f"labeling has no map for view {m} (views given: {sorted(labeling)})")
@@ -449,13 +511,15 @@ def _layers(st, sizes):
 
 
 def MidV2(data, iterations=5, pmIterations=2, doDual=False, smooth_weight=None, filterRadious=20, device="cuda", seed=1, lib=None, params=None,
-          vdisp=0.0, random_vdisp=0.0, **kw):
+          vdisp=0.0, random_vdisp=0.0, init=None, **kw):
     """MidV2 (LES/main.cpp:270-328) on a data dict of io.load_data: image-based matching cost, layers 5/15/25, error
     threshold 0.5, disparities quantised to the ground-truth precision before evaluation.  params: PARAMS_GF (the reference's choice,
     default) or PARAMS_BF (or a dict with their keys): filter, eps, alpha, th_col, th_grad; smooth_weight (default: params' lambda_)
     and filterRadious override lambda_ and windR as the reference's options do (:284-286).
     vdisp: the vertical-disparity range of the energy (MAX_VDISPARITY, :281): initial labels draw v in [-vdisp, vdisp].  As in main.cpp
     the random proposer keeps range 0 (RandomProposer(7, maxdisp)); random_vdisp (opt-in, not in main.cpp) gives it its own maxVDisp.
+    init: the start labelling of run() -- None (the default): the reference's random start; "wta": every view starts from the winner-take-all
+    map of its filtered cost volume (FastGCStereo.run's labeling="wta").
     Further keywords go to FastGCStereo (cross_view=n with doDual: cross-view fusion after every n-th graph-cut iteration)."""
     p = dict(PARAMS_GF if params is None else params)
     lam = p["lambda_"] if smooth_weight is None else smooth_weight
@@ -467,20 +531,20 @@ def MidV2(data, iterations=5, pmIterations=2, doDual=False, smooth_weight=None, 
                       random_vdisp=random_vdisp, **kw)
     st.setEvaluator(io.Evaluator(data["dispGT"], data["nonocc"], 0.5), precision=data.get("gt_prec", -1.0))
     _layers(st, (5, 15, 25))
-    lab, raw = st.run(iterations, (0, 1) if doDual else (0,), pmIterations)
+    lab, raw = st.run(iterations, (0, 1) if doDual else (0,), pmIterations, labeling=init)
     st.close()
     e.close()
     return st, lab, raw
 
 
 def MidV3(data, volL=None, volR=None, iterations=5, pmIterations=2, doDual=False, smooth_weight=0.5, mc_threshold=0.5, filterRadious=20,
-          error_threshold=1.0, device="cuda", seed=1, lib=None, params=None, interpolate=1, lambda_ad=10.0, lambda_census=30.0, **kw):
+          error_threshold=1.0, device="cuda", seed=1, lib=None, params=None, interpolate=1, lambda_ad=10.0, lambda_census=30.0, init=None, **kw):
     """MidV3 (LES/main.cpp:330-420): cost-volume energy (volumes ingested on the device), layers 1 % / 3 % / 9 % of the
     image width.  volL / volR: host arrays / memmaps [ndisp][H][W] (volR None: synthesised from the left one).  params: PARAMS_GF
     (default) or PARAMS_BF: filter and eps; smooth_weight, mc_threshold and filterRadious override lambda_, th_col and windR (:351-353).
     interpolate: the energy's setInterpolationMethod (LES/CostVolumeEnergy.h:45-48) -- 0 nearest, 1 linear (default), 2 quadratic.
     volL None: no volume files -- both views' AD-Census volumes (io.build_volumes; lambda_ad, lambda_census) are built on the device from
-    data["imL"], data["imR"] and data["ndisp"].  Further keywords go to FastGCStereo (cross_view=n with doDual: cross-view fusion after every
+    data["imL"], data["imR"] and data["ndisp"].  init: as for MidV2 (None: the random start; "wta": the winner-take-all start).  Further keywords go to FastGCStereo (cross_view=n with doDual: cross-view fusion after every
     n-th graph-cut iteration)."""
     p = dict(PARAMS_GF if params is None else params)
     maxdisp = float(data["ndisp"] - 1)
@@ -497,7 +561,7 @@ def MidV3(data, volL=None, volR=None, iterations=5, pmIterations=2, doDual=False
     st = FastGCStereo(e, data["imL"], data["imR"], dict(p, lambda_=smooth_weight, windR=filterRadious, th_col=mc_threshold), device=device, seed=seed, **kw)
     st.setEvaluator(io.Evaluator(data["dispGT"], data["nonocc"], error_threshold), precision=-1.0)
     _layers(st, (int(W * 0.01), int(W * 0.03), int(W * 0.09)))
-    lab, raw = st.run(iterations, (0, 1) if doDual else (0,), pmIterations)
+    lab, raw = st.run(iterations, (0, 1) if doDual else (0,), pmIterations, labeling=init)
     st.close()
     e.close()
     del tl, tr
