@@ -446,6 +446,25 @@ int les_hip_slab_argmin_finish(les_hip_ctx* ctx, const void* d_state, int K, int
  * other entry points may run beside it on other threads. */
 int les_hip_wta_labels(les_hip_ctx* ctx, int mode, int chunk, int subpixel, les_hip_plane* d_labels, float* d_cost);
 
+/* ---- slanted planes fitted to a disparity map (csrc/les_planefit.h holds the definition) ----
+ * No reference counterpart: the reference's only start is one random plane per finest-layer cell (initCurrentFast, LES/FastGCStereo.h:94-115).
+ * Per pixel p of view `mode` an edge-aware weighted least-squares plane through the disparities of its (2 radius + 1)^2 window: the input is
+ * EITHER d_labels (H x W planes; d = (a x + b y) + c, the output keeps the centre label's v) OR d_disp (H x W floats; v = 0), the other one
+ * NULL.  A tap s is taken iff its disparity is finite and |d(s) - d(p)| <= gate0 + gate_slope max(|dx|, |dy|); its weight is
+ * exp(-|I(p) - I(s)|_1 / sig) of the view's 8-bit guide colours (sig == 0: 1).  The nine sums are taken in fp64 in a fixed tap order and the
+ * 3 x 3 normal equations solved by cofactors, so the result is a function of the inputs only.  The fit (a, b, c, v) is accepted -- d_kind 2 --
+ * iff it has at least min_support taps, its support is not collinear (det > 1e-3 S^3), it passes within gate0 of d(p), |a|, |b| <= max_slope
+ * and the plane is a valid label at p (IsValiLabel).  Otherwise the pixel gets (0, 0, d(p), v) -- d_kind 1 -- when d(p) lies in the energy's
+ * disparity range, else -- d_kind 0, also when d(p) is not finite -- d_fallback's label bit for bit ((0, 0, min_disparity, 0) when
+ * d_fallback is NULL).  d_kind may be NULL.  d_out may be d_fallback; it may not be the input map.
+ * radius 1 .. 15 (above: LES_HIP_ERR_UNSUPPORTED); sig >= 0, gate0 > 0, gate_slope >= 0, max_slope > 0, all finite; min_support >= 3;
+ * anything else, both or neither input map, a null d_out, a view without an image: LES_HIP_ERR_ARG, nothing launched.
+ * Enqueue only, on the calling thread's stream (les_hip_set_thread_stream is honoured), except that the first call with a value of sig
+ * uploads its 766-entry weight table and waits for that stream; the context keeps the tables of the last 8 values. */
+int les_hip_fit_planes(les_hip_ctx* ctx, int mode, const les_hip_plane* d_labels /* or NULL */, const float* d_disp /* or NULL */,
+                       const les_hip_plane* d_fallback /* may be NULL */, les_hip_plane* d_out, unsigned char* d_kind /* may be NULL */, int radius,
+                       float sig, float gate0, float gate_slope, float max_slope, int min_support);
+
 /* replaces: PMStereoBase::postProcess (LES/PMStereoBase.h:146-256), called by FastGCStereo::run for two-view runs
  * (LES/FastGCStereo.h:199-203, threshold 1.5): consistency check, horizontal fill of the failed pixels from the nearest
  * consistent neighbours (smaller disparity wins), then the colour-weighted median of the labels over the

@@ -29,6 +29,7 @@ SYMBOLS = [
     "les_hip_costvol_tables", "les_hip_census", "les_hip_build_cost_volume", "les_hip_costvol_last_times",
     "les_hip_warp_labels",
     "les_hip_slab_argmin_state_bytes", "les_hip_slab_argmin", "les_hip_slab_argmin_finish", "les_hip_wta_labels",
+    "les_hip_fit_planes",
 ]
 
 
@@ -178,6 +179,7 @@ def load(path=None):
         "les_hip_slab_argmin": (ci, [vp, vp, ci, ci, vp]),
         "les_hip_slab_argmin_finish": (ci, [vp, vp, ci, ci, vp, vp]),
         "les_hip_wta_labels": (ci, [vp, ci, ci, ci, vp, vp]),
+        "les_hip_fit_planes": (ci, [vp, ci, vp, vp, vp, vp, vp, ci, C.c_float, C.c_float, C.c_float, C.c_float, ci]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -254,6 +256,8 @@ def build_cost_volume(imL_dev_ptr, imR_dev_ptr, vol_dev_ptr, D, H, W, mode, d0=0
                                             lambda_ad, lambda_census, device, C.c_void_p(int(stream))))
 
 
+FIT_MAX_RADIUS = 15            # kFitMaxR of csrc/les_planefit.h (the one source; tests/planefit_cases.py: case_independence_and_errors holds this copy to it)
+FIT_DEFAULTS = dict(radius=5, sig=10.0, gate0=1.0, gate_slope=0.5, max_slope=2.0, min_support=6)      # of every fit_planes above the C ABI
 WARP_MAX_WIDTH = 8192          # kWarpMaxW of csrc/les_crossview.h (the one source; tests/crossview_cases.py: case_width_limit holds this copy to it)
 
 
@@ -750,6 +754,48 @@ class HipCostVolumeEnergy:
         self._chk(self.L.les_hip_wta_labels(self.h, int(mode), int(chunk), int(bool(subpixel)), C.c_void_p(int(labels_ptr)) if labels_ptr else None,
                                             C.c_void_p(int(cost_ptr)) if cost_ptr else None))
         return out
+
+    # -- slanted planes fitted to a disparity map (csrc/les_planefit.h; no reference counterpart) --------------------------
+    def fit_planes_ptr(self, mode, labels_ptr, disp_ptr, fallback_ptr, out_ptr, kind_ptr=None, **params):
+        """les_hip_fit_planes on device addresses (exactly one of labels_ptr / disp_ptr; fallback_ptr and kind_ptr may be None; out_ptr may be
+        fallback_ptr).  params: radius, sig, gate0, gate_slope, max_slope, min_support (FIT_DEFAULTS).  Enqueue only once the table of `sig` exists."""
+        q = dict(FIT_DEFAULTS, **params)
+        if set(q) != set(FIT_DEFAULTS):
+            raise TypeError(f"fit_planes: unknown parameters {sorted(set(q) - set(FIT_DEFAULTS))}")
+        vp = lambda p: C.c_void_p(int(p)) if p else None
+        self._chk(self.L.les_hip_fit_planes(self.h, int(mode), vp(labels_ptr), vp(disp_ptr), vp(fallback_ptr), vp(out_ptr), vp(kind_ptr), int(q["radius"]),
+                                            C.c_float(q["sig"]), C.c_float(q["gate0"]), C.c_float(q["gate_slope"]), C.c_float(q["max_slope"]), int(q["min_support"])))
+
+    def fit_planes(self, src, mode=0, fallback=None, with_kind=False, device=None, **params):
+        """Slanted planes from a disparity map: per pixel of view `mode` an edge-aware weighted least-squares plane through the disparities of its
+        window (les_hip_fit_planes).  src: an H x W x 4 label map or an H x W disparity map; fallback: an H x W x 4 label map for the pixels that
+        get neither a fit nor their own disparity (None: (0, 0, min_disp, 0)); both float32 torch tensors or arrays (a tensor on `device` is
+        used where it is, anything else is copied there).  params: radius=5, sig=10, gate0=1, gate_slope=0.5, max_slope=2, min_support=6.
+        -> the H x W x 4 map as a new tensor on `device` (None: this context's GPU; the simulator build takes "cpu"); with_kind: (map, kind), kind
+        H x W uint8 -- 2 slanted fit, 1 fronto-parallel at the pixel's own disparity, 0 fallback.  Asynchronous on the calling thread's stream."""
+        import torch
+        dev = torch.device(device if device is not None else f"cuda:{self.params.device}")
+
+        def on_device(a):
+            if torch.is_tensor(a) and a.device == dev and a.dtype == torch.float32:
+                return a.contiguous()
+            if torch.is_tensor(a):
+                return a.to(device=dev, dtype=torch.float32).contiguous()
+            return torch.from_numpy(np.array(a, dtype=np.float32, order="C")).to(dev)          # (a copy: torch wants a writable array)
+        s = on_device(src)
+        if tuple(s.shape) not in ((self.H, self.W, 4), (self.H, self.W)):
+            raise ValueError(f"fit_planes: a {self.H} x {self.W} x 4 label map or a {self.H} x {self.W} disparity map, not {tuple(s.shape)}")
+        fb = None
+        if fallback is not None:
+            fb = on_device(fallback)
+            if tuple(fb.shape) != (self.H, self.W, 4):
+                raise ValueError(f"fit_planes: the fallback is a {self.H} x {self.W} x 4 label map, not {tuple(fb.shape)}")
+        out = torch.empty((self.H, self.W, 4), dtype=torch.float32, device=dev)
+        kind = torch.empty((self.H, self.W), dtype=torch.uint8, device=dev) if with_kind else None
+        labels = s.dim() == 3
+        self.fit_planes_ptr(mode, s.data_ptr() if labels else None, None if labels else s.data_ptr(), fb.data_ptr() if fb is not None else None,
+                            out.data_ptr(), kind.data_ptr() if with_kind else None, **params)
+        return (out, kind) if with_kind else out
 
     def wta_update(self, rects, planes, cur_cost_dev, prop_cost_dev, labels_dev, planes_on_device=False):
         rects = _rects(rects)

@@ -166,6 +166,34 @@ public:
         return ok;
     }
 
+    // Slanted planes fitted to a disparity map (les_hip_fit_planes, csrc/les_planefit.h; no reference counterpart): per pixel of view `mode` an
+    // edge-aware weighted least-squares plane through the disparities of its (2 radius + 1)^2 window, guided by that view's image.  Exactly one of
+    // labels (planes whose own disparities are fitted; the result keeps their v) and disp (a disparity map) is given, the other one null; fallback
+    // (may be null: (0, 0, MIN_DISPARITY, 0)) supplies the pixels that get neither a fit nor their own disparity; kind (may be null): 2 slanted fit,
+    // 1 fronto-parallel at the pixel's own disparity, 0 fallback.  All maps: width * height elements in HOST memory; out may be fallback.  A start
+    // for run() or a second labelling for a fusion move.  Returns false (and reports on stderr) when the library refuses the call.
+    bool fitPlanes(const Plane* labels, const float* disp, const Plane* fallback, Plane* out, unsigned char* kind = nullptr, int mode = 0, int radius = 5,
+                   float sig = 10.f, float gate0 = 1.f, float gate_slope = 0.5f, float max_slope = 2.f, int min_support = 6) const
+    {
+        static_assert(sizeof(Plane) == sizeof(les_hip_plane), "ABI layout");
+        const size_t P = (size_t)width * height;
+        les_hip_plane *d_lab = nullptr, *d_fb = nullptr, *d_out = nullptr;
+        float* d_disp = nullptr;
+        unsigned char* d_kind = nullptr;
+        bool ok = les_hip_malloc(ctx_, (void**)&d_out, P * sizeof(les_hip_plane)) == LES_HIP_OK;
+        if (labels) ok = ok && les_hip_malloc(ctx_, (void**)&d_lab, P * sizeof(les_hip_plane)) == LES_HIP_OK && les_hip_memcpy_h2d(ctx_, d_lab, labels, P * sizeof(les_hip_plane)) == LES_HIP_OK;
+        if (disp) ok = ok && les_hip_malloc(ctx_, (void**)&d_disp, P * sizeof(float)) == LES_HIP_OK && les_hip_memcpy_h2d(ctx_, d_disp, disp, P * sizeof(float)) == LES_HIP_OK;
+        if (fallback) ok = ok && les_hip_malloc(ctx_, (void**)&d_fb, P * sizeof(les_hip_plane)) == LES_HIP_OK && les_hip_memcpy_h2d(ctx_, d_fb, fallback, P * sizeof(les_hip_plane)) == LES_HIP_OK;
+        if (kind) ok = ok && les_hip_malloc(ctx_, (void**)&d_kind, P) == LES_HIP_OK;
+        ok = ok && les_hip_fit_planes(ctx_, mode, d_lab, d_disp, d_fb, d_out, d_kind, radius, sig, gate0, gate_slope, max_slope, min_support) == LES_HIP_OK &&
+             les_hip_synchronize(ctx_) == LES_HIP_OK;
+        ok = ok && les_hip_memcpy_d2h(ctx_, out, d_out, P * sizeof(les_hip_plane)) == LES_HIP_OK && (!kind || les_hip_memcpy_d2h(ctx_, kind, d_kind, P) == LES_HIP_OK);
+        if (!ok) fprintf(stderr, "HipCostVolumeEnergy: %s\n", les_hip_last_error());
+        for (void* q : {(void*)d_lab, (void*)d_disp, (void*)d_fb, (void*)d_out, (void*)d_kind})
+            if (q) les_hip_free(ctx_, q);
+        return ok;
+    }
+
     // CostVolumeEnergy::setInterpolationMethod (LES/CostVolumeEnergy.h:45-48): 0 nearest slice, 1 linear (the default), 2 quadratic.  Like the
     // reference's setter it is not synchronised with evaluations running on other threads.
     virtual void setInterpolationMethod(int none_lin_quad)

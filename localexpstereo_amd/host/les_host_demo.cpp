@@ -292,6 +292,20 @@ static int cmd_run(int argc, char** argv)
             tbad += !(wta[i].a == 0.f && wta[i].b == 0.f && wta[i].v == 0.f && std::isfinite(wta[i].c) && std::isfinite(wcost[i])) || memcmp(&wta[i], &wta2[i], sizeof(Plane)) != 0;
         printf("wtaLabels: %zu of %zu pixels are not a finite fronto-parallel plane or depend on the chunking\n", tbad, P);
         if (!okt || tbad) { printf("FAIL: wtaLabels\n"); fail = 1; }
+        // the planes fitted to that map through the adapter: every pixel a finite plane of its kind, from the labels and from their disparities alike
+        std::vector<Plane> fit(P), fit2(P);
+        std::vector<unsigned char> kind(P);
+        std::vector<float> wdisp(P);
+        for (size_t i = 0; i < P; i++) wdisp[i] = wta[i].c;            // (fronto-parallel planes: d = c)
+        const bool okf = hip.fitPlanes(wta.data(), nullptr, wta.data(), fit.data(), kind.data(), 0) && hip.fitPlanes(nullptr, wdisp.data(), wta.data(), fit2.data(), nullptr, 0);
+        size_t fbad = 0, slanted = 0;
+        for (size_t i = 0; i < P; i++) {
+            fbad += kind[i] > 2 || !(std::isfinite(fit[i].a) && std::isfinite(fit[i].b) && std::isfinite(fit[i].c)) || memcmp(&fit[i], &fit2[i], sizeof(Plane)) != 0 ||
+                    (kind[i] == 1 && !(fit[i].a == 0.f && fit[i].b == 0.f && fit[i].c == wta[i].c));
+            slanted += kind[i] == 2;
+        }
+        printf("fitPlanes: %zu of %zu pixels are not a finite plane of their kind or depend on the input form; %zu slanted fits\n", fbad, P, slanted);
+        if (!okf || fbad || !slanted) { printf("FAIL: fitPlanes\n"); fail = 1; }
     }
     printf(fail ? "les_host_demo: FAILED\n" : "les_host_demo: OK\n");
     return fail;

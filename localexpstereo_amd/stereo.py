@@ -36,6 +36,10 @@ class FastGCStereo:
         # pass), so the last row's `data` belongs to the labels it is logged with.  Off (the default, the reference's behaviour,
         # LES/FastGCStereo.h:205-206): that row reports the data term of the labels before the left-right check, fill and weighted median.
         self.recost_after_post = bool(recost_after_post)
+        # what every plane fit of this driver uses (fit_planes, run(labeling="wta+planes" / a disparity map), wta(slanted=True)): keywords of
+        # api.HipCostVolumeEnergy.fit_planes (radius, sig, gate0, gate_slope, max_slope, min_support); {}: its defaults
+        self.fit_params = {}
+        self.slant_stats = {}                     # run(labeling="wta+planes") / wta(slanted=True): view -> the runner's fuse report + kind_pixels [fallback, fronto, slanted]
         self.raw_labelings = {}                   # run(): view -> its H x W x 4 labelling before the post-processing (what a later run resumes from)
         self.random_vdisp = random_vdisp          # maxVDisp of the RANDOM proposals (pm.PMRunner); None: the energy's setting (0 by default)
         # Parameters::filterName: the energy aggregates with the filter it was built with; a params dict that names another one is a mistake
@@ -146,7 +150,11 @@ class FastGCStereo:
         start labelling (the reference's `labeling` argument; every view starts from it, as in the reference), or a dict {view: H x W x 4
         map} that gives each view of a two-view run its own (self.raw_labelings of an earlier run resumes it), or the string "wta": each view starts
         from the winner-take-all map of its own filtered cost volume (les_hip_wta_labels, csrc/les_wtavol.h; the map stays on the device; single
-        rank).  The costs of a start labelling come from one dense device pass per view (pm.PMRunner.init_from_labels)."""
+        rank).  A map that is H x W (alone or in the dict) is a disparity map: the view starts from the planes fitted to it (fit_planes:
+        les_hip_fit_planes, csrc/les_planefit.h; self.fit_params).  "wta+planes": the "wta" start, and right after begin_gc, before the first
+        graph-cut iteration, each view fuses the planes fitted to its WTA map (the WTA map is the fit's fallback) into its solution by fusion
+        moves (pm.PMRunner.fuse; the report goes to self.slant_stats; no map visits the host; with maxIteration == 0 the start is the WTA map
+        alone; single rank).  The costs of a start labelling come from one dense device pass per view (pm.PMRunner.init_from_labels)."""
         try:
             return self._run(maxIteration, viewModes, pmInit, labeling)
         finally:                 # the device evaluators of the run, also when it raised
@@ -191,6 +199,25 @@ class FastGCStereo:
             self._dev_eval = None
             runner.close()
             g.close()
+
+    def fit_planes(self, disp_or_labeling, viewMode=0, **params):
+        """Slanted planes from a disparity map (no reference counterpart; csrc/les_planefit.h): per pixel of view viewMode an edge-aware weighted
+        least-squares plane through the disparities of its window, guided by that view's image (api.HipCostVolumeEnergy.fit_planes).
+        disp_or_labeling: an H x W disparity map (a PFM file, another matcher, the previous frame) or an H x W x 4 label map, whose own
+        disparities are fitted.  Pixels without an accepted fit keep their own disparity as a fronto-parallel plane; non-finite or out-of-range
+        ones get (0, 0, min_disp, 0).  params: over self.fit_params (radius, sig, gate0, gate_slope, max_slope, min_support).
+        -> the H x W x 4 map, a start for run(labeling=) or a second labelling for fuse()."""
+        out = self.e.fit_planes(disp_or_labeling, mode=int(viewMode), device=self.device, **dict(self.fit_params, **params))
+        self.e.synchronize()
+        return out.cpu().numpy().copy()
+
+    def _fuse_fitted(self, runner, wta_map):
+        """A runner that is ready to cut (begin_gc) fuses the planes fitted to `wta_map` (a device map, also the fit's fallback) into its solution.
+        -> the runner's fuse report + kind_pixels: how many pixels of the fitted map are [fallback, fronto-parallel, slanted]"""
+        fitted, kind = self.e.fit_planes(wta_map, mode=runner.mode, fallback=wta_map, with_kind=True, device=self.device, **self.fit_params)
+        report = runner.fuse(fitted, nthreads=self.host_threads)
+        report["kind_pixels"] = torch.bincount(kind.flatten().to(torch.int64), minlength=3).tolist()
+        return report
 
     def _cross_view_step(self, runners, layers=None):
         """One cross-view step on two runners that are ready to cut (begin_gc): both label maps are snapshotted on the device, then each view fuses
@@ -237,7 +264,7 @@ class FastGCStereo:
                 r.close()
             g.close()
 
-    def wta(self, viewModes=(0,), post_process=True, subpixel=True):
+    def wta(self, viewModes=(0,), post_process=True, subpixel=True, slanted=False):
         """Cost-volume filtering without a graph cut (no reference counterpart; csrc/les_wtavol.h): every view of viewModes gets the winner-take-all
         map of its filtered cost volume -- per pixel the fronto-parallel plane of least aggregated cost, refined to sub-pixel when `subpixel`
         (les_hip_wta_labels: the H1 workload and a streaming arg-min over its slabs, a few milliseconds).  With an evaluator set, self.log gets one
@@ -245,13 +272,37 @@ class FastGCStereo:
         from the maps before any post-processing, through the device evaluator when evaluate_on_device (the host route has no pairwise sum without
         a graph-cut context: smooth is NaN there, as in run() before the first cut).  With two views and post_process, the left-right check, fill
         and weighted median of run() follow (threshold 1.5, the run's omega).  Sets self.raw_labelings.  Single rank.
+        slanted (opt-in; needs the layers of addLayer, it raises without): before the rows and the post-processing each view fuses the planes
+        fitted to its WTA map (les_hip_fit_planes, csrc/les_planefit.h; self.fit_params) into that map by fusion moves over every disjoint set of
+        the layers (pm.PMRunner.fuse); a pixel ends with its WTA label or its fitted one, and the costs of the rows are the dense re-scoring's.
+        The reports go to self.slant_stats.
         -> (labeling, rawlabeling) of the left view as run() does (None without the left view)."""
         if self.world > 1:
             raise NotImplementedError("FastGCStereo.wta is single-rank: the multi-rank form is not implemented")
         views = tuple(int(m) for m in viewModes)
         t0 = time.perf_counter()
         self.eval_seconds, self.log = 0.0, []
+        if slanted and not self.units:
+            raise ValueError("wta(slanted=True) fuses over the cells of the layers: add layers (addLayer) first")
         maps = {m: self.e.wta_labels(mode=m, subpixel=subpixel, device=self.device) for m in views}
+        if slanted:
+            self.slant_stats = {}
+            g = gc.GraphCut(self.imL, self.imR, lambda_=self.p["lambda_"], th_smooth=self.p["th_smooth"], omega=self.p["omega"], epsilon=self.p["epsilon"])
+            try:
+                for m in views:
+                    runner = pm.PMRunner(self.e, self.units, self.table, seed=self.seed + 7919 * m, device=self.device, mode=m, random_vdisp=self.random_vdisp)
+                    try:
+                        runner.init_from_labels(maps[m][0])
+                        if self.device_cuts is not None:
+                            runner.device_cuts = self.device_cuts
+                        runner.begin_gc(g, mode=m)
+                        self.slant_stats[m] = self._fuse_fitted(runner, maps[m][0])
+                        runner._sync()
+                        maps[m] = (runner.labels.clone(), runner.cur.clone())
+                    finally:
+                        runner.close()
+            finally:
+                g.close()
         self.e.synchronize()
         self.raw_labelings = {m: maps[m][0].cpu().numpy().copy() for m in views}
         if self.evaluator is not None:
@@ -302,10 +353,12 @@ class FastGCStereo:
 
     def _run(self, maxIteration, viewModes, pmInit, labeling):
         if isinstance(labeling, str):
-            if labeling != "wta":
-                raise ValueError(f"labeling {labeling!r}: a label map, a dict of them, or \"wta\"")
+            if labeling not in ("wta", "wta+planes"):
+                raise ValueError(f"labeling {labeling!r}: a label map, a disparity map, a dict of them, \"wta\" or \"wta+planes\"")
             if self.world > 1:
-                raise NotImplementedError("labeling=\"wta\" is single-rank: the multi-rank start is not implemented")
+                raise NotImplementedError(f"labeling=\"{labeling}\" is single-rank: the multi-rank start is not implemented")
+        with_planes = isinstance(labeling, str) and labeling == "wta+planes" and maxIteration > 0
+        wta_maps, self.slant_stats = {}, {}
         if self.inner_loop_log and self.world > 1:
             raise ValueError("inner_loop_log is a single-rank log: with several ranks a rank holds only its band of a set's cells until the exchange")
         if self.cross_view > 0:
@@ -347,7 +400,7 @@ class FastGCStereo:
         if self.inner_loop_log:
             for m in viewModes:
                 r = runners[m]
-                ev = api.DeviceEvaluator(self.e, max_rows=max(1, len(r.sets) * (maxIteration + pmInit + len(cross_after))), **(ev_args if m == 0 else {}))
+                ev = api.DeviceEvaluator(self.e, max_rows=max(1, len(r.sets) * (maxIteration + pmInit + len(cross_after) + int(with_planes))), **(ev_args if m == 0 else {}))
                 inner[m] = r.inner_log = SimpleNamespace(evaluator=ev, params=self._pairwise(), meta=[])
         g = gc.GraphCut(self.imL, self.imR, lambda_=self.p["lambda_"], th_smooth=self.p["th_smooth"], omega=self.p["omega"],
                         epsilon=self.p["epsilon"]) if maxIteration > 0 else None
@@ -355,11 +408,17 @@ class FastGCStereo:
             if labeling is None:
                 runners[m].init_labels()
             elif isinstance(labeling, str):
-                runners[m].init_from_labels(self.e.wta_labels(mode=m, device=self.device)[0])
+                wta_maps[m] = self.e.wta_labels(mode=m, device=self.device)[0]
+                runners[m].init_from_labels(wta_maps[m])
             else:
                 if isinstance(labeling, dict) and m not in labeling:
                     raise ValueError(f"labeling has no map for view {m} (views given: {sorted(labeling)})")
-                runners[m].init_from_labels(labeling[m] if isinstance(labeling, dict) else labeling)     # warm start (LES/FastGCStereo.h:116-130)
+                start = labeling[m] if isinstance(labeling, dict) else labeling
+                if not hasattr(start, "shape"):
+                    start = np.asarray(start, np.float32)
+                if len(start.shape) == 2:                  # a disparity map: the planes fitted to it, made on the device
+                    start = self.e.fit_planes(start, mode=m, device=self.device, **self.fit_params)
+                runners[m].init_from_labels(start)         # warm start (LES/FastGCStereo.h:116-130)
             self._evaluate(0, m, runners[m], None, t0)
         # the reference starts its clock HERE -- START_TIMER after initCurrentFast and the first evaluation (LES/FastGCStereo.h:135-141),
         # with the layers (addLayer, LES/main.cpp:395-397) and the energy built before run() -- `seconds` below keeps counting from the top
@@ -376,6 +435,8 @@ class FastGCStereo:
                 if self.device_cuts is not None:
                     runners[m].device_cuts = self.device_cuts
                 runners[m].begin_gc(g, mode=m)
+                if with_planes:
+                    self.slant_stats[m] = self._fuse_fitted(runners[m], wta_maps[m])
             main_device = torch.cuda.current_device() if torch.device(self.device).type == "cuda" else 0
 
             def one_view(m, it, nthreads=None):
@@ -519,7 +580,8 @@ def MidV2(data, iterations=5, pmIterations=2, doDual=False, smooth_weight=None, 
     vdisp: the vertical-disparity range of the energy (MAX_VDISPARITY, :281): initial labels draw v in [-vdisp, vdisp].  As in main.cpp
     the random proposer keeps range 0 (RandomProposer(7, maxdisp)); random_vdisp (opt-in, not in main.cpp) gives it its own maxVDisp.
     init: the start labelling of run() -- None (the default): the reference's random start; "wta": every view starts from the winner-take-all
-    map of its filtered cost volume (FastGCStereo.run's labeling="wta").
+    map of its filtered cost volume (FastGCStereo.run's labeling="wta"); "wta+planes": that start, and the slanted planes fitted to it are fused
+    in before the first graph-cut iteration (labeling="wta+planes").
     Further keywords go to FastGCStereo (cross_view=n with doDual: cross-view fusion after every n-th graph-cut iteration)."""
     p = dict(PARAMS_GF if params is None else params)
     lam = p["lambda_"] if smooth_weight is None else smooth_weight
@@ -544,7 +606,7 @@ def MidV3(data, volL=None, volR=None, iterations=5, pmIterations=2, doDual=False
     (default) or PARAMS_BF: filter and eps; smooth_weight, mc_threshold and filterRadious override lambda_, th_col and windR (:351-353).
     interpolate: the energy's setInterpolationMethod (LES/CostVolumeEnergy.h:45-48) -- 0 nearest, 1 linear (default), 2 quadratic.
     volL None: no volume files -- both views' AD-Census volumes (io.build_volumes; lambda_ad, lambda_census) are built on the device from
-    data["imL"], data["imR"] and data["ndisp"].  init: as for MidV2 (None: the random start; "wta": the winner-take-all start).  Further keywords go to FastGCStereo (cross_view=n with doDual: cross-view fusion after every
+    data["imL"], data["imR"] and data["ndisp"].  init: as for MidV2 (None: the random start; "wta": the winner-take-all start; "wta+planes": with its fitted planes fused in).  Further keywords go to FastGCStereo (cross_view=n with doDual: cross-view fusion after every
     n-th graph-cut iteration)."""
     p = dict(PARAMS_GF if params is None else params)
     maxdisp = float(data["ndisp"] - 1)
