@@ -446,6 +446,31 @@ int les_hip_slab_argmin_finish(les_hip_ctx* ctx, const void* d_state, int K, int
  * other entry points may run beside it on other threads. */
 int les_hip_wta_labels(les_hip_ctx* ctx, int mode, int chunk, int subpixel, les_hip_plane* d_labels, float* d_cost);
 
+/* ---- semi-global matching over a view's matching-cost volume (csrc/les_sgm.h holds the definition) ----
+ * No reference counterpart (as above).  The classic step between local aggregation and a global graph cut: scan-line dynamic programming over the
+ * RAW volume of view `mode` (float [D][H][W], slice k = disparity min_disparity + k; K = int(max_disparity - min_disparity) + 1 slices are
+ * used, K <= D) along the first `paths` (2, 4 or 8) of the directions (+1,0) (-1,0) (0,+1) (0,-1) (+1,+1) (-1,-1) (-1,+1) (+1,-1).  Costs are
+ * truncated first: C' = C where C is finite and below th_col, else th_col.  Along direction r, with q = p - r: L(p,k) = C'(p,k) where q lies
+ * outside the image, else C'(p,k) + (min(L(q,k), min(L(q,k-1), L(q,k+1)) + p1, m + p2) - m) with m = min_j L(q,j) and only the neighbours that
+ * exist.  S = ((L_0 + L_1) + L_2) + ... in direction order, all in f32, a function of the inputs only (no atomics; the directions are successive
+ * launches).  The read-out over S(p, 0..K-1) is les_hip_wta_labels' rule: the first minimum wins, the parabola offset when subpixel != 0;
+ * label (0, 0, (k* + off) + min_disparity, 0) into d_labels (H x W planes), S(p,k*) into d_sum (H x W floats; may be NULL).
+ * A view that was not supplied at creation, a null d_labels, paths outside {2, 4, 8}, a negative or non-finite penalty, p2 < p1, a non-finite
+ * th_col, K > D: LES_HIP_ERR_ARG.  A context of the image-based energy (it holds no volume), K > 512, H > 65535: LES_HIP_ERR_UNSUPPORTED.
+ * Nothing is launched and nothing written in either case.
+ * The workspace -- the transposed volume and S, 2 H W Kp floats with Kp = K rounded up to 64, 128, 256 or 512: les_hip_sgm_workspace_bytes for the
+ * current disparity range, 0 where les_hip_sgm_labels would refuse the context -- belongs to the context: built by the first call, regrown when the
+ * disparity range grows (hipMalloc: an implicit synchronisation), freed by les_hip_destroy.  Otherwise enqueue only, on the calling thread's stream
+ * (les_hip_set_thread_stream is honoured).  ONE host thread and ONE stream at a time may use this on a context (the two views one after the other):
+ * the calls share the workspace and nothing orders them across streams, so a call on another stream than the context's last SGM call must follow a
+ * synchronisation of that one.  Other entry points may run beside it on other threads.
+ * LES_HIP_SGM_TIMING=1 (read per call): the call brackets its kernels with events and waits for the last; les_hip_sgm_last_times then gives the
+ * calling thread the device milliseconds of its last call: *n = paths + 2 values (transpose, one per direction, read-out), the first min(*n, cap)
+ * of them into ms.  LES_HIP_ERR_ARG when the thread has made no such call. */
+size_t les_hip_sgm_workspace_bytes(const les_hip_ctx* ctx);
+int les_hip_sgm_labels(les_hip_ctx* ctx, int mode, int paths, float p1, float p2, int subpixel, les_hip_plane* d_labels, float* d_sum /* may be NULL */);
+int les_hip_sgm_last_times(float* ms, int cap, int* n);
+
 /* ---- slanted planes fitted to a disparity map (csrc/les_planefit.h holds the definition) ----
  * No reference counterpart: the reference's only start is one random plane per finest-layer cell (initCurrentFast, LES/FastGCStereo.h:94-115).
  * Per pixel p of view `mode` an edge-aware weighted least-squares plane through the disparities of its (2 radius + 1)^2 window: the input is

@@ -29,6 +29,7 @@ SYMBOLS = [
     "les_hip_costvol_tables", "les_hip_census", "les_hip_build_cost_volume", "les_hip_costvol_last_times",
     "les_hip_warp_labels",
     "les_hip_slab_argmin_state_bytes", "les_hip_slab_argmin", "les_hip_slab_argmin_finish", "les_hip_wta_labels",
+    "les_hip_sgm_workspace_bytes", "les_hip_sgm_labels", "les_hip_sgm_last_times",
     "les_hip_fit_planes",
 ]
 
@@ -179,6 +180,9 @@ def load(path=None):
         "les_hip_slab_argmin": (ci, [vp, vp, ci, ci, vp]),
         "les_hip_slab_argmin_finish": (ci, [vp, vp, ci, ci, vp, vp]),
         "les_hip_wta_labels": (ci, [vp, ci, ci, ci, vp, vp]),
+        "les_hip_sgm_workspace_bytes": (C.c_size_t, [vp]),
+        "les_hip_sgm_labels": (ci, [vp, ci, ci, C.c_float, C.c_float, ci, vp, vp]),
+        "les_hip_sgm_last_times": (ci, [C.POINTER(C.c_float), ci, C.POINTER(ci)]),
         "les_hip_fit_planes": (ci, [vp, ci, vp, vp, vp, vp, vp, ci, C.c_float, C.c_float, C.c_float, C.c_float, ci]),
     }
     for name, (res, args) in sig.items():
@@ -754,6 +758,45 @@ class HipCostVolumeEnergy:
         self._chk(self.L.les_hip_wta_labels(self.h, int(mode), int(chunk), int(bool(subpixel)), C.c_void_p(int(labels_ptr)) if labels_ptr else None,
                                             C.c_void_p(int(cost_ptr)) if cost_ptr else None))
         return out
+
+    # -- semi-global matching over the view's own cost volume (csrc/les_sgm.h; no reference counterpart) -------------------
+    def sgm_workspace_bytes(self):
+        """les_hip_sgm_workspace_bytes: the bytes sgm_labels keeps on the context for the current disparity range (the transposed volume and the
+        path sums, 2 H W Kp floats); 0 where sgm_labels would refuse the context."""
+        return int(self.L.les_hip_sgm_workspace_bytes(self.h))
+
+    def sgm_penalties(self, p1=None, p2=None):
+        """The penalties sgm_labels uses: P1 = 0.16 th_col and P2 = 1.28 th_col where None (as float32)."""
+        th = np.float32(self.params.th_col)
+        return (np.float32(0.16) * th if p1 is None else np.float32(p1)), (np.float32(1.28) * th if p2 is None else np.float32(p2))
+
+    def sgm_labels(self, mode=0, paths=8, p1=None, p2=None, subpixel=True, labels_ptr=None, cost_ptr=None, device=None):
+        """les_hip_sgm_labels: semi-global matching over the raw cost volume of view `mode` -- the costs truncated at th_col, scan-line dynamic
+        programming along the first `paths` (2, 4 or 8) directions with penalties p1 <= p2 (None: 0.16 th_col and 1.28 th_col), summed, read out per
+        pixel as wta_labels does (first minimum, parabola offset when `subpixel`) -- as the label map (0, 0, k* + off + min_disp, 0) and the summed
+        path cost S(p, k*) of the winner (NOT the energy's unary cost).  Not for the image-based energy (error 3).  Asynchronous on the calling
+        thread's stream once the context's workspace exists.  With labels_ptr (device address of the H x W x 4 float map; cost_ptr: the H x W float
+        map or None) it writes there and returns None; without it returns (labels, cost) as new torch tensors on `device` (None: this context's
+        GPU; the simulator build takes "cpu")."""
+        if labels_ptr is None and cost_ptr is not None:
+            raise ValueError("sgm_labels: cost_ptr without labels_ptr")
+        p1, p2 = self.sgm_penalties(p1, p2)
+        out = None
+        if labels_ptr is None:
+            import torch
+            dev = torch.device(device if device is not None else f"cuda:{self.params.device}")
+            out = (torch.empty((self.H, self.W, 4), dtype=torch.float32, device=dev), torch.empty((self.H, self.W), dtype=torch.float32, device=dev))
+            labels_ptr, cost_ptr = out[0].data_ptr(), out[1].data_ptr()
+        self._chk(self.L.les_hip_sgm_labels(self.h, int(mode), int(paths), C.c_float(p1), C.c_float(p2), int(bool(subpixel)),
+                                            C.c_void_p(int(labels_ptr)) if labels_ptr else None, C.c_void_p(int(cost_ptr)) if cost_ptr else None))
+        return out
+
+    def sgm_last_times(self):
+        """les_hip_sgm_last_times: the device milliseconds of this thread's last sgm_labels under LES_HIP_SGM_TIMING=1 -- [transpose, one per
+        direction ..., read-out]."""
+        ms, n = (C.c_float * 10)(), C.c_int(0)
+        self._chk(self.L.les_hip_sgm_last_times(ms, 10, C.byref(n)))
+        return [float(ms[i]) for i in range(min(n.value, 10))]
 
     # -- slanted planes fitted to a disparity map (csrc/les_planefit.h; no reference counterpart) --------------------------
     def fit_planes_ptr(self, mode, labels_ptr, disp_ptr, fallback_ptr, out_ptr, kind_ptr=None, **params):

@@ -129,6 +129,8 @@ void les_hip_destroy(les_hip_ctx* c)
     c->mt_idle.clear();
     wtavol_free(c->wtavol);                                     // (its batches go before the context they were prepared on)
     c->wtavol = nullptr;
+    sgm_free(c->sgm);
+    c->sgm = nullptr;
     fit_tables_free(c->fit_tables);
     c->fit_tables = nullptr;
     delete c;                                                   // the views' buffers and every owned table

@@ -112,6 +112,30 @@ __device__ inline uint32_t ballot_low(bool f, int n)
 __device__ inline int sbfe1(uint32_t w, int bit) { return -(int)((w >> bit) & 1u); }
 // one 16-byte LDS store
 __device__ inline void lds_store4(int4* p, int x, int y, int z, int w) { *p = int4{x, y, z, w}; }
+// ---- primitives of the scan-line recurrence (les_sgm.h); every lane of the wave must call them
+// minimum over the 64 lanes of the wave; the operands are finite (no NaN handling).  Every lane gets the same VALUE; where the minimum is a zero
+// its sign is not defined (the lanes may differ in it): callers add +0.0f
+__device__ inline float wave_min_finite(float v)
+{
+    for (int m = 1; m < 64; m <<= 1) {
+        const float o = hipsim::wave_xor(v, m);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+// value of v in lane l - 1 (lane 0 gets fill) / in lane l + 1 (lane 63 gets fill)
+__device__ inline float wave_from_lower(float v, float fill)
+{
+    const int l = hipsim::g_block->current & 63;
+    const int r = hipsim::wave_readlane(__float_as_int(v), l > 0 ? l - 1 : 0);
+    return l > 0 ? __int_as_float(r) : fill;
+}
+__device__ inline float wave_from_upper(float v, float fill)
+{
+    const int l = hipsim::g_block->current & 63;
+    const int r = hipsim::wave_readlane(__float_as_int(v), l < 63 ? l + 1 : 63);
+    return l < 63 ? __int_as_float(r) : fill;
+}
 
 #else
 
@@ -314,6 +338,36 @@ __device__ __forceinline__ void lds_store4(int4* p, int x, int y, int z, int w)
 }
 __device__ __forceinline__ float fmin3(float a, float b, float c) { return __builtin_fminf(__builtin_fminf(a, b), c); }    // folds to v_min3_f32
 __device__ __forceinline__ float fmax3(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
+// ---- primitives of the scan-line recurrence (les_sgm.h); every lane of the wave must call them
+// One step of a DPP reduction: lanes the control gives no source lane keep their own value (old = v, bound_ctrl off), and min(v, v) = v
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ float dpp_min_step(float v)
+{
+    const float o = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
+    return o < v ? o : v;
+}
+// minimum over the 64 lanes of the wave; the operands are finite (no NaN handling).  Every lane gets the same VALUE; where the minimum is a zero
+// its sign is not defined: callers add +0.0f.  quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror: every lane holds its row's minimum;
+// row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3: lane 63 holds the wave's, read back as a scalar
+__device__ __forceinline__ float wave_min_finite(float v)
+{
+    v = dpp_min_step<0xB1, 0xf>(v);
+    v = dpp_min_step<0x4E, 0xf>(v);
+    v = dpp_min_step<0x141, 0xf>(v);
+    v = dpp_min_step<0x140, 0xf>(v);
+    v = dpp_min_step<0x142, 0xa>(v);
+    v = dpp_min_step<0x143, 0xc>(v);
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
+// value of v in lane l - 1 (lane 0 gets fill) / in lane l + 1 (lane 63 gets fill): wave_shr:1 / wave_shl:1, lanes without a source keep `old`
+__device__ __forceinline__ float wave_from_lower(float v, float fill)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v), 0x138, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float wave_from_upper(float v, float fill)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v), 0x130, 0xf, 0xf, false));
+}
 
 #endif
 

@@ -42,6 +42,18 @@ __host__ __device__ __forceinline__ size_t argmin_plane_words(size_t P) { return
 
 __device__ __forceinline__ bool argmin_finite(float f) { return (__float_as_uint(f) & 0x7f800000u) != 0x7f800000u; }
 
+// the parabola offset of the winner ks of K costs: c0 its cost, cm / cp the costs of slabs ks - 1 / ks + 1 (read only when they exist); also the
+// read-out of les_sgm.h
+__device__ __forceinline__ float argmin_offset(int ks, int K, int subpixel, float c0, float cm, float cp)
+{
+    float off = 0.0f;
+    if (subpixel && ks > 0 && ks < K - 1 && argmin_finite(cm) && argmin_finite(cp)) {
+        const float den = (cm - c0) + (cp - c0);
+        if (den > 0.0f) off = 0.5f * (cm - cp) / den;
+    }
+    return off;
+}
+
 // slab g (counted over the whole volume) offers cost c to a pixel
 __device__ __forceinline__ void argmin_take(float c, int g, float& best, int& ks, float& cm, float& cp, float& prev)
 {
@@ -137,11 +149,7 @@ les_slab_argmin_finish_kernel(const float* __restrict__ state, size_t P, int K, 
         cost[i] = __builtin_inff();
         return;
     }
-    float off = 0.0f;
-    if (subpixel && ks > 0 && ks < K - 1 && argmin_finite(cm) && argmin_finite(cp)) {
-        const float den = (cm - c0) + (cp - c0);
-        if (den > 0.0f) off = 0.5f * (cm - cp) / den;
-    }
+    const float off = argmin_offset(ks, K, subpixel, c0, cm, cp);
     labels[i] = make_float4(0.0f, 0.0f, ((float)ks + off) + d0, 0.0f);
     cost[i] = c0;
 }

@@ -39,6 +39,8 @@ class FastGCStereo:
         # what every plane fit of this driver uses (fit_planes, run(labeling="wta+planes" / a disparity map), wta(slanted=True)): keywords of
         # api.HipCostVolumeEnergy.fit_planes (radius, sig, gate0, gate_slope, max_slope, min_support); {}: its defaults
         self.fit_params = {}
+        # what the "sgm" / "sgm+planes" starts of run() use: keywords of api.HipCostVolumeEnergy.sgm_labels (paths, p1, p2, subpixel); {}: its defaults
+        self.sgm_params = {}
         self.slant_stats = {}                     # run(labeling="wta+planes") / wta(slanted=True): view -> the runner's fuse report + kind_pixels [fallback, fronto, slanted]
         self.raw_labelings = {}                   # run(): view -> its H x W x 4 labelling before the post-processing (what a later run resumes from)
         self.random_vdisp = random_vdisp          # maxVDisp of the RANDOM proposals (pm.PMRunner); None: the energy's setting (0 by default)
@@ -154,7 +156,8 @@ class FastGCStereo:
         les_hip_fit_planes, csrc/les_planefit.h; self.fit_params).  "wta+planes": the "wta" start, and right after begin_gc, before the first
         graph-cut iteration, each view fuses the planes fitted to its WTA map (the WTA map is the fit's fallback) into its solution by fusion
         moves (pm.PMRunner.fuse; the report goes to self.slant_stats; no map visits the host; with maxIteration == 0 the start is the WTA map
-        alone; single rank).  The costs of a start labelling come from one dense device pass per view (pm.PMRunner.init_from_labels)."""
+        alone; single rank).  "sgm" / "sgm+planes": the same two starts from the semi-global matching map of each view's own raw cost volume
+        (les_hip_sgm_labels, csrc/les_sgm.h; self.sgm_params; not for the image-based energy: ValueError).  The costs of a start labelling come from one dense device pass per view (pm.PMRunner.init_from_labels)."""
         try:
             return self._run(maxIteration, viewModes, pmInit, labeling)
         finally:                 # the device evaluators of the run, also when it raised
@@ -277,14 +280,35 @@ class FastGCStereo:
         the layers (pm.PMRunner.fuse); a pixel ends with its WTA label or its fitted one, and the costs of the rows are the dense re-scoring's.
         The reports go to self.slant_stats.
         -> (labeling, rawlabeling) of the left view as run() does (None without the left view)."""
+        return self._volume_maps("wta", viewModes, post_process, slanted, lambda m: self.e.wta_labels(mode=m, subpixel=subpixel, device=self.device))
+
+    def _sgm_map(self, m, **params):
+        """View m's SGM label map and the unary costs of its labels (one dense device pass: the summed path cost is not the energy's unary cost),
+        both on the device."""
+        lab, cost = self.e.sgm_labels(mode=m, device=self.device, **params)
+        self.e.unary_labels(lab.data_ptr(), cost.data_ptr(), mode=m, check=True)
+        return lab, cost
+
+    def sgm(self, viewModes=(0,), paths=8, p1=None, p2=None, post_process=True, subpixel=True, slanted=False):
+        """Semi-global matching without a graph cut (no reference counterpart; csrc/les_sgm.h), the twin of wta(): every view of viewModes gets the
+        SGM map of its own RAW cost volume -- the costs truncated at th_col, scan-line dynamic programming along `paths` (2, 4 or 8) directions
+        with the penalties p1 <= p2 (None: 0.16 th_col and 1.28 th_col), summed, read out per pixel as wta() does (les_hip_sgm_labels).  The rows of
+        self.log, the two-view post-processing, `slanted`, self.raw_labelings, self.slant_stats and the return value are wta()'s; the costs of the
+        rows are the dense re-scoring of the labels (the summed path cost is not the energy's unary cost).  Not for the image-based energy
+        (api.LesHipError, error 3: it holds no volume).  Single rank."""
+        return self._volume_maps("sgm", viewModes, post_process, slanted, lambda m: self._sgm_map(m, paths=paths, p1=p1, p2=p2, subpixel=subpixel))
+
+    def _volume_maps(self, what, viewModes, post_process, slanted, make_map):
+        """The body wta() and sgm() share: make_map(view) -> (labels, costs) on the device; then the optional fusion of the fitted planes, the rows,
+        the two-view post-processing."""
         if self.world > 1:
-            raise NotImplementedError("FastGCStereo.wta is single-rank: the multi-rank form is not implemented")
+            raise NotImplementedError(f"FastGCStereo.{what} is single-rank: the multi-rank form is not implemented")
         views = tuple(int(m) for m in viewModes)
         t0 = time.perf_counter()
         self.eval_seconds, self.log = 0.0, []
         if slanted and not self.units:
-            raise ValueError("wta(slanted=True) fuses over the cells of the layers: add layers (addLayer) first")
-        maps = {m: self.e.wta_labels(mode=m, subpixel=subpixel, device=self.device) for m in views}
+            raise ValueError(f"{what}(slanted=True) fuses over the cells of the layers: add layers (addLayer) first")
+        maps = {m: make_map(m) for m in views}
         if slanted:
             self.slant_stats = {}
             g = gc.GraphCut(self.imL, self.imR, lambda_=self.p["lambda_"], th_smooth=self.p["th_smooth"], omega=self.p["omega"], epsilon=self.p["epsilon"])
@@ -353,11 +377,14 @@ class FastGCStereo:
 
     def _run(self, maxIteration, viewModes, pmInit, labeling):
         if isinstance(labeling, str):
-            if labeling not in ("wta", "wta+planes"):
-                raise ValueError(f"labeling {labeling!r}: a label map, a disparity map, a dict of them, \"wta\" or \"wta+planes\"")
+            if labeling not in ("wta", "wta+planes", "sgm", "sgm+planes"):
+                raise ValueError(f"labeling {labeling!r}: a label map, a disparity map, a dict of them, \"wta\", \"wta+planes\", \"sgm\" or \"sgm+planes\"")
+            if labeling.startswith("sgm") and self.e.sgm_workspace_bytes() == 0:
+                raise ValueError(f"labeling=\"{labeling}\": semi-global matching runs over a cost volume of at most 512 disparities; this energy (the image-based "
+                                 "one holds no volume) has none it can use")
             if self.world > 1:
                 raise NotImplementedError(f"labeling=\"{labeling}\" is single-rank: the multi-rank start is not implemented")
-        with_planes = isinstance(labeling, str) and labeling == "wta+planes" and maxIteration > 0
+        with_planes = isinstance(labeling, str) and labeling.endswith("+planes") and maxIteration > 0
         wta_maps, self.slant_stats = {}, {}
         if self.inner_loop_log and self.world > 1:
             raise ValueError("inner_loop_log is a single-rank log: with several ranks a rank holds only its band of a set's cells until the exchange")
@@ -408,7 +435,8 @@ class FastGCStereo:
             if labeling is None:
                 runners[m].init_labels()
             elif isinstance(labeling, str):
-                wta_maps[m] = self.e.wta_labels(mode=m, device=self.device)[0]
+                wta_maps[m] = (self.e.sgm_labels(mode=m, device=self.device, **self.sgm_params) if labeling.startswith("sgm")
+                               else self.e.wta_labels(mode=m, device=self.device))[0]
                 runners[m].init_from_labels(wta_maps[m])
             else:
                 if isinstance(labeling, dict) and m not in labeling:
@@ -581,8 +609,11 @@ def MidV2(data, iterations=5, pmIterations=2, doDual=False, smooth_weight=None, 
     the random proposer keeps range 0 (RandomProposer(7, maxdisp)); random_vdisp (opt-in, not in main.cpp) gives it its own maxVDisp.
     init: the start labelling of run() -- None (the default): the reference's random start; "wta": every view starts from the winner-take-all
     map of its filtered cost volume (FastGCStereo.run's labeling="wta"); "wta+planes": that start, and the slanted planes fitted to it are fused
-    in before the first graph-cut iteration (labeling="wta+planes").
+    in before the first graph-cut iteration (labeling="wta+planes").  "sgm" / "sgm+planes" (MidV3's semi-global matching starts) raise ValueError
+    here: MidV2 uses the image-based energy, which holds no cost volume to run them over.
     Further keywords go to FastGCStereo (cross_view=n with doDual: cross-view fusion after every n-th graph-cut iteration)."""
+    if isinstance(init, str) and init.startswith("sgm"):
+        raise ValueError(f"MidV2(init={init!r}): MidV2 uses the image-based energy, which holds no cost volume; semi-global matching runs over one (MidV3)")
     p = dict(PARAMS_GF if params is None else params)
     lam = p["lambda_"] if smooth_weight is None else smooth_weight
     maxdisp = float(data["ndisp"] - 1)
@@ -606,7 +637,7 @@ def MidV3(data, volL=None, volR=None, iterations=5, pmIterations=2, doDual=False
     (default) or PARAMS_BF: filter and eps; smooth_weight, mc_threshold and filterRadious override lambda_, th_col and windR (:351-353).
     interpolate: the energy's setInterpolationMethod (LES/CostVolumeEnergy.h:45-48) -- 0 nearest, 1 linear (default), 2 quadratic.
     volL None: no volume files -- both views' AD-Census volumes (io.build_volumes; lambda_ad, lambda_census) are built on the device from
-    data["imL"], data["imR"] and data["ndisp"].  init: as for MidV2 (None: the random start; "wta": the winner-take-all start; "wta+planes": with its fitted planes fused in).  Further keywords go to FastGCStereo (cross_view=n with doDual: cross-view fusion after every
+    data["imL"], data["imR"] and data["ndisp"].  init: as for MidV2 (None: the random start; "wta": the winner-take-all start; "wta+planes": with its fitted planes fused in), and "sgm" / "sgm+planes": every view starts from the semi-global matching map of its own raw volume (FastGCStereo.run's labeling="sgm" / "sgm+planes"; csrc/les_sgm.h).  Further keywords go to FastGCStereo (cross_view=n with doDual: cross-view fusion after every
     n-th graph-cut iteration)."""
     p = dict(PARAMS_GF if params is None else params)
     maxdisp = float(data["ndisp"] - 1)
