@@ -85,8 +85,15 @@ class _Shard:
         self.xchg = api.Exchange(e, rank, [tgt[cells[bounds[r]:bounds[r + 1]]] for r in range(world)]) if world > 1 else None
 
 
+def disparities(labels):
+    """The disparity map of an H x W x 4 label map, on its device."""
+    H, W = labels.shape[:2]
+    ys, xs = torch.meshgrid(torch.arange(H, device=labels.device, dtype=torch.float32), torch.arange(W, device=labels.device, dtype=torch.float32), indexing="ij")
+    return labels[..., 0] * xs + labels[..., 1] * ys + labels[..., 2]
+
+
 class PMRunner:
-    def __init__(self, energy, layer_units, proposer_table, seed=1, rank=0, world=1, device="cuda", mode=0, group=None, random_vdisp=None):
+    def __init__(self, energy, layer_units, proposer_table, seed=1, rank=0, world=1, device="cuda", mode=0, group=None, random_vdisp=None, device_cuts=None):
         """rank / world: this process's place among the ranks that share THIS view's cells; group: their torch.distributed process group
         (None = the default group).  Two-view runs on several ranks give each view its own group (stereo.FastGCStereo.run).
         random_vdisp: maxVDisp of the RANDOM proposals (RandomProposer(K, maxDisp, minDisp, maxVDisp)); None leaves the energy's setting."""
@@ -126,8 +133,8 @@ class PMRunner:
         self.exchanges = 0                       # all-gathers issued
         self._xevents = []
         self._xbuf = None                        # send / receive slots of the tile exchange: single-rank runs never exchange
-        # the two switches a caller may set between construction and begin_gc
-        self.device_cuts = None                  # None | True | False | "all" | "fine" | "none": see begin_gc, which replaces it by one of the three names
+        # the two switches a caller may set between construction and begin_gc (device_cuts: or give it here)
+        self.device_cuts = device_cuts           # None | True | False | "all" | "fine" | "none": see begin_gc, which replaces it by one of the three names
         self.speculative_sets_on_cpu = False     # tests: take _gc_set_without_round_trips on the simulator too
         # graph-cut state: set by begin_gc; the buffers are sized from all shards and allocated by the first lock-step that needs them
         # (runs without graph-cut iterations, or with every cut on the device, never do)
@@ -707,9 +714,7 @@ class PMRunner:
         return self.labels, self.cur
 
     def disparities(self):
-        ys, xs = torch.meshgrid(torch.arange(self.H, device=self.device, dtype=torch.float32),
-                                torch.arange(self.W, device=self.device, dtype=torch.float32), indexing="ij")
-        return self.labels[..., 0] * xs + self.labels[..., 1] * ys + self.labels[..., 2]
+        return disparities(self.labels)
 
     def close(self):
         for lk in self._joint.values():

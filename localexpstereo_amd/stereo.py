@@ -1,10 +1,13 @@
 """Python driver of the whole local expansion loop around the GPU path (mirror of FastGCStereo / PMStereoBase,
 LES/FastGCStereo.h:88-227, LES/PMStereoBase.h) and of the two data-set front ends MidV2 / MidV3 (LES/main.cpp:270-420).
 
-What runs where: proposals, unary costs, winner-take-all updates, post-processing -> MI355X through the C ABI
-(liblocalexp_hip.so); graph cuts of the main iterations -> host cores (liblocalexp_host.so); file formats and the
-Evaluator -> numpy (io.py).  One process per GPU: pass rank/world to shard the cells of every disjoint set.
+What runs where: proposals, unary costs, winner-take-all updates, graph construction, the graph cuts of the main iterations and of the
+fusion moves, post-processing -> MI355X through the C ABI (liblocalexp_hip.so); the host cores (liblocalexp_host.so) cut only what device_cuts
+leaves to them ("fine" / "none", the simulator build) or the device solvers hand over, and serve check_flow_energy=True; file formats and the
+Evaluator -> numpy (io.py), or the device evaluator (evaluate_on_device).  One process per GPU: pass rank/world to shard the cells of every
+disjoint set.
 """
+import contextlib
 import os
 import time
 from types import SimpleNamespace
@@ -50,7 +53,7 @@ class FastGCStereo:
         self.device, self.rank, self.world, self.seed = device, rank, world, seed
         self.units, self.table = [], []
         self.evaluator = None
-        self._dev_eval, self._inner = None, {}      # run(): the device evaluators of the log rows / per view of the inner-loop log
+        self._dev_eval, self._inner = None, {}      # set by run() / fuse(), open while they work: the device evaluators of the log rows / per view of the inner-loop log
         self.log = []
         # the reference's flow == energy self-check (LES/FastGCStereo.h:561-594).  True: the iteration moves to the host route (host maps, host graph
         # construction, host cuts: what the reference does).  "device": it stays on the device path -- device graphs, device cuts, the region energies of
@@ -107,44 +110,77 @@ class FastGCStereo:
     def setEvaluator(self, evaluator, precision=-1.0):
         self.evaluator, self.precision = evaluator, precision
 
+    def _pairwise(self):
+        return dict(lambda_=float(self.p["lambda_"]), th_smooth=float(self.p["th_smooth"]), omega=float(self.p["omega"]), epsilon=float(self.p["epsilon"]))
+
+    # -- what every entry point makes: each registers with the caller's contextlib.ExitStack, which closes it also when the call raises
+    def _runner(self, stack, m, **ranks):
+        """View m's runner.  The views' seeds are 7919 apart; every runner gets random_vdisp (pm.PMRunner sets the energy's setting from it).
+        ranks: rank, world, group of the ranks that share this view's cells."""
+        return stack.enter_context(contextlib.closing(pm.PMRunner(self.e, self.units, self.table, seed=self.seed + 7919 * m, device=self.device, mode=m,
+                                                                  random_vdisp=self.random_vdisp, device_cuts=self.device_cuts, **ranks)))
+
+    def _graph_cut(self, stack):
+        return stack.enter_context(contextlib.closing(gc.GraphCut(self.imL, self.imR, **self._pairwise())))
+
+    def _eval_args(self):
+        """The evaluator as keywords of api.DeviceEvaluator ({}: no ground truth, the rows carry the energy only)."""
+        return {} if self.evaluator is None else dict(dispGT=self.evaluator.gt, nonocc=self.evaluator.nonocc, error_threshold=self.evaluator.threshold, precision=self.precision)
+
+    def _device_evaluator(self, stack, max_rows, rates=True):
+        return stack.enter_context(contextlib.closing(api.DeviceEvaluator(self.e, max_rows=max_rows, **(self._eval_args() if rates else {}))))
+
+    def _start(self, runner, start):
+        """The first half of ready to cut.  None: the reference's random start; else the warm start (LES/FastGCStereo.h:116-130) from a host or device map."""
+        if start is None:
+            runner.init_labels()
+        else:
+            runner.init_from_labels(start)
+
+    def _ready_to_cut(self, runner, start, g):
+        """Both halves: the runner starts from `start` and begins its cuts on g.  (run() has its PatchMatch iterations between the two.)"""
+        self._start(runner, start)
+        runner.begin_gc(g)
+        return runner
+
+    def _row(self, labels, cost, mode, index, t0, g=None, ev=None, rates=True):
+        """Evaluator::evaluate (LES/Evaluator.h:113-187) of a view's device maps -> the row of the log.  ev: the api.DeviceEvaluator of the device
+        route; None: the host route, whose sums are those of the host graph-cut context g (None, before the first cut: no pairwise sum, smooth is
+        NaN).  rates: the row carries all / nonocc (the ground truth is the left view's)."""
+        row = dict(index=index, time=time.perf_counter() - t0 - self.eval_seconds)
+        if ev is not None:
+            ev.evaluate(labels.data_ptr(), cost.data_ptr(), mode=mode, index=index, **self._pairwise())
+            r = ev.rows()[-1]
+            row.update(energy=r["data"] + r["smooth"], data=r["data"], smooth=r["smooth"])
+            if rates:
+                row["all"], row["nonocc"] = r["all"], r["nonocc"]
+            return row
+        d = pm.disparities(labels).cpu().numpy() if rates else None
+        if g is not None:
+            g.labels[mode][...], g.costs[mode][...] = labels.cpu().numpy(), cost.cpu().numpy()
+            dc, sc = g.data_cost(mode), g.smoothness_cost(mode)
+        else:
+            dc, sc = float(cost.sum(dtype=torch.float64)), float("nan")
+        row.update(energy=dc + (0.0 if sc != sc else sc), data=dc, smooth=sc)
+        if rates:
+            if self.precision > 0:                                         # Evaluator::quantize, LES/Evaluator.h:106-111
+                d = (np.rint(d / np.float32(self.precision)) * np.float32(self.precision)).astype(np.float32)
+            row["all"], row["nonocc"] = self.evaluator.evaluate(d)
+        return row
+
+    def _evaluate_body(self, index, mode, runner, g, t0):
+        ev = self._dev_eval[mode] if self._dev_eval is not None else None
+        self.log.append(self._row(runner.labels, runner.cur, mode, index, t0, g if runner.gc is g else None, ev, rates=self.evaluator is not None))
+
     def _evaluate(self, index, mode, runner, g, t0):
-        """Evaluator::evaluate (LES/Evaluator.h:113-187).  Like the reference's evaluator, it stops the run's clock while it
-        works (stop() / start() around the body, :115-116,183-184): `time` excludes evaluation."""
-        if mode != 0:
-            return
+        """A row of the runner's view.  Like the reference's evaluator, it stops the run's clock while it works (stop() / start() around the body,
+        LES/Evaluator.h:115-116,183-184): `time` excludes evaluation."""
         runner._sync()
         te = time.perf_counter()
         try:
             self._evaluate_body(index, mode, runner, g, t0)
         finally:
             self.eval_seconds += time.perf_counter() - te
-
-    def _pairwise(self):
-        return dict(lambda_=float(self.p["lambda_"]), th_smooth=float(self.p["th_smooth"]), omega=float(self.p["omega"]), epsilon=float(self.p["epsilon"]))
-
-    def _evaluate_body(self, index, mode, runner, g, t0):
-        if self._dev_eval is not None:
-            ev = self._dev_eval[mode]
-            ev.evaluate(runner.labels.data_ptr(), runner.cur.data_ptr(), mode=mode, index=index, **self._pairwise())
-            r = ev.rows()[-1]
-            row = dict(index=index, time=time.perf_counter() - t0 - self.eval_seconds, energy=r["data"] + r["smooth"], data=r["data"], smooth=r["smooth"])
-            if self.evaluator is not None:
-                row["all"], row["nonocc"] = r["all"], r["nonocc"]
-            self.log.append(row)
-            return
-        disp = runner.disparities().cpu().numpy()
-        if g is not None and runner.gc is g:
-            runner.sync_gc_state()
-            dc, sc = g.data_cost(mode), g.smoothness_cost(mode)
-        else:
-            dc, sc = float(runner.cur.sum(dtype=torch.float64)), float("nan")
-        row = dict(index=index, time=time.perf_counter() - t0 - self.eval_seconds, energy=dc + (0.0 if sc != sc else sc), data=dc, smooth=sc)
-        if self.evaluator is not None:
-            d = disp
-            if self.precision > 0:                                         # Evaluator::quantize, LES/Evaluator.h:106-111
-                d = (np.rint(disp / np.float32(self.precision)) * np.float32(self.precision)).astype(np.float32)
-            row["all"], row["nonocc"] = self.evaluator.evaluate(d)
-        self.log.append(row)
 
     def run(self, maxIteration, viewModes=(0,), pmInit=0, labeling=None):
         """FastGCStereo::run (LES/FastGCStereo.h:133-227).  Returns (labeling, rawlabeling) of the left view as
@@ -158,12 +194,8 @@ class FastGCStereo:
         moves (pm.PMRunner.fuse; the report goes to self.slant_stats; no map visits the host; with maxIteration == 0 the start is the WTA map
         alone; single rank).  "sgm" / "sgm+planes": the same two starts from the semi-global matching map of each view's own raw cost volume
         (les_hip_sgm_labels, csrc/les_sgm.h; self.sgm_params; not for the image-based energy: ValueError).  The costs of a start labelling come from one dense device pass per view (pm.PMRunner.init_from_labels)."""
-        try:
-            return self._run(maxIteration, viewModes, pmInit, labeling)
-        finally:                 # the device evaluators of the run, also when it raised
-            for ev in list((self._dev_eval or {}).values()) + [lg.evaluator for lg in self._inner.values()]:
-                ev.close()
-            self._dev_eval, self._inner = None, {}
+        with contextlib.ExitStack() as stack:        # closes the runners, the graph-cut context and the device evaluators of the run, also when it raises
+            return self._run(stack, maxIteration, tuple(viewModes), pmInit, labeling)
 
     def fuse(self, labeling, others, viewMode=0, layers=None):
         """Fusion moves (FastGCStereo::fusionMoveBK, LES/FastGCStereo.h:241-410, which no mode of the reference reaches): starts from `labeling`
@@ -177,31 +209,18 @@ class FastGCStereo:
         t0 = time.perf_counter()
         self.eval_seconds, self.log, self.fuse_stats = 0.0, [], []
         m = int(viewMode)
-        runner = pm.PMRunner(self.e, self.units, self.table, seed=self.seed + 7919 * m, device=self.device, mode=m, random_vdisp=self.random_vdisp)
-        g = gc.GraphCut(self.imL, self.imR, lambda_=self.p["lambda_"], th_smooth=self.p["th_smooth"], omega=self.p["omega"], epsilon=self.p["epsilon"])
-        ev_args = {} if self.evaluator is None else dict(dispGT=self.evaluator.gt, nonocc=self.evaluator.nonocc, error_threshold=self.evaluator.threshold,
-                                                         precision=self.precision)
-        try:
-            if self.evaluate_on_device:
-                self._dev_eval = {m: api.DeviceEvaluator(self.e, max_rows=len(others) + 1, **ev_args)}
-            runner.init_from_labels(labeling)                # warm start (LES/FastGCStereo.h:116-130)
-            if self.device_cuts is not None:
-                runner.device_cuts = self.device_cuts
-            runner.begin_gc(g, mode=m)
+        with contextlib.ExitStack() as stack:
+            runner, g = self._runner(stack, m), self._graph_cut(stack)
+            self._dev_eval = {m: self._device_evaluator(stack, len(others) + 1)} if self.evaluate_on_device else None
+            self._ready_to_cut(runner, labeling, g)
             if self.evaluator is not None:
-                self._evaluate_row(0, m, runner, g, t0)
+                self._evaluate(0, m, runner, g, t0)
             for k, other in enumerate(others):
                 self.fuse_stats.append(runner.fuse(other, layers=layers, nthreads=self.host_threads))
                 if self.evaluator is not None:
-                    self._evaluate_row(k + 1, m, runner, g, t0)
+                    self._evaluate(k + 1, m, runner, g, t0)
             runner._sync()
             return runner.labels.cpu().numpy().copy()
-        finally:
-            for ev in (self._dev_eval or {}).values():
-                ev.close()
-            self._dev_eval = None
-            runner.close()
-            g.close()
 
     def fit_planes(self, disp_or_labeling, viewMode=0, **params):
         """Slanted planes from a disparity map (no reference counterpart; csrc/les_planefit.h): per pixel of view viewMode an edge-aware weighted
@@ -247,25 +266,17 @@ class FastGCStereo:
             raise NotImplementedError("FastGCStereo.cross_fuse is single-rank: multi-rank cross-view fusion is not implemented")
         if sorted(labelings) != [0, 1]:
             raise ValueError(f"cross_fuse takes the maps of both views, {{0: L, 1: R}} (views given: {sorted(labelings)})")
-        runners = {m: pm.PMRunner(self.e, self.units, self.table, seed=self.seed + 7919 * m, device=self.device, mode=m, random_vdisp=self.random_vdisp)
-                   for m in (0, 1)}
-        g = gc.GraphCut(self.imL, self.imR, lambda_=self.p["lambda_"], th_smooth=self.p["th_smooth"], omega=self.p["omega"], epsilon=self.p["epsilon"])
-        try:
+        with contextlib.ExitStack() as stack:
+            runners = {m: self._runner(stack, m) for m in (0, 1)}
+            g = self._graph_cut(stack)
             before = {}
             for m in (0, 1):
-                runners[m].init_from_labels(labelings[m])
-                if self.device_cuts is not None:
-                    runners[m].device_cuts = self.device_cuts
-                runners[m].begin_gc(g, mode=m)
+                self._ready_to_cut(runners[m], labelings[m], g)
                 before[m] = sum(runners[m].energy(self._pairwise()))
             self.cross_stats = self._cross_view_step(runners, layers)
             for m in (0, 1):
                 self.cross_stats[m].update(energy_before=before[m], energy_after=sum(runners[m].energy(self._pairwise())))
             return {m: runners[m].labels.cpu().numpy().copy() for m in (0, 1)}
-        finally:
-            for r in runners.values():
-                r.close()
-            g.close()
 
     def wta(self, viewModes=(0,), post_process=True, subpixel=True, slanted=False):
         """Cost-volume filtering without a graph cut (no reference counterpart; csrc/les_wtavol.h): every view of viewModes gets the winner-take-all
@@ -280,14 +291,7 @@ class FastGCStereo:
         the layers (pm.PMRunner.fuse); a pixel ends with its WTA label or its fitted one, and the costs of the rows are the dense re-scoring's.
         The reports go to self.slant_stats.
         -> (labeling, rawlabeling) of the left view as run() does (None without the left view)."""
-        return self._volume_maps("wta", viewModes, post_process, slanted, lambda m: self.e.wta_labels(mode=m, subpixel=subpixel, device=self.device))
-
-    def _sgm_map(self, m, **params):
-        """View m's SGM label map and the unary costs of its labels (one dense device pass: the summed path cost is not the energy's unary cost),
-        both on the device."""
-        lab, cost = self.e.sgm_labels(mode=m, device=self.device, **params)
-        self.e.unary_labels(lab.data_ptr(), cost.data_ptr(), mode=m, check=True)
-        return lab, cost
+        return self._volume_maps("wta", viewModes, post_process, slanted, subpixel=subpixel)
 
     def sgm(self, viewModes=(0,), paths=8, p1=None, p2=None, post_process=True, subpixel=True, slanted=False):
         """Semi-global matching without a graph cut (no reference counterpart; csrc/les_sgm.h), the twin of wta(): every view of viewModes gets the
@@ -296,43 +300,44 @@ class FastGCStereo:
         self.log, the two-view post-processing, `slanted`, self.raw_labelings, self.slant_stats and the return value are wta()'s; the costs of the
         rows are the dense re-scoring of the labels (the summed path cost is not the energy's unary cost).  Not for the image-based energy
         (api.LesHipError, error 3: it holds no volume).  Single rank."""
-        return self._volume_maps("sgm", viewModes, post_process, slanted, lambda m: self._sgm_map(m, paths=paths, p1=p1, p2=p2, subpixel=subpixel))
+        return self._volume_maps("sgm", viewModes, post_process, slanted, paths=paths, p1=p1, p2=p2, subpixel=subpixel)
 
-    def _volume_maps(self, what, viewModes, post_process, slanted, make_map):
-        """The body wta() and sgm() share: make_map(view) -> (labels, costs) on the device; then the optional fusion of the fitted planes, the rows,
-        the two-view post-processing."""
+    def _volume_map(self, source, m, **params):
+        """View m's "wta" / "sgm" map -> (labels, the read-out's costs), both on the device: what wta(), sgm() and run(labeling=<name>) start from."""
+        return (self.e.sgm_labels if source == "sgm" else self.e.wta_labels)(mode=m, device=self.device, **params)
+
+    def _volume_maps(self, source, viewModes, post_process, slanted, **params):
+        """The body wta() and sgm() share: each view's _volume_map, the optional fusion of the fitted planes, the rows, the two-view post-processing."""
         if self.world > 1:
-            raise NotImplementedError(f"FastGCStereo.{what} is single-rank: the multi-rank form is not implemented")
+            raise NotImplementedError(f"FastGCStereo.{source} is single-rank: the multi-rank form is not implemented")
         views = tuple(int(m) for m in viewModes)
         t0 = time.perf_counter()
         self.eval_seconds, self.log = 0.0, []
         if slanted and not self.units:
-            raise ValueError(f"{what}(slanted=True) fuses over the cells of the layers: add layers (addLayer) first")
-        maps = {m: make_map(m) for m in views}
+            raise ValueError(f"{source}(slanted=True) fuses over the cells of the layers: add layers (addLayer) first")
+        maps = {}
+        for m in views:
+            maps[m] = lab, cost = self._volume_map(source, m, **params)
+            if source == "sgm":          # the summed path cost is not the energy's unary cost: the costs of the labels from one dense device pass
+                self.e.unary_labels(lab.data_ptr(), cost.data_ptr(), mode=m, check=True)
         if slanted:
             self.slant_stats = {}
-            g = gc.GraphCut(self.imL, self.imR, lambda_=self.p["lambda_"], th_smooth=self.p["th_smooth"], omega=self.p["omega"], epsilon=self.p["epsilon"])
-            try:
+            with contextlib.ExitStack() as stack:
+                g = self._graph_cut(stack)
                 for m in views:
-                    runner = pm.PMRunner(self.e, self.units, self.table, seed=self.seed + 7919 * m, device=self.device, mode=m, random_vdisp=self.random_vdisp)
-                    try:
-                        runner.init_from_labels(maps[m][0])
-                        if self.device_cuts is not None:
-                            runner.device_cuts = self.device_cuts
-                        runner.begin_gc(g, mode=m)
+                    with contextlib.ExitStack() as view_stack:
+                        runner = self._ready_to_cut(self._runner(view_stack, m), maps[m][0], g)
                         self.slant_stats[m] = self._fuse_fitted(runner, maps[m][0])
                         runner._sync()
                         maps[m] = (runner.labels.clone(), runner.cur.clone())
-                    finally:
-                        runner.close()
-            finally:
-                g.close()
         self.e.synchronize()
         self.raw_labelings = {m: maps[m][0].cpu().numpy().copy() for m in views}
         if self.evaluator is not None:
             for m in views:
                 te = time.perf_counter()
-                self.log.append(self._wta_row(m, maps[m][0], maps[m][1], t0))
+                with contextlib.ExitStack() as stack:          # (the ground truth is the left view's: the other view's row carries no rates)
+                    ev = self._device_evaluator(stack, 1, rates=m == 0) if self.evaluate_on_device else None
+                    self.log.append(dict(index=m, mode=m) | self._row(maps[m][0], maps[m][1], m, m, t0, ev=ev, rates=m == 0))
                 self.eval_seconds += time.perf_counter() - te
         if len(views) == 2 and post_process:
             self.e.post_process(maps[0][0].data_ptr(), maps[1][0].data_ptr(), 1.5, self.p["omega"])
@@ -341,51 +346,18 @@ class FastGCStereo:
         self.seconds = time.perf_counter() - t0 - self.eval_seconds
         return lab, self.raw_labelings.get(0)
 
-    def _wta_row(self, m, labels, cost, t0):
-        """The Evaluator row of a view's device maps (wta(): there is no runner)."""
-        row = dict(index=m, mode=m, time=time.perf_counter() - t0 - self.eval_seconds)
-        rates = m == 0                      # (the ground truth is the left view's)
-        if self.evaluate_on_device:
-            ev_args = dict(dispGT=self.evaluator.gt, nonocc=self.evaluator.nonocc, error_threshold=self.evaluator.threshold, precision=self.precision) if rates else {}
-            ev = api.DeviceEvaluator(self.e, max_rows=1, **ev_args)
-            try:
-                ev.evaluate(labels.data_ptr(), cost.data_ptr(), mode=m, index=m, **self._pairwise())
-                r = ev.rows()[0]
-            finally:
-                ev.close()
-            row.update(energy=r["data"] + r["smooth"], data=r["data"], smooth=r["smooth"])
-            if rates:
-                row["all"], row["nonocc"] = r["all"], r["nonocc"]
-            return row
-        dc = float(cost.sum(dtype=torch.float64))
-        row.update(energy=dc, data=dc, smooth=float("nan"))
-        if rates:
-            d = disparities(labels.cpu().numpy())
-            if self.precision > 0:                                         # Evaluator::quantize, LES/Evaluator.h:106-111
-                d = (np.rint(d / np.float32(self.precision)) * np.float32(self.precision)).astype(np.float32)
-            row["all"], row["nonocc"] = self.evaluator.evaluate(d)
-        return row
-
-    def _evaluate_row(self, index, mode, runner, g, t0):
-        """_evaluate for the view that fuse() works on (the rows of run() are the left view's)."""
-        runner._sync()
-        te = time.perf_counter()
-        try:
-            self._evaluate_body(index, mode, runner, g, t0)
-        finally:
-            self.eval_seconds += time.perf_counter() - te
-
-    def _run(self, maxIteration, viewModes, pmInit, labeling):
+    # -- run(), stage by stage
+    def _check_run(self, maxIteration, viewModes, labeling):
+        """What run() refuses.  -> (with_planes: each view fuses the planes fitted to its start map in before the first cut; the graph-cut
+        iterations, counted from 1, that end with a cross-view step: every cross_view-th one and the last one)"""
+        with_planes = False
         if isinstance(labeling, str):
-            if labeling not in ("wta", "wta+planes", "sgm", "sgm+planes"):
-                raise ValueError(f"labeling {labeling!r}: a label map, a disparity map, a dict of them, \"wta\", \"wta+planes\", \"sgm\" or \"sgm+planes\"")
-            if labeling.startswith("sgm") and self.e.sgm_workspace_bytes() == 0:
+            source, with_planes = _parse_start(labeling)
+            if source == "sgm" and self.e.sgm_workspace_bytes() == 0:
                 raise ValueError(f"labeling=\"{labeling}\": semi-global matching runs over a cost volume of at most 512 disparities; this energy (the image-based "
                                  "one holds no volume) has none it can use")
             if self.world > 1:
                 raise NotImplementedError(f"labeling=\"{labeling}\" is single-rank: the multi-rank start is not implemented")
-        with_planes = isinstance(labeling, str) and labeling.endswith("+planes") and maxIteration > 0
-        wta_maps, self.slant_stats = {}, {}
         if self.inner_loop_log and self.world > 1:
             raise ValueError("inner_loop_log is a single-rank log: with several ranks a rank holds only its band of a set's cells until the exchange")
         if self.cross_view > 0:
@@ -393,171 +365,145 @@ class FastGCStereo:
                 raise NotImplementedError("cross_view is single-rank: multi-rank cross-view fusion is not implemented")
             if sorted(viewModes) != [0, 1]:
                 raise ValueError("cross_view needs a two-view run (viewModes (0, 1)): there is no other view to fuse with")
-        # graph-cut iterations (counted from 1) that end with a cross-view step: every cross_view-th one and the last one
         cross_after = {it + 1 for it in range(maxIteration) if (it + 1) % self.cross_view == 0 or it + 1 == maxIteration} if self.cross_view > 0 else set()
-        self.cross_view_stats = []
-        t0 = time.perf_counter()
-        self.eval_seconds = 0.0
-        # Several ranks and two views: the views are independent until the post-processing (LES/FastGCStereo.h:172-185), so the ranks are
-        # split into one group per view -- the first ceil(world / 2) ranks advance the left view, the others the right one -- and each
-        # group shards the cells of ITS view.  A coarse layer has only 4-6 cells per disjoint set (SURVEY 8 geometry table): spread
-        # over world / 2 ranks instead of world, and the two views no longer take turns.  The groups meet once, before the
-        # post-processing: one broadcast per view of its final label map.
-        all_views = tuple(viewModes)
-        view_group, view_rank, view_world, view_root = None, self.rank, self.world, {}
-        if self.world > 1 and len(all_views) == 2:
-            import torch.distributed as dist
-            n0 = (self.world + 1) // 2
-            if self._view_groups is None:                      # (every rank creates both groups; once per object, not per run)
-                self._view_groups = [dist.new_group(list(range(0, n0))), dist.new_group(list(range(n0, self.world)))]
-            groups = self._view_groups
-            mine = 0 if self.rank < n0 else 1
-            view_group, view_rank, view_world = groups[mine], self.rank - (0 if mine == 0 else n0), (n0 if mine == 0 else self.world - n0)
-            view_root = {all_views[0]: 0, all_views[1]: n0}
-            viewModes = (all_views[mine],)
-        runners = {m: pm.PMRunner(self.e, self.units, self.table, seed=self.seed + 7919 * m, rank=view_rank, world=view_world,
-                                  device=self.device, mode=m, group=view_group, random_vdisp=self.random_vdisp) for m in viewModes}
-        # device evaluation: one evaluator for the rows of the log (the left view's, as the host route's), one per view for the inner-loop log
-        # (the ground truth is the left view's: the right view's rows carry the energy only)
-        self._dev_eval, self.inner_log, inner = None, [], self._inner
-        ev_args = {} if self.evaluator is None else dict(dispGT=self.evaluator.gt, nonocc=self.evaluator.nonocc, error_threshold=self.evaluator.threshold,
-                                                         precision=self.precision)
-        if self.evaluate_on_device or self.inner_loop_log:
-            self._dev_eval = {0: api.DeviceEvaluator(self.e, max_rows=maxIteration + pmInit + 3, **ev_args)}
+        return with_planes and maxIteration > 0, cross_after
+
+    def _split_views(self, all_views):
+        """Several ranks and two views: the views are independent until the post-processing (LES/FastGCStereo.h:172-185), so the ranks are
+        split into one group per view -- the first ceil(world / 2) ranks advance the left view, the others the right one -- and each
+        group shards the cells of ITS view.  A coarse layer has only 4-6 cells per disjoint set (SURVEY 8 geometry table): spread
+        over world / 2 ranks instead of world, and the two views no longer take turns.  The groups meet once, before the
+        post-processing (_gather).  -> (this rank's group, its rank and world within it, {view: its group's first rank}, this rank's views)"""
+        if self.world == 1 or len(all_views) != 2:
+            return None, self.rank, self.world, {}, all_views
+        import torch.distributed as dist
+        n0 = (self.world + 1) // 2
+        if self._view_groups is None:                      # (every rank creates both groups; once per object, not per run)
+            self._view_groups = [dist.new_group(list(range(0, n0))), dist.new_group(list(range(n0, self.world)))]
+        mine = 0 if self.rank < n0 else 1
+        return (self._view_groups[mine], self.rank - (0 if mine == 0 else n0), (n0 if mine == 0 else self.world - n0),
+                {all_views[0]: 0, all_views[1]: n0}, (all_views[mine],))
+
+    def _open_evaluators(self, stack, runners, log_rows, inner_rows_per_set):
+        """Device evaluation: one evaluator for the rows of the log (the left view's, as the host route's), one per view for the inner-loop log
+        (the ground truth is the left view's: the right view's rows carry the energy only)."""
+        self._dev_eval = {0: self._device_evaluator(stack, log_rows)} if self.evaluate_on_device or self.inner_loop_log else None
+        self._inner, self.inner_log = {}, []
         if self.inner_loop_log:
-            for m in viewModes:
-                r = runners[m]
-                ev = api.DeviceEvaluator(self.e, max_rows=max(1, len(r.sets) * (maxIteration + pmInit + len(cross_after) + int(with_planes))), **(ev_args if m == 0 else {}))
-                inner[m] = r.inner_log = SimpleNamespace(evaluator=ev, params=self._pairwise(), meta=[])
-        g = gc.GraphCut(self.imL, self.imR, lambda_=self.p["lambda_"], th_smooth=self.p["th_smooth"], omega=self.p["omega"],
-                        epsilon=self.p["epsilon"]) if maxIteration > 0 else None
-        for m in viewModes:
-            if labeling is None:
-                runners[m].init_labels()
-            elif isinstance(labeling, str):
-                wta_maps[m] = (self.e.sgm_labels(mode=m, device=self.device, **self.sgm_params) if labeling.startswith("sgm")
-                               else self.e.wta_labels(mode=m, device=self.device))[0]
-                runners[m].init_from_labels(wta_maps[m])
-            else:
-                if isinstance(labeling, dict) and m not in labeling:
-                    raise ValueError(f"labeling has no map for view {m} (views given: {sorted(labeling)})")
-                start = labeling[m] if isinstance(labeling, dict) else labeling
-                if not hasattr(start, "shape"):
-                    start = np.asarray(start, np.float32)
-                if len(start.shape) == 2:                  # a disparity map: the planes fitted to it, made on the device
-                    start = self.e.fit_planes(start, mode=m, device=self.device, **self.fit_params)
-                runners[m].init_from_labels(start)         # warm start (LES/FastGCStereo.h:116-130)
-            self._evaluate(0, m, runners[m], None, t0)
-        # the reference starts its clock HERE -- START_TIMER after initCurrentFast and the first evaluation (LES/FastGCStereo.h:135-141),
-        # with the layers (addLayer, LES/main.cpp:395-397) and the energy built before run() -- `seconds` below keeps counting from the top
-        # of this function; `seconds_reference_clock` is the same run on the reference's clock
-        self.init_seconds = time.perf_counter() - t0 - self.eval_seconds
-        for it in range(pmInit):
-            for m in viewModes:
-                runners[m].inner_iteration = it + 1
-                runners[m].iteration(it)
-                self._evaluate(it + 1, m, runners[m], None, t0)
-        self.gc_max_gap, self.gc_seconds, self.gc_moves_raised = 0.0, {}, 0
-        if maxIteration > 0:
-            for m in viewModes:
-                if self.device_cuts is not None:
-                    runners[m].device_cuts = self.device_cuts
-                runners[m].begin_gc(g, mode=m)
-                if with_planes:
-                    self.slant_stats[m] = self._fuse_fitted(runners[m], wta_maps[m])
-            main_device = torch.cuda.current_device() if torch.device(self.device).type == "cuda" else 0
+            for m, r in runners.items():
+                ev = self._device_evaluator(stack, max(1, len(r.sets) * inner_rows_per_set), rates=m == 0)
+                self._inner[m] = r.inner_log = SimpleNamespace(evaluator=ev, params=self._pairwise(), meta=[])
 
-            def one_view(m, it, nthreads=None):
-                dev = torch.device(self.device)
-                if dev.type == "cuda":
-                    torch.cuda.set_device(dev.index if dev.index is not None else main_device)   # current device is per host thread
-                runners[m].gc_iteration(it, check=self.check_flow_energy, nthreads=self.host_threads if nthreads is None else nthreads)
-            for it in range(maxIteration):
-                for m in viewModes:
-                    runners[m].inner_iteration = it + 1 + pmInit
-                if len(viewModes) == 2 and self.joint_views and self.world == 1 and not self.check_flow_energy:
-                    # the two views are independent until the post-processing (LES/FastGCStereo.h:172-185)
-                    pm.PMRunner.gc_iteration_joint([runners[m] for m in viewModes], it, nthreads=self.host_threads)
-                elif len(viewModes) == 2 and self.concurrent_views:
-                    # their graph-cut iterations run in two host threads (the C calls release the GIL) sharing the GPU stream
-                    import threading
-                    errors = []
+    def _start_map(self, labeling, m):
+        """What view m starts from, of run()'s `labeling`: None (the random start), a name (the view's _volume_map, on the device), an H x W x 4
+        map, an H x W disparity map (the planes fitted to it, made on the device) or a dict {view: one of the two}."""
+        if labeling is None:
+            return None
+        if isinstance(labeling, str):
+            source = _parse_start(labeling)[0]
+            return self._volume_map(source, m, **(self.sgm_params if source == "sgm" else {}))[0]
+        if isinstance(labeling, dict) and m not in labeling:
+            raise ValueError(f"labeling has no map for view {m} (views given: {sorted(labeling)})")
+        start = labeling[m] if isinstance(labeling, dict) else labeling
+        if not hasattr(start, "shape"):
+            start = np.asarray(start, np.float32)
+        if len(start.shape) == 2:
+            start = self.e.fit_planes(start, mode=m, device=self.device, **self.fit_params)
+        return start
 
-                    # two teams cut at the same time: 16 threads each measured best on the 2 x 64-core host (1436 x 992, two views:
-                    # 12 threads 10.3 s, 16 threads 10.2 s, 24 threads 10.8 s, 32 threads 11.1 s, 64 threads 11.7 s)
-                    per_view = self.host_threads if self.host_threads > 0 else 16
+    def _cut_view(self, runner, it, main_device, nthreads):
+        """Graph-cut iteration `it` of one view, on the calling thread (the current device is per host thread)."""
+        dev = torch.device(self.device)
+        if dev.type == "cuda":
+            torch.cuda.set_device(dev.index if dev.index is not None else main_device)
+        runner.gc_iteration(it, check=self.check_flow_energy, nthreads=nthreads)
 
-                    on_gpu = torch.device(self.device).type == "cuda"
+    def _cut_view_in_thread(self, runner, it, main_device, nthreads, errors):
+        """The thread body of the concurrent schedule.  On the GPU each view advances on its own stream: its synchronisations (one per lock-step)
+        then wait for its own kernels only, and the two views' kernels overlap.  An error goes to `errors` (re-raised on the caller's thread)."""
+        try:
+            dev = torch.device(self.device)
+            if dev.type != "cuda":
+                return self._cut_view(runner, it, main_device, nthreads)
+            torch.cuda.set_device(dev.index if dev.index is not None else main_device)
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.default_stream())
+            with torch.cuda.stream(side):
+                self.e.set_thread_stream(side.cuda_stream)
+                try:
+                    self._cut_view(runner, it, main_device, nthreads)
+                    side.synchronize()
+                finally:
+                    self.e.set_thread_stream(0, bind=False)
+        except BaseException as ex:
+            errors.append(ex)
 
-                    def guarded(m):
-                        try:
-                            if on_gpu:
-                                # each view advances on its own stream: its synchronisations (one per lock-step) then wait for its
-                                # own kernels only, and the two views' kernels overlap on the GPU
-                                dev = torch.device(self.device)
-                                torch.cuda.set_device(dev.index if dev.index is not None else main_device)
-                                side = torch.cuda.Stream()
-                                side.wait_stream(torch.cuda.default_stream())
-                                with torch.cuda.stream(side):
-                                    self.e.set_thread_stream(side.cuda_stream)
-                                    try:
-                                        one_view(m, it, per_view)
-                                        side.synchronize()
-                                    finally:
-                                        self.e.set_thread_stream(0, bind=False)
-                            else:
-                                one_view(m, it, per_view)
-                        except BaseException as ex:          # re-raised in the caller's thread below
-                            errors.append(ex)
-                    ths = [threading.Thread(target=guarded, args=(m,)) for m in (reversed(viewModes) if self._swap_view_threads else viewModes)]
-                    for th in ths:
-                        th.start()
-                    for th in ths:
-                        th.join()
-                    if errors:
-                        raise errors[0]
-                else:
-                    for m in viewModes:
-                        one_view(m, it)
-                if it + 1 in cross_after:
-                    # whichever schedule cut the iteration: both views are at rest here, on the driver's thread and stream (the fusion's sets
-                    # add their rows to the inner-loop log under this iteration, after the rows of its cuts)
-                    self.cross_view_stats.append(dict(iteration=it + 1, views=self._cross_view_step(runners)))
-                for m in viewModes:
-                    self._evaluate(it + 1 + pmInit, m, runners[m], g, t0)
-            for m in viewModes:
-                self.gc_max_gap = max(self.gc_max_gap, runners[m].gc_max_gap)
-                self.gc_moves_raised += int(runners[m].gc_seconds.get("moves_raised", 0))
-                for k, v in runners[m].gc_seconds.items():      # sums over the views; a worst gap is the worst of the views
-                    self.gc_seconds[k] = max(self.gc_seconds.get(k, 0.0), v) if k.startswith("own_max_gap_") else self.gc_seconds.get(k, 0.0) + v
-        if view_root:
-            # the view groups meet: every rank receives both final label maps (16 B/px each) from the first rank of each group
-            import torch.distributed as dist
-            H_, W_ = self.e.H, self.e.W
-            other = {m: torch.zeros((H_, W_, 4), dtype=torch.float32, device=torch.device(self.device)) for m in all_views if m not in runners}
-            final = {m: (runners[m].labels if m in runners else other[m]) for m in all_views}
-            for m in all_views:
-                if final[m].is_cuda and dist.get_backend() == "gloo":          # (one-GPU functional tests of the multi-rank path: gloo moves host memory)
-                    h = final[m].cpu()
-                    dist.broadcast(h, src=view_root[m])
-                    final[m].copy_(h)
-                else:
-                    dist.broadcast(final[m], src=view_root[m])
+    def _gc_iteration(self, runners, it, main_device):
+        """Graph-cut iteration `it` of this rank's views under the chosen schedule (the two views are independent until the post-processing,
+        LES/FastGCStereo.h:172-185): joint, concurrent or one view after the other."""
+        views = list(runners)
+        if len(views) == 2 and self.joint_views and self.world == 1 and not self.check_flow_energy:
+            pm.PMRunner.gc_iteration_joint([runners[m] for m in views], it, nthreads=self.host_threads)
+        elif len(views) == 2 and self.concurrent_views:
+            # two host threads (the C calls release the GIL).  Two teams cut at the same time: 16 threads each measured best on the 2 x 64-core host
+            # (1436 x 992, two views: 12 threads 10.3 s, 16 threads 10.2 s, 24 threads 10.8 s, 32 threads 11.1 s, 64 threads 11.7 s)
+            import threading
+            errors, per_view = [], self.host_threads if self.host_threads > 0 else 16
+            ths = [threading.Thread(target=self._cut_view_in_thread, args=(runners[m], it, main_device, per_view, errors))
+                   for m in (reversed(views) if self._swap_view_threads else views)]
+            for th in ths:
+                th.start()
+            for th in ths:
+                th.join()
+            if errors:
+                raise errors[0]
         else:
-            final = {m: runners[m].labels for m in all_views}
-        self.raw_labelings = {m: final[m].cpu().numpy().copy() for m in all_views}
-        raw = self.raw_labelings.get(0)
-        if len(all_views) == 2:
-            self.e.post_process(final[0].data_ptr(), final[1].data_ptr(), 1.5, self.p["omega"])     # (left, right) whatever the order of viewModes; LES/FastGCStereo.h:202
-            if self.recost_after_post:
-                for m in runners:
-                    runners[m].recost()
+            for m in views:
+                self._cut_view(runners[m], it, main_device, self.host_threads)
+
+    def _graph_cuts(self, runners, g, maxIteration, pmInit, fit_from, cross_after, t0):
+        """The graph-cut iterations of this rank's views (fit_from: view -> the start map whose fitted planes it fuses in before the first one); then
+        what their runners counted, summed over the views."""
+        for m, r in runners.items():
+            r.begin_gc(g)
+            if m in fit_from:
+                self.slant_stats[m] = self._fuse_fitted(r, fit_from[m])
+        main_device = torch.cuda.current_device() if torch.device(self.device).type == "cuda" else 0
+        for it in range(maxIteration):
+            for r in runners.values():
+                r.inner_iteration = it + 1 + pmInit
+            self._gc_iteration(runners, it, main_device)
+            if it + 1 in cross_after:
+                # whichever schedule cut the iteration: both views are at rest here, on the driver's thread and stream (the fusion's sets
+                # add their rows to the inner-loop log under this iteration, after the rows of its cuts)
+                self.cross_view_stats.append(dict(iteration=it + 1, views=self._cross_view_step(runners)))
             if 0 in runners:
-                self._evaluate(maxIteration + 1 + pmInit, 0, runners[0], None, t0)
-            # (the rows of the log belong to the ranks of the left view's group)
-        lab = final[0].cpu().numpy().copy() if 0 in final else None
-        self.seconds = time.perf_counter() - t0 - self.eval_seconds          # evaluation excluded (as in the reference), set-up and initialisation included (unlike it)
-        self.seconds_reference_clock = self.seconds - self.init_seconds
+                self._evaluate(it + 1 + pmInit, 0, runners[0], g, t0)
+        for r in runners.values():
+            self.gc_max_gap = max(self.gc_max_gap, r.gc_max_gap)
+            self.gc_moves_raised += int(r.gc_seconds.get("moves_raised", 0))
+            for k, v in r.gc_seconds.items():      # sums over the views; a worst gap is the worst of the views
+                self.gc_seconds[k] = max(self.gc_seconds.get(k, 0.0), v) if k.startswith("own_max_gap_") else self.gc_seconds.get(k, 0.0) + v
+
+    def _gather(self, runners, all_views, view_root):
+        """-> {view: its final label map on the device}.  Where the ranks were split into view groups, the groups meet here: every rank receives
+        both maps (16 B/px each) from the first rank of each group."""
+        if not view_root:
+            return {m: runners[m].labels for m in all_views}
+        import torch.distributed as dist
+        final = {m: (runners[m].labels if m in runners else torch.zeros((self.e.H, self.e.W, 4), dtype=torch.float32, device=torch.device(self.device)))
+                 for m in all_views}
+        for m in all_views:
+            if final[m].is_cuda and dist.get_backend() == "gloo":          # (one-GPU functional tests of the multi-rank path: gloo moves host memory)
+                h = final[m].cpu()
+                dist.broadcast(h, src=view_root[m])
+                final[m].copy_(h)
+            else:
+                dist.broadcast(final[m], src=view_root[m])
+        return final
+
+    def _collect_stats(self, runners):
+        """What the runners counted, before they close: the exchanges, the tiled solver's lock-steps, the inner-loop log."""
         self.bytes_exchanged = sum(r.bytes_exchanged for r in runners.values())
         self.all_gathers = sum(r.exchanges for r in runners.values())
         self.exchange_seconds = sum(r.exchange_seconds() for r in runners.values())     # device time inside pack -> all-gather -> unpack on this rank
@@ -570,15 +516,61 @@ class FastGCStereo:
                                                                        ms_max=round(float(a[:, 0].max()), 2), ms_sum=round(float(a[:, 0].sum()), 1), launches_p50=int(np.percentile(a[:, 1], 50)),
                                                                        launches_max=int(a[:, 1].max()))
         # the inner-loop log: read once, here (each view's rows were enqueued on the stream that ran its sets)
-        for m, lg in inner.items():
+        for m, lg in self._inner.items():
             for (iteration, li, k), r in zip(lg.meta, lg.evaluator.rows()):
                 self.inner_log.append(dict(iteration=iteration, layer=li, set=k, mode=m, data=r["data"], smooth=r["smooth"], energy=r["data"] + r["smooth"],
                                            all=r.get("all"), nonocc=r.get("nonocc")))
-        for r in runners.values():
-            r.close()
-        if g is not None:
-            g.close()
-        return lab, raw
+
+    def _run(self, stack, maxIteration, all_views, pmInit, labeling):
+        with_planes, cross_after = self._check_run(maxIteration, all_views, labeling)
+        self.slant_stats, self.cross_view_stats = {}, []
+        t0 = time.perf_counter()
+        self.eval_seconds = 0.0
+        view_group, view_rank, view_world, view_root, views = self._split_views(all_views)
+        runners = {m: self._runner(stack, m, rank=view_rank, world=view_world, group=view_group) for m in views}
+        self._open_evaluators(stack, runners, maxIteration + pmInit + 3, maxIteration + pmInit + len(cross_after) + int(with_planes))
+        g = self._graph_cut(stack) if maxIteration > 0 else None
+        starts = {}
+        for m, r in runners.items():       # per view: its start map, its costs, its first row
+            starts[m] = self._start_map(labeling, m)
+            self._start(r, starts[m])
+            if m == 0:                     # (the rows of run() are the left view's)
+                self._evaluate(0, 0, r, None, t0)
+        # the reference starts its clock HERE -- START_TIMER after initCurrentFast and the first evaluation (LES/FastGCStereo.h:135-141),
+        # with the layers (addLayer, LES/main.cpp:395-397) and the energy built before run() -- `seconds` below keeps counting from the top
+        # of this function; `seconds_reference_clock` is the same run on the reference's clock
+        self.init_seconds = time.perf_counter() - t0 - self.eval_seconds
+        for it in range(pmInit):
+            for m, r in runners.items():
+                r.inner_iteration = it + 1
+                r.iteration(it)
+                if m == 0:
+                    self._evaluate(it + 1, 0, r, None, t0)
+        self.gc_max_gap, self.gc_seconds, self.gc_moves_raised = 0.0, {}, 0
+        if maxIteration > 0:
+            self._graph_cuts(runners, g, maxIteration, pmInit, starts if with_planes else {}, cross_after, t0)
+        final = self._gather(runners, all_views, view_root)
+        self.raw_labelings = {m: final[m].cpu().numpy().copy() for m in all_views}
+        if len(all_views) == 2:
+            self.e.post_process(final[0].data_ptr(), final[1].data_ptr(), 1.5, self.p["omega"])     # (left, right) whatever the order of viewModes; LES/FastGCStereo.h:202
+            if self.recost_after_post:
+                for r in runners.values():
+                    r.recost()
+            if 0 in runners:               # (the rows of the log belong to the ranks of the left view's group)
+                self._evaluate(maxIteration + 1 + pmInit, 0, runners[0], None, t0)
+        lab = final[0].cpu().numpy().copy() if 0 in final else None
+        self.seconds = time.perf_counter() - t0 - self.eval_seconds          # evaluation excluded (as in the reference), set-up and initialisation included (unlike it)
+        self.seconds_reference_clock = self.seconds - self.init_seconds
+        self._collect_stats(runners)
+        return lab, self.raw_labelings.get(0)
+
+
+def _parse_start(name):
+    """A start's name -> (source "wta" / "sgm", with_planes)"""
+    if name not in ("wta", "wta+planes", "sgm", "sgm+planes"):
+        raise ValueError(f"labeling {name!r}: a label map, a disparity map, a dict of them, \"wta\", \"wta+planes\", \"sgm\" or \"sgm+planes\"")
+    source, _, planes = name.partition("+")
+    return source, bool(planes)
 
 
 def disparities(labeling):
@@ -599,6 +591,22 @@ def _layers(st, sizes):
     st.addLayer(sizes[2], [(e, 2), (r, 1)])
 
 
+def _front_end(e, data, params, evaluator, precision, layer_sizes, iterations, pmIterations, doDual, init, **kw):
+    """The tail MidV2 and MidV3 share: the driver on energy `e` with the evaluator and the three layers runs, and driver and energy close, also
+    when it raises.  -> (the driver, labeling, rawlabeling)"""
+    try:
+        st = FastGCStereo(e, data["imL"], data["imR"], params, **kw)
+        try:
+            st.setEvaluator(evaluator, precision=precision)
+            _layers(st, layer_sizes)
+            lab, raw = st.run(iterations, (0, 1) if doDual else (0,), pmIterations, labeling=init)
+        finally:
+            st.close()
+    finally:
+        e.close()
+    return st, lab, raw
+
+
 def MidV2(data, iterations=5, pmIterations=2, doDual=False, smooth_weight=None, filterRadious=20, device="cuda", seed=1, lib=None, params=None,
           vdisp=0.0, random_vdisp=0.0, init=None, **kw):
     """MidV2 (LES/main.cpp:270-328) on a data dict of io.load_data: image-based matching cost, layers 5/15/25, error
@@ -612,7 +620,7 @@ def MidV2(data, iterations=5, pmIterations=2, doDual=False, smooth_weight=None, 
     in before the first graph-cut iteration (labeling="wta+planes").  "sgm" / "sgm+planes" (MidV3's semi-global matching starts) raise ValueError
     here: MidV2 uses the image-based energy, which holds no cost volume to run them over.
     Further keywords go to FastGCStereo (cross_view=n with doDual: cross-view fusion after every n-th graph-cut iteration)."""
-    if isinstance(init, str) and init.startswith("sgm"):
+    if isinstance(init, str) and _parse_start(init)[0] == "sgm":
         raise ValueError(f"MidV2(init={init!r}): MidV2 uses the image-based energy, which holds no cost volume; semi-global matching runs over one (MidV3)")
     p = dict(PARAMS_GF if params is None else params)
     lam = p["lambda_"] if smooth_weight is None else smooth_weight
@@ -620,14 +628,8 @@ def MidV2(data, iterations=5, pmIterations=2, doDual=False, smooth_weight=None, 
     e = api.HipCostVolumeEnergy.naive(data["imL"], data["imR"], windR=filterRadious, eps=p["eps"], alpha=p["alpha"],
                                       th_col=p["th_col"], th_grad=p["th_grad"], max_disp=maxdisp,
                                       device=torch.device(device).index or 0, lib=lib, filter=p["filter"], max_vdisp=vdisp)
-    st = FastGCStereo(e, data["imL"], data["imR"], dict(p, lambda_=lam, windR=filterRadious), device=device, seed=seed,
-                      random_vdisp=random_vdisp, **kw)
-    st.setEvaluator(io.Evaluator(data["dispGT"], data["nonocc"], 0.5), precision=data.get("gt_prec", -1.0))
-    _layers(st, (5, 15, 25))
-    lab, raw = st.run(iterations, (0, 1) if doDual else (0,), pmIterations, labeling=init)
-    st.close()
-    e.close()
-    return st, lab, raw
+    return _front_end(e, data, dict(p, lambda_=lam, windR=filterRadious), io.Evaluator(data["dispGT"], data["nonocc"], 0.5), data.get("gt_prec", -1.0), (5, 15, 25),
+                      iterations, pmIterations, doDual, init, device=device, seed=seed, random_vdisp=random_vdisp, **kw)
 
 
 def MidV3(data, volL=None, volR=None, iterations=5, pmIterations=2, doDual=False, smooth_weight=0.5, mc_threshold=0.5, filterRadious=20,
@@ -651,11 +653,6 @@ def MidV3(data, volL=None, volR=None, iterations=5, pmIterations=2, doDual=False
     e = api.HipCostVolumeEnergy(data["imL"], data["imR"], tl.data_ptr(), tr.data_ptr(), windR=filterRadious, eps=p["eps"],
                                 th_col=mc_threshold, max_disp=maxdisp, device=torch.device(device).index or 0, volumes_on_device=True,
                                 shape=(D, H, W), lib=lib, filter=p["filter"], interpolate=interpolate)
-    st = FastGCStereo(e, data["imL"], data["imR"], dict(p, lambda_=smooth_weight, windR=filterRadious, th_col=mc_threshold), device=device, seed=seed, **kw)
-    st.setEvaluator(io.Evaluator(data["dispGT"], data["nonocc"], error_threshold), precision=-1.0)
-    _layers(st, (int(W * 0.01), int(W * 0.03), int(W * 0.09)))
-    lab, raw = st.run(iterations, (0, 1) if doDual else (0,), pmIterations, labeling=init)
-    st.close()
-    e.close()
-    del tl, tr
-    return st, lab, raw
+    # (tl, tr: the energy reads the volumes in place; they live until the run has returned)
+    return _front_end(e, data, dict(p, lambda_=smooth_weight, windR=filterRadious, th_col=mc_threshold), io.Evaluator(data["dispGT"], data["nonocc"], error_threshold), -1.0,
+                      (int(W * 0.01), int(W * 0.03), int(W * 0.09)), iterations, pmIterations, doDual, init, device=device, seed=seed, **kw)

@@ -115,7 +115,7 @@ def disparities(labels):
 
 
 def quantize(d, precision):
-    """Evaluator::quantize (LES/Evaluator.h:106-111) as stereo.FastGCStereo._evaluate_body does it."""
+    """Evaluator::quantize (LES/Evaluator.h:106-111) as stereo.FastGCStereo._row does it."""
     if precision > 0:
         with np.errstate(invalid="ignore"):
             return (np.rint(d / F(precision)) * F(precision)).astype(F)
