@@ -490,6 +490,40 @@ int les_hip_fit_planes(les_hip_ctx* ctx, int mode, const les_hip_plane* d_labels
                        const les_hip_plane* d_fallback /* may be NULL */, les_hip_plane* d_out, unsigned char* d_kind /* may be NULL */, int radius,
                        float sig, float gate0, float gate_slope, float max_slope, int min_support);
 
+/* ---- a half-resolution solve as a start: pooled images and volumes, upsampled planes (csrc/les_pyramid.h holds the definitions) ----
+ * No reference counterpart: the reference solves at one resolution (LES/FastGCStereo.h:133-227).  Sizes: Hh = (H + 1) / 2, Wh = (W + 1) / 2,
+ * Dh = (D + 1) / 2; every source index clamps to its range.  All three operations are exact (integers, or f32 in a fixed order with
+ * power-of-two multipliers only): the same inputs give the same bytes on every build.
+ * les_hip_pool_image: u8 [H][W][3] -> [Hh][Wh][3] in DEVICE memory, per channel (p00 + p01 + p10 + p11 + 2) >> 2.
+ * les_hip_pool_volume: f32 [D][H][W] -> [Dh][Hh][Wh] in DEVICE memory; half slice k is full slice 2k: per pixel of the 2 x 2 block
+ * t = (0.25 C[2k - 1] + 0.5 C[2k]) + 0.25 C[2k + 1], result (((t00 + t01) + t10) + t11) 0.25; NaN and +-inf propagate.  Reads the volume once.
+ * LES_HIP_PYRAMID_NT=1 / 0 selects non-temporal / plain loads (default: non-temporal).
+ * Both are context-free and enqueue only on hip_stream of `device`.  LES_HIP_ERR_ARG for null pointers and non-positive sizes;
+ * LES_HIP_ERR_UNSUPPORTED for volumes of 2^32 or more floats; nothing is written on a refused call. */
+int les_hip_pool_image(const uint8_t* d_src, uint8_t* d_dst, int H, int W, int device, void* hip_stream);
+int les_hip_pool_volume(const float* d_src, float* d_dst, int D, int H, int W, int device, void* hip_stream);
+/* A new, independent context of the same kind as src (cost-volume or image-based energy), filter and interpolation at half resolution, built
+ * from src's own device images and volumes: the images pooled, every volume pooled into memory the new context owns, guide statistics, march
+ * tables and the tiled copy exactly as les_hip_create* would build them from the same pooled inputs.  Its parameters: H, W, D -> Hh, Wh, Dh;
+ * max_disparity, min_disparity and the two vertical-disparity settings halved; windR -> max(1, (windR + 1) / 2); everything else (eps,
+ * th_col, alpha, th_grad, device, the context's stream) unchanged.  src may be destroyed before it.  A min_disparity that is not an even integer:
+ * LES_HIP_ERR_UNSUPPORTED (half slice k would not sit on an integer disparity); null arguments: LES_HIP_ERR_ARG; a halved radius no kernel
+ * serves: what les_hip_create* returns for it.  Synchronises the calling thread's stream of src. */
+int les_hip_create_half(les_hip_ctx** out, const les_hip_ctx* src);
+/* The H x W x 3 u8 BGR image of view `mode` as the context holds it, into HOST memory (for a context of les_hip_create_half: the pooled
+ * image, so that a caller need not pool it again).  A view without an image, null pointers: LES_HIP_ERR_ARG.  Synchronous. */
+int les_hip_get_image(les_hip_ctx* ctx, int mode, uint8_t* out_host);
+/* The way up: d_src, the Hh x Wh planes of view `mode` found on ctx_half, re-expressed at full resolution into d_out (H x W planes; not d_src),
+ * guided by the two contexts' images of that view.  Full pixel (X, Y) takes, of the half pixels (X >> 1, Y >> 1), its horizontal neighbour on
+ * the side of X's parity, the vertical one likewise and the diagonal one (coordinates clamped), the one whose pooled colour is nearest to the
+ * pixel's own in L1 (the first wins ties); its plane (a, b, c, v) becomes (a, b, (2c - a / 2) - b / 2, 2v), i.e. d_full(X, Y) =
+ * 2 d_half((X - 1/2) / 2, (Y - 1/2) / 2).  Kept -- d_kind 0 -- iff it is a valid label of ctx_full at (X, Y) (IsValiLabel); otherwise
+ * (0, 0, its disparity at (X, Y) clamped to ctx_full's range, 0) -- d_kind 1 -- or, when that disparity is not finite, (0, 0, min_disparity, 0)
+ * -- d_kind 2.  d_kind: H x W bytes or NULL.  ctx_half must have the half size of ctx_full and its device; a view without an image, null
+ * pointers: LES_HIP_ERR_ARG.  Enqueue only, on the calling thread's stream of ctx_full (les_hip_set_thread_stream is honoured). */
+int les_hip_upsample_labels(les_hip_ctx* ctx_full, const les_hip_ctx* ctx_half, int mode, const les_hip_plane* d_src, les_hip_plane* d_out,
+                            unsigned char* d_kind /* may be NULL */);
+
 /* replaces: PMStereoBase::postProcess (LES/PMStereoBase.h:146-256), called by FastGCStereo::run for two-view runs
  * (LES/FastGCStereo.h:199-203, threshold 1.5): consistency check, horizontal fill of the failed pixels from the nearest
  * consistent neighbours (smaller disparity wins), then the colour-weighted median of the labels over the

@@ -31,6 +31,7 @@ SYMBOLS = [
     "les_hip_slab_argmin_state_bytes", "les_hip_slab_argmin", "les_hip_slab_argmin_finish", "les_hip_wta_labels",
     "les_hip_sgm_workspace_bytes", "les_hip_sgm_labels", "les_hip_sgm_last_times",
     "les_hip_fit_planes",
+    "les_hip_pool_image", "les_hip_pool_volume", "les_hip_create_half", "les_hip_get_image", "les_hip_upsample_labels",
 ]
 
 
@@ -184,6 +185,11 @@ def load(path=None):
         "les_hip_sgm_labels": (ci, [vp, ci, ci, C.c_float, C.c_float, ci, vp, vp]),
         "les_hip_sgm_last_times": (ci, [C.POINTER(C.c_float), ci, C.POINTER(ci)]),
         "les_hip_fit_planes": (ci, [vp, ci, vp, vp, vp, vp, vp, ci, C.c_float, C.c_float, C.c_float, C.c_float, ci]),
+        "les_hip_pool_image": (ci, [vp, vp, ci, ci, ci, vp]),
+        "les_hip_pool_volume": (ci, [vp, vp, ci, ci, ci, ci, vp]),
+        "les_hip_create_half": (ci, [C.POINTER(vp), vp]),
+        "les_hip_get_image": (ci, [vp, ci, vp]),
+        "les_hip_upsample_labels": (ci, [vp, vp, ci, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -258,6 +264,26 @@ def build_cost_volume(imL_dev_ptr, imR_dev_ptr, vol_dev_ptr, D, H, W, mode, d0=0
     L = load(lib)
     _chk_lib(L, L.les_hip_build_cost_volume(C.c_void_p(int(imL_dev_ptr)), C.c_void_p(int(imR_dev_ptr)), C.c_void_p(int(vol_dev_ptr)), D, H, W, mode, d0,
                                             lambda_ad, lambda_census, device, C.c_void_p(int(stream))))
+
+
+def half_size(n):
+    """The pooled size of a dimension of n (csrc/les_pyramid.h): (n + 1) // 2."""
+    return (int(n) + 1) // 2
+
+
+def pool_image(src_dev_ptr, dst_dev_ptr, H, W, device=0, stream=0, lib=None):
+    """les_hip_pool_image: a device H x W x 3 u8 image pooled by two into the device half_size(H) x half_size(W) x 3 one, per channel
+    (p00 + p01 + p10 + p11 + 2) >> 2 with the source indices clamped (csrc/les_pyramid.h).  Enqueue only."""
+    L = load(lib)
+    _chk_lib(L, L.les_hip_pool_image(C.c_void_p(int(src_dev_ptr)), C.c_void_p(int(dst_dev_ptr)), H, W, device, C.c_void_p(int(stream))))
+
+
+def pool_volume(src_dev_ptr, dst_dev_ptr, D, H, W, device=0, stream=0, lib=None):
+    """les_hip_pool_volume: a device float [D][H][W] volume pooled by two in every dimension into the device [half_size(D)][half_size(H)]
+    [half_size(W)] one: half slice k is full slice 2k, weights (1/4, 1/2, 1/4) over the slices 2k - 1 .. 2k + 1 and the mean of the 2 x 2 pixels,
+    source indices clamped, in the fixed f32 order of csrc/les_pyramid.h (exact: the same bytes on every build).  Enqueue only."""
+    L = load(lib)
+    _chk_lib(L, L.les_hip_pool_volume(C.c_void_p(int(src_dev_ptr)), C.c_void_p(int(dst_dev_ptr)), D, H, W, device, C.c_void_p(int(stream))))
 
 
 FIT_MAX_RADIUS = 15            # kFitMaxR of csrc/les_planefit.h (the one source; tests/planefit_cases.py: case_independence_and_errors holds this copy to it)
@@ -838,6 +864,55 @@ class HipCostVolumeEnergy:
         labels = s.dim() == 3
         self.fit_planes_ptr(mode, s.data_ptr() if labels else None, None if labels else s.data_ptr(), fb.data_ptr() if fb is not None else None,
                             out.data_ptr(), kind.data_ptr() if with_kind else None, **params)
+        return (out, kind) if with_kind else out
+
+    # -- a half-resolution solve as a start (csrc/les_pyramid.h; no reference counterpart) ------------------------------------
+    def image(self, mode=0):
+        """les_hip_get_image: the H x W x 3 u8 image of view `mode` as the context holds it."""
+        out = np.empty((self.H, self.W, 3), np.uint8)
+        self._chk(self.L.les_hip_get_image(self.h, int(mode), _ptr(out)))
+        return out
+
+    def half(self):
+        """les_hip_create_half: a new, independent HipCostVolumeEnergy of the same kind, filter and interpolation at half resolution, built on the
+        device from this context's own images and volumes (pooled: csrc/les_pyramid.h).  H, W, D -> half_size of each; max_disp, min_disp and the
+        vertical-disparity settings halved; windR -> max(1, (windR + 1) // 2).  It owns its volumes and outlives this context.  A min_disp that
+        is not an even integer raises (error 3).  The caller closes it."""
+        h = C.c_void_p()
+        self._chk(self.L.les_hip_create_half(C.byref(h), self.h))
+        o = type(self).__new__(type(self))
+        o.L, o.h, o.filter, o._keep = self.L, h, self.filter, None
+        p = self.params
+        o.H, o.W = half_size(self.H), half_size(self.W)
+        o.D = half_size(self.D)
+        o.max_disp = float(np.float32(0.5) * np.float32(p.max_disparity))
+        o.params = Params(o.H, o.W, o.D, max(1, (p.windR + 1) // 2), p.eps, p.th_col, o.max_disp, float(np.float32(0.5) * np.float32(p.min_disparity)),
+                          p.device, p.volumes_on_device)
+        o.interpolate = self.interpolate
+        o.max_vdisp, o.random_vdisp = 0.5 * getattr(self, "max_vdisp", 0.0), 0.5 * getattr(self, "random_vdisp", 0.0)
+        o.imL = o.image(0) if self.imL is not None else None
+        o.imR = o.image(1) if self.imR is not None else None
+        return o
+
+    def upsample_labels(self, half, src, mode=0, with_kind=False, device=None):
+        """les_hip_upsample_labels: `src`, the half.H x half.W x 4 label map of view `mode` found on `half` (this context's half()), re-expressed
+        at this context's resolution, edge-aware: every pixel takes the plane of the nearest-coloured of its four surrounding half pixels,
+        rewritten as (a, b, (2c - a / 2) - b / 2, 2v), when that is a valid label here, else the fronto-parallel plane at its clamped disparity
+        (csrc/les_pyramid.h).  src: a float32 torch tensor (on `device`: used where it is) or an array.  -> the H x W x 4 map as a new tensor on
+        `device` (None: this context's GPU; the simulator build takes "cpu"); with_kind: (map, kind), kind H x W uint8 -- 0 kept, 1 clamped,
+        2 non-finite.  Asynchronous on the calling thread's stream."""
+        import torch
+        dev = torch.device(device if device is not None else f"cuda:{self.params.device}")
+        if torch.is_tensor(src):
+            s = src.to(device=dev, dtype=torch.float32).contiguous()
+        else:
+            s = torch.from_numpy(np.array(src, dtype=np.float32, order="C")).to(dev)
+        if tuple(s.shape) != (half.H, half.W, 4):
+            raise ValueError(f"upsample_labels: a {half.H} x {half.W} x 4 label map of the half context, not {tuple(s.shape)}")
+        out = torch.empty((self.H, self.W, 4), dtype=torch.float32, device=dev)
+        kind = torch.empty((self.H, self.W), dtype=torch.uint8, device=dev) if with_kind else None
+        self._chk(self.L.les_hip_upsample_labels(self.h, half.h, int(mode), C.c_void_p(s.data_ptr()), C.c_void_p(out.data_ptr()),
+                                                 C.c_void_p(kind.data_ptr()) if with_kind else None))
         return (out, kind) if with_kind else out
 
     def wta_update(self, rects, planes, cur_cost_dev, prop_cost_dev, labels_dev, planes_on_device=False):

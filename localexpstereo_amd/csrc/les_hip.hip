@@ -23,6 +23,7 @@
 #include "les_wtavol.h"
 #include "les_sgm.h"
 #include "les_planefit.h"
+#include "les_pyramid.h"
 
 #include "../host/ResidualCut.h"      // the host cores' finisher of the tiled max-flow (plain C++: search trees / push-relabel on a residual graph)
 
@@ -177,6 +178,7 @@ struct les_hip_ctx {
     les::Geom geom;
     ViewData v[2];
     float naive_alpha = 0;
+    float naive_th_grad = 0;             // Parameters::th_grad as given (th_grad below is scaled by alpha): what les_hip_create_half hands on
     int naive = 0;                       // 1: raw cost from the feature images (les_hip_create_naive), no volume
     float th_color = 0, th_grad = 0;
     // vertical disparity (Plane::v): the energy's MAX_VDISPARITY (les_hip_set_max_vdisparity: createRandomLabel, PROPOSE_INIT) and the
@@ -314,3 +316,4 @@ float naive_alpha(const les_hip_ctx* c) { return c->naive_alpha; }
 #include "les_hip_wtavol.inc"
 #include "les_hip_sgm.inc"
 #include "les_hip_planefit.inc"
+#include "les_hip_pyramid.inc"

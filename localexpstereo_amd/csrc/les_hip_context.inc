@@ -72,6 +72,7 @@ static int create_common(les_hip_ctx** out, const les_hip_params* params, const 
         c->th_color = p.th_col * (1.0f - alpha);                 // LES/StereoEnergy.h:662
         c->th_grad = th_grad * alpha;                            // LES/StereoEnergy.h:663
         c->naive_alpha = alpha;
+        c->naive_th_grad = th_grad;
     }
     const uint8_t* ims[2] = {imL, imR};
     const float* vols[2] = {volL, volR};

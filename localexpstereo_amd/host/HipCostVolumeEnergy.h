@@ -11,8 +11,10 @@
 #pragma once
 
 #include <cstdio>
+#include <memory>
 #include <mutex>
 #include <stdexcept>
+#include <vector>
 
 #include "StereoEnergy.h"
 #include "localexp_hip.h"
@@ -71,6 +73,19 @@ protected:
             throw std::invalid_argument("les_hip_set_max_vdisparity: " + e);
         }
         setImages(imL, imR);
+    }
+
+    // the half-resolution twin of `src` (half() below): adopts the context les_hip_create_half built
+    struct HalfTag {};
+    HipCostVolumeEnergy(HalfTag, const HipCostVolumeEnergy& src, les_hip_ctx* ctx, Parameters p)
+        : StereoEnergy((src.width + 1) / 2, (src.height + 1) / 2, std::move(p), 0.5f * src.MAX_DISPARITY, 0.5f * src.MIN_DISPARITY, 0.5f * src.MAX_VDISPARITY), ctx_(ctx)
+    {
+        std::vector<uint8_t> im[2];
+        for (int m = 0; m < 2; m++) {
+            im[m].resize((size_t)width * height * 3);
+            if (les_hip_get_image(ctx_, m, im[m].data()) != LES_HIP_OK) im[m].clear();      // (a view the source was built without)
+        }
+        setImages(im[0].empty() ? nullptr : im[0].data(), im[1].empty() ? nullptr : im[1].data());
     }
 
 public:
@@ -190,6 +205,48 @@ public:
         ok = ok && les_hip_memcpy_d2h(ctx_, out, d_out, P * sizeof(les_hip_plane)) == LES_HIP_OK && (!kind || les_hip_memcpy_d2h(ctx_, kind, d_kind, P) == LES_HIP_OK);
         if (!ok) fprintf(stderr, "HipCostVolumeEnergy: %s\n", les_hip_last_error());
         for (void* q : {(void*)d_lab, (void*)d_disp, (void*)d_fb, (void*)d_out, (void*)d_kind})
+            if (q) les_hip_free(ctx_, q);
+        return ok;
+    }
+
+    // The half-resolution twin of this energy (les_hip_create_half, csrc/les_pyramid.h; no reference counterpart): a new, independent energy of the
+    // same kind, filter and interpolation over this one's images and volumes pooled by two on the device -- width, height and slices (n + 1) / 2,
+    // the disparity ranges halved, windR -> max(1, (windR + 1) / 2).  Its Parameters are this one's with that windR and, because disparity
+    // differences halve, lambda x 2 and th_smooth / 2 (a reasoned default, not tuned).  A solution found on it is a start for this one through
+    // upsampleLabels.  Throws std::runtime_error when the library refuses (a MIN_DISPARITY that is not an even integer).
+    std::unique_ptr<HipCostVolumeEnergy> half() const
+    {
+        les_hip_ctx* h = nullptr;
+        if (les_hip_create_half(&h, ctx_) != LES_HIP_OK) throw std::runtime_error(std::string("les_hip_create_half: ") + les_hip_last_error());
+        Parameters p = params;
+        p.windR = std::max(1, (params.windR + 1) / 2);
+        p.lambda = params.lambda * 2;
+        p.th_smooth = params.th_smooth / 2;
+        try {
+            return std::unique_ptr<HipCostVolumeEnergy>(new HipCostVolumeEnergy(HalfTag{}, *this, h, std::move(p)));
+        } catch (...) {
+            les_hip_destroy(h);
+            throw;
+        }
+    }
+
+    // The way up (les_hip_upsample_labels): `src`, the label map of view `mode` found on `half` (this energy's half()), re-expressed at this
+    // energy's resolution, edge-aware, into `out`; kind (may be null): 0 the upsampled plane was kept, 1 it was not a valid label here and the
+    // pixel got the fronto-parallel plane at its clamped disparity, 2 its disparity was not finite.  src: half.width * half.height planes, out and
+    // kind: width * height elements, all in HOST memory.  Returns false (and reports on stderr) when the library refuses the call.
+    bool upsampleLabels(const HipCostVolumeEnergy& half, const Plane* src, Plane* out, unsigned char* kind = nullptr, int mode = 0) const
+    {
+        static_assert(sizeof(Plane) == sizeof(les_hip_plane), "ABI layout");
+        const size_t P = (size_t)width * height, Ph = (size_t)half.width * half.height;
+        les_hip_plane *d_src = nullptr, *d_out = nullptr;
+        unsigned char* d_kind = nullptr;
+        bool ok = les_hip_malloc(ctx_, (void**)&d_src, Ph * sizeof(les_hip_plane)) == LES_HIP_OK && les_hip_malloc(ctx_, (void**)&d_out, P * sizeof(les_hip_plane)) == LES_HIP_OK &&
+                  (!kind || les_hip_malloc(ctx_, (void**)&d_kind, P) == LES_HIP_OK);
+        ok = ok && les_hip_memcpy_h2d(ctx_, d_src, src, Ph * sizeof(les_hip_plane)) == LES_HIP_OK;
+        ok = ok && les_hip_upsample_labels(ctx_, half.ctx_, mode, d_src, d_out, d_kind) == LES_HIP_OK && les_hip_synchronize(ctx_) == LES_HIP_OK;
+        ok = ok && les_hip_memcpy_d2h(ctx_, out, d_out, P * sizeof(les_hip_plane)) == LES_HIP_OK && (!kind || les_hip_memcpy_d2h(ctx_, kind, d_kind, P) == LES_HIP_OK);
+        if (!ok) fprintf(stderr, "HipCostVolumeEnergy: %s\n", les_hip_last_error());
+        for (void* q : {(void*)d_src, (void*)d_out, (void*)d_kind})
             if (q) les_hip_free(ctx_, q);
         return ok;
     }

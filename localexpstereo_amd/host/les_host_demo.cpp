@@ -306,6 +306,17 @@ static int cmd_run(int argc, char** argv)
         }
         printf("fitPlanes: %zu of %zu pixels are not a finite plane of their kind or depend on the input form; %zu slanted fits\n", fbad, P, slanted);
         if (!okf || fbad || !slanted) { printf("FAIL: fitPlanes\n"); fail = 1; }
+        // the half-resolution twin through the adapter: a fronto-parallel half map at disparity 3 comes up as disparity 6 everywhere, v doubled
+        auto halfE = hip.half();
+        const size_t Ph = (size_t)((W + 1) / 2) * ((H + 1) / 2);
+        std::vector<Plane> hsrc(Ph, Plane(0.f, 0.f, 3.f, 0.25f)), up(P);
+        std::vector<unsigned char> ukind(P, 9);
+        const bool oku = hip.upsampleLabels(*halfE, hsrc.data(), up.data(), ukind.data(), 0);
+        const Plane uwant(0.f, 0.f, 6.f, 0.5f);
+        size_t ubad = 0;
+        for (size_t i = 0; i < P; i++) ubad += memcmp(&up[i], &uwant, sizeof(Plane)) != 0 || ukind[i] != 0;
+        printf("half / upsampleLabels: a %d x %d twin with windR %d; %zu of %zu pixels differ from the expected map\n", (W + 1) / 2, (H + 1) / 2, halfE->params.windR, ubad, P);
+        if (!oku || ubad || halfE->maxDisparity() != 0.5f * hip.maxDisparity()) { printf("FAIL: half / upsampleLabels\n"); fail = 1; }
     }
     printf(fail ? "les_host_demo: FAILED\n" : "les_host_demo: OK\n");
     return fail;

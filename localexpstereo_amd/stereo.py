@@ -25,7 +25,7 @@ PARAMS_BF = dict(PARAMS_GF, lambda_=20.0, windR=20, eps=10.0, filter="BF")
 
 class FastGCStereo:
     def __init__(self, energy, imL, imR, params, device="cuda", rank=0, world=1, seed=1, host_threads=0, device_cuts=None, random_vdisp=None,
-                 evaluate_on_device=False, inner_loop_log=False, check_flow_energy=False, recost_after_post=False, cross_view=0):
+                 evaluate_on_device=False, inner_loop_log=False, check_flow_energy=False, recost_after_post=False, cross_view=0, coarse_params=None):
         self.e, self.imL, self.imR, self.p = energy, imL, imR, dict(PARAMS_GF, **params)
         # Opt-in, no reference counterpart (the reference's views meet only in the post-processing): n > 0 -- in a two-view run, after every n-th
         # graph-cut iteration and after the last one, each view fuses the other view's solution, warped into its own coordinates on the device
@@ -44,6 +44,12 @@ class FastGCStereo:
         self.fit_params = {}
         # what the "sgm" / "sgm+planes" starts of run() use: keywords of api.HipCostVolumeEnergy.sgm_labels (paths, p1, p2, subpixel); {}: its defaults
         self.sgm_params = {}
+        # what the "half" start of run() solves at half resolution first (_half_starts): graph-cut and PatchMatch iterations and the start of that
+        # nested run (None, "wta", "sgm", "half": the next level down), over the same viewModes; an optional key coarse_params gives the next
+        # level its own settings (without it a "half" below runs these defaults)
+        self.coarse_params = dict(COARSE_DEFAULTS, **(coarse_params or {}))
+        self.coarse_seconds, self.coarse_stats = 0.0, {}    # run(labeling="half"): wall-clock of the way down, the nested run and the way up; what the nested run reports
+        self._coarse = False                      # set on the nested driver of a "half" start: no post-processing, the views' maps stay on the device (self._device_maps)
         self.slant_stats = {}                     # run(labeling="wta+planes") / wta(slanted=True): view -> the runner's fuse report + kind_pixels [fallback, fronto, slanted]
         self.raw_labelings = {}                   # run(): view -> its H x W x 4 labelling before the post-processing (what a later run resumes from)
         self.random_vdisp = random_vdisp          # maxVDisp of the RANDOM proposals (pm.PMRunner); None: the energy's setting (0 by default)
@@ -193,7 +199,11 @@ class FastGCStereo:
         graph-cut iteration, each view fuses the planes fitted to its WTA map (the WTA map is the fit's fallback) into its solution by fusion
         moves (pm.PMRunner.fuse; the report goes to self.slant_stats; no map visits the host; with maxIteration == 0 the start is the WTA map
         alone; single rank).  "sgm" / "sgm+planes": the same two starts from the semi-global matching map of each view's own raw cost volume
-        (les_hip_sgm_labels, csrc/les_sgm.h; self.sgm_params; not for the image-based energy: ValueError).  The costs of a start labelling come from one dense device pass per view (pm.PMRunner.init_from_labels)."""
+        (les_hip_sgm_labels, csrc/les_sgm.h; self.sgm_params; not for the image-based energy: ValueError).  "half": coarse to fine -- the energy's
+        half-resolution twin (api.HipCostVolumeEnergy.half: images and volumes pooled on the device, csrc/les_pyramid.h) is solved first by a nested
+        driver with self.coarse_params, and each view starts from its coarse planes re-expressed at full resolution on the device
+        (les_hip_upsample_labels); see _half_starts for the nested run's layers and pairwise parameters (a reasoned default, not tuned);
+        self.coarse_seconds and self.coarse_stats report it; single rank.  The costs of a start labelling come from one dense device pass per view (pm.PMRunner.init_from_labels)."""
         with contextlib.ExitStack() as stack:        # closes the runners, the graph-cut context and the device evaluators of the run, also when it raises
             return self._run(stack, maxIteration, tuple(viewModes), pmInit, labeling)
 
@@ -394,13 +404,54 @@ class FastGCStereo:
                 ev = self._device_evaluator(stack, max(1, len(r.sets) * inner_rows_per_set), rates=m == 0)
                 self._inner[m] = r.inner_log = SimpleNamespace(evaluator=ev, params=self._pairwise(), meta=[])
 
-    def _start_map(self, labeling, m):
-        """What view m starts from, of run()'s `labeling`: None (the random start), a name (the view's _volume_map, on the device), an H x W x 4
-        map, an H x W disparity map (the planes fitted to it, made on the device) or a dict {view: one of the two}."""
+    def _half_starts(self, views):
+        """The "half" start: the energy's half-resolution twin solved by a nested driver, each view's coarse map upsampled on the device.
+        The nested driver has the same seed, device, host threads and cut settings, no evaluator and no post-processing; its layers are those of
+        addLayer with unit sizes max(3, (s + 1) // 2), duplicates dropped; its rows (the energy only) come from the device evaluator; its pairwise parameters are lambda_ x 2 and th_smooth / 2, because
+        disparity differences halve with the resolution (a reasoned default, not tuned); iterations, pmInit and labeling come from
+        self.coarse_params.  The labels make no host round trip.  -> {view: H x W x 4 device map}"""
+        t0 = time.perf_counter()
+        cp = dict(COARSE_DEFAULTS, **self.coarse_params)
+        below = cp.pop("coarse_params", None)
+        if set(cp) != set(COARSE_DEFAULTS):
+            raise TypeError(f"coarse_params: unknown keys {sorted(set(cp) - set(COARSE_DEFAULTS))}")
+        if not self.units:
+            raise ValueError("labeling=\"half\" solves over the layers halved: add layers (addLayer) first")
+        with contextlib.ExitStack() as stack:
+            half = stack.enter_context(contextlib.closing(self.e.half()))
+            params = {k: v for k, v in self.p.items() if k != "filter"}
+            params.update(lambda_=2.0 * float(self.p["lambda_"]), th_smooth=0.5 * float(self.p["th_smooth"]), windR=half.params.windR)
+            st = FastGCStereo(half, half.imL, half.imR, params, device=self.device, seed=self.seed, host_threads=self.host_threads, device_cuts=self.device_cuts,
+                              random_vdisp=None if self.random_vdisp is None else 0.5 * self.random_vdisp, evaluate_on_device=True)
+            st._coarse = True
+            st.fit_params, st.sgm_params = dict(self.fit_params), dict(self.sgm_params)
+            if below is not None:
+                st.coarse_params = dict(below)
+            for s, table in zip(self.units, self.table):
+                u = max(3, (s + 1) // 2)
+                if u not in st.units:
+                    st.addLayer(u, table)
+            st.run(int(cp["iterations"]), views, int(cp["pmInit"]), labeling=cp["labeling"])
+            starts, kinds = {}, {}
+            for m in views:
+                starts[m], kind = self.e.upsample_labels(half, st._device_maps[m], mode=m, with_kind=True, device=self.device)
+                kinds[m] = torch.bincount(kind.flatten().to(torch.int64), minlength=3).tolist()       # (synchronises: the half context may close)
+            self.coarse_stats = dict(shape=(half.H, half.W, half.D), windR=half.params.windR, units=list(st.units), iterations=int(cp["iterations"]), pmInit=int(cp["pmInit"]),
+                                     labeling=cp["labeling"], lambda_=params["lambda_"], th_smooth=params["th_smooth"], seconds=st.seconds, log=st.log,
+                                     gc_seconds=dict(st.gc_seconds), kind_pixels=kinds, coarse_seconds=st.coarse_seconds, coarse_stats=st.coarse_stats)
+        self.coarse_seconds = time.perf_counter() - t0
+        return starts
+
+    def _start_map(self, labeling, m, named=None):
+        """What view m starts from, of run()'s `labeling`: None (the random start), a name (the view's _volume_map, on the device; "half": its map
+        of `named`, what _half_starts returned), an H x W x 4 map, an H x W disparity map (the planes fitted to it, made on the device) or a dict
+        {view: one of the two}."""
         if labeling is None:
             return None
         if isinstance(labeling, str):
             source = _parse_start(labeling)[0]
+            if source == "half":
+                return named[m]
             return self._volume_map(source, m, **(self.sgm_params if source == "sgm" else {}))[0]
         if isinstance(labeling, dict) and m not in labeling:
             raise ValueError(f"labeling has no map for view {m} (views given: {sorted(labeling)})")
@@ -531,8 +582,10 @@ class FastGCStereo:
         self._open_evaluators(stack, runners, maxIteration + pmInit + 3, maxIteration + pmInit + len(cross_after) + int(with_planes))
         g = self._graph_cut(stack) if maxIteration > 0 else None
         starts = {}
+        self.coarse_seconds, self.coarse_stats = 0.0, {}
+        named = self._half_starts(views) if isinstance(labeling, str) and _parse_start(labeling)[0] == "half" else None
         for m, r in runners.items():       # per view: its start map, its costs, its first row
-            starts[m] = self._start_map(labeling, m)
+            starts[m] = self._start_map(labeling, m, named)
             self._start(r, starts[m])
             if m == 0:                     # (the rows of run() are the left view's)
                 self._evaluate(0, 0, r, None, t0)
@@ -550,6 +603,13 @@ class FastGCStereo:
         if maxIteration > 0:
             self._graph_cuts(runners, g, maxIteration, pmInit, starts if with_planes else {}, cross_after, t0)
         final = self._gather(runners, all_views, view_root)
+        if self._coarse:                   # the nested run of a "half" start: its maps stay on the device, raw (the views meet at full resolution)
+            self._device_maps = {m: final[m].clone() for m in all_views}
+            self.raw_labelings = {}
+            self.seconds = time.perf_counter() - t0 - self.eval_seconds
+            self.seconds_reference_clock = self.seconds - self.init_seconds
+            self._collect_stats(runners)
+            return None, None
         self.raw_labelings = {m: final[m].cpu().numpy().copy() for m in all_views}
         if len(all_views) == 2:
             self.e.post_process(final[0].data_ptr(), final[1].data_ptr(), 1.5, self.p["omega"])     # (left, right) whatever the order of viewModes; LES/FastGCStereo.h:202
@@ -565,10 +625,13 @@ class FastGCStereo:
         return lab, self.raw_labelings.get(0)
 
 
+COARSE_DEFAULTS = dict(iterations=5, pmInit=2, labeling=None)      # FastGCStereo.coarse_params: the nested run of the "half" start
+
+
 def _parse_start(name):
-    """A start's name -> (source "wta" / "sgm", with_planes)"""
-    if name not in ("wta", "wta+planes", "sgm", "sgm+planes"):
-        raise ValueError(f"labeling {name!r}: a label map, a disparity map, a dict of them, \"wta\", \"wta+planes\", \"sgm\" or \"sgm+planes\"")
+    """A start's name -> (source "wta" / "sgm" / "half", with_planes)"""
+    if name not in ("wta", "wta+planes", "sgm", "sgm+planes", "half"):
+        raise ValueError(f"labeling {name!r}: a label map, a disparity map, a dict of them, \"wta\", \"wta+planes\", \"sgm\", \"sgm+planes\" or \"half\"")
     source, _, planes = name.partition("+")
     return source, bool(planes)
 
@@ -618,7 +681,9 @@ def MidV2(data, iterations=5, pmIterations=2, doDual=False, smooth_weight=None, 
     init: the start labelling of run() -- None (the default): the reference's random start; "wta": every view starts from the winner-take-all
     map of its filtered cost volume (FastGCStereo.run's labeling="wta"); "wta+planes": that start, and the slanted planes fitted to it are fused
     in before the first graph-cut iteration (labeling="wta+planes").  "sgm" / "sgm+planes" (MidV3's semi-global matching starts) raise ValueError
-    here: MidV2 uses the image-based energy, which holds no cost volume to run them over.
+    here: MidV2 uses the image-based energy, which holds no cost volume to run them over.  "half": coarse to fine -- the half-resolution problem
+    (both images pooled) is solved first and its planes, upsampled, are the start (FastGCStereo.run's labeling="half"; coarse_params=dict(...)
+    among the further keywords sets the nested run's iterations, pmInit and labeling).
     Further keywords go to FastGCStereo (cross_view=n with doDual: cross-view fusion after every n-th graph-cut iteration)."""
     if isinstance(init, str) and _parse_start(init)[0] == "sgm":
         raise ValueError(f"MidV2(init={init!r}): MidV2 uses the image-based energy, which holds no cost volume; semi-global matching runs over one (MidV3)")
@@ -639,7 +704,7 @@ def MidV3(data, volL=None, volR=None, iterations=5, pmIterations=2, doDual=False
     (default) or PARAMS_BF: filter and eps; smooth_weight, mc_threshold and filterRadious override lambda_, th_col and windR (:351-353).
     interpolate: the energy's setInterpolationMethod (LES/CostVolumeEnergy.h:45-48) -- 0 nearest, 1 linear (default), 2 quadratic.
     volL None: no volume files -- both views' AD-Census volumes (io.build_volumes; lambda_ad, lambda_census) are built on the device from
-    data["imL"], data["imR"] and data["ndisp"].  init: as for MidV2 (None: the random start; "wta": the winner-take-all start; "wta+planes": with its fitted planes fused in), and "sgm" / "sgm+planes": every view starts from the semi-global matching map of its own raw volume (FastGCStereo.run's labeling="sgm" / "sgm+planes"; csrc/les_sgm.h).  Further keywords go to FastGCStereo (cross_view=n with doDual: cross-view fusion after every
+    data["imL"], data["imR"] and data["ndisp"].  init: as for MidV2 (None: the random start; "wta": the winner-take-all start; "wta+planes": with its fitted planes fused in), and "sgm" / "sgm+planes": every view starts from the semi-global matching map of its own raw volume (FastGCStereo.run's labeling="sgm" / "sgm+planes"; csrc/les_sgm.h); "half": the coarse-to-fine start over the pooled volumes (labeling="half"; csrc/les_pyramid.h).  Further keywords go to FastGCStereo (cross_view=n with doDual: cross-view fusion after every
     n-th graph-cut iteration)."""
     p = dict(PARAMS_GF if params is None else params)
     maxdisp = float(data["ndisp"] - 1)
