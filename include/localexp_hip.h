@@ -531,6 +531,26 @@ int les_hip_upsample_labels(les_hip_ctx* ctx_full, const les_hip_ctx* ctx_half, 
  * Both device label maps are updated in place.  Needs both views' images in the context; windR <= 31. */
 int les_hip_post_process(les_hip_ctx* ctx, les_hip_plane* d_labelsL, les_hip_plane* d_labelsR, float threshold, float omega);
 
+/* ---- speckle filter (csrc/les_speckle.h holds the definition; no reference counterpart, the convention is OpenCV's filterSpeckles) ----
+ * The connected components of the disparity map of a device label map (H x W planes; d = (a x + b y) + c in float, un-fused, whatever the
+ * view): two 4-neighbours are connected iff both disparities are finite and fabsf(d(p) - d(q)) <= max_diff; a pixel with a non-finite
+ * disparity is a component of its own.  A pixel is a speckle iff its component has at most max_size pixels (max_size 0: none is).
+ * d_mask: H x W bytes, 255 speckle / 0; d_root (H x W ints or NULL): per pixel the smallest linear index y W + x of its component; d_size
+ * (H x W ints or NULL): per pixel its component's pixel count.  Exact integers, a function of the inputs alone.  Runs on the calling
+ * thread's stream and synchronises it before it returns.  max_size < 0, max_diff negative or NaN, null labels or mask: LES_HIP_ERR_ARG;
+ * H W >= 2^31: LES_HIP_ERR_UNSUPPORTED.  Scratch: 12 bytes per pixel for the call's duration. */
+int les_hip_speckle_mask(les_hip_ctx* ctx, const les_hip_plane* d_labels, int max_size, float max_diff, unsigned char* d_mask /* 255 / 0 */,
+                         int* d_root /* or NULL */, int* d_size /* or NULL */);
+/* The tile one workgroup of the component labelling owns (rows, columns): the compiled-in geometry, for tests and diagnostics. */
+int les_hip_speckle_tile(int* th, int* tw);
+/* les_hip_post_process with the failure mask widened: per view, fail = (left-right check failed) OR (speckle of that view's map); both
+ * masks come from the labels before any label is modified; the dilation, the fill and the weighted median then run as in
+ * les_hip_post_process.  One of the two label pointers may be NULL -- the one-view form: the mask is the speckle mask alone, only that
+ * view's image is needed, `threshold` is ignored.  max_size 0: with both views exactly les_hip_post_process, with one view the labels stay
+ * untouched.  Both pointers NULL, max_size < 0, max_diff negative or NaN: LES_HIP_ERR_ARG; windR > 31: LES_HIP_ERR_UNSUPPORTED. */
+int les_hip_post_process_speckle(les_hip_ctx* ctx, les_hip_plane* d_labelsL /* or NULL */, les_hip_plane* d_labelsR /* or NULL */,
+                                 float threshold, float omega, int max_size, float max_diff);
+
 /* ---- multi-GPU: publishing the tiles a rank updated (not in the reference, which is single-process; SURVEY 8(e): the cells of a
  * disjoint set -- LES/LayerManager.h:168-172 -- are split over the ranks, replicas of the label / cost maps are kept coherent by one
  * all-gather per set of the label (16 B/px) and cost (4 B/px) tiles of the shared regions, LES/FastGCStereo.h:22-72).

@@ -32,6 +32,7 @@ SYMBOLS = [
     "les_hip_sgm_workspace_bytes", "les_hip_sgm_labels", "les_hip_sgm_last_times",
     "les_hip_fit_planes",
     "les_hip_pool_image", "les_hip_pool_volume", "les_hip_create_half", "les_hip_get_image", "les_hip_upsample_labels",
+    "les_hip_speckle_mask", "les_hip_speckle_tile", "les_hip_post_process_speckle",
 ]
 
 
@@ -190,6 +191,9 @@ def load(path=None):
         "les_hip_create_half": (ci, [C.POINTER(vp), vp]),
         "les_hip_get_image": (ci, [vp, ci, vp]),
         "les_hip_upsample_labels": (ci, [vp, vp, ci, vp, vp, vp]),
+        "les_hip_speckle_mask": (ci, [vp, vp, ci, C.c_float, vp, vp, vp]),
+        "les_hip_speckle_tile": (ci, [C.POINTER(ci), C.POINTER(ci)]),
+        "les_hip_post_process_speckle": (ci, [vp, vp, vp, C.c_float, C.c_float, ci, C.c_float]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -718,23 +722,61 @@ class HipCostVolumeEnergy:
         self._chk(self.L.les_hip_consistency_check(self.h, C.c_void_p(int(labelsL_dev)), C.c_void_p(int(labelsR_dev)), C.c_float(threshold),
                                                    C.c_void_p(int(failL_dev)), C.c_void_p(int(failR_dev))))
 
-    def post_process(self, labelsL_dev, labelsR_dev, threshold=1.5, omega=10.0):
-        """PMStereoBase::postProcess in place on two device label maps (FastGCStereo::run calls it with 1.5)."""
-        self._chk(self.L.les_hip_post_process(self.h, C.c_void_p(int(labelsL_dev)), C.c_void_p(int(labelsR_dev)), C.c_float(threshold), C.c_float(omega)))
+    def post_process(self, labelsL_dev, labelsR_dev, threshold=1.5, omega=10.0, speckle=None):
+        """PMStereoBase::postProcess in place on two device label maps (FastGCStereo::run calls it with 1.5).
+        speckle=(max_size, max_diff): les_hip_post_process_speckle -- the failure mask of each view widened by the speckle mask of its map
+        (speckle_mask); one of the two maps may then be None: the one-view form, whose mask is the speckle mask alone."""
+        if speckle is None:
+            self._chk(self.L.les_hip_post_process(self.h, C.c_void_p(int(labelsL_dev)), C.c_void_p(int(labelsR_dev)), C.c_float(threshold), C.c_float(omega)))
+            return
+        max_size, max_diff = speckle
+        vp = lambda p: C.c_void_p(int(p)) if p else None
+        self._chk(self.L.les_hip_post_process_speckle(self.h, vp(labelsL_dev), vp(labelsR_dev), C.c_float(threshold), C.c_float(omega), int(max_size),
+                                                      C.c_float(max_diff)))
 
-    def post_process_host(self, labelsL, labelsR, threshold=1.5, omega=10.0):
-        """Convenience form for host label maps (H x W planes): upload, post-process on the device, download."""
-        out = []
-        bufs = [DeviceBuffer(self, self.H * self.W * 16) for _ in range(2)]
+    def post_process_host(self, labelsL, labelsR, threshold=1.5, omega=10.0, speckle=None):
+        """Convenience form for host label maps (H x W planes): upload, post-process on the device, download.  With speckle=(max_size, max_diff)
+        either map may be None (post_process); its place in the returned pair is None then."""
+        maps = (labelsL, labelsR)
+        bufs = [DeviceBuffer(self, self.H * self.W * 16) if l is not None else None for l in maps]
         try:
-            for b, l in zip(bufs, (labelsL, labelsR)):
-                b.upload(np.ascontiguousarray(l).view(np.float32).reshape(self.H, self.W, 4))
-            self.post_process(bufs[0].ptr, bufs[1].ptr, threshold, omega)
-            out = [b.download((self.H, self.W, 4), np.float32) for b in bufs]
+            for b, l in zip(bufs, maps):
+                if b is not None:
+                    b.upload(np.ascontiguousarray(l).view(np.float32).reshape(self.H, self.W, 4))
+            self.post_process(*(b.ptr if b is not None else None for b in bufs), threshold, omega, speckle=speckle)
+            out = [b.download((self.H, self.W, 4), np.float32) if b is not None else None for b in bufs]
         finally:
             for b in bufs:
-                b.free()
+                if b is not None:
+                    b.free()
         return out
+
+    # -- speckle filter (csrc/les_speckle.h; no reference counterpart) ------------------------------------
+    def speckle_mask_ptr(self, labels_ptr, max_size, max_diff, mask_ptr, root_ptr=None, size_ptr=None):
+        """les_hip_speckle_mask on device addresses (root_ptr and size_ptr may be None).  Synchronises the calling thread's stream."""
+        vp = lambda p: C.c_void_p(int(p)) if p else None
+        self._chk(self.L.les_hip_speckle_mask(self.h, vp(labels_ptr), int(max_size), C.c_float(max_diff), vp(mask_ptr), vp(root_ptr), vp(size_ptr)))
+
+    def speckle_mask(self, labels, max_size, max_diff, components=False, device=None):
+        """The speckle mask of an H x W x 4 label map (les_hip_speckle_mask): H x W uint8, 255 where the pixel's connected component of the
+        disparity map -- 4-neighbours whose finite disparities differ by at most max_diff -- has at most max_size pixels, else 0.  components:
+        (mask, root, size), root and size H x W int32 -- per pixel the smallest linear index of its component and the component's pixel
+        count.  labels: a float32 torch tensor (on `device`: used where it is) or an array.  All results are new tensors on `device` (None:
+        this context's GPU; the simulator build takes "cpu")."""
+        import torch
+        dev = torch.device(device if device is not None else f"cuda:{self.params.device}")
+        if torch.is_tensor(labels):
+            s = labels.to(device=dev, dtype=torch.float32).contiguous()
+        else:
+            s = torch.from_numpy(np.array(labels, dtype=np.float32, order="C")).to(dev)
+        if tuple(s.shape) != (self.H, self.W, 4):
+            raise ValueError(f"speckle_mask: a {self.H} x {self.W} x 4 label map, not {tuple(s.shape)}")
+        mask = torch.empty((self.H, self.W), dtype=torch.uint8, device=dev)
+        root = torch.empty((self.H, self.W), dtype=torch.int32, device=dev) if components else None
+        size = torch.empty((self.H, self.W), dtype=torch.int32, device=dev) if components else None
+        self.speckle_mask_ptr(s.data_ptr(), max_size, max_diff, mask.data_ptr(), root.data_ptr() if components else None,
+                              size.data_ptr() if components else None)
+        return (mask, root, size) if components else mask
 
     # -- cross-view fusion (csrc/les_crossview.h; no reference counterpart) -----------------------------
     def warp_labels(self, src_mode, src_ptr, fallback_ptr, out_ptr, hit_ptr=None):

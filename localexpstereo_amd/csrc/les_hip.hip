@@ -24,6 +24,7 @@
 #include "les_sgm.h"
 #include "les_planefit.h"
 #include "les_pyramid.h"
+#include "les_speckle.h"
 
 #include "../host/ResidualCut.h"      // the host cores' finisher of the tiled max-flow (plain C++: search trees / push-relabel on a residual graph)
 
@@ -308,6 +309,7 @@ float naive_alpha(const les_hip_ctx* c) { return c->naive_alpha; }
 #include "les_hip_batch.inc"
 #include "les_hip_cuts.inc"
 #include "les_hip_eval.inc"
+#include "les_hip_speckle.inc"
 #include "les_hip_ingest_post.inc"
 #include "les_hip_exchange.inc"
 #include "les_hip_dense.inc"

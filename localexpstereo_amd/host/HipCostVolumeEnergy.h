@@ -251,6 +251,51 @@ public:
         return ok;
     }
 
+    // The speckle mask of a label map (les_hip_speckle_mask, csrc/les_speckle.h; no reference counterpart, OpenCV's filterSpeckles convention):
+    // mask 255 where the pixel's connected component of the disparity map -- 4-neighbours whose finite disparities differ by at most max_diff --
+    // has at most max_size pixels, else 0; root / size (may be null): per pixel the smallest linear index of its component and the component's
+    // pixel count.  All maps: width * height elements in HOST memory.  Returns false (and reports on stderr) when the library refuses the call.
+    bool speckleMask(const Plane* labels, int max_size, float max_diff, unsigned char* mask, int* root = nullptr, int* size = nullptr) const
+    {
+        static_assert(sizeof(Plane) == sizeof(les_hip_plane), "ABI layout");
+        const size_t P = (size_t)width * height;
+        les_hip_plane* d_lab = nullptr;
+        unsigned char* d_mask = nullptr;
+        int *d_root = nullptr, *d_size = nullptr;
+        bool ok = les_hip_malloc(ctx_, (void**)&d_lab, P * sizeof(les_hip_plane)) == LES_HIP_OK && les_hip_malloc(ctx_, (void**)&d_mask, P) == LES_HIP_OK &&
+                  (!root || les_hip_malloc(ctx_, (void**)&d_root, P * sizeof(int)) == LES_HIP_OK) && (!size || les_hip_malloc(ctx_, (void**)&d_size, P * sizeof(int)) == LES_HIP_OK);
+        ok = ok && les_hip_memcpy_h2d(ctx_, d_lab, labels, P * sizeof(les_hip_plane)) == LES_HIP_OK;
+        ok = ok && les_hip_speckle_mask(ctx_, d_lab, max_size, max_diff, d_mask, d_root, d_size) == LES_HIP_OK;
+        ok = ok && les_hip_memcpy_d2h(ctx_, mask, d_mask, P) == LES_HIP_OK && (!root || les_hip_memcpy_d2h(ctx_, root, d_root, P * sizeof(int)) == LES_HIP_OK) &&
+             (!size || les_hip_memcpy_d2h(ctx_, size, d_size, P * sizeof(int)) == LES_HIP_OK);
+        if (!ok) fprintf(stderr, "HipCostVolumeEnergy: %s\n", les_hip_last_error());
+        for (void* q : {(void*)d_lab, (void*)d_mask, (void*)d_root, (void*)d_size})
+            if (q) les_hip_free(ctx_, q);
+        return ok;
+    }
+
+    // PMStereoBase::postProcess with the failure mask widened by the speckle mask (les_hip_post_process_speckle), in place on HOST label maps of
+    // width * height planes.  One of labelsL / labelsR may be null: the one-view form, whose mask is the speckle mask alone (threshold is ignored).
+    // max_size 0: with both views PMStereoBase::postProcess itself, with one view nothing changes.  Returns false (and reports on stderr) when the
+    // library refuses the call.
+    bool postProcessSpeckle(Plane* labelsL, Plane* labelsR, float threshold, float omega, int max_size, float max_diff) const
+    {
+        static_assert(sizeof(Plane) == sizeof(les_hip_plane), "ABI layout");
+        const size_t B = (size_t)width * height * sizeof(les_hip_plane);
+        Plane* host[2] = {labelsL, labelsR};
+        les_hip_plane* d[2] = {nullptr, nullptr};
+        bool ok = true;
+        for (int m = 0; m < 2 && ok; m++)
+            if (host[m]) ok = les_hip_malloc(ctx_, (void**)&d[m], B) == LES_HIP_OK && les_hip_memcpy_h2d(ctx_, d[m], host[m], B) == LES_HIP_OK;
+        ok = ok && les_hip_post_process_speckle(ctx_, d[0], d[1], threshold, omega, max_size, max_diff) == LES_HIP_OK;
+        for (int m = 0; m < 2 && ok; m++)
+            if (host[m]) ok = les_hip_memcpy_d2h(ctx_, host[m], d[m], B) == LES_HIP_OK;
+        if (!ok) fprintf(stderr, "HipCostVolumeEnergy: %s\n", les_hip_last_error());
+        for (int m = 0; m < 2; m++)
+            if (d[m]) les_hip_free(ctx_, d[m]);
+        return ok;
+    }
+
     // CostVolumeEnergy::setInterpolationMethod (LES/CostVolumeEnergy.h:45-48): 0 nearest slice, 1 linear (the default), 2 quadratic.  Like the
     // reference's setter it is not synchronised with evaluations running on other threads.
     virtual void setInterpolationMethod(int none_lin_quad)

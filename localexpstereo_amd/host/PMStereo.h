@@ -445,7 +445,8 @@ public:
             if (d_tiled) les_hip_free(ctx, d_tiled);
         }
         // two-view runs end with the left-right post-processing (LES/FastGCStereo.h:199-203)
-        if (ok && viewModes.size() == 2) ok = postProcess(1.5f);
+        // (opt-in: with a speckle filter set the mask is widened, and a one-view run is post-processed with the speckle mask alone)
+        if (ok && (viewModes.size() == 2 || speckleSize > 0)) ok = postProcess(1.5f, viewModes);
         if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         for (auto& lb : batches)
             for (SetBatch& sb : lb) { les_hip_batch_destroy(sb.b); les_hip_free(ctx, sb.rng); les_hip_free(ctx, sb.planes); les_hip_exchange_destroy(sb.x); }
@@ -458,21 +459,33 @@ public:
 
     // PMStereoBase::postProcess (LES/PMStereoBase.h:146-256) on the device: consistency check, fill, weighted median of both
     // views' label maps.  rawLabeling0 keeps the left labelling before it (the reference's `rawlabeling`).
-    bool postProcess(float threshold = 1.5f)
+    // speckleSize > 0 (opt-in, no reference counterpart): every pixel whose connected component of its view's disparity map -- 4-neighbours within
+    // speckleDiff -- has at most speckleSize pixels fails as well (les_hip_post_process_speckle), and `views` may then name one view alone.
+    int speckleSize = 0;
+    float speckleDiff = 1.0f;
+    bool postProcess(float threshold = 1.5f, const std::vector<int>& views = {0, 1})
     {
         auto* hip = dynamic_cast<HipCostVolumeEnergy*>(stereoEnergy.get());
         if (!hip) return false;
         les_hip_ctx* ctx = hip->handle();
         const size_t bytes = (size_t)width * height * sizeof(les_hip_plane);
-        rawLabeling0 = currentLabeling_[0];
+        bool has[2] = {false, false};
+        for (int m : views)
+            if (m == 0 || m == 1) has[m] = true;
+        if (speckleSize <= 0 && !(has[0] && has[1])) { fprintf(stderr, "PMStereo::postProcess: one view needs a speckle filter (speckleSize > 0)\n"); return false; }
+        if (has[0]) rawLabeling0 = currentLabeling_[0];
         les_hip_plane* d[2] = {nullptr, nullptr};
         bool ok = true;
         for (int m = 0; m < 2 && ok; m++)
-            ok = les_hip_malloc(ctx, (void**)&d[m], bytes) == LES_HIP_OK && les_hip_memcpy_h2d(ctx, d[m], currentLabeling_[m].data.data(), bytes) == LES_HIP_OK;
-        if (ok) ok = les_hip_post_process(ctx, d[0], d[1], threshold, params.omega) == LES_HIP_OK;
-        for (int m = 0; m < 2 && ok; m++) ok = les_hip_memcpy_d2h(ctx, currentLabeling_[m].data.data(), d[m], bytes) == LES_HIP_OK;
+            if (has[m]) ok = les_hip_malloc(ctx, (void**)&d[m], bytes) == LES_HIP_OK && les_hip_memcpy_h2d(ctx, d[m], currentLabeling_[m].data.data(), bytes) == LES_HIP_OK;
+        if (ok)
+            ok = (speckleSize > 0 ? les_hip_post_process_speckle(ctx, d[0], d[1], threshold, params.omega, speckleSize, speckleDiff)
+                                  : les_hip_post_process(ctx, d[0], d[1], threshold, params.omega)) == LES_HIP_OK;
+        for (int m = 0; m < 2 && ok; m++)
+            if (has[m]) ok = les_hip_memcpy_d2h(ctx, currentLabeling_[m].data.data(), d[m], bytes) == LES_HIP_OK;
         if (!ok) fprintf(stderr, "PMStereo::postProcess: %s\n", les_hip_last_error());
-        for (int m = 0; m < 2; m++) les_hip_free(ctx, d[m]);
+        for (int m = 0; m < 2; m++)
+            if (d[m]) les_hip_free(ctx, d[m]);
         return ok;
     }
     LabelMap rawLabeling0;

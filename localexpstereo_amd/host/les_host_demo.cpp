@@ -317,6 +317,39 @@ static int cmd_run(int argc, char** argv)
         for (size_t i = 0; i < P; i++) ubad += memcmp(&up[i], &uwant, sizeof(Plane)) != 0 || ukind[i] != 0;
         printf("half / upsampleLabels: a %d x %d twin with windR %d; %zu of %zu pixels differ from the expected map\n", (W + 1) / 2, (H + 1) / 2, halfE->params.windR, ubad, P);
         if (!oku || ubad || halfE->maxDisparity() != 0.5f * hip.maxDisparity()) { printf("FAIL: half / upsampleLabels\n"); fail = 1; }
+        // the speckle filter through the adapter: a fronto-parallel map at disparity 3 with planted 2 x 3 islands at disparity 9.  The mask is the
+        // islands; the one-view post-processing changes every island pixel and nothing else (so nothing outside the dilated mask); with
+        // max_size 0 the two-view form leaves the bytes of les_hip_post_process
+        std::vector<Plane> smap(P, Plane(0.f, 0.f, 3.f, 0.f));
+        std::vector<unsigned char> island(P, 0), smask(P, 9);
+        std::vector<int> sroot(P), ssize(P);
+        size_t planted = 0;
+        for (int y0 = 5; y0 + 2 <= H - 5; y0 += 9)
+            for (int x0 = 6; x0 + 3 <= W - 6; x0 += 11)
+                for (int y = y0; y < y0 + 2; y++)
+                    for (int x = x0; x < x0 + 3; x++) { smap[(size_t)y * W + x] = Plane(0.f, 0.f, 9.f, 1.f); island[(size_t)y * W + x] = 255; planted++; }
+        std::vector<Plane> sone = smap, sl = smap, sr = smap, pl = smap, pr = smap;
+        bool oks = hip.speckleMask(smap.data(), 20, 1.0f, smask.data(), sroot.data(), ssize.data());
+        oks = oks && hip.postProcessSpeckle(sone.data(), nullptr, 1.5f, hip.params.omega, 20, 1.0f);
+        oks = oks && hip.postProcessSpeckle(sl.data(), sr.data(), 1.5f, hip.params.omega, 0, 1.0f);
+        {
+            les_hip_plane* d[2] = {nullptr, nullptr};
+            Plane* h2[2] = {pl.data(), pr.data()};
+            for (int m = 0; m < 2; m++) oks = oks && les_hip_malloc(hip.handle(), (void**)&d[m], P * sizeof(Plane)) == LES_HIP_OK && les_hip_memcpy_h2d(hip.handle(), d[m], h2[m], P * sizeof(Plane)) == LES_HIP_OK;
+            oks = oks && les_hip_post_process(hip.handle(), d[0], d[1], 1.5f, hip.params.omega) == LES_HIP_OK;
+            for (int m = 0; m < 2; m++) {
+                oks = oks && les_hip_memcpy_d2h(hip.handle(), h2[m], d[m], P * sizeof(Plane)) == LES_HIP_OK;
+                if (d[m]) les_hip_free(hip.handle(), d[m]);
+            }
+        }
+        size_t mbad = 0, cbad = 0, zbad = 0;
+        for (size_t i = 0; i < P; i++) {
+            mbad += smask[i] != island[i] || ssize[i] != (island[i] ? 6 : (int)(P - planted)) || sroot[i] > (int)i;
+            cbad += (memcmp(&sone[i], &smap[i], sizeof(Plane)) != 0) != (island[i] != 0);
+            zbad += memcmp(&sl[i], &pl[i], sizeof(Plane)) != 0 || memcmp(&sr[i], &pr[i], sizeof(Plane)) != 0;
+        }
+        printf("speckle filter: %zu planted island pixels; %zu mask / size / root errors, %zu pixels changed or kept wrongly, %zu differ from postProcess at max_size 0\n", planted, mbad, cbad, zbad);
+        if (!oks || !planted || mbad || cbad || zbad) { printf("FAIL: speckle filter\n"); fail = 1; }
     }
     printf(fail ? "les_host_demo: FAILED\n" : "les_host_demo: OK\n");
     return fail;

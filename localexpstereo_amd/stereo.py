@@ -25,8 +25,16 @@ PARAMS_BF = dict(PARAMS_GF, lambda_=20.0, windR=20, eps=10.0, filter="BF")
 
 class FastGCStereo:
     def __init__(self, energy, imL, imR, params, device="cuda", rank=0, world=1, seed=1, host_threads=0, device_cuts=None, random_vdisp=None,
-                 evaluate_on_device=False, inner_loop_log=False, check_flow_energy=False, recost_after_post=False, cross_view=0, coarse_params=None):
+                 evaluate_on_device=False, inner_loop_log=False, check_flow_energy=False, recost_after_post=False, cross_view=0, coarse_params=None,
+                 speckle=None):
         self.e, self.imL, self.imR, self.p = energy, imL, imR, dict(PARAMS_GF, **params)
+        # Opt-in, no reference counterpart: (max_size, max_diff) -- the post-processing step of run(), wta() and sgm() also treats as failed every
+        # pixel whose connected component of the view's disparity map (4-neighbours within max_diff) has at most max_size pixels
+        # (les_hip_post_process_speckle, csrc/les_speckle.h), and a one-view call, which has no left-right check, is post-processed with that mask
+        # alone.  None (the default): nothing changes -- two views get the left-right check, one view returns its raw map.
+        self.speckle = None if speckle is None else (int(speckle[0]), float(speckle[1]))
+        if self.speckle is not None and (self.speckle[0] < 0 or not self.speckle[1] >= 0):
+            raise ValueError(f"speckle {speckle}: None or (max_size >= 0, max_diff >= 0)")
         # Opt-in, no reference counterpart (the reference's views meet only in the post-processing): n > 0 -- in a two-view run, after every n-th
         # graph-cut iteration and after the last one, each view fuses the other view's solution, warped into its own coordinates on the device
         # (les_hip_warp_labels, csrc/les_crossview.h), into its own by fusion moves (pm.PMRunner.fuse).  0 (the default): nothing changes.
@@ -190,7 +198,8 @@ class FastGCStereo:
 
     def run(self, maxIteration, viewModes=(0,), pmInit=0, labeling=None):
         """FastGCStereo::run (LES/FastGCStereo.h:133-227).  Returns (labeling, rawlabeling) of the left view as
-        H x W x 4 float arrays (the raw one is the labelling before the two-view post-processing).  `labeling`: optional
+        H x W x 4 float arrays (the raw one is the labelling before the post-processing: of two-view runs, and with FastGCStereo(speckle=)
+        of one-view runs too, whose mask is then the speckle mask alone).  `labeling`: optional
         start labelling (the reference's `labeling` argument; every view starts from it, as in the reference), or a dict {view: H x W x 4
         map} that gives each view of a two-view run its own (self.raw_labelings of an earlier run resumes it), or the string "wta": each view starts
         from the winner-take-all map of its own filtered cost volume (les_hip_wta_labels, csrc/les_wtavol.h; the map stays on the device; single
@@ -295,7 +304,8 @@ class FastGCStereo:
         row per view (index = mode = the view; energy, data, smooth; all / nonocc for the left view, whose ground truth the evaluator holds), made
         from the maps before any post-processing, through the device evaluator when evaluate_on_device (the host route has no pairwise sum without
         a graph-cut context: smooth is NaN there, as in run() before the first cut).  With two views and post_process, the left-right check, fill
-        and weighted median of run() follow (threshold 1.5, the run's omega).  Sets self.raw_labelings.  Single rank.
+        and weighted median of run() follow (threshold 1.5, the run's omega); with FastGCStereo(speckle=) the mask is widened by the speckle mask and one
+        view is post-processed too (with that mask alone).  Sets self.raw_labelings.  Single rank.
         slanted (opt-in; needs the layers of addLayer, it raises without): before the rows and the post-processing each view fuses the planes
         fitted to its WTA map (les_hip_fit_planes, csrc/les_planefit.h; self.fit_params) into that map by fusion moves over every disjoint set of
         the layers (pm.PMRunner.fuse); a pixel ends with its WTA label or its fitted one, and the costs of the rows are the dense re-scoring's.
@@ -349,12 +359,25 @@ class FastGCStereo:
                     ev = self._device_evaluator(stack, 1, rates=m == 0) if self.evaluate_on_device else None
                     self.log.append(dict(index=m, mode=m) | self._row(maps[m][0], maps[m][1], m, m, t0, ev=ev, rates=m == 0))
                 self.eval_seconds += time.perf_counter() - te
-        if len(views) == 2 and post_process:
-            self.e.post_process(maps[0][0].data_ptr(), maps[1][0].data_ptr(), 1.5, self.p["omega"])
+        if post_process and self._post_processes(views):
+            self._post_process({m: maps[m][0] for m in views})
             self.e.synchronize()
         lab = maps[0][0].cpu().numpy().copy() if 0 in maps else None
         self.seconds = time.perf_counter() - t0 - self.eval_seconds
         return lab, self.raw_labelings.get(0)
+
+    def _post_processes(self, views):
+        """Whether a call over `views` ends with the post-processing: two views always, one view when a speckle filter is set."""
+        return len(views) == 2 or self.speckle is not None
+
+    def _post_process(self, maps):
+        """The post-processing step of run(), wta() and sgm() in place on the device label maps {view: map}: threshold 1.5, the run's omega
+        (LES/FastGCStereo.h:202), (left, right) whatever the order of the views; with self.speckle the widened mask, and the one-view form."""
+        ptr = {m: maps[m].data_ptr() if m in maps else None for m in (0, 1)}
+        if self.speckle is None:
+            self.e.post_process(ptr[0], ptr[1], 1.5, self.p["omega"])
+        else:
+            self.e.post_process(ptr[0], ptr[1], 1.5, self.p["omega"], speckle=self.speckle)
 
     # -- run(), stage by stage
     def _check_run(self, maxIteration, viewModes, labeling):
@@ -611,8 +634,8 @@ class FastGCStereo:
             self._collect_stats(runners)
             return None, None
         self.raw_labelings = {m: final[m].cpu().numpy().copy() for m in all_views}
-        if len(all_views) == 2:
-            self.e.post_process(final[0].data_ptr(), final[1].data_ptr(), 1.5, self.p["omega"])     # (left, right) whatever the order of viewModes; LES/FastGCStereo.h:202
+        if self._post_processes(all_views):
+            self._post_process(final)
             if self.recost_after_post:
                 for r in runners.values():
                     r.recost()

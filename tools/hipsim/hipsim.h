@@ -166,6 +166,18 @@ static inline unsigned atomicMax(unsigned* p, unsigned v)
 }
 
 static inline int atomicAdd(int* p, int v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
+static inline int atomicMin(int* p, int v)
+{
+    int old = __atomic_load_n(p, __ATOMIC_RELAXED);
+    while (old > v && !__atomic_compare_exchange_n(p, &old, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+    return old;
+}
+// scoped atomic loads / stores (workgroups run on OS threads: these are real atomics; the scope has no meaning here)
+#define __HIP_MEMORY_SCOPE_AGENT 4
+template <typename T>
+static inline T __hip_atomic_load(const T* p, int order, int) { return __atomic_load_n(p, order); }
+template <typename T>
+static inline void __hip_atomic_store(T* p, T v, int order, int) { __atomic_store_n(p, v, order); }
 
 static inline void __syncthreads() { hipsim::sync_block(); }
 
