@@ -446,6 +446,40 @@ int les_hip_slab_argmin_finish(les_hip_ctx* ctx, const void* d_state, int K, int
  * other entry points may run beside it on other threads. */
 int les_hip_wta_labels(les_hip_ctx* ctx, int mode, int chunk, int subpixel, les_hip_plane* d_labels, float* d_cost);
 
+/* ---- the confidence of a label map under the aggregated cost volume (csrc/les_confidence.h holds the definition) ----
+ * No reference counterpart: the reference hands back disparities without saying which to trust.  The cost-margin measure on the filtered volume,
+ * a second reduction over the slabs les_hip_wta_labels reduces: a pixel with label (a, b, c, v) has its own disparity d = (a x + b y) + c
+ * (un-fused) and u = d - min_disparity; slab k is in band iff fabsf((float)k - u) <= band.  own = the least cost of the slabs in band, rival =
+ * the least cost of the others and k_r its slab (comparisons c < best from +inf: NaN and +inf never win, of equal costs the lowest k wins).
+ * conf = 0 when no in-band slab won (a label outside the volume's range, a NaN label, costs all NaN / +inf), else 1 when no rival won, else
+ * (rival - own) / scale clamped to [0, 1] (NaN: 0).  All in f32.
+ *
+ * The reduction streams: les_hip_slab_confidence consumes one chunk of n slabs ([n][H][W] floats on the device; slab i is slab k_first + i of
+ * the volume) and updates d_state (les_hip_slab_confidence_state_bytes(H, W) bytes on the device, 16-byte aligned, opaque).  k_first == 0
+ * initialises the state from d_labels (H x W planes), which is read only then (it may be NULL for k_first > 0); `band` is the same in every call
+ * of one volume; the chunks are fed in order, each slab once.  les_hip_slab_confidence_finish turns the state into d_conf (H x W floats in
+ * [0, 1]) and, where not NULL, d_own, d_rival (H x W floats: +inf where nothing won) and d_krival (H x W ints: -1 where no rival won).  How the
+ * slabs are cut into chunks changes no bit of the outputs.  Both are enqueue only, on the calling thread's stream (les_hip_set_thread_stream is
+ * honoured): no allocation, no synchronisation; calls on distinct states may come from distinct host threads.
+ * A null pointer, n or k_first negative, a state that is not 16-byte aligned, band negative or NaN, scale not positive or not finite:
+ * LES_HIP_ERR_ARG, nothing is launched or written. */
+size_t les_hip_slab_confidence_state_bytes(int H, int W);
+int les_hip_slab_confidence(les_hip_ctx* ctx, const les_hip_plane* d_labels, const float* d_slabs, int n, int k_first, float band, void* d_state);
+int les_hip_slab_confidence_finish(les_hip_ctx* ctx, const void* d_state, float scale, float* d_conf, float* d_own /* may be NULL */,
+                                   float* d_rival /* may be NULL */, int* d_krival /* may be NULL */);
+/* The whole operation for the device label map d_labels of view `mode`: the K planes of les_hip_wta_labels run through the batch path `chunk`
+ * at a time (chunk <= 0: 32; clamped to K) and each chunk is reduced as it lands.  It shares les_hip_wta_labels' planes, prepared batches and
+ * slab workspace on the context; the confidence state is a buffer of its own (freed with the context), so a call changes nothing a later
+ * les_hip_wta_labels returns, and the converse.  d_labels is only read.  A sensible `scale` is the largest value a raw matching cost of the
+ * context can take: th_col for the cost-volume energy, (1 - alpha) th_col + alpha th_grad for the image-based one.
+ * A null context, d_labels or d_conf, a view that was not supplied at creation, band negative or NaN, scale not positive or not finite, a
+ * disparity range les_hip_wta_labels refuses: LES_HIP_ERR_ARG, nothing is launched or written.
+ * Threading and streams as for les_hip_wta_labels: asynchronous on the calling thread's stream, except that a call that has to allocate (the
+ * first on a context, a larger chunk, a changed disparity range) synchronises; the workspace is one per context, so ONE host thread at a time may
+ * call this or les_hip_wta_labels on a context, and calls on different streams must be ordered by the caller; other entry points may run beside it. */
+int les_hip_confidence(les_hip_ctx* ctx, int mode, const les_hip_plane* d_labels, int chunk, float band, float scale, float* d_conf,
+                       float* d_own /* may be NULL */, float* d_rival /* may be NULL */, int* d_krival /* may be NULL */);
+
 /* ---- semi-global matching over a view's matching-cost volume (csrc/les_sgm.h holds the definition) ----
  * No reference counterpart (as above).  The classic step between local aggregation and a global graph cut: scan-line dynamic programming over the
  * RAW volume of view `mode` (float [D][H][W], slice k = disparity min_disparity + k; K = int(max_disparity - min_disparity) + 1 slices are
@@ -550,6 +584,13 @@ int les_hip_speckle_tile(int* th, int* tw);
  * untouched.  Both pointers NULL, max_size < 0, max_diff negative or NaN: LES_HIP_ERR_ARG; windR > 31: LES_HIP_ERR_UNSUPPORTED. */
 int les_hip_post_process_speckle(les_hip_ctx* ctx, les_hip_plane* d_labelsL /* or NULL */, les_hip_plane* d_labelsR /* or NULL */,
                                  float threshold, float omega, int max_size, float max_diff);
+/* les_hip_post_process_speckle with the caller's own failure masks: d_failL / d_failR are H x W bytes on the device, nonzero = failed (a
+ * thresholded les_hip_confidence map, say); either may be NULL.  Per view, fail = (left-right check failed) OR (speckle) OR (the caller's
+ * mask); all masks are taken before any label is modified.  With both masks NULL it is les_hip_post_process_speckle, byte for byte; the
+ * one-view form (one label pointer NULL; that view's mask is ignored) and the refusals are those of les_hip_post_process_speckle. */
+int les_hip_post_process_masked(les_hip_ctx* ctx, les_hip_plane* d_labelsL /* or NULL */, les_hip_plane* d_labelsR /* or NULL */, float threshold,
+                                float omega, int max_size, float max_diff, const unsigned char* d_failL /* or NULL */,
+                                const unsigned char* d_failR /* or NULL */);
 
 /* ---- multi-GPU: publishing the tiles a rank updated (not in the reference, which is single-process; SURVEY 8(e): the cells of a
  * disjoint set -- LES/LayerManager.h:168-172 -- are split over the ranks, replicas of the label / cost maps are kept coherent by one

@@ -33,6 +33,7 @@ SYMBOLS = [
     "les_hip_fit_planes",
     "les_hip_pool_image", "les_hip_pool_volume", "les_hip_create_half", "les_hip_get_image", "les_hip_upsample_labels",
     "les_hip_speckle_mask", "les_hip_speckle_tile", "les_hip_post_process_speckle",
+    "les_hip_slab_confidence_state_bytes", "les_hip_slab_confidence", "les_hip_slab_confidence_finish", "les_hip_confidence", "les_hip_post_process_masked",
 ]
 
 
@@ -194,6 +195,11 @@ def load(path=None):
         "les_hip_speckle_mask": (ci, [vp, vp, ci, C.c_float, vp, vp, vp]),
         "les_hip_speckle_tile": (ci, [C.POINTER(ci), C.POINTER(ci)]),
         "les_hip_post_process_speckle": (ci, [vp, vp, vp, C.c_float, C.c_float, ci, C.c_float]),
+        "les_hip_slab_confidence_state_bytes": (C.c_size_t, [ci, ci]),
+        "les_hip_slab_confidence": (ci, [vp, vp, vp, ci, ci, C.c_float, vp]),
+        "les_hip_slab_confidence_finish": (ci, [vp, vp, C.c_float, vp, vp, vp, vp]),
+        "les_hip_confidence": (ci, [vp, ci, vp, ci, C.c_float, C.c_float, vp, vp, vp, vp]),
+        "les_hip_post_process_masked": (ci, [vp, vp, vp, C.c_float, C.c_float, ci, C.c_float, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -603,6 +609,7 @@ class HipCostVolumeEnergy:
             self._chk(self.L.les_hip_create_naive_filtered(C.byref(h), C.byref(self.params), self.filter, _ptr(self.imL), _ptr(self.imR),
                                                            C.c_float(alpha), C.c_float(th_grad)))
         self.h = h
+        self.naive_cost = (float(alpha), float(th_grad))       # what raw_cost_max needs of the image-based cost
         self.interpolate = 1      # (no volume: les_hip_set_interpolation refuses this context)
         self.max_vdisp = self.random_vdisp = 0.0
         if max_vdisp:
@@ -722,31 +729,44 @@ class HipCostVolumeEnergy:
         self._chk(self.L.les_hip_consistency_check(self.h, C.c_void_p(int(labelsL_dev)), C.c_void_p(int(labelsR_dev)), C.c_float(threshold),
                                                    C.c_void_p(int(failL_dev)), C.c_void_p(int(failR_dev))))
 
-    def post_process(self, labelsL_dev, labelsR_dev, threshold=1.5, omega=10.0, speckle=None):
+    def post_process(self, labelsL_dev, labelsR_dev, threshold=1.5, omega=10.0, speckle=None, fail=None):
         """PMStereoBase::postProcess in place on two device label maps (FastGCStereo::run calls it with 1.5).
         speckle=(max_size, max_diff): les_hip_post_process_speckle -- the failure mask of each view widened by the speckle mask of its map
-        (speckle_mask); one of the two maps may then be None: the one-view form, whose mask is the speckle mask alone."""
-        if speckle is None:
+        (speckle_mask); one of the two maps may then be None: the one-view form, whose mask is the speckle mask alone.
+        fail=(maskL, maskR): les_hip_post_process_masked -- the caller's own failure masks, device addresses of H x W bytes (nonzero = failed),
+        either may be None, OR-ed into each view's mask; the one-view form is allowed as with speckle (without speckle: max_size 0, no speckle mask)."""
+        if speckle is None and fail is None:
             self._chk(self.L.les_hip_post_process(self.h, C.c_void_p(int(labelsL_dev)), C.c_void_p(int(labelsR_dev)), C.c_float(threshold), C.c_float(omega)))
             return
-        max_size, max_diff = speckle
+        max_size, max_diff = speckle if speckle is not None else (0, 0.0)
         vp = lambda p: C.c_void_p(int(p)) if p else None
-        self._chk(self.L.les_hip_post_process_speckle(self.h, vp(labelsL_dev), vp(labelsR_dev), C.c_float(threshold), C.c_float(omega), int(max_size),
-                                                      C.c_float(max_diff)))
+        if fail is None:
+            self._chk(self.L.les_hip_post_process_speckle(self.h, vp(labelsL_dev), vp(labelsR_dev), C.c_float(threshold), C.c_float(omega), int(max_size),
+                                                          C.c_float(max_diff)))
+            return
+        self._chk(self.L.les_hip_post_process_masked(self.h, vp(labelsL_dev), vp(labelsR_dev), C.c_float(threshold), C.c_float(omega), int(max_size),
+                                                     C.c_float(max_diff), vp(fail[0]), vp(fail[1])))
 
-    def post_process_host(self, labelsL, labelsR, threshold=1.5, omega=10.0, speckle=None):
+    def post_process_host(self, labelsL, labelsR, threshold=1.5, omega=10.0, speckle=None, fail=None):
         """Convenience form for host label maps (H x W planes): upload, post-process on the device, download.  With speckle=(max_size, max_diff)
-        either map may be None (post_process); its place in the returned pair is None then."""
+        or fail=(maskL, maskR) -- host H x W masks, nonzero / True = failed, either may be None -- either map may be None (post_process); its place
+        in the returned pair is None then."""
         maps = (labelsL, labelsR)
+        masks = tuple(fail) if fail is not None else (None, None)
         bufs = [DeviceBuffer(self, self.H * self.W * 16) if l is not None else None for l in maps]
+        mbufs = [DeviceBuffer(self, self.H * self.W) if m is not None else None for m in masks]
         try:
             for b, l in zip(bufs, maps):
                 if b is not None:
                     b.upload(np.ascontiguousarray(l).view(np.float32).reshape(self.H, self.W, 4))
-            self.post_process(*(b.ptr if b is not None else None for b in bufs), threshold, omega, speckle=speckle)
+            for b, m in zip(mbufs, masks):
+                if b is not None:
+                    b.upload((np.asarray(m).reshape(self.H, self.W) != 0).astype(np.uint8))
+            self.post_process(*(b.ptr if b is not None else None for b in bufs), threshold, omega, speckle=speckle,
+                              fail=None if fail is None else tuple(b.ptr if b is not None else None for b in mbufs))
             out = [b.download((self.H, self.W, 4), np.float32) if b is not None else None for b in bufs]
         finally:
-            for b in bufs:
+            for b in bufs + mbufs:
                 if b is not None:
                     b.free()
         return out
@@ -826,6 +846,66 @@ class HipCostVolumeEnergy:
         self._chk(self.L.les_hip_wta_labels(self.h, int(mode), int(chunk), int(bool(subpixel)), C.c_void_p(int(labels_ptr)) if labels_ptr else None,
                                             C.c_void_p(int(cost_ptr)) if cost_ptr else None))
         return out
+
+    # -- the confidence of a label map under the aggregated cost volume (csrc/les_confidence.h; no reference counterpart) ---------------
+    def raw_cost_max(self):
+        """The largest value a raw matching cost of this context can take (float32): th_col for the volume energy (the costs are truncated
+        there), (1 - alpha) th_col + alpha th_grad for the image-based one (its two truncated terms).  The default `scale` of confidence."""
+        th = np.float32(self.params.th_col)
+        if not hasattr(self, "naive_cost"):
+            return th
+        alpha, th_grad = (np.float32(v) for v in self.naive_cost)
+        return np.float32((np.float32(1) - alpha) * th + alpha * th_grad)
+
+    def slab_confidence_state_bytes(self):
+        """Bytes of the per-pixel state of slab_confidence for this context's image (16-byte aligned device memory, opaque)."""
+        return int(self.L.les_hip_slab_confidence_state_bytes(self.H, self.W))
+
+    def slab_confidence(self, labels_ptr, slabs_ptr, n, k_first, band, state_ptr):
+        """les_hip_slab_confidence: the running own / rival minima over one chunk of n slabs ([n][H][W] floats on the device, slab i = slab
+        k_first + i of the volume) into the state; k_first == 0 initialises it from the H x W x 4 label map at labels_ptr (read only then).
+        Enqueue only."""
+        vp = lambda p: C.c_void_p(int(p)) if p else None
+        self._chk(self.L.les_hip_slab_confidence(self.h, vp(labels_ptr), vp(slabs_ptr), int(n), int(k_first), C.c_float(band), vp(state_ptr)))
+
+    def slab_confidence_finish(self, state_ptr, scale, conf_ptr, own_ptr=None, rival_ptr=None, krival_ptr=None):
+        """les_hip_slab_confidence_finish: the state -> the H x W confidence map and, where given, the own and rival costs (float) and the
+        rival's slab (int32).  Enqueue only."""
+        vp = lambda p: C.c_void_p(int(p)) if p else None
+        self._chk(self.L.les_hip_slab_confidence_finish(self.h, vp(state_ptr), C.c_float(scale), vp(conf_ptr), vp(own_ptr), vp(rival_ptr), vp(krival_ptr)))
+
+    def confidence_ptr(self, mode, labels_ptr, chunk, band, scale, conf_ptr, own_ptr=None, rival_ptr=None, krival_ptr=None):
+        """les_hip_confidence on device addresses (own_ptr, rival_ptr and krival_ptr may be None)."""
+        vp = lambda p: C.c_void_p(int(p)) if p else None
+        self._chk(self.L.les_hip_confidence(self.h, int(mode), vp(labels_ptr), int(chunk), C.c_float(band), C.c_float(scale), vp(conf_ptr), vp(own_ptr),
+                                            vp(rival_ptr), vp(krival_ptr)))
+
+    def confidence(self, labels, mode=0, band=1.0, scale=None, chunk=0, parts=False, device=None):
+        """les_hip_confidence: the confidence in [0, 1] of every pixel of the H x W x 4 label map `labels` under view `mode`'s aggregated cost
+        volume -- how much cheaper the aggregated cost is within `band` slabs of the pixel's own disparity than anywhere else on its cost curve,
+        (rival - own) / scale clamped (csrc/les_confidence.h); 0 for a label outside the disparity range or not finite, 1 where the band covers
+        every finite cost.  scale None: raw_cost_max().  The num_fronto_planes planes run through the batch path `chunk` at a time (0: the
+        library's default).  labels: a float32 torch tensor (on `device`: used where it is) or an array.  -> the H x W float32 map as a new
+        tensor on `device` (None: this context's GPU; the simulator build takes "cpu"); parts: (conf, own, rival, k_rival), the in-band and
+        rival minima (float32, +inf where none) and the rival's slab (int32, -1 where none).  Asynchronous on the calling thread's stream once
+        the context's workspace exists."""
+        import torch
+        dev = torch.device(device if device is not None else f"cuda:{self.params.device}")
+        if torch.is_tensor(labels):
+            s = labels.to(device=dev, dtype=torch.float32).contiguous()
+        else:
+            s = torch.from_numpy(np.array(labels, dtype=np.float32, order="C")).to(dev)
+        if tuple(s.shape) != (self.H, self.W, 4):
+            raise ValueError(f"confidence: a {self.H} x {self.W} x 4 label map, not {tuple(s.shape)}")
+        conf = torch.empty((self.H, self.W), dtype=torch.float32, device=dev)
+        own = torch.empty_like(conf) if parts else None
+        rival = torch.empty_like(conf) if parts else None
+        kr = torch.empty((self.H, self.W), dtype=torch.int32, device=dev) if parts else None
+        self.confidence_ptr(mode, s.data_ptr(), chunk, band, self.raw_cost_max() if scale is None else scale, conf.data_ptr(),
+                            *(t.data_ptr() if parts else None for t in (own, rival, kr)))
+        if s is not labels:                  # (a copy made here must outlive the launches that read it)
+            self.synchronize()
+        return (conf, own, rival, kr) if parts else conf
 
     # -- semi-global matching over the view's own cost volume (csrc/les_sgm.h; no reference counterpart) -------------------
     def sgm_workspace_bytes(self):
@@ -931,6 +1011,8 @@ class HipCostVolumeEnergy:
         o.params = Params(o.H, o.W, o.D, max(1, (p.windR + 1) // 2), p.eps, p.th_col, o.max_disp, float(np.float32(0.5) * np.float32(p.min_disparity)),
                           p.device, p.volumes_on_device)
         o.interpolate = self.interpolate
+        if hasattr(self, "naive_cost"):
+            o.naive_cost = self.naive_cost
         o.max_vdisp, o.random_vdisp = 0.5 * getattr(self, "max_vdisp", 0.0), 0.5 * getattr(self, "random_vdisp", 0.0)
         o.imL = o.image(0) if self.imL is not None else None
         o.imR = o.image(1) if self.imR is not None else None

@@ -21,6 +21,7 @@
 #include "les_costvol.h"
 #include "les_crossview.h"
 #include "les_wtavol.h"
+#include "les_confidence.h"
 #include "les_sgm.h"
 #include "les_planefit.h"
 #include "les_pyramid.h"
@@ -198,7 +199,7 @@ struct les_hip_ctx {
     bool maxflow_lds_ready = false;      // the per-device dynamic-LDS opt-in of les_maxflow_kernel has been made on this context's device
     bool maxflow_tiled_lds_ready = false;   // ... and of les_maxflow_tiled_kernel
     std::vector<les_hip_scratch*> own_scratch;   // scratch objects created behind les_hip_unary_one (one per calling thread), freed with the context
-    WtaVol* wtavol = nullptr;            // les_hip_wta_labels' planes, batches, slab workspace and state (les_hip_wtavol.inc), built on first use, freed by les_hip_destroy
+    WtaVol* wtavol = nullptr;            // les_hip_wta_labels' planes, batches, slab workspace and state, and les_hip_confidence's own state (les_hip_wtavol.inc), built on first use, freed by les_hip_destroy
     SgmWork* sgm = nullptr;              // les_hip_sgm_labels' transposed volume and path sums (les_hip_sgm.inc), built on first use, freed by les_hip_destroy
     FitTables* fit_tables = nullptr;     // les_hip_fit_planes' weight tables, one per sig seen (les_hip_planefit.inc), built on first use, freed by les_hip_destroy
     std::vector<MtHost*> mt_idle; // host-mapped flag words + hand-over staging of the tiled max-flow: one per CONCURRENT caller, reused, freed with the context
@@ -316,6 +317,7 @@ float naive_alpha(const les_hip_ctx* c) { return c->naive_alpha; }
 #include "les_hip_costvol.inc"
 #include "les_hip_crossview.inc"
 #include "les_hip_wtavol.inc"
+#include "les_hip_confidence.inc"
 #include "les_hip_sgm.inc"
 #include "les_hip_planefit.inc"
 #include "les_hip_pyramid.inc"

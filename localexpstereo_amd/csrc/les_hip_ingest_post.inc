@@ -45,9 +45,11 @@ int post_disparities(les_hip_ctx* c, PostScratch& ps, const les_hip_plane* const
 
 struct SpeckleParams { int max_size; float max_diff; };
 
-// The body of les_hip_post_process and les_hip_post_process_speckle: per view present, the failure mask -- the left-right check when both views
-// are there, OR the speckle mask when `sp` asks for one -- its dilation and the fill; then per view the weighted median.
-int post_process_body(les_hip_ctx* c, les_hip_plane* const labels[2], float threshold, float omega, const SpeckleParams* sp)
+// The body of les_hip_post_process, les_hip_post_process_speckle and les_hip_post_process_masked: per view present, the failure mask -- the
+// left-right check when both views are there, OR the speckle mask when `sp` asks for one, OR the caller's own mask user[m] (H x W bytes on the
+// device, nonzero = failed; `user` or either entry may be null) -- its dilation and the fill; then per view the weighted median.
+int post_process_body(les_hip_ctx* c, les_hip_plane* const labels[2], float threshold, float omega, const SpeckleParams* sp,
+                      const unsigned char* const* user = nullptr)
 {
     const bool both = labels[0] && labels[1];
     for (int m = 0; m < 2; m++)
@@ -84,6 +86,7 @@ int post_process_body(les_hip_ctx* c, les_hip_plane* const labels[2], float thre
         if (both) hipLaunchKernelGGL(les::les_lr_check_kernel, g, b, 0, cur_stream(c), d_self, d_other, failm, H, W, sign, threshold);
         else HIPCHECK(hipMemsetAsync(failm, 0, P, cur_stream(c)));
         if (sp && sp->max_size > 0 && (rc = speckle_launch(c, ss, d_self, sp->max_size, sp->max_diff, failm, nullptr, nullptr, 1))) return rc;
+        if (user && user[m]) hipLaunchKernelGGL(les::les_fail_or_kernel, g, b, 0, cur_stream(c), (const uint8_t*)user[m], failm, H, W);
         hipLaunchKernelGGL(les::les_fail_dilate_kernel, g, b, 0, cur_stream(c), failm, failb, fail2, H, W);
         hipLaunchKernelGGL(les::les_nn_fill_kernel, g, b, 0, cur_stream(c), failb, fail2, lab, H, W);
     }
@@ -148,6 +151,18 @@ int les_hip_post_process_speckle(les_hip_ctx* c, les_hip_plane* d_labelsL, les_h
     les_hip_plane* labels[2] = {d_labelsL, d_labelsR};
     const SpeckleParams sp = {max_size, max_diff};
     return post_process_body(c, labels, threshold, omega, &sp);
+}
+
+int les_hip_post_process_masked(les_hip_ctx* c, les_hip_plane* d_labelsL, les_hip_plane* d_labelsR, float threshold, float omega, int max_size,
+                                float max_diff, const unsigned char* d_failL, const unsigned char* d_failR)
+{
+    if (!c || (!d_labelsL && !d_labelsR)) return fail(LES_HIP_ERR_ARG, "null argument");
+    const int rc = speckle_check_args(c, max_size, max_diff);
+    if (rc) return rc;
+    les_hip_plane* labels[2] = {d_labelsL, d_labelsR};
+    const unsigned char* user[2] = {d_failL, d_failR};
+    const SpeckleParams sp = {max_size, max_diff};
+    return post_process_body(c, labels, threshold, omega, &sp, user);
 }
 
 }  // extern "C"

@@ -1,11 +1,13 @@
 // les_hip_wtavol.inc -- part of the single translation unit les_hip.hip (included there; not compiled on its own): winner-take-all labels of the aggregated cost volume (les_wtavol.h holds the definition and the kernels) -- the reduction's two entry points and the whole operation for one view
 // What les_hip_wta_labels keeps on its context, built on first use and freed with the context: the K fronto-parallel planes, one prepared batch
 // per chunk length seen (n calls with filterRect = targetRect = the image, one slab each), the slab workspace and the reduction's state.
+// les_hip_confidence (les_hip_confidence.inc) shares all of it but the state.
 struct WtaVol {
     int K = 0; float d0 = 0.0f;                 // what d_planes holds: (0, 0, d0 + k, 0) for k < K
     DevBuf<float4> d_planes;
     std::vector<std::pair<int, les_hip_batch*>> batches;
     DevBuf<float> d_slabs, d_state;
+    DevBuf<float> d_conf_state;                 // les_hip_confidence's own state (les_hip_confidence.inc): a confidence call leaves the arg-min's alone
     ~WtaVol() { for (auto& b : batches) les_hip_batch_destroy(b.second); }
 };
 
@@ -44,6 +46,42 @@ int wtavol_batch(les_hip_ctx* c, WtaVol* w, int n, les_hip_batch** out)
     return LES_HIP_OK;
 }
 
+// K = int(max_disparity - min_disparity) + 1, or the refusal of a range that is negative, NaN or 65536 and more
+int wtavol_range(const les_hip_ctx* c, const char* who, int* K)
+{
+    const float range = c->p.max_disparity - c->p.min_disparity;
+    if (!(range >= 0.0f) || range >= 65536.0f) return fail(LES_HIP_ERR_ARG, "%s: disparity range [%g, %g]", who, (double)c->p.min_disparity, (double)c->p.max_disparity);
+    *K = (int)range + 1;
+    return LES_HIP_OK;
+}
+
+// What les_hip_wta_labels and les_hip_confidence share, on the calling thread's stream: the disparity range checked (*K planes), *chunk resolved
+// (<= 0: 32; clamped to K), the context's WtaVol with its K planes uploaded and its slab workspace grown to *chunk slabs.  Launches nothing.
+int wtavol_prepare(les_hip_ctx* c, const char* who, int* chunk, int* Kout)
+{
+    int K = 0;
+    int rc = wtavol_range(c, who, &K);
+    if (rc) return rc;
+    const float d0 = c->p.min_disparity;
+    if (*chunk <= 0) *chunk = 32;
+    *chunk = std::min(*chunk, K);
+    hipStream_t stream = cur_stream(c);
+    const size_t P = (size_t)c->p.H * c->p.W;
+    if (!c->wtavol) c->wtavol = new WtaVol();
+    WtaVol* w = c->wtavol;
+    if (w->K != K || w->d0 != d0) {
+        std::vector<float4> planes((size_t)K);
+        for (int k = 0; k < K; k++) planes[(size_t)k] = make_float4(0.0f, 0.0f, d0 + (float)k, 0.0f);
+        if ((rc = w->d_planes.grow((size_t)K, 0, stream))) return rc;
+        HIPCHECK(hipStreamSynchronize(stream));              // (an earlier call's launches may still read the old planes)
+        HIPCHECK(hipMemcpy(w->d_planes.p, planes.data(), (size_t)K * sizeof(float4), hipMemcpyHostToDevice));
+        w->K = K; w->d0 = d0;
+    }
+    if ((rc = w->d_slabs.grow((size_t)*chunk * P, 0, stream))) return rc;
+    *Kout = K;
+    return LES_HIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -79,25 +117,12 @@ int les_hip_wta_labels(les_hip_ctx* c, int mode, int chunk, int subpixel, les_hi
     int rc = view_ok(c, mode);
     if (rc) return rc;
     (void)hipSetDevice(c->p.device);                        // HIP's current device is per host thread
+    int K = 0;
+    if ((rc = wtavol_prepare(c, "les_hip_wta_labels", &chunk, &K))) return rc;
     const float d0 = c->p.min_disparity;
-    const float range = c->p.max_disparity - d0;
-    if (!(range >= 0.0f) || range >= 65536.0f) return fail(LES_HIP_ERR_ARG, "les_hip_wta_labels: disparity range [%g, %g]", (double)d0, (double)c->p.max_disparity);
-    const int K = (int)range + 1;
-    if (chunk <= 0) chunk = 32;
-    chunk = std::min(chunk, K);
     hipStream_t stream = cur_stream(c);
     const size_t P = (size_t)c->p.H * c->p.W;
-    if (!c->wtavol) c->wtavol = new WtaVol();
     WtaVol* w = c->wtavol;
-    if (w->K != K || w->d0 != d0) {
-        std::vector<float4> planes((size_t)K);
-        for (int k = 0; k < K; k++) planes[(size_t)k] = make_float4(0.0f, 0.0f, d0 + (float)k, 0.0f);
-        if ((rc = w->d_planes.grow((size_t)K, 0, stream))) return rc;
-        HIPCHECK(hipStreamSynchronize(stream));              // (an earlier call's launches may still read the old planes)
-        HIPCHECK(hipMemcpy(w->d_planes.p, planes.data(), (size_t)K * sizeof(float4), hipMemcpyHostToDevice));
-        w->K = K; w->d0 = d0;
-    }
-    if ((rc = w->d_slabs.grow((size_t)chunk * P, 0, stream))) return rc;
     if ((rc = w->d_state.grow(les::kArgminStatePlanes * les::argmin_plane_words(P), 0, stream))) return rc;
     const float4* d_planes = w->d_planes.p;
     float* d_slabs = w->d_slabs.p;

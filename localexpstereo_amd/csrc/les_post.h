@@ -42,6 +42,14 @@ __global__ void les_lr_check_kernel(const float* __restrict__ disp_self, const f
     fail[(size_t)y * W + x] = f;
 }
 
+// a caller's failure mask (nonzero = failed) OR-ed into the view's: les_hip_post_process_masked
+__global__ void les_fail_or_kernel(const uint8_t* __restrict__ user, uint8_t* __restrict__ fail, int H, int W)
+{
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= W) return;
+    if (user[(size_t)y * W + x]) fail[(size_t)y * W + x] = 255;
+}
+
 // fail > 0 -> 255, and its 3x3 dilation (cv::dilate default kernel; pixels outside the image do not contribute)
 __global__ void les_fail_dilate_kernel(const uint8_t* __restrict__ fail, uint8_t* __restrict__ failb, uint8_t* __restrict__ fail2, int H, int W)
 {

@@ -57,7 +57,7 @@ protected:
     struct NaiveTag {};
     HipCostVolumeEnergy(NaiveTag, const uint8_t* imL, const uint8_t* imR, int width, int height, Parameters p, float MAX_DISPARITY,
                         float MIN_DISPARITY, float MAX_VDISPARITY, int device)
-        : StereoEnergy(width, height, std::move(p), MAX_DISPARITY, MIN_DISPARITY, MAX_VDISPARITY), ctx_(nullptr)
+        : StereoEnergy(width, height, std::move(p), MAX_DISPARITY, MIN_DISPARITY, MAX_VDISPARITY), ctx_(nullptr), naive_(true)
     {
         const int filter = filter_kind(params.filterName);
         les_hip_params hp;
@@ -78,7 +78,7 @@ protected:
     // the half-resolution twin of `src` (half() below): adopts the context les_hip_create_half built
     struct HalfTag {};
     HipCostVolumeEnergy(HalfTag, const HipCostVolumeEnergy& src, les_hip_ctx* ctx, Parameters p)
-        : StereoEnergy((src.width + 1) / 2, (src.height + 1) / 2, std::move(p), 0.5f * src.MAX_DISPARITY, 0.5f * src.MIN_DISPARITY, 0.5f * src.MAX_VDISPARITY), ctx_(ctx)
+        : StereoEnergy((src.width + 1) / 2, (src.height + 1) / 2, std::move(p), 0.5f * src.MAX_DISPARITY, 0.5f * src.MIN_DISPARITY, 0.5f * src.MAX_VDISPARITY), ctx_(ctx), naive_(src.naive_)
     {
         std::vector<uint8_t> im[2];
         for (int m = 0; m < 2; m++) {
@@ -178,6 +178,38 @@ public:
         if (!ok) fprintf(stderr, "HipCostVolumeEnergy: %s\n", les_hip_last_error());
         if (d_lab) les_hip_free(ctx_, d_lab);
         if (d_cost) les_hip_free(ctx_, d_cost);
+        return ok;
+    }
+
+    // The largest value a raw matching cost of this energy can take: th_col for the volume energy (its costs are truncated there),
+    // (1 - alpha) th_col + alpha th_grad for the image-based one.  The default scale of confidence().
+    float rawCostMax() const { return naive_ ? (1.0f - params.alpha) * params.th_col + params.alpha * params.th_grad : params.th_col; }
+
+    // The confidence of a label map under view `mode`'s aggregated cost volume (les_hip_confidence, csrc/les_confidence.h; no reference
+    // counterpart): conf in [0, 1] per pixel -- how much cheaper the aggregated cost is within `band` slabs of the pixel's own disparity than
+    // anywhere else on its cost curve, (rival - own) / scale clamped; 0 for a label outside the disparity range or not finite, 1 where the band
+    // covers every finite cost.  own / rival / krival (may be null): the in-band and the rival minimum (+inf where none) and the rival's slab
+    // (-1 where none).  scale <= 0: rawCostMax(); chunk: planes per launch (0: the library's choice).  All maps: width * height elements in HOST
+    // memory.  Returns false (and reports on stderr) when the library refuses the call.
+    bool confidence(const Plane* labels, float* conf, float* own = nullptr, float* rival = nullptr, int* krival = nullptr, int mode = 0, float band = 1.f,
+                    float scale = 0.f, int chunk = 0) const
+    {
+        static_assert(sizeof(Plane) == sizeof(les_hip_plane), "ABI layout");
+        const size_t P = (size_t)width * height;
+        les_hip_plane* d_lab = nullptr;
+        float *d_conf = nullptr, *d_own = nullptr, *d_rival = nullptr;
+        int* d_kr = nullptr;
+        bool ok = les_hip_malloc(ctx_, (void**)&d_lab, P * sizeof(les_hip_plane)) == LES_HIP_OK && les_hip_malloc(ctx_, (void**)&d_conf, P * sizeof(float)) == LES_HIP_OK &&
+                  (!own || les_hip_malloc(ctx_, (void**)&d_own, P * sizeof(float)) == LES_HIP_OK) && (!rival || les_hip_malloc(ctx_, (void**)&d_rival, P * sizeof(float)) == LES_HIP_OK) &&
+                  (!krival || les_hip_malloc(ctx_, (void**)&d_kr, P * sizeof(int)) == LES_HIP_OK);
+        ok = ok && les_hip_memcpy_h2d(ctx_, d_lab, labels, P * sizeof(les_hip_plane)) == LES_HIP_OK;
+        ok = ok && les_hip_confidence(ctx_, mode, d_lab, chunk, band, scale > 0.f ? scale : rawCostMax(), d_conf, d_own, d_rival, d_kr) == LES_HIP_OK &&
+             les_hip_synchronize(ctx_) == LES_HIP_OK;
+        ok = ok && les_hip_memcpy_d2h(ctx_, conf, d_conf, P * sizeof(float)) == LES_HIP_OK && (!own || les_hip_memcpy_d2h(ctx_, own, d_own, P * sizeof(float)) == LES_HIP_OK) &&
+             (!rival || les_hip_memcpy_d2h(ctx_, rival, d_rival, P * sizeof(float)) == LES_HIP_OK) && (!krival || les_hip_memcpy_d2h(ctx_, krival, d_kr, P * sizeof(int)) == LES_HIP_OK);
+        if (!ok) fprintf(stderr, "HipCostVolumeEnergy: %s\n", les_hip_last_error());
+        for (void* q : {(void*)d_lab, (void*)d_conf, (void*)d_own, (void*)d_rival, (void*)d_kr})
+            if (q) les_hip_free(ctx_, q);
         return ok;
     }
 
@@ -323,6 +355,7 @@ private:
     }
 
     les_hip_ctx* ctx_;
+    bool naive_ = false;                 // the image-based energy (HipNaiveStereoEnergy): what rawCostMax() tells apart
     mutable std::mutex mu_;
 };
 

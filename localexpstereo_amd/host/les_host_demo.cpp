@@ -292,6 +292,19 @@ static int cmd_run(int argc, char** argv)
             tbad += !(wta[i].a == 0.f && wta[i].b == 0.f && wta[i].v == 0.f && std::isfinite(wta[i].c) && std::isfinite(wcost[i])) || memcmp(&wta[i], &wta2[i], sizeof(Plane)) != 0;
         printf("wtaLabels: %zu of %zu pixels are not a finite fronto-parallel plane or depend on the chunking\n", tbad, P);
         if (!okt || tbad) { printf("FAIL: wtaLabels\n"); fail = 1; }
+        // the confidence of that map through the adapter: in [0, 1], the in-band minimum of a WTA label is the WTA cost itself and no rival lies
+        // below it, and the chunking does not change a bit
+        std::vector<float> conf(P), conf2(P), cown(P), crival(P);
+        std::vector<int> ckr(P);
+        const bool okc = hip.confidence(wta.data(), conf.data(), cown.data(), crival.data(), ckr.data(), 0) &&
+                         hip.confidence(wta.data(), conf2.data(), nullptr, nullptr, nullptr, 0, 1.f, 0.f, 3);
+        size_t qbad = 0, qpos = 0;
+        for (size_t i = 0; i < P; i++) {
+            qbad += !(conf[i] >= 0.f && conf[i] <= 1.f) || memcmp(&conf[i], &conf2[i], sizeof(float)) != 0 || cown[i] != wcost[i] || (ckr[i] >= 0 && crival[i] < cown[i]);
+            qpos += conf[i] > 0.f;
+        }
+        printf("confidence: %zu of %zu pixels are outside [0, 1], disagree with the WTA cost or depend on the chunking; %zu are above 0\n", qbad, P, qpos);
+        if (!okc || qbad || !qpos) { printf("FAIL: confidence\n"); fail = 1; }
         // the planes fitted to that map through the adapter: every pixel a finite plane of its kind, from the labels and from their disparities alike
         std::vector<Plane> fit(P), fit2(P);
         std::vector<unsigned char> kind(P);

@@ -225,3 +225,29 @@ class Evaluator:
         all_ = 100.0 * (1.0 - (good & self.valid).sum() / nv) if nv else float("nan")
         non_ = 100.0 * (1.0 - (good & self.nonocc).sum() / nn) if nn else float("nan")
         return float(all_), float(non_)
+
+
+def sparsification(disp, gt, conf, valid=None, threshold=1.0):
+    """How well a confidence map ranks the errors of a disparity map (the sparsification curve of the confidence literature), in host numpy.
+    valid: the pixels that count (None: gt > 0 and finite, as the Evaluator); a valid pixel is bad when not |disp - gt| <= threshold (a
+    non-finite disparity is bad).  The valid pixels are ordered by descending confidence with a stable sort (a NaN confidence ranks last);
+    -> dict(bad: the bad-pixel rate of all valid pixels, which is what a random order gives in expectation; auc: the mean, over every prefix
+    of that order, of the bad-pixel rate of the prefix -- the area under the curve "rate of the n most confident pixels"; auc_optimal: the
+    same with the pixels ordered by the error itself, the least any confidence can reach).  Rates are fractions in [0, 1]; NaN without a valid
+    pixel."""
+    disp, gt, conf = np.asarray(disp, np.float32), np.asarray(gt, np.float32), np.asarray(conf, np.float32)
+    if not disp.shape == gt.shape == conf.shape:
+        raise ValueError(f"sparsification: maps of one shape, not {disp.shape}, {gt.shape}, {conf.shape}")
+    valid = (gt > 0) & np.isfinite(gt) if valid is None else np.asarray(valid, bool)
+    n = int(valid.sum())
+    if n == 0:
+        return dict(bad=float("nan"), auc=float("nan"), auc_optimal=float("nan"))
+    with np.errstate(invalid="ignore"):
+        err = np.abs(disp[valid].astype(np.float64) - gt[valid])
+    err = np.where(np.isnan(err), np.inf, err)
+    bad = ~(err <= threshold)
+    c = conf[valid].astype(np.float64)
+    c = np.where(np.isnan(c), -np.inf, c)
+    counts = np.arange(1, n + 1, dtype=np.float64)
+    area = lambda order: float((np.cumsum(bad[order], dtype=np.float64) / counts).mean())
+    return dict(bad=float(bad.mean()), auc=area(np.argsort(-c, kind="stable")), auc_optimal=area(np.argsort(err, kind="stable")))

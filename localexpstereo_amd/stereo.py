@@ -26,8 +26,22 @@ PARAMS_BF = dict(PARAMS_GF, lambda_=20.0, windR=20, eps=10.0, filter="BF")
 class FastGCStereo:
     def __init__(self, energy, imL, imR, params, device="cuda", rank=0, world=1, seed=1, host_threads=0, device_cuts=None, random_vdisp=None,
                  evaluate_on_device=False, inner_loop_log=False, check_flow_energy=False, recost_after_post=False, cross_view=0, coarse_params=None,
-                 speckle=None):
+                 speckle=None, confidence=False, min_confidence=None, confidence_band=1.0):
         self.e, self.imL, self.imR, self.p = energy, imL, imR, dict(PARAMS_GF, **params)
+        # Opt-in, no reference counterpart (csrc/les_confidence.h): confidence=True -- run(), wta() and sgm() set self.confidences = {view: H x W
+        # float32 in [0, 1]}, the confidence of each view's RAW labelling (before the post-processing) under that view's aggregated cost volume
+        # (les_hip_confidence: how much cheaper the cost is within confidence_band slabs of the pixel's own disparity than anywhere else on its cost
+        # curve), taken on the device; the returned labellings are unchanged.  min_confidence=t, 0 < t <= 1, implies it and adds conf < t to each
+        # view's failure mask of the post-processing (les_hip_post_process_masked), and a one-view call is then post-processed with that mask (and
+        # the speckle mask, when set) alone.  Single rank.  The defaults change nothing.
+        self.min_confidence = None if min_confidence is None else float(min_confidence)
+        if self.min_confidence is not None and not 0.0 < self.min_confidence <= 1.0:
+            raise ValueError(f"min_confidence {min_confidence}: None or a threshold in (0, 1]")
+        self.confidence_band = float(confidence_band)
+        if not self.confidence_band >= 0.0:
+            raise ValueError(f"confidence_band {confidence_band}: a half-width in slabs, >= 0")
+        self.with_confidence = bool(confidence) or self.min_confidence is not None
+        self.confidences = {}                     # run(), wta(), sgm() with confidence=True: view -> the H x W confidence map of its raw labelling
         # Opt-in, no reference counterpart: (max_size, max_diff) -- the post-processing step of run(), wta() and sgm() also treats as failed every
         # pixel whose connected component of the view's disparity map (4-neighbours within max_diff) has at most max_size pixels
         # (les_hip_post_process_speckle, csrc/les_speckle.h), and a one-view call, which has no left-right check, is post-processed with that mask
@@ -297,6 +311,27 @@ class FastGCStereo:
                 self.cross_stats[m].update(energy_before=before[m], energy_after=sum(runners[m].energy(self._pairwise())))
             return {m: runners[m].labels.cpu().numpy().copy() for m in (0, 1)}
 
+    def confidence(self, labeling, viewMode=0, **kw):
+        """The confidence of any H x W x 4 label map of view viewMode under that view's aggregated cost volume (no reference counterpart;
+        csrc/les_confidence.h; api.HipCostVolumeEnergy.confidence, whose keywords -- band (default: confidence_band), scale, chunk, parts -- kw
+        passes on).  -> the H x W float32 map in [0, 1]; parts=True: (conf, own, rival, k_rival).  Single rank."""
+        if self.world > 1:
+            raise NotImplementedError("FastGCStereo.confidence is single-rank: the multi-rank form is not implemented")
+        out = self.e.confidence(labeling, mode=int(viewMode), device=self.device, **dict(dict(band=self.confidence_band), **kw))
+        self.e.synchronize()
+        return tuple(t.cpu().numpy() for t in out) if isinstance(out, tuple) else out.cpu().numpy()
+
+    def _confidences(self, maps):
+        """With confidence=True: self.confidences of the device label maps {view: map} as they are (raw), -> {view: the device confidence map};
+        otherwise {} (and self.confidences is emptied)."""
+        self.confidences = {}
+        if not self.with_confidence:
+            return {}
+        conf = {m: self.e.confidence(lab, mode=m, band=self.confidence_band, device=self.device) for m, lab in maps.items()}
+        self.e.synchronize()
+        self.confidences = {m: c.cpu().numpy() for m, c in conf.items()}
+        return conf
+
     def wta(self, viewModes=(0,), post_process=True, subpixel=True, slanted=False):
         """Cost-volume filtering without a graph cut (no reference counterpart; csrc/les_wtavol.h): every view of viewModes gets the winner-take-all
         map of its filtered cost volume -- per pixel the fronto-parallel plane of least aggregated cost, refined to sub-pixel when `subpixel`
@@ -359,22 +394,30 @@ class FastGCStereo:
                     ev = self._device_evaluator(stack, 1, rates=m == 0) if self.evaluate_on_device else None
                     self.log.append(dict(index=m, mode=m) | self._row(maps[m][0], maps[m][1], m, m, t0, ev=ev, rates=m == 0))
                 self.eval_seconds += time.perf_counter() - te
+        conf = self._confidences({m: maps[m][0] for m in views})
         if post_process and self._post_processes(views):
-            self._post_process({m: maps[m][0] for m in views})
+            self._post_process({m: maps[m][0] for m in views}, conf)
             self.e.synchronize()
         lab = maps[0][0].cpu().numpy().copy() if 0 in maps else None
         self.seconds = time.perf_counter() - t0 - self.eval_seconds
         return lab, self.raw_labelings.get(0)
 
     def _post_processes(self, views):
-        """Whether a call over `views` ends with the post-processing: two views always, one view when a speckle filter is set."""
-        return len(views) == 2 or self.speckle is not None
+        """Whether a call over `views` ends with the post-processing: two views always, one view when a speckle filter or min_confidence is set."""
+        return len(views) == 2 or self.speckle is not None or self.min_confidence is not None
 
-    def _post_process(self, maps):
+    def _post_process(self, maps, conf=None):
         """The post-processing step of run(), wta() and sgm() in place on the device label maps {view: map}: threshold 1.5, the run's omega
-        (LES/FastGCStereo.h:202), (left, right) whatever the order of the views; with self.speckle the widened mask, and the one-view form."""
+        (LES/FastGCStereo.h:202), (left, right) whatever the order of the views; with self.speckle the widened mask, and the one-view form; with
+        self.min_confidence each view's mask widened by conf[view] < min_confidence (conf: what _confidences returned for the same maps)."""
         ptr = {m: maps[m].data_ptr() if m in maps else None for m in (0, 1)}
-        if self.speckle is None:
+        if self.min_confidence is not None:
+            low = {m: (conf[m] < self.min_confidence).to(torch.uint8).contiguous() for m in maps}
+            if any(t.is_cuda for t in low.values()):     # (torch made the masks on its stream; the library reads them on the context's)
+                torch.cuda.current_stream().synchronize()
+            self.e.post_process(ptr[0], ptr[1], 1.5, self.p["omega"], speckle=self.speckle, fail=tuple(low[m].data_ptr() if m in low else None for m in (0, 1)))
+            self.e.synchronize()                 # (the masks live until the launches that read them are done)
+        elif self.speckle is None:
             self.e.post_process(ptr[0], ptr[1], 1.5, self.p["omega"])
         else:
             self.e.post_process(ptr[0], ptr[1], 1.5, self.p["omega"], speckle=self.speckle)
@@ -391,6 +434,8 @@ class FastGCStereo:
                                  "one holds no volume) has none it can use")
             if self.world > 1:
                 raise NotImplementedError(f"labeling=\"{labeling}\" is single-rank: the multi-rank start is not implemented")
+        if self.with_confidence and self.world > 1:
+            raise NotImplementedError("confidence / min_confidence are single-rank: the multi-rank form is not implemented")
         if self.inner_loop_log and self.world > 1:
             raise ValueError("inner_loop_log is a single-rank log: with several ranks a rank holds only its band of a set's cells until the exchange")
         if self.cross_view > 0:
@@ -634,8 +679,9 @@ class FastGCStereo:
             self._collect_stats(runners)
             return None, None
         self.raw_labelings = {m: final[m].cpu().numpy().copy() for m in all_views}
+        conf = self._confidences(final)
         if self._post_processes(all_views):
-            self._post_process(final)
+            self._post_process(final, conf)
             if self.recost_after_post:
                 for r in runners.values():
                     r.recost()
