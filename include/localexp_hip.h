@@ -592,6 +592,40 @@ int les_hip_post_process_masked(les_hip_ctx* ctx, les_hip_plane* d_labelsL /* or
                                 float omega, int max_size, float max_diff, const unsigned char* d_failL /* or NULL */,
                                 const unsigned char* d_failR /* or NULL */);
 
+/* ---- 3D reconstruction: points, normals and a mesh from a label map (csrc/les_reproject.h holds the definition; the reference only paints
+ * the normals as a picture, computeNormalMap, LES/StereoEnergy.h:274-289) ----
+ * The calibration of a rectified pinhole pair, Middlebury v3's calib.txt: f = cam0[0][0], cx = cam0[0][2], cy = cam0[1][2] (pixels), doffs
+ * (pixels) and baseline (any length unit: the points come out in it).  View m has cx_m = cx + (m ? doffs : 0); each view's points are in
+ * that view's own camera frame, X right, Y down, Z forward, so X_left = X_right + baseline. */
+typedef struct les_hip_calib {
+    float f, cx, cy, doffs, baseline;
+} les_hip_calib;
+/* Per pixel (x, y) of the device label map of view `mode`, d = (a x + b y) + c in float, un-fused; then in double, rounded to float once:
+ * D = d + doffs, Z = (f baseline) / D, X = ((x - cx_m) Z) / f, Y = ((y - cy) Z) / f, and the unit normal -n / |n| of the label's plane,
+ * n = (a f, b f, ((a cx_m + b cy) + c) + doffs) -- the plane is exactly n . P = f baseline, and the normal faces the camera.  A pixel is valid
+ * iff d is finite, D > 0, d_drop_mask (H x W bytes or NULL) is zero there, and Z <= z_max when z_max > 0.  d_points / d_normals: H x W x 3
+ * floats each (either may be NULL), NaN at invalid pixels; d_valid: H x W bytes, 255 / 0.  Enqueue only (the calling thread's stream).
+ * A null context, label map, calibration or valid map, a view not supplied at creation, f or baseline not finite or <= 0: LES_HIP_ERR_ARG;
+ * H W >= 2^31: LES_HIP_ERR_UNSUPPORTED. */
+int les_hip_reproject(les_hip_ctx* ctx, int mode, const les_hip_plane* d_labels, const unsigned char* d_drop_mask /* or NULL */,
+                      const les_hip_calib* calib, float z_max, float* d_points /* or NULL */, float* d_normals /* or NULL */,
+                      unsigned char* d_valid);
+/* The triangle mesh over the pixel grid.  Pixels p, q are connected iff d_valid is nonzero at both and
+ * |l_p(p) - l_q(p)| + |l_p(q) - l_q(q)| <= max_jump in float (the un-truncated pairwise term, LES/StereoEnergy.h:238-241; +inf connects every
+ * valid neighbour).  Quad (x, y) with corners p00, p10, p01, p11 (first index: the x offset) yields T0 = (p00, p01, p10) and
+ * T1 = (p10, p01, p11) -- the order whose geometric normal faces the camera -- each emitted iff its three edges are connected.  Vertex k is
+ * the k-th valid pixel in row-major order; triangles are in row-major quad order, T0 before T1: a function of the inputs alone.
+ * d_vertex_index: H x W ints, the pixel's vertex number or -1; d_vertex_pixel: room for H W ints, entry k = the linear pixel index of vertex
+ * k; d_triangles: room for 2 (H - 1) (W - 1) x 3 ints (at least 1), vertex numbers; d_counts: two long longs on the device, the vertex and
+ * the triangle count.  Four launches (count, scan, two emits), no atomics, no workgroup waits on another.  The tile workspace is kept on the
+ * context per view: once it exists a call only enqueues on the calling thread's stream.  A null argument, a view not supplied at creation,
+ * max_jump negative or NaN: LES_HIP_ERR_ARG; H W >= 2^31: LES_HIP_ERR_UNSUPPORTED. */
+int les_hip_mesh(les_hip_ctx* ctx, int mode, const les_hip_plane* d_labels, const unsigned char* d_valid, float max_jump, int* d_vertex_index,
+                 int* d_vertex_pixel, int* d_triangles, long long* d_counts);
+/* The flat run of pixels one workgroup of the mesh kernels owns and the tiles the scan takes per turn of its loop: the compiled-in geometry,
+ * for tests and diagnostics. */
+int les_hip_mesh_tile(int* pixels, int* scan_width);
+
 /* ---- multi-GPU: publishing the tiles a rank updated (not in the reference, which is single-process; SURVEY 8(e): the cells of a
  * disjoint set -- LES/LayerManager.h:168-172 -- are split over the ranks, replicas of the label / cost maps are kept coherent by one
  * all-gather per set of the label (16 B/px) and cost (4 B/px) tiles of the shared regions, LES/FastGCStereo.h:22-72).

@@ -34,6 +34,7 @@ SYMBOLS = [
     "les_hip_pool_image", "les_hip_pool_volume", "les_hip_create_half", "les_hip_get_image", "les_hip_upsample_labels",
     "les_hip_speckle_mask", "les_hip_speckle_tile", "les_hip_post_process_speckle",
     "les_hip_slab_confidence_state_bytes", "les_hip_slab_confidence", "les_hip_slab_confidence_finish", "les_hip_confidence", "les_hip_post_process_masked",
+    "les_hip_reproject", "les_hip_mesh", "les_hip_mesh_tile",
 ]
 
 
@@ -66,6 +67,11 @@ class EvalRow(C.Structure):
     """les_hip_eval_row (include/localexp_hip.h)."""
     _fields_ = [("index", C.c_int), ("mode", C.c_int), ("data", C.c_double), ("smooth", C.c_double), ("good_valid", C.c_longlong),
                 ("good_nonocc", C.c_longlong), ("n_valid", C.c_longlong), ("n_nonocc", C.c_longlong)]
+
+
+class Calib(C.Structure):
+    """les_hip_calib (include/localexp_hip.h): a rectified pinhole pair; io.calib3d makes one from a Middlebury calib.txt."""
+    _fields_ = [("f", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("doffs", C.c_float), ("baseline", C.c_float)]
 
 
 class Params(C.Structure):
@@ -200,6 +206,9 @@ def load(path=None):
         "les_hip_slab_confidence_finish": (ci, [vp, vp, C.c_float, vp, vp, vp, vp]),
         "les_hip_confidence": (ci, [vp, ci, vp, ci, C.c_float, C.c_float, vp, vp, vp, vp]),
         "les_hip_post_process_masked": (ci, [vp, vp, vp, C.c_float, C.c_float, ci, C.c_float, vp, vp]),
+        "les_hip_reproject": (ci, [vp, ci, vp, vp, C.POINTER(Calib), C.c_float, vp, vp, vp]),
+        "les_hip_mesh": (ci, [vp, ci, vp, vp, C.c_float, vp, vp, vp, vp]),
+        "les_hip_mesh_tile": (ci, [C.POINTER(ci), C.POINTER(ci)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -987,6 +996,98 @@ class HipCostVolumeEnergy:
         self.fit_planes_ptr(mode, s.data_ptr() if labels else None, None if labels else s.data_ptr(), fb.data_ptr() if fb is not None else None,
                             out.data_ptr(), kind.data_ptr() if with_kind else None, **params)
         return (out, kind) if with_kind else out
+
+    # -- 3D reconstruction: points, normals and a mesh from a label map (csrc/les_reproject.h; no reference counterpart) --------------------
+    def _label_map(self, labels, dev, who):
+        """The H x W x 4 float32 label map on dev: a tensor that is there already is used where it is."""
+        import torch
+        if torch.is_tensor(labels) and labels.device == dev and labels.dtype == torch.float32:
+            s = labels.contiguous()
+        elif torch.is_tensor(labels):
+            s = labels.to(device=dev, dtype=torch.float32).contiguous()
+        else:
+            s = torch.from_numpy(np.array(labels, dtype=np.float32, order="C")).to(dev)
+        if tuple(s.shape) != (self.H, self.W, 4):
+            raise ValueError(f"{who}: a {self.H} x {self.W} x 4 label map, not {tuple(s.shape)}")
+        return s
+
+    def _byte_map(self, mask, dev, who):
+        import torch
+        if torch.is_tensor(mask) and mask.device == dev and mask.dtype == torch.uint8:
+            m = mask.contiguous()
+        elif torch.is_tensor(mask):
+            m = (mask != 0).to(device=dev, dtype=torch.uint8).contiguous()
+        else:
+            m = torch.from_numpy((np.asarray(mask) != 0).astype(np.uint8)).to(dev)
+        if tuple(m.shape) != (self.H, self.W):
+            raise ValueError(f"{who}: a {self.H} x {self.W} mask, not {tuple(m.shape)}")
+        return m
+
+    def reproject_ptr(self, mode, labels_ptr, drop_ptr, calib, z_max, points_ptr, normals_ptr, valid_ptr):
+        """les_hip_reproject on device addresses (drop_ptr, points_ptr and normals_ptr may be None; calib: a Calib or None).  Enqueue only."""
+        vp = lambda p: C.c_void_p(int(p)) if p else None
+        self._chk(self.L.les_hip_reproject(self.h, int(mode), vp(labels_ptr), vp(drop_ptr), C.byref(calib) if calib is not None else None,
+                                           C.c_float(0.0 if z_max is None else z_max), vp(points_ptr), vp(normals_ptr), vp(valid_ptr)))
+
+    def reproject(self, labels, calib, mode=0, drop=None, z_max=None, device=None):
+        """les_hip_reproject: the H x W x 4 label map of view `mode` as 3D geometry -- (points, normals, valid): per pixel the point (X, Y, Z) of
+        its disparity d = a x + b y + c and the unit normal of its label's plane, both H x W x 3 float32 in the view's own camera frame (X right,
+        Y down, Z forward; the normal faces the camera), and valid, H x W uint8 255 / 0.  calib: a Calib (io.calib3d); Z = f baseline / (d + doffs),
+        view 1 has its principal point at cx + doffs, so X_left = X_right + baseline.  A pixel is invalid -- NaN in both maps -- where d is not
+        finite, d + doffs <= 0, `drop` (an H x W mask, nonzero = drop) is set, or Z > z_max (z_max None or <= 0: no limit).  The arithmetic is
+        fp64 from the float inputs, rounded once (csrc/les_reproject.h).  labels / drop: torch tensors (on `device`: used where they are) or
+        arrays.  -> new tensors on `device` (None: this context's GPU; the simulator build takes "cpu").  Asynchronous on the calling thread's
+        stream."""
+        import torch
+        dev = torch.device(device if device is not None else f"cuda:{self.params.device}")
+        s = self._label_map(labels, dev, "reproject")
+        m = self._byte_map(drop, dev, "reproject") if drop is not None else None
+        points = torch.empty((self.H, self.W, 3), dtype=torch.float32, device=dev)
+        normals = torch.empty((self.H, self.W, 3), dtype=torch.float32, device=dev)
+        valid = torch.empty((self.H, self.W), dtype=torch.uint8, device=dev)
+        copied = s is not labels or (m is not None and m is not drop)
+        if copied and dev.type == "cuda":        # (torch made the copies on its stream; the library reads them on the context's)
+            torch.cuda.current_stream(dev).synchronize()
+        self.reproject_ptr(mode, s.data_ptr(), m.data_ptr() if m is not None else None, calib, z_max, points.data_ptr(), normals.data_ptr(), valid.data_ptr())
+        if copied:                               # (a copy made here must outlive the launch that reads it)
+            self.synchronize()
+        return points, normals, valid
+
+    def mesh_tile(self):
+        """les_hip_mesh_tile: (pixels a workgroup of the mesh kernels owns, tiles the scan takes per turn)."""
+        a, b = C.c_int(0), C.c_int(0)
+        self._chk(self.L.les_hip_mesh_tile(C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def mesh_ptr(self, mode, labels_ptr, valid_ptr, max_jump, vertex_index_ptr, vertex_pixel_ptr, triangles_ptr, counts_ptr):
+        """les_hip_mesh on device addresses (vertex_index H x W int32, vertex_pixel H W int32, triangles 2 (H - 1) (W - 1) x 3 int32, counts two
+        int64).  Enqueue only once the context's tile workspace exists."""
+        vp = lambda p: C.c_void_p(int(p)) if p else None
+        self._chk(self.L.les_hip_mesh(self.h, int(mode), vp(labels_ptr), vp(valid_ptr), C.c_float(max_jump), vp(vertex_index_ptr), vp(vertex_pixel_ptr),
+                                      vp(triangles_ptr), vp(counts_ptr)))
+
+    def mesh(self, labels, valid, max_jump, mode=0, device=None):
+        """les_hip_mesh: the triangle mesh over the pixel grid of the H x W x 4 label map -- (vertex_index, vertex_pixel, triangles).  Vertex k is
+        the k-th pixel of `valid` (H x W, nonzero = valid: reproject's map) in row-major order: vertex_index is H x W int32 (-1 where invalid),
+        vertex_pixel[k] the linear pixel index of vertex k.  Two pixels are connected iff both are valid and the un-truncated pairwise term of
+        their labels, |l_p(p) - l_q(p)| + |l_p(q) - l_q(q)|, is <= max_jump (inf: every valid neighbour); quad (x, y) yields the triangles
+        (p00, p01, p10) and (p10, p01, p11), each iff its three edges are connected, in row-major quad order, as nt x 3 int32 vertex numbers
+        whose winding faces the camera.  The order is a function of the inputs alone.  -> new tensors on `device`, cut to the counts (which
+        waits for the device)."""
+        import torch
+        dev = torch.device(device if device is not None else f"cuda:{self.params.device}")
+        s = self._label_map(labels, dev, "mesh")
+        m = self._byte_map(valid, dev, "mesh")
+        vi = torch.empty((self.H, self.W), dtype=torch.int32, device=dev)
+        vpix = torch.empty((self.H * self.W,), dtype=torch.int32, device=dev)
+        tri = torch.empty((max(1, 2 * (self.H - 1) * (self.W - 1)), 3), dtype=torch.int32, device=dev)
+        counts = torch.zeros((2,), dtype=torch.int64, device=dev)
+        if dev.type == "cuda":                   # (torch made the copies and the zeros on its stream; the library works on the context's)
+            torch.cuda.current_stream(dev).synchronize()
+        self.mesh_ptr(mode, s.data_ptr(), m.data_ptr(), max_jump, vi.data_ptr(), vpix.data_ptr(), tri.data_ptr(), counts.data_ptr())
+        self.synchronize()
+        nv, nt = (int(v) for v in counts.cpu())
+        return vi, vpix[:nv], tri[:nt]
 
     # -- a half-resolution solve as a start (csrc/les_pyramid.h; no reference counterpart) ------------------------------------
     def image(self, mode=0):

@@ -26,6 +26,7 @@
 #include "les_planefit.h"
 #include "les_pyramid.h"
 #include "les_speckle.h"
+#include "les_reproject.h"
 
 #include "../host/ResidualCut.h"      // the host cores' finisher of the tiled max-flow (plain C++: search trees / push-relabel on a residual graph)
 
@@ -202,6 +203,7 @@ struct les_hip_ctx {
     WtaVol* wtavol = nullptr;            // les_hip_wta_labels' planes, batches, slab workspace and state, and les_hip_confidence's own state (les_hip_wtavol.inc), built on first use, freed by les_hip_destroy
     SgmWork* sgm = nullptr;              // les_hip_sgm_labels' transposed volume and path sums (les_hip_sgm.inc), built on first use, freed by les_hip_destroy
     FitTables* fit_tables = nullptr;     // les_hip_fit_planes' weight tables, one per sig seen (les_hip_planefit.inc), built on first use, freed by les_hip_destroy
+    DevBuf<long long> mesh_ws[2];        // les_hip_mesh's tile offsets and counts, one per view (les_hip_reproject.inc), grown under the lock, later calls only enqueue
     std::vector<MtHost*> mt_idle; // host-mapped flag words + hand-over staging of the tiled max-flow: one per CONCURRENT caller, reused, freed with the context
     // what stays raw (les_hip_mem.h): the views' buffers and d_planes; every other table frees itself
     ~les_hip_ctx()
@@ -321,3 +323,4 @@ float naive_alpha(const les_hip_ctx* c) { return c->naive_alpha; }
 #include "les_hip_sgm.inc"
 #include "les_hip_planefit.inc"
 #include "les_hip_pyramid.inc"
+#include "les_hip_reproject.inc"

@@ -10,6 +10,7 @@
 // no HIP device / library is available -- there is no CPU fallback.
 #pragma once
 
+#include <algorithm>
 #include <cstdio>
 #include <memory>
 #include <mutex>
@@ -302,6 +303,67 @@ public:
              (!size || les_hip_memcpy_d2h(ctx_, size, d_size, P * sizeof(int)) == LES_HIP_OK);
         if (!ok) fprintf(stderr, "HipCostVolumeEnergy: %s\n", les_hip_last_error());
         for (void* q : {(void*)d_lab, (void*)d_mask, (void*)d_root, (void*)d_size})
+            if (q) les_hip_free(ctx_, q);
+        return ok;
+    }
+
+    // 3D geometry of a label map of view `mode` (les_hip_reproject, csrc/les_reproject.h; the reference only paints computeNormalMap): per pixel
+    // the point of its disparity and the exact unit normal of its label's plane in the view's own camera frame (X right, Y down, Z forward;
+    // the normal faces the camera), width * height * 3 floats each (either may be null), NaN where invalid; valid: width * height bytes, 255 / 0.
+    // drop (may be null): width * height bytes, nonzero = invalid; z_max <= 0: no depth limit.  All maps in HOST memory.  Returns false (and
+    // reports on stderr) when the library refuses the call.
+    bool reproject(const Plane* labels, const les_hip_calib& calib, float* points, float* normals, unsigned char* valid, int mode = 0,
+                   const unsigned char* drop = nullptr, float z_max = 0.f) const
+    {
+        static_assert(sizeof(Plane) == sizeof(les_hip_plane), "ABI layout");
+        const size_t P = (size_t)width * height;
+        les_hip_plane* d_lab = nullptr;
+        unsigned char *d_drop = nullptr, *d_valid = nullptr;
+        float *d_points = nullptr, *d_normals = nullptr;
+        bool ok = les_hip_malloc(ctx_, (void**)&d_lab, P * sizeof(les_hip_plane)) == LES_HIP_OK && les_hip_malloc(ctx_, (void**)&d_valid, P) == LES_HIP_OK &&
+                  (!drop || les_hip_malloc(ctx_, (void**)&d_drop, P) == LES_HIP_OK) && (!points || les_hip_malloc(ctx_, (void**)&d_points, 3 * P * sizeof(float)) == LES_HIP_OK) &&
+                  (!normals || les_hip_malloc(ctx_, (void**)&d_normals, 3 * P * sizeof(float)) == LES_HIP_OK);
+        ok = ok && les_hip_memcpy_h2d(ctx_, d_lab, labels, P * sizeof(les_hip_plane)) == LES_HIP_OK && (!drop || les_hip_memcpy_h2d(ctx_, d_drop, drop, P) == LES_HIP_OK);
+        ok = ok && les_hip_reproject(ctx_, mode, d_lab, d_drop, &calib, z_max, d_points, d_normals, d_valid) == LES_HIP_OK && les_hip_synchronize(ctx_) == LES_HIP_OK;
+        ok = ok && les_hip_memcpy_d2h(ctx_, valid, d_valid, P) == LES_HIP_OK && (!points || les_hip_memcpy_d2h(ctx_, points, d_points, 3 * P * sizeof(float)) == LES_HIP_OK) &&
+             (!normals || les_hip_memcpy_d2h(ctx_, normals, d_normals, 3 * P * sizeof(float)) == LES_HIP_OK);
+        if (!ok) fprintf(stderr, "HipCostVolumeEnergy: %s\n", les_hip_last_error());
+        for (void* q : {(void*)d_lab, (void*)d_drop, (void*)d_valid, (void*)d_points, (void*)d_normals})
+            if (q) les_hip_free(ctx_, q);
+        return ok;
+    }
+
+    // The triangle mesh over the pixel grid (les_hip_mesh): vertex k is the k-th valid pixel in row-major order; neighbours are joined iff both are
+    // valid and the un-truncated pairwise term of their labels is <= max_jump (the energy's th_smooth is the natural choice); quad (x, y) yields
+    // (p00, p01, p10) and (p10, p01, p11), each iff its three edges are joined, in row-major quad order.  vertex_index: width * height ints (-1
+    // where invalid); vertex_pixel: the linear pixel index per vertex; triangles: 3 vertex numbers each.  HOST memory; the vectors are resized
+    // to the counts.  Returns false (and reports on stderr) when the library refuses the call.
+    bool mesh(const Plane* labels, const unsigned char* valid, float max_jump, std::vector<int>& vertex_index, std::vector<int>& vertex_pixel,
+              std::vector<int>& triangles, int mode = 0) const
+    {
+        static_assert(sizeof(Plane) == sizeof(les_hip_plane), "ABI layout");
+        const size_t P = (size_t)width * height, T = std::max<size_t>(1, 2 * (size_t)(width - 1) * (size_t)(height - 1));
+        les_hip_plane* d_lab = nullptr;
+        unsigned char* d_valid = nullptr;
+        int *d_vi = nullptr, *d_vp = nullptr, *d_tri = nullptr;
+        long long* d_counts = nullptr;
+        long long counts[2] = {0, 0};
+        bool ok = les_hip_malloc(ctx_, (void**)&d_lab, P * sizeof(les_hip_plane)) == LES_HIP_OK && les_hip_malloc(ctx_, (void**)&d_valid, P) == LES_HIP_OK &&
+                  les_hip_malloc(ctx_, (void**)&d_vi, P * sizeof(int)) == LES_HIP_OK && les_hip_malloc(ctx_, (void**)&d_vp, P * sizeof(int)) == LES_HIP_OK &&
+                  les_hip_malloc(ctx_, (void**)&d_tri, 3 * T * sizeof(int)) == LES_HIP_OK && les_hip_malloc(ctx_, (void**)&d_counts, sizeof counts) == LES_HIP_OK;
+        ok = ok && les_hip_memcpy_h2d(ctx_, d_lab, labels, P * sizeof(les_hip_plane)) == LES_HIP_OK && les_hip_memcpy_h2d(ctx_, d_valid, valid, P) == LES_HIP_OK;
+        ok = ok && les_hip_mesh(ctx_, mode, d_lab, d_valid, max_jump, d_vi, d_vp, d_tri, d_counts) == LES_HIP_OK && les_hip_synchronize(ctx_) == LES_HIP_OK;
+        ok = ok && les_hip_memcpy_d2h(ctx_, counts, d_counts, sizeof counts) == LES_HIP_OK;
+        if (ok) {
+            vertex_index.resize(P);
+            vertex_pixel.resize((size_t)counts[0]);
+            triangles.resize(3 * (size_t)counts[1]);
+            ok = les_hip_memcpy_d2h(ctx_, vertex_index.data(), d_vi, P * sizeof(int)) == LES_HIP_OK &&
+                 (!counts[0] || les_hip_memcpy_d2h(ctx_, vertex_pixel.data(), d_vp, vertex_pixel.size() * sizeof(int)) == LES_HIP_OK) &&
+                 (!counts[1] || les_hip_memcpy_d2h(ctx_, triangles.data(), d_tri, triangles.size() * sizeof(int)) == LES_HIP_OK);
+        }
+        if (!ok) fprintf(stderr, "HipCostVolumeEnergy: %s\n", les_hip_last_error());
+        for (void* q : {(void*)d_lab, (void*)d_valid, (void*)d_vi, (void*)d_vp, (void*)d_tri, (void*)d_counts})
             if (q) les_hip_free(ctx_, q);
         return ok;
     }

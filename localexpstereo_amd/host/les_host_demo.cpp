@@ -363,6 +363,29 @@ static int cmd_run(int argc, char** argv)
         }
         printf("speckle filter: %zu planted island pixels; %zu mask / size / root errors, %zu pixels changed or kept wrongly, %zu differ from postProcess at max_size 0\n", planted, mbad, cbad, zbad);
         if (!oks || !planted || mbad || cbad || zbad) { printf("FAIL: speckle filter\n"); fail = 1; }
+        // the 3D reconstruction through the adapter: the speckle scene (disparity 3, islands at 9) as points, normals and a mesh.  Every pixel is a
+        // vertex; fronto-parallel labels have the normal (0, 0, -1) and the depth f baseline / d; at max_jump 1 exactly the quads that touch an
+        // island border lose their triangles, and the triangles of a one-surface map are all 2 (W - 1) (H - 1)
+        const les_hip_calib cal = {1000.f, 0.5f * W, 0.5f * H, 0.f, 100.f};
+        std::vector<float> pts(3 * P), nrm(3 * P);
+        std::vector<unsigned char> rvalid(P, 9);
+        std::vector<int> vindex, vpixel, tris, tris1;
+        std::vector<Plane> flat(P, Plane(0.f, 0.f, 3.f, 0.f));
+        bool okr = hip.reproject(smap.data(), cal, pts.data(), nrm.data(), rvalid.data(), 0) && hip.mesh(smap.data(), rvalid.data(), 1.0f, vindex, vpixel, tris, 0) &&
+                   hip.mesh(flat.data(), rvalid.data(), 1.0f, vindex, vpixel, tris1, 0);
+        size_t rbad = 0, torn = 0;
+        for (size_t i = 0; okr && i < P; i++)
+            rbad += rvalid[i] != 255 || nrm[3 * i] != 0.f || nrm[3 * i + 1] != 0.f || nrm[3 * i + 2] != -1.f || pts[3 * i + 2] != (float)(100000.0 / (island[i] ? 9.0 : 3.0)) ||
+                    vindex[i] != (int)i || vpixel[i] != (int)i;
+        for (int y = 0; y + 1 < H; y++)
+            for (int x = 0; x + 1 < W; x++) {
+                const unsigned char a = island[(size_t)y * W + x], b = island[(size_t)y * W + x + 1], c = island[(size_t)(y + 1) * W + x], d = island[(size_t)(y + 1) * W + x + 1];
+                torn += (size_t)(!(a == b && a == c)) + (size_t)(!(b == c && b == d));
+            }
+        const size_t all_tris = 2 * (size_t)(W - 1) * (size_t)(H - 1);
+        printf("reproject / mesh: %zu of %zu pixels differ from the expected geometry; %zu triangles, %zu torn at the island borders, %zu on one surface\n", rbad, P, tris.size() / 3, torn,
+               tris1.size() / 3);
+        if (!okr || rbad || !torn || tris.size() / 3 != all_tris - torn || tris1.size() / 3 != all_tris) { printf("FAIL: reproject / mesh\n"); fail = 1; }
     }
     printf(fail ? "les_host_demo: FAILED\n" : "les_host_demo: OK\n");
     return fail;

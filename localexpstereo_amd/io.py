@@ -154,6 +154,105 @@ def read_calib(path):
     return out
 
 
+def calib3d(calib):
+    """api.Calib (les_hip_calib) of a Middlebury v3 calibration -- read_calib's dict, or a plain dict with the keys f, cx, cy, doffs, baseline:
+    f = cam0[0][0], cx = cam0[0][2], cy = cam0[1][2] (pixels), doffs (pixels), baseline (the unit the points come out in; Middlebury: mm).
+    View m has cx_m = cx + (m ? doffs : 0), and each view's points are in its own camera frame (X right, Y down, Z forward), so
+    X_left = X_right + baseline.  An api.Calib passes through."""
+    if isinstance(calib, api.Calib):
+        return calib
+    if "cam0" in calib:
+        cam0 = np.asarray(calib["cam0"], np.float32)
+        if cam0.shape != (3, 3):
+            raise ValueError(f"calib3d: cam0 is a 3 x 3 matrix, not {cam0.shape}")
+        f, cx, cy = cam0[0, 0], cam0[0, 2], cam0[1, 2]
+    else:
+        f, cx, cy = calib["f"], calib["cx"], calib["cy"]
+    return api.Calib(float(f), float(cx), float(cy), float(calib.get("doffs", 0.0)), float(calib["baseline"]))
+
+
+# ------------------------------------------------------------------------------------------------
+# PLY meshes and point clouds
+# ------------------------------------------------------------------------------------------------
+_PLY_TYPES = {"float": "<f4", "float32": "<f4", "uchar": "u1", "uint8": "u1", "int": "<i4", "int32": "<i4"}
+
+
+def write_ply(path, vertices, normals=None, colors=None, triangles=None):
+    """A binary little-endian PLY: vertices N x 3 float32 (x y z), optional normals N x 3 float32 (nx ny nz), colors N x 3 uint8 RGB
+    (red green blue) and triangles M x 3 int32 (vertex_indices: uchar count 3, int indices).  Every value is stored as given, bit for bit."""
+    v = np.ascontiguousarray(vertices, "<f4").reshape(-1, 3)
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    cols = [v]
+    if normals is not None:
+        n = np.ascontiguousarray(normals, "<f4").reshape(-1, 3)
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        cols.append(n)
+    if colors is not None:
+        c = np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        cols.append(c)
+    if any(len(a) != len(v) for a in cols):
+        raise ValueError("write_ply: normals and colors need one row per vertex")
+    rec = np.empty(len(v), np.dtype(fields))
+    names = [f[0] for f in fields]
+    for k, a in enumerate(cols):
+        for j in range(3):
+            rec[names[3 * k + j]] = a[:, j]
+    head = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"]
+    head += [f"property {'uchar' if t == 'u1' else 'float'} {name}" for name, t in fields]
+    tri = None
+    if triangles is not None:
+        t = np.ascontiguousarray(triangles, "<i4").reshape(-1, 3)
+        tri = np.empty(len(t), np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+        tri["n"] = 3
+        tri["v"] = t
+        head += [f"element face {len(t)}", "property list uchar int vertex_indices"]
+    head.append("end_header")
+    with open(path, "wb") as f:
+        f.write(("\n".join(head) + "\n").encode("ascii"))
+        f.write(rec.tobytes())
+        if tri is not None:
+            f.write(tri.tobytes())
+
+
+def read_ply(path):
+    """What write_ply wrote: dict(vertices, normals, colors, triangles), None for what the file does not hold.  Binary little-endian files whose
+    vertex properties are scalars and whose faces are all triangles (list uchar int)."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header\n")
+    if not data.startswith(b"ply") or end < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    lines = data[:end].decode("ascii").split("\n")
+    body = data[end + len(b"end_header\n"):]
+    if "format binary_little_endian 1.0" not in lines:
+        raise ValueError(f"{path}: only binary little-endian PLY files are read")
+    counts, props, element = {}, {}, None
+    for line in lines:
+        tok = line.split()
+        if tok[:1] == ["element"]:
+            element = tok[1]
+            counts[element], props[element] = int(tok[2]), []
+        elif tok[:1] == ["property"]:
+            props[element].append(tok[1:])
+    if list(counts) not in (["vertex"], ["vertex", "face"]) or any(len(p) != 2 for p in props["vertex"]):
+        raise ValueError(f"{path}: a vertex element of scalar properties, then an optional face element, expected")
+    dt = np.dtype([(name, _PLY_TYPES[t]) for t, name in props["vertex"]])
+    nv = counts["vertex"]
+    rec = np.frombuffer(body, dt, nv)
+    grab = lambda names, t: np.stack([rec[n] for n in names], 1).astype(t) if all(n in dt.names for n in names) else None
+    out = dict(vertices=grab(("x", "y", "z"), np.float32), normals=grab(("nx", "ny", "nz"), np.float32), colors=grab(("red", "green", "blue"), np.uint8),
+               triangles=None)
+    if "face" in counts:
+        if props["face"] != [["list", "uchar", "int", "vertex_indices"]]:
+            raise ValueError(f"{path}: faces as 'property list uchar int vertex_indices' expected")
+        tri = np.frombuffer(body, np.dtype([("n", "u1"), ("v", "<i4", (3,))]), counts["face"], offset=nv * dt.itemsize)
+        if not (tri["n"] == 3).all():
+            raise ValueError(f"{path}: a face that is not a triangle")
+        out["triangles"] = np.ascontiguousarray(tri["v"], np.int32)
+    return out
+
+
 def _imread_bgr(path, gray=False):
     from PIL import Image           # only the data-set loader needs an image decoder
     if not os.path.exists(path):

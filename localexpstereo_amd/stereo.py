@@ -321,6 +321,43 @@ class FastGCStereo:
         self.e.synchronize()
         return tuple(t.cpu().numpy() for t in out) if isinstance(out, tuple) else out.cpu().numpy()
 
+    def reconstruct(self, labeling, calib, viewMode=0, conf=None, min_confidence=None, speckle=None, max_jump=None, z_max=None):
+        """The 3D reconstruction of any H x W x 4 label map of view viewMode (no reference counterpart; csrc/les_reproject.h;
+        api.HipCostVolumeEnergy.reproject and .mesh): every label is a surface element, so the points AND the normals are exact, and the surface
+        is torn where the energy's own smoothness term says two pixels lie on different surfaces.  calib: io.calib3d's Calib, read_calib's dict or
+        a plain dict(f, cx, cy, doffs, baseline); the points are in the view's own camera frame (X right, Y down, Z forward) in the baseline's
+        unit.  A pixel is dropped where conf (an H x W map, FastGCStereo.confidence's) < min_confidence, or where the speckle mask of
+        speckle=(max_size, max_diff) is set (api.speckle_mask), when either is given; or where Z > z_max.  max_jump: two neighbouring pixels
+        are joined iff the un-truncated pairwise term of their labels is <= max_jump (None: this energy's th_smooth, where the term saturates).
+        -> dict(points, normals: H x W x 3 float32, NaN where invalid; valid: H x W bool; vertices, vertex_normals: N x 3 float32 and colors:
+        N x 3 uint8 RGB from the context's image, per vertex in row-major pixel order; vertex_pixel: N int32 linear pixel indices; triangles:
+        M x 3 int32 vertex numbers whose winding faces the camera), host arrays ready for io.write_ply.  It changes no estimate.  Single rank."""
+        if self.world > 1:
+            raise NotImplementedError("FastGCStereo.reconstruct is single-rank: the multi-rank form is not implemented")
+        if (conf is None) != (min_confidence is None):
+            raise ValueError("reconstruct: give conf and min_confidence together, or neither")
+        from . import io as lio
+        m, dev = int(viewMode), torch.device(self.device)
+        lab = labeling if torch.is_tensor(labeling) else torch.from_numpy(np.array(labeling, dtype=np.float32, order="C"))
+        lab = lab.to(device=dev, dtype=torch.float32).contiguous()
+        drop = None
+        if speckle is not None:
+            drop = self.e.speckle_mask(lab, int(speckle[0]), float(speckle[1]), device=dev)        # (synchronises)
+        if conf is not None:
+            c = conf if torch.is_tensor(conf) else torch.from_numpy(np.array(conf, dtype=np.float32, order="C"))
+            low = (c.to(device=dev, dtype=torch.float32) < float(min_confidence)).to(torch.uint8) * 255
+            drop = low if drop is None else torch.maximum(drop, low)
+        jump = float(self.p["th_smooth"]) if max_jump is None else float(max_jump)
+        points, normals, valid = self.e.reproject(lab, lio.calib3d(calib), mode=m, drop=drop, z_max=z_max, device=dev)
+        self.e.synchronize()
+        vindex, vpixel, tri = self.e.mesh(lab, valid, jump, mode=m, device=dev)
+        # per-vertex gathers: plumbing, torch indexing by vertex_pixel
+        idx = vpixel.long()
+        rgb = torch.from_numpy(np.ascontiguousarray(self.e.image(m)[..., ::-1])).to(dev)
+        out = dict(points=points, normals=normals, valid=valid != 0, vertices=points.reshape(-1, 3)[idx], vertex_normals=normals.reshape(-1, 3)[idx],
+                   colors=rgb.reshape(-1, 3)[idx], vertex_pixel=vpixel, triangles=tri)
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
     def _confidences(self, maps):
         """With confidence=True: self.confidences of the device label maps {view: map} as they are (raw), -> {view: the device confidence map};
         otherwise {} (and self.confidences is emptied)."""

@@ -181,5 +181,19 @@ static inline void __hip_atomic_store(T* p, T v, int order, int) { __atomic_stor
 
 static inline void __syncthreads() { hipsim::sync_block(); }
 
+// wave-64 ballot: bit i = predicate of work-item i of this wave (every work-item of the wave must call it), and the 64-bit popcount
+static inline unsigned long long __ballot(int predicate)
+{
+    hipsim::Block* B = hipsim::g_block;
+    const int tid = B->current;
+    B->exch[tid] = predicate ? 1u : 0u;
+    hipsim::group_sync(6);
+    unsigned long long m = 0;
+    for (int i = 0; i < 64; i++) m |= (unsigned long long)(B->exch[(tid & ~63) + i] & 1u) << i;
+    hipsim::group_sync(6);
+    return m;
+}
+static inline int __popcll(unsigned long long v) { return __builtin_popcountll(v); }
+
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \
     hipsim::launch((grid), (block), [=]() { kernel(__VA_ARGS__); })
