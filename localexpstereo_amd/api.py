@@ -226,6 +226,19 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _vp(p):
+    """A nullable device address (an int, or None / 0 for an optional map that is not there) as the ABI takes it."""
+    return C.c_void_p(int(p)) if p else None
+
+
+def _float_tensor(a, dev):
+    """`a` as a contiguous float32 torch tensor on dev: a tensor that is all that already is returned itself, anything else is copied."""
+    import torch
+    if torch.is_tensor(a):
+        return a.to(device=dev, dtype=torch.float32).contiguous()
+    return torch.from_numpy(np.array(a, dtype=np.float32, order="C")).to(dev)          # (a copy: torch wants a writable array)
+
+
 def _rects(r):
     r = np.asarray(r)
     if r.dtype != RECT_DT:
@@ -367,7 +380,7 @@ class Exchange:
         self.e._chk(self.e.L.les_hip_exchange_unpack(self.e.h, self.h, C.c_void_p(int(gathered_ptr)), C.c_void_p(int(labels_ptr)), C.c_void_p(int(cost_ptr))))
 
     def tiles(self, nccl_comm, labels_ptr, cost_ptr):
-        self.e._chk(self.e.L.les_hip_exchange_tiles(self.e.h, self.h, C.c_void_p(int(nccl_comm)) if nccl_comm else None, C.c_void_p(int(labels_ptr)),
+        self.e._chk(self.e.L.les_hip_exchange_tiles(self.e.h, self.h, _vp(nccl_comm), C.c_void_p(int(labels_ptr)),
                                                     C.c_void_p(int(cost_ptr))))
 
     def destroy(self):
@@ -449,8 +462,7 @@ class Batch:
         f0 = np.zeros(self.n, np.float64) if want_flow0 else None
         self.e._chk(self.e.L.les_hip_batch_fusion_graph(self.e.h, self.h, mode, C.c_void_p(int(labels1_dev)), C.c_void_p(int(labels_dev)),
                                                         C.c_void_p(int(cur_dev)), C.c_void_p(int(prop_dev)), lambda_, th_smooth, omega, epsilon,
-                                                        C.c_void_p(int(payload_dev)), _ptr(f0),
-                                                        C.c_void_p(int(nonsubmodular_dev)) if nonsubmodular_dev else None))
+                                                        C.c_void_p(int(payload_dev)), _ptr(f0), _vp(nonsubmodular_dev)))
         return f0
 
     MAXFLOW_MAX_NODES = 2304          # LES_HIP_MAXFLOW_MAX_NODES
@@ -470,8 +482,7 @@ class Batch:
         MAXFLOW_MAX_NODES nodes.  masks (uint8 per node), status (int32 per cell: 0 solved, 1 = cut it on the host), flows (float64 per
         cell, optional) are device pointers; unsolved_total (optional): a device int that grows by one per cell that hit the iteration limit."""
         self.e._chk(self.e.L.les_hip_batch_solve_graphs_counted(self.e.h, self.h, C.c_void_p(int(payload_dev)), C.c_void_p(int(masks_dev)), C.c_void_p(int(status_dev)),
-                                                                C.c_void_p(int(flows_dev)) if flows_dev else None,
-                                                                C.c_void_p(int(unsolved_total_dev)) if unsolved_total_dev else None))
+                                                                _vp(flows_dev), _vp(unsolved_total_dev)))
 
     def tiled_workspace_bytes(self):
         """Device scratch les_hip_batch_solve_graphs_tiled needs for this batch (109 bytes per graph node)."""
@@ -484,7 +495,7 @@ class Batch:
         self.tiled_stats = the call's les_hip_tiled_stats (cells / nodes the host cores finished from their residual graphs, their milliseconds)."""
         st = TiledStats()
         self.e._chk(self.e.L.les_hip_batch_solve_graphs_tiled_stats(self.e.h, self.h, C.c_void_p(int(payload_dev)), C.c_void_p(int(masks_dev)), C.c_void_p(int(status_dev)),
-                                                                    C.c_void_p(int(flows_dev)) if flows_dev else None, C.c_void_p(int(workspace_dev)),
+                                                                    _vp(flows_dev), C.c_void_p(int(workspace_dev)),
                                                                     C.c_longlong(int(workspace_bytes)), C.byref(st)))
         self.tiled_unsolved = st.unsolved
         self.tiled_stats = dict(launches=st.launches, unsolved=st.unsolved, handed_cells=st.handed_cells, handed_nodes=st.handed_nodes, host_ms=st.host_ms)
@@ -570,7 +581,7 @@ class HipCostVolumeEnergy:
         self.H, self.W = im.shape[:2]
         if volumes_on_device:
             self.D = int(shape[0])
-            vl, vr = (C.c_void_p(int(volL)) if volL else None), (C.c_void_p(int(volR)) if volR else None)
+            vl, vr = _vp(volL), _vp(volR)
             self._keep = None
         else:
             self._keep = [np.ascontiguousarray(v, np.float32) if v is not None else None for v in (volL, volR)]
@@ -645,7 +656,7 @@ class HipCostVolumeEnergy:
 
     def set_thread_stream(self, stream_ptr, bind=True):
         """The calling host thread's launches on this context go to `stream_ptr` (bind=False: back to the context's stream)."""
-        self._chk(self.L.les_hip_set_thread_stream(self.h, C.c_void_p(int(stream_ptr)) if stream_ptr else None, int(bool(bind))))
+        self._chk(self.L.les_hip_set_thread_stream(self.h, _vp(stream_ptr), int(bool(bind))))
 
     def synchronize(self):
         self._chk(self.L.les_hip_synchronize(self.h))
@@ -748,13 +759,12 @@ class HipCostVolumeEnergy:
             self._chk(self.L.les_hip_post_process(self.h, C.c_void_p(int(labelsL_dev)), C.c_void_p(int(labelsR_dev)), C.c_float(threshold), C.c_float(omega)))
             return
         max_size, max_diff = speckle if speckle is not None else (0, 0.0)
-        vp = lambda p: C.c_void_p(int(p)) if p else None
         if fail is None:
-            self._chk(self.L.les_hip_post_process_speckle(self.h, vp(labelsL_dev), vp(labelsR_dev), C.c_float(threshold), C.c_float(omega), int(max_size),
+            self._chk(self.L.les_hip_post_process_speckle(self.h, _vp(labelsL_dev), _vp(labelsR_dev), C.c_float(threshold), C.c_float(omega), int(max_size),
                                                           C.c_float(max_diff)))
             return
-        self._chk(self.L.les_hip_post_process_masked(self.h, vp(labelsL_dev), vp(labelsR_dev), C.c_float(threshold), C.c_float(omega), int(max_size),
-                                                     C.c_float(max_diff), vp(fail[0]), vp(fail[1])))
+        self._chk(self.L.les_hip_post_process_masked(self.h, _vp(labelsL_dev), _vp(labelsR_dev), C.c_float(threshold), C.c_float(omega), int(max_size),
+                                                     C.c_float(max_diff), _vp(fail[0]), _vp(fail[1])))
 
     def post_process_host(self, labelsL, labelsR, threshold=1.5, omega=10.0, speckle=None, fail=None):
         """Convenience form for host label maps (H x W planes): upload, post-process on the device, download.  With speckle=(max_size, max_diff)
@@ -780,11 +790,62 @@ class HipCostVolumeEnergy:
                     b.free()
         return out
 
+    # -- the tensor wrappers' ingestion of their maps, and their one rule for streams ------------------------------------
+    def _device(self, device):
+        """The torch device of a wrapper's results: `device`, or this context's GPU (the simulator build takes "cpu")."""
+        import torch
+        return torch.device(device if device is not None else f"cuda:{self.params.device}")
+
+    def _labels_and_cost(self, device):
+        """New (labels, cost) result tensors of wta_labels / sgm_labels: H x W x 4 and H x W float32."""
+        import torch
+        dev = self._device(device)
+        return torch.empty((self.H, self.W, 4), dtype=torch.float32, device=dev), torch.empty((self.H, self.W), dtype=torch.float32, device=dev)
+
+    def _label_map(self, labels, dev, who, shape=None, what="label map"):
+        """The H x W x 4 float32 label map on dev (shape: another (H, W)): a tensor that is there already is used where it is."""
+        h, w = shape or (self.H, self.W)
+        s = _float_tensor(labels, dev)
+        if tuple(s.shape) != (h, w, 4):
+            raise ValueError(f"{who} a {h} x {w} x 4 {what}, not {tuple(s.shape)}")
+        return s
+
+    def _label_or_disparity_map(self, src, dev, who, shape=None):
+        """fit_planes' source on dev: an H x W x 4 label map or an H x W disparity map, float32."""
+        h, w = shape or (self.H, self.W)
+        s = _float_tensor(src, dev)
+        if tuple(s.shape) not in ((h, w, 4), (h, w)):
+            raise ValueError(f"{who} a {h} x {w} x 4 label map or a {h} x {w} disparity map, not {tuple(s.shape)}")
+        return s
+
+    def _byte_map(self, mask, dev, who, shape=None):
+        """The H x W uint8 mask on dev (nonzero = set): a uint8 tensor that is there already is used where it is."""
+        import torch
+        h, w = shape or (self.H, self.W)
+        if torch.is_tensor(mask):
+            m = (mask if mask.dtype == torch.uint8 else mask != 0).to(device=dev, dtype=torch.uint8).contiguous()
+        else:
+            m = torch.from_numpy((np.asarray(mask) != 0).astype(np.uint8)).to(dev)
+        if tuple(m.shape) != (h, w):
+            raise ValueError(f"{who} a {h} x {w} mask, not {tuple(m.shape)}")
+        return m
+
+    def _staged(self, dev, copied, call, *args, **kwargs):
+        """call(*args, **kwargs) on maps a wrapper ingested.  copied: ingestion made a copy (a dtype or device conversion, an upload of an
+        array) -- torch made it on ITS current stream and the library reads it on the context's, so torch's stream is waited for before the
+        call, and the context after it: the copy goes back to torch's allocator when the wrapper returns and must outlive the launch that
+        reads it.  A caller's tensor used where it is (the drivers' case) adds no wait."""
+        if copied and dev.type == "cuda":
+            import torch
+            torch.cuda.current_stream(dev).synchronize()
+        call(*args, **kwargs)
+        if copied:
+            self.synchronize()
+
     # -- speckle filter (csrc/les_speckle.h; no reference counterpart) ------------------------------------
     def speckle_mask_ptr(self, labels_ptr, max_size, max_diff, mask_ptr, root_ptr=None, size_ptr=None):
         """les_hip_speckle_mask on device addresses (root_ptr and size_ptr may be None).  Synchronises the calling thread's stream."""
-        vp = lambda p: C.c_void_p(int(p)) if p else None
-        self._chk(self.L.les_hip_speckle_mask(self.h, vp(labels_ptr), int(max_size), C.c_float(max_diff), vp(mask_ptr), vp(root_ptr), vp(size_ptr)))
+        self._chk(self.L.les_hip_speckle_mask(self.h, _vp(labels_ptr), int(max_size), C.c_float(max_diff), _vp(mask_ptr), _vp(root_ptr), _vp(size_ptr)))
 
     def speckle_mask(self, labels, max_size, max_diff, components=False, device=None):
         """The speckle mask of an H x W x 4 label map (les_hip_speckle_mask): H x W uint8, 255 where the pixel's connected component of the
@@ -793,18 +854,13 @@ class HipCostVolumeEnergy:
         count.  labels: a float32 torch tensor (on `device`: used where it is) or an array.  All results are new tensors on `device` (None:
         this context's GPU; the simulator build takes "cpu")."""
         import torch
-        dev = torch.device(device if device is not None else f"cuda:{self.params.device}")
-        if torch.is_tensor(labels):
-            s = labels.to(device=dev, dtype=torch.float32).contiguous()
-        else:
-            s = torch.from_numpy(np.array(labels, dtype=np.float32, order="C")).to(dev)
-        if tuple(s.shape) != (self.H, self.W, 4):
-            raise ValueError(f"speckle_mask: a {self.H} x {self.W} x 4 label map, not {tuple(s.shape)}")
+        dev = self._device(device)
+        s = self._label_map(labels, dev, "speckle_mask:")
         mask = torch.empty((self.H, self.W), dtype=torch.uint8, device=dev)
         root = torch.empty((self.H, self.W), dtype=torch.int32, device=dev) if components else None
         size = torch.empty((self.H, self.W), dtype=torch.int32, device=dev) if components else None
-        self.speckle_mask_ptr(s.data_ptr(), max_size, max_diff, mask.data_ptr(), root.data_ptr() if components else None,
-                              size.data_ptr() if components else None)
+        self._staged(dev, s is not labels, self.speckle_mask_ptr, s.data_ptr(), max_size, max_diff, mask.data_ptr(),
+                     root.data_ptr() if components else None, size.data_ptr() if components else None)
         return (mask, root, size) if components else mask
 
     # -- cross-view fusion (csrc/les_crossview.h; no reference counterpart) -----------------------------
@@ -814,7 +870,7 @@ class HipCostVolumeEnergy:
         the target view (the largest disparity wins), every other one fallback_ptr's plane.  hit_ptr: H x W bytes (1 = warped, 0 = fallback) or
         None.  Enqueue only (the calling thread's stream).  Rows wider than WARP_MAX_WIDTH raise (error 3)."""
         self._chk(self.L.les_hip_warp_labels(self.h, int(src_mode), C.c_void_p(int(src_ptr)), C.c_void_p(int(fallback_ptr)), C.c_void_p(int(out_ptr)),
-                                             C.c_void_p(int(hit_ptr)) if hit_ptr else None))
+                                             _vp(hit_ptr)))
 
     # -- winner-take-all labels of the aggregated cost volume (csrc/les_wtavol.h; no reference counterpart) ---------------
     @property
@@ -829,13 +885,11 @@ class HipCostVolumeEnergy:
     def slab_argmin(self, slabs_ptr, n, k_first, state_ptr):
         """les_hip_slab_argmin: the running arg-min over one chunk of n slabs ([n][H][W] floats on the device, slab i = slab k_first + i of the
         volume) into the state; k_first == 0 initialises it.  Enqueue only."""
-        self._chk(self.L.les_hip_slab_argmin(self.h, C.c_void_p(int(slabs_ptr)) if slabs_ptr else None, int(n), int(k_first),
-                                             C.c_void_p(int(state_ptr)) if state_ptr else None))
+        self._chk(self.L.les_hip_slab_argmin(self.h, _vp(slabs_ptr), int(n), int(k_first), _vp(state_ptr)))
 
     def slab_argmin_finish(self, state_ptr, K, labels_ptr, cost_ptr, subpixel=True):
         """les_hip_slab_argmin_finish: the state after K slabs -> the H x W plane map (0, 0, k* + off + min_disp, 0) and the H x W cost map."""
-        self._chk(self.L.les_hip_slab_argmin_finish(self.h, C.c_void_p(int(state_ptr)) if state_ptr else None, int(K), int(bool(subpixel)),
-                                                    C.c_void_p(int(labels_ptr)) if labels_ptr else None, C.c_void_p(int(cost_ptr)) if cost_ptr else None))
+        self._chk(self.L.les_hip_slab_argmin_finish(self.h, _vp(state_ptr), int(K), int(bool(subpixel)), _vp(labels_ptr), _vp(cost_ptr)))
 
     def wta_labels(self, mode=0, chunk=0, subpixel=True, labels_ptr=None, cost_ptr=None, device=None):
         """les_hip_wta_labels: the winner-take-all label map of view `mode` -- per pixel the fronto-parallel plane of least aggregated cost among
@@ -848,12 +902,9 @@ class HipCostVolumeEnergy:
             raise ValueError("wta_labels: give both labels_ptr and cost_ptr, or neither")
         out = None
         if labels_ptr is None:
-            import torch
-            dev = torch.device(device if device is not None else f"cuda:{self.params.device}")
-            out = (torch.empty((self.H, self.W, 4), dtype=torch.float32, device=dev), torch.empty((self.H, self.W), dtype=torch.float32, device=dev))
+            out = self._labels_and_cost(device)
             labels_ptr, cost_ptr = out[0].data_ptr(), out[1].data_ptr()
-        self._chk(self.L.les_hip_wta_labels(self.h, int(mode), int(chunk), int(bool(subpixel)), C.c_void_p(int(labels_ptr)) if labels_ptr else None,
-                                            C.c_void_p(int(cost_ptr)) if cost_ptr else None))
+        self._chk(self.L.les_hip_wta_labels(self.h, int(mode), int(chunk), int(bool(subpixel)), _vp(labels_ptr), _vp(cost_ptr)))
         return out
 
     # -- the confidence of a label map under the aggregated cost volume (csrc/les_confidence.h; no reference counterpart) ---------------
@@ -874,20 +925,17 @@ class HipCostVolumeEnergy:
         """les_hip_slab_confidence: the running own / rival minima over one chunk of n slabs ([n][H][W] floats on the device, slab i = slab
         k_first + i of the volume) into the state; k_first == 0 initialises it from the H x W x 4 label map at labels_ptr (read only then).
         Enqueue only."""
-        vp = lambda p: C.c_void_p(int(p)) if p else None
-        self._chk(self.L.les_hip_slab_confidence(self.h, vp(labels_ptr), vp(slabs_ptr), int(n), int(k_first), C.c_float(band), vp(state_ptr)))
+        self._chk(self.L.les_hip_slab_confidence(self.h, _vp(labels_ptr), _vp(slabs_ptr), int(n), int(k_first), C.c_float(band), _vp(state_ptr)))
 
     def slab_confidence_finish(self, state_ptr, scale, conf_ptr, own_ptr=None, rival_ptr=None, krival_ptr=None):
         """les_hip_slab_confidence_finish: the state -> the H x W confidence map and, where given, the own and rival costs (float) and the
         rival's slab (int32).  Enqueue only."""
-        vp = lambda p: C.c_void_p(int(p)) if p else None
-        self._chk(self.L.les_hip_slab_confidence_finish(self.h, vp(state_ptr), C.c_float(scale), vp(conf_ptr), vp(own_ptr), vp(rival_ptr), vp(krival_ptr)))
+        self._chk(self.L.les_hip_slab_confidence_finish(self.h, _vp(state_ptr), C.c_float(scale), _vp(conf_ptr), _vp(own_ptr), _vp(rival_ptr), _vp(krival_ptr)))
 
     def confidence_ptr(self, mode, labels_ptr, chunk, band, scale, conf_ptr, own_ptr=None, rival_ptr=None, krival_ptr=None):
         """les_hip_confidence on device addresses (own_ptr, rival_ptr and krival_ptr may be None)."""
-        vp = lambda p: C.c_void_p(int(p)) if p else None
-        self._chk(self.L.les_hip_confidence(self.h, int(mode), vp(labels_ptr), int(chunk), C.c_float(band), C.c_float(scale), vp(conf_ptr), vp(own_ptr),
-                                            vp(rival_ptr), vp(krival_ptr)))
+        self._chk(self.L.les_hip_confidence(self.h, int(mode), _vp(labels_ptr), int(chunk), C.c_float(band), C.c_float(scale), _vp(conf_ptr), _vp(own_ptr),
+                                            _vp(rival_ptr), _vp(krival_ptr)))
 
     def confidence(self, labels, mode=0, band=1.0, scale=None, chunk=0, parts=False, device=None):
         """les_hip_confidence: the confidence in [0, 1] of every pixel of the H x W x 4 label map `labels` under view `mode`'s aggregated cost
@@ -897,23 +945,16 @@ class HipCostVolumeEnergy:
         library's default).  labels: a float32 torch tensor (on `device`: used where it is) or an array.  -> the H x W float32 map as a new
         tensor on `device` (None: this context's GPU; the simulator build takes "cpu"); parts: (conf, own, rival, k_rival), the in-band and
         rival minima (float32, +inf where none) and the rival's slab (int32, -1 where none).  Asynchronous on the calling thread's stream once
-        the context's workspace exists."""
+        the context's workspace exists where the maps are used where they are; a map the wrapper had to copy is waited for (_staged)."""
         import torch
-        dev = torch.device(device if device is not None else f"cuda:{self.params.device}")
-        if torch.is_tensor(labels):
-            s = labels.to(device=dev, dtype=torch.float32).contiguous()
-        else:
-            s = torch.from_numpy(np.array(labels, dtype=np.float32, order="C")).to(dev)
-        if tuple(s.shape) != (self.H, self.W, 4):
-            raise ValueError(f"confidence: a {self.H} x {self.W} x 4 label map, not {tuple(s.shape)}")
+        dev = self._device(device)
+        s = self._label_map(labels, dev, "confidence:")
         conf = torch.empty((self.H, self.W), dtype=torch.float32, device=dev)
         own = torch.empty_like(conf) if parts else None
         rival = torch.empty_like(conf) if parts else None
         kr = torch.empty((self.H, self.W), dtype=torch.int32, device=dev) if parts else None
-        self.confidence_ptr(mode, s.data_ptr(), chunk, band, self.raw_cost_max() if scale is None else scale, conf.data_ptr(),
-                            *(t.data_ptr() if parts else None for t in (own, rival, kr)))
-        if s is not labels:                  # (a copy made here must outlive the launches that read it)
-            self.synchronize()
+        self._staged(dev, s is not labels, self.confidence_ptr, mode, s.data_ptr(), chunk, band, self.raw_cost_max() if scale is None else scale,
+                     conf.data_ptr(), *(t.data_ptr() if parts else None for t in (own, rival, kr)))
         return (conf, own, rival, kr) if parts else conf
 
     # -- semi-global matching over the view's own cost volume (csrc/les_sgm.h; no reference counterpart) -------------------
@@ -940,12 +981,9 @@ class HipCostVolumeEnergy:
         p1, p2 = self.sgm_penalties(p1, p2)
         out = None
         if labels_ptr is None:
-            import torch
-            dev = torch.device(device if device is not None else f"cuda:{self.params.device}")
-            out = (torch.empty((self.H, self.W, 4), dtype=torch.float32, device=dev), torch.empty((self.H, self.W), dtype=torch.float32, device=dev))
+            out = self._labels_and_cost(device)
             labels_ptr, cost_ptr = out[0].data_ptr(), out[1].data_ptr()
-        self._chk(self.L.les_hip_sgm_labels(self.h, int(mode), int(paths), C.c_float(p1), C.c_float(p2), int(bool(subpixel)),
-                                            C.c_void_p(int(labels_ptr)) if labels_ptr else None, C.c_void_p(int(cost_ptr)) if cost_ptr else None))
+        self._chk(self.L.les_hip_sgm_labels(self.h, int(mode), int(paths), C.c_float(p1), C.c_float(p2), int(bool(subpixel)), _vp(labels_ptr), _vp(cost_ptr)))
         return out
 
     def sgm_last_times(self):
@@ -962,8 +1000,7 @@ class HipCostVolumeEnergy:
         q = dict(FIT_DEFAULTS, **params)
         if set(q) != set(FIT_DEFAULTS):
             raise TypeError(f"fit_planes: unknown parameters {sorted(set(q) - set(FIT_DEFAULTS))}")
-        vp = lambda p: C.c_void_p(int(p)) if p else None
-        self._chk(self.L.les_hip_fit_planes(self.h, int(mode), vp(labels_ptr), vp(disp_ptr), vp(fallback_ptr), vp(out_ptr), vp(kind_ptr), int(q["radius"]),
+        self._chk(self.L.les_hip_fit_planes(self.h, int(mode), _vp(labels_ptr), _vp(disp_ptr), _vp(fallback_ptr), _vp(out_ptr), _vp(kind_ptr), int(q["radius"]),
                                             C.c_float(q["sig"]), C.c_float(q["gate0"]), C.c_float(q["gate_slope"]), C.c_float(q["max_slope"]), int(q["min_support"])))
 
     def fit_planes(self, src, mode=0, fallback=None, with_kind=False, device=None, **params):
@@ -972,62 +1009,24 @@ class HipCostVolumeEnergy:
         get neither a fit nor their own disparity (None: (0, 0, min_disp, 0)); both float32 torch tensors or arrays (a tensor on `device` is
         used where it is, anything else is copied there).  params: radius=5, sig=10, gate0=1, gate_slope=0.5, max_slope=2, min_support=6.
         -> the H x W x 4 map as a new tensor on `device` (None: this context's GPU; the simulator build takes "cpu"); with_kind: (map, kind), kind
-        H x W uint8 -- 2 slanted fit, 1 fronto-parallel at the pixel's own disparity, 0 fallback.  Asynchronous on the calling thread's stream."""
+        H x W uint8 -- 2 slanted fit, 1 fronto-parallel at the pixel's own disparity, 0 fallback.  Asynchronous on the calling thread's stream
+        where the maps are used where they are; a map the wrapper had to copy is waited for (_staged)."""
         import torch
-        dev = torch.device(device if device is not None else f"cuda:{self.params.device}")
-
-        def on_device(a):
-            if torch.is_tensor(a) and a.device == dev and a.dtype == torch.float32:
-                return a.contiguous()
-            if torch.is_tensor(a):
-                return a.to(device=dev, dtype=torch.float32).contiguous()
-            return torch.from_numpy(np.array(a, dtype=np.float32, order="C")).to(dev)          # (a copy: torch wants a writable array)
-        s = on_device(src)
-        if tuple(s.shape) not in ((self.H, self.W, 4), (self.H, self.W)):
-            raise ValueError(f"fit_planes: a {self.H} x {self.W} x 4 label map or a {self.H} x {self.W} disparity map, not {tuple(s.shape)}")
-        fb = None
-        if fallback is not None:
-            fb = on_device(fallback)
-            if tuple(fb.shape) != (self.H, self.W, 4):
-                raise ValueError(f"fit_planes: the fallback is a {self.H} x {self.W} x 4 label map, not {tuple(fb.shape)}")
+        dev = self._device(device)
+        s = self._label_or_disparity_map(src, dev, "fit_planes:")
+        fb = self._label_map(fallback, dev, "fit_planes: the fallback is") if fallback is not None else None
         out = torch.empty((self.H, self.W, 4), dtype=torch.float32, device=dev)
         kind = torch.empty((self.H, self.W), dtype=torch.uint8, device=dev) if with_kind else None
         labels = s.dim() == 3
-        self.fit_planes_ptr(mode, s.data_ptr() if labels else None, None if labels else s.data_ptr(), fb.data_ptr() if fb is not None else None,
-                            out.data_ptr(), kind.data_ptr() if with_kind else None, **params)
+        self._staged(dev, s is not src or fb is not fallback, self.fit_planes_ptr, mode, s.data_ptr() if labels else None, None if labels else s.data_ptr(),
+                     fb.data_ptr() if fb is not None else None, out.data_ptr(), kind.data_ptr() if with_kind else None, **params)
         return (out, kind) if with_kind else out
 
     # -- 3D reconstruction: points, normals and a mesh from a label map (csrc/les_reproject.h; no reference counterpart) --------------------
-    def _label_map(self, labels, dev, who):
-        """The H x W x 4 float32 label map on dev: a tensor that is there already is used where it is."""
-        import torch
-        if torch.is_tensor(labels) and labels.device == dev and labels.dtype == torch.float32:
-            s = labels.contiguous()
-        elif torch.is_tensor(labels):
-            s = labels.to(device=dev, dtype=torch.float32).contiguous()
-        else:
-            s = torch.from_numpy(np.array(labels, dtype=np.float32, order="C")).to(dev)
-        if tuple(s.shape) != (self.H, self.W, 4):
-            raise ValueError(f"{who}: a {self.H} x {self.W} x 4 label map, not {tuple(s.shape)}")
-        return s
-
-    def _byte_map(self, mask, dev, who):
-        import torch
-        if torch.is_tensor(mask) and mask.device == dev and mask.dtype == torch.uint8:
-            m = mask.contiguous()
-        elif torch.is_tensor(mask):
-            m = (mask != 0).to(device=dev, dtype=torch.uint8).contiguous()
-        else:
-            m = torch.from_numpy((np.asarray(mask) != 0).astype(np.uint8)).to(dev)
-        if tuple(m.shape) != (self.H, self.W):
-            raise ValueError(f"{who}: a {self.H} x {self.W} mask, not {tuple(m.shape)}")
-        return m
-
     def reproject_ptr(self, mode, labels_ptr, drop_ptr, calib, z_max, points_ptr, normals_ptr, valid_ptr):
         """les_hip_reproject on device addresses (drop_ptr, points_ptr and normals_ptr may be None; calib: a Calib or None).  Enqueue only."""
-        vp = lambda p: C.c_void_p(int(p)) if p else None
-        self._chk(self.L.les_hip_reproject(self.h, int(mode), vp(labels_ptr), vp(drop_ptr), C.byref(calib) if calib is not None else None,
-                                           C.c_float(0.0 if z_max is None else z_max), vp(points_ptr), vp(normals_ptr), vp(valid_ptr)))
+        self._chk(self.L.les_hip_reproject(self.h, int(mode), _vp(labels_ptr), _vp(drop_ptr), C.byref(calib) if calib is not None else None,
+                                           C.c_float(0.0 if z_max is None else z_max), _vp(points_ptr), _vp(normals_ptr), _vp(valid_ptr)))
 
     def reproject(self, labels, calib, mode=0, drop=None, z_max=None, device=None):
         """les_hip_reproject: the H x W x 4 label map of view `mode` as 3D geometry -- (points, normals, valid): per pixel the point (X, Y, Z) of
@@ -1037,20 +1036,16 @@ class HipCostVolumeEnergy:
         finite, d + doffs <= 0, `drop` (an H x W mask, nonzero = drop) is set, or Z > z_max (z_max None or <= 0: no limit).  The arithmetic is
         fp64 from the float inputs, rounded once (csrc/les_reproject.h).  labels / drop: torch tensors (on `device`: used where they are) or
         arrays.  -> new tensors on `device` (None: this context's GPU; the simulator build takes "cpu").  Asynchronous on the calling thread's
-        stream."""
+        stream where the maps are used where they are; a map the wrapper had to copy is waited for (_staged)."""
         import torch
-        dev = torch.device(device if device is not None else f"cuda:{self.params.device}")
-        s = self._label_map(labels, dev, "reproject")
-        m = self._byte_map(drop, dev, "reproject") if drop is not None else None
+        dev = self._device(device)
+        s = self._label_map(labels, dev, "reproject:")
+        m = self._byte_map(drop, dev, "reproject:") if drop is not None else None
         points = torch.empty((self.H, self.W, 3), dtype=torch.float32, device=dev)
         normals = torch.empty((self.H, self.W, 3), dtype=torch.float32, device=dev)
         valid = torch.empty((self.H, self.W), dtype=torch.uint8, device=dev)
-        copied = s is not labels or (m is not None and m is not drop)
-        if copied and dev.type == "cuda":        # (torch made the copies on its stream; the library reads them on the context's)
-            torch.cuda.current_stream(dev).synchronize()
-        self.reproject_ptr(mode, s.data_ptr(), m.data_ptr() if m is not None else None, calib, z_max, points.data_ptr(), normals.data_ptr(), valid.data_ptr())
-        if copied:                               # (a copy made here must outlive the launch that reads it)
-            self.synchronize()
+        self._staged(dev, s is not labels or m is not drop, self.reproject_ptr, mode, s.data_ptr(), m.data_ptr() if m is not None else None, calib, z_max,
+                     points.data_ptr(), normals.data_ptr(), valid.data_ptr())
         return points, normals, valid
 
     def mesh_tile(self):
@@ -1062,9 +1057,8 @@ class HipCostVolumeEnergy:
     def mesh_ptr(self, mode, labels_ptr, valid_ptr, max_jump, vertex_index_ptr, vertex_pixel_ptr, triangles_ptr, counts_ptr):
         """les_hip_mesh on device addresses (vertex_index H x W int32, vertex_pixel H W int32, triangles 2 (H - 1) (W - 1) x 3 int32, counts two
         int64).  Enqueue only once the context's tile workspace exists."""
-        vp = lambda p: C.c_void_p(int(p)) if p else None
-        self._chk(self.L.les_hip_mesh(self.h, int(mode), vp(labels_ptr), vp(valid_ptr), C.c_float(max_jump), vp(vertex_index_ptr), vp(vertex_pixel_ptr),
-                                      vp(triangles_ptr), vp(counts_ptr)))
+        self._chk(self.L.les_hip_mesh(self.h, int(mode), _vp(labels_ptr), _vp(valid_ptr), C.c_float(max_jump), _vp(vertex_index_ptr), _vp(vertex_pixel_ptr),
+                                      _vp(triangles_ptr), _vp(counts_ptr)))
 
     def mesh(self, labels, valid, max_jump, mode=0, device=None):
         """les_hip_mesh: the triangle mesh over the pixel grid of the H x W x 4 label map -- (vertex_index, vertex_pixel, triangles).  Vertex k is
@@ -1075,17 +1069,15 @@ class HipCostVolumeEnergy:
         whose winding faces the camera.  The order is a function of the inputs alone.  -> new tensors on `device`, cut to the counts (which
         waits for the device)."""
         import torch
-        dev = torch.device(device if device is not None else f"cuda:{self.params.device}")
-        s = self._label_map(labels, dev, "mesh")
-        m = self._byte_map(valid, dev, "mesh")
+        dev = self._device(device)
+        s = self._label_map(labels, dev, "mesh:")
+        m = self._byte_map(valid, dev, "mesh:")
         vi = torch.empty((self.H, self.W), dtype=torch.int32, device=dev)
         vpix = torch.empty((self.H * self.W,), dtype=torch.int32, device=dev)
         tri = torch.empty((max(1, 2 * (self.H - 1) * (self.W - 1)), 3), dtype=torch.int32, device=dev)
         counts = torch.zeros((2,), dtype=torch.int64, device=dev)
-        if dev.type == "cuda":                   # (torch made the copies and the zeros on its stream; the library works on the context's)
-            torch.cuda.current_stream(dev).synchronize()
-        self.mesh_ptr(mode, s.data_ptr(), m.data_ptr(), max_jump, vi.data_ptr(), vpix.data_ptr(), tri.data_ptr(), counts.data_ptr())
-        self.synchronize()
+        # (copied, always: torch wrote the zeros on its stream, and the counts are read next)
+        self._staged(dev, True, self.mesh_ptr, mode, s.data_ptr(), m.data_ptr(), max_jump, vi.data_ptr(), vpix.data_ptr(), tri.data_ptr(), counts.data_ptr())
         nv, nt = (int(v) for v in counts.cpu())
         return vi, vpix[:nv], tri[:nt]
 
@@ -1119,25 +1111,24 @@ class HipCostVolumeEnergy:
         o.imR = o.image(1) if self.imR is not None else None
         return o
 
+    def upsample_labels_ptr(self, half, mode, src_ptr, out_ptr, kind_ptr=None):
+        """les_hip_upsample_labels on device addresses (kind_ptr may be None).  Enqueue only."""
+        self._chk(self.L.les_hip_upsample_labels(self.h, half.h, int(mode), _vp(src_ptr), _vp(out_ptr), _vp(kind_ptr)))
+
     def upsample_labels(self, half, src, mode=0, with_kind=False, device=None):
         """les_hip_upsample_labels: `src`, the half.H x half.W x 4 label map of view `mode` found on `half` (this context's half()), re-expressed
         at this context's resolution, edge-aware: every pixel takes the plane of the nearest-coloured of its four surrounding half pixels,
         rewritten as (a, b, (2c - a / 2) - b / 2, 2v), when that is a valid label here, else the fronto-parallel plane at its clamped disparity
         (csrc/les_pyramid.h).  src: a float32 torch tensor (on `device`: used where it is) or an array.  -> the H x W x 4 map as a new tensor on
         `device` (None: this context's GPU; the simulator build takes "cpu"); with_kind: (map, kind), kind H x W uint8 -- 0 kept, 1 clamped,
-        2 non-finite.  Asynchronous on the calling thread's stream."""
+        2 non-finite.  Asynchronous on the calling thread's stream
+        where the maps are used where they are; a map the wrapper had to copy is waited for (_staged)."""
         import torch
-        dev = torch.device(device if device is not None else f"cuda:{self.params.device}")
-        if torch.is_tensor(src):
-            s = src.to(device=dev, dtype=torch.float32).contiguous()
-        else:
-            s = torch.from_numpy(np.array(src, dtype=np.float32, order="C")).to(dev)
-        if tuple(s.shape) != (half.H, half.W, 4):
-            raise ValueError(f"upsample_labels: a {half.H} x {half.W} x 4 label map of the half context, not {tuple(s.shape)}")
+        dev = self._device(device)
+        s = self._label_map(src, dev, "upsample_labels:", (half.H, half.W), "label map of the half context")
         out = torch.empty((self.H, self.W, 4), dtype=torch.float32, device=dev)
         kind = torch.empty((self.H, self.W), dtype=torch.uint8, device=dev) if with_kind else None
-        self._chk(self.L.les_hip_upsample_labels(self.h, half.h, int(mode), C.c_void_p(s.data_ptr()), C.c_void_p(out.data_ptr()),
-                                                 C.c_void_p(kind.data_ptr()) if with_kind else None))
+        self._staged(dev, s is not src, self.upsample_labels_ptr, half, mode, s.data_ptr(), out.data_ptr(), kind.data_ptr() if with_kind else None)
         return (out, kind) if with_kind else out
 
     def wta_update(self, rects, planes, cur_cost_dev, prop_cost_dev, labels_dev, planes_on_device=False):

@@ -5,6 +5,8 @@
   build_oracle()  g++ -> oracle/libles_oracle.so        (CPU restatement: test infrastructure only)
   build_sim()     g++ -> tools/hipsim/liblocalexp_sim.so (CPU SIMT simulator build of the same sources:
                   test infrastructure only, never loaded by the package)
+  build_host_sim() g++ -> localexpstereo_amd/host/les_host_demo_sim (the host demo linked against that simulator
+                  build: its `adapter` command on the CPU; test infrastructure only)
 """
 import os
 import shutil
@@ -65,18 +67,30 @@ def build_hip_plain(force=False):
     return PLAIN_SO
 
 
-def build_host(force=False):
-    exe = os.path.join(HOST, "les_host_demo")
+def _build_host_demo(name, lib, force):
+    """g++ -> localexpstereo_amd/host/<name>: les_host_demo.cpp linked against the C ABI library `lib` (rpath to its directory)."""
+    exe = os.path.join(HOST, name)
     srcs = [os.path.join(HOST, f) for f in os.listdir(HOST) if f.endswith((".h", ".cpp"))] if os.path.isdir(HOST) else []
     main = os.path.join(HOST, "les_host_demo.cpp")
     if not os.path.exists(main):
         return None
-    if not force and _newer(exe, srcs + [HIP_SO]):
+    if not force and _newer(exe, srcs + [lib]):
         return exe
+    libdir, libname = os.path.dirname(lib), os.path.basename(lib)[len("lib"):-len(".so")]
     cmd = ["g++", "-O2", "-std=c++17", "-fopenmp", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), main, "-o", exe,
-           "-L", CSRC, "-llocalexp_hip", "-Wl,-rpath," + CSRC, "-ldl"]
+           "-L", libdir, "-l" + libname, "-Wl,-rpath," + libdir, "-ldl"]
     subprocess.check_call(cmd, cwd=HOST)
     return exe
+
+
+def build_host(force=False):
+    return _build_host_demo("les_host_demo", HIP_SO, force)
+
+
+def build_host_sim(force=False):
+    """localexpstereo_amd/host/les_host_demo_sim: the same demo linked against the CPU simulator build of the library (build_sim), so
+    that its `adapter` command runs without a GPU.  Test infrastructure only, like the simulator itself."""
+    return _build_host_demo("les_host_demo_sim", build_sim(), force)
 
 
 HOST_SO = os.path.join(HOST, "liblocalexp_host.so")

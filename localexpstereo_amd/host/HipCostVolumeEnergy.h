@@ -17,6 +17,7 @@
 #include <stdexcept>
 #include <vector>
 
+#include "DeviceArray.h"
 #include "StereoEnergy.h"
 #include "localexp_hip.h"
 
@@ -122,22 +123,14 @@ public:
     // keep what cost_map held.  Returns false (and reports on stderr) when the library refuses the call.
     bool ComputeUnaryPotentialOfLabels(const Plane* labels, float* cost_map, int mode = 0, bool check = true, const Rect* region = nullptr) const
     {
-        static_assert(sizeof(Plane) == sizeof(les_hip_plane), "ABI layout");
         const size_t P = (size_t)width * height;
-        les_hip_plane* d_lab = nullptr;
-        float* d_cost = nullptr;
-        bool ok = les_hip_malloc(ctx_, (void**)&d_lab, P * sizeof(les_hip_plane)) == LES_HIP_OK && les_hip_malloc(ctx_, (void**)&d_cost, P * sizeof(float)) == LES_HIP_OK;
-        ok = ok && les_hip_memcpy_h2d(ctx_, d_lab, labels, P * sizeof(les_hip_plane)) == LES_HIP_OK && les_hip_memcpy_h2d(ctx_, d_cost, cost_map, P * sizeof(float)) == LES_HIP_OK;
-        if (ok) {
-            les_hip_rect r{0, 0, width, height};
-            if (region) r = les_hip_rect{region->x, region->y, region->width, region->height};
-            ok = les_hip_unary_labels(ctx_, mode, &r, d_lab, d_cost, check ? 1 : 0) == LES_HIP_OK;
-        }
-        ok = ok && les_hip_memcpy_d2h(ctx_, cost_map, d_cost, P * sizeof(float)) == LES_HIP_OK;
-        if (!ok) fprintf(stderr, "HipCostVolumeEnergy: %s\n", les_hip_last_error());
-        if (d_lab) les_hip_free(ctx_, d_lab);
-        if (d_cost) les_hip_free(ctx_, d_cost);
-        return ok;
+        Status st(kWho);
+        DeviceArray<Plane> d_lab(ctx_, st, labels, P);
+        DeviceArray<float> d_cost(ctx_, st, cost_map, P);
+        les_hip_rect r{0, 0, width, height};
+        if (region) r = les_hip_rect{region->x, region->y, region->width, region->height};
+        if (st.ok()) st(les_hip_unary_labels(ctx_, mode, &r, abi(d_lab), d_cost.get(), check ? 1 : 0));
+        return d_cost.download(cost_map, P);
     }
 
     // Cross-view fusion's warp (les_hip_warp_labels, csrc/les_crossview.h; no reference counterpart): the label map `src` of view src_mode (0 left,
@@ -146,20 +139,12 @@ public:
     // on stderr) when the library refuses the call (rows wider than 8192 pixels).
     bool warpLabels(int src_mode, const Plane* src, const Plane* fallback, Plane* out, unsigned char* hit = nullptr) const
     {
-        static_assert(sizeof(Plane) == sizeof(les_hip_plane), "ABI layout");
-        const size_t P = (size_t)width * height, B = P * sizeof(les_hip_plane);
-        les_hip_plane *d_src = nullptr, *d_out = nullptr;
-        unsigned char* d_hit = nullptr;
-        bool ok = les_hip_malloc(ctx_, (void**)&d_src, B) == LES_HIP_OK && les_hip_malloc(ctx_, (void**)&d_out, B) == LES_HIP_OK &&
-                  (!hit || les_hip_malloc(ctx_, (void**)&d_hit, P) == LES_HIP_OK);
-        ok = ok && les_hip_memcpy_h2d(ctx_, d_src, src, B) == LES_HIP_OK && les_hip_memcpy_h2d(ctx_, d_out, fallback, B) == LES_HIP_OK;
-        ok = ok && les_hip_warp_labels(ctx_, src_mode, d_src, d_out, d_out, d_hit) == LES_HIP_OK && les_hip_synchronize(ctx_) == LES_HIP_OK;
-        ok = ok && les_hip_memcpy_d2h(ctx_, out, d_out, B) == LES_HIP_OK && (!hit || les_hip_memcpy_d2h(ctx_, hit, d_hit, P) == LES_HIP_OK);
-        if (!ok) fprintf(stderr, "HipCostVolumeEnergy: %s\n", les_hip_last_error());
-        if (d_src) les_hip_free(ctx_, d_src);
-        if (d_out) les_hip_free(ctx_, d_out);
-        if (d_hit) les_hip_free(ctx_, d_hit);
-        return ok;
+        const size_t P = (size_t)width * height;
+        Status st(kWho);
+        DeviceArray<Plane> d_src(ctx_, st, src, P), d_out(ctx_, st, fallback, P);
+        DeviceArray<unsigned char> d_hit(ctx_, st, hit ? P : 0);
+        if (st.ok() && st(les_hip_warp_labels(ctx_, src_mode, abi(d_src), abi(d_out), abi(d_out), d_hit.get()))) st(les_hip_synchronize(ctx_));
+        return d_out.download(out, P) && d_hit.download(hit, P);
     }
 
     // Winner-take-all labels of the aggregated cost volume (les_hip_wta_labels, csrc/les_wtavol.h; no reference counterpart): per pixel of view
@@ -169,17 +154,12 @@ public:
     // library's choice).  Returns false (and reports on stderr) when the library refuses the call (a view without data).
     bool wtaLabels(Plane* labels, float* cost = nullptr, int mode = 0, bool subpixel = true, int chunk = 0) const
     {
-        static_assert(sizeof(Plane) == sizeof(les_hip_plane), "ABI layout");
         const size_t P = (size_t)width * height;
-        les_hip_plane* d_lab = nullptr;
-        float* d_cost = nullptr;
-        bool ok = les_hip_malloc(ctx_, (void**)&d_lab, P * sizeof(les_hip_plane)) == LES_HIP_OK && les_hip_malloc(ctx_, (void**)&d_cost, P * sizeof(float)) == LES_HIP_OK;
-        ok = ok && les_hip_wta_labels(ctx_, mode, chunk, subpixel ? 1 : 0, d_lab, d_cost) == LES_HIP_OK && les_hip_synchronize(ctx_) == LES_HIP_OK;
-        ok = ok && les_hip_memcpy_d2h(ctx_, labels, d_lab, P * sizeof(les_hip_plane)) == LES_HIP_OK && (!cost || les_hip_memcpy_d2h(ctx_, cost, d_cost, P * sizeof(float)) == LES_HIP_OK);
-        if (!ok) fprintf(stderr, "HipCostVolumeEnergy: %s\n", les_hip_last_error());
-        if (d_lab) les_hip_free(ctx_, d_lab);
-        if (d_cost) les_hip_free(ctx_, d_cost);
-        return ok;
+        Status st(kWho);
+        DeviceArray<Plane> d_lab(ctx_, st, P);
+        DeviceArray<float> d_cost(ctx_, st, P);
+        if (st.ok() && st(les_hip_wta_labels(ctx_, mode, chunk, subpixel ? 1 : 0, abi(d_lab), d_cost.get()))) st(les_hip_synchronize(ctx_));
+        return d_lab.download(labels, P) && d_cost.download(cost, P);
     }
 
     // The largest value a raw matching cost of this energy can take: th_col for the volume energy (its costs are truncated there),
@@ -195,23 +175,13 @@ public:
     bool confidence(const Plane* labels, float* conf, float* own = nullptr, float* rival = nullptr, int* krival = nullptr, int mode = 0, float band = 1.f,
                     float scale = 0.f, int chunk = 0) const
     {
-        static_assert(sizeof(Plane) == sizeof(les_hip_plane), "ABI layout");
         const size_t P = (size_t)width * height;
-        les_hip_plane* d_lab = nullptr;
-        float *d_conf = nullptr, *d_own = nullptr, *d_rival = nullptr;
-        int* d_kr = nullptr;
-        bool ok = les_hip_malloc(ctx_, (void**)&d_lab, P * sizeof(les_hip_plane)) == LES_HIP_OK && les_hip_malloc(ctx_, (void**)&d_conf, P * sizeof(float)) == LES_HIP_OK &&
-                  (!own || les_hip_malloc(ctx_, (void**)&d_own, P * sizeof(float)) == LES_HIP_OK) && (!rival || les_hip_malloc(ctx_, (void**)&d_rival, P * sizeof(float)) == LES_HIP_OK) &&
-                  (!krival || les_hip_malloc(ctx_, (void**)&d_kr, P * sizeof(int)) == LES_HIP_OK);
-        ok = ok && les_hip_memcpy_h2d(ctx_, d_lab, labels, P * sizeof(les_hip_plane)) == LES_HIP_OK;
-        ok = ok && les_hip_confidence(ctx_, mode, d_lab, chunk, band, scale > 0.f ? scale : rawCostMax(), d_conf, d_own, d_rival, d_kr) == LES_HIP_OK &&
-             les_hip_synchronize(ctx_) == LES_HIP_OK;
-        ok = ok && les_hip_memcpy_d2h(ctx_, conf, d_conf, P * sizeof(float)) == LES_HIP_OK && (!own || les_hip_memcpy_d2h(ctx_, own, d_own, P * sizeof(float)) == LES_HIP_OK) &&
-             (!rival || les_hip_memcpy_d2h(ctx_, rival, d_rival, P * sizeof(float)) == LES_HIP_OK) && (!krival || les_hip_memcpy_d2h(ctx_, krival, d_kr, P * sizeof(int)) == LES_HIP_OK);
-        if (!ok) fprintf(stderr, "HipCostVolumeEnergy: %s\n", les_hip_last_error());
-        for (void* q : {(void*)d_lab, (void*)d_conf, (void*)d_own, (void*)d_rival, (void*)d_kr})
-            if (q) les_hip_free(ctx_, q);
-        return ok;
+        Status st(kWho);
+        DeviceArray<Plane> d_lab(ctx_, st, labels, P);
+        DeviceArray<float> d_conf(ctx_, st, P), d_own(ctx_, st, own ? P : 0), d_rival(ctx_, st, rival ? P : 0);
+        DeviceArray<int> d_kr(ctx_, st, krival ? P : 0);
+        if (st.ok() && st(les_hip_confidence(ctx_, mode, abi(d_lab), chunk, band, scale > 0.f ? scale : rawCostMax(), d_conf.get(), d_own.get(), d_rival.get(), d_kr.get()))) st(les_hip_synchronize(ctx_));
+        return d_conf.download(conf, P) && d_own.download(own, P) && d_rival.download(rival, P) && d_kr.download(krival, P);
     }
 
     // Slanted planes fitted to a disparity map (les_hip_fit_planes, csrc/les_planefit.h; no reference counterpart): per pixel of view `mode` an
@@ -223,23 +193,13 @@ public:
     bool fitPlanes(const Plane* labels, const float* disp, const Plane* fallback, Plane* out, unsigned char* kind = nullptr, int mode = 0, int radius = 5,
                    float sig = 10.f, float gate0 = 1.f, float gate_slope = 0.5f, float max_slope = 2.f, int min_support = 6) const
     {
-        static_assert(sizeof(Plane) == sizeof(les_hip_plane), "ABI layout");
         const size_t P = (size_t)width * height;
-        les_hip_plane *d_lab = nullptr, *d_fb = nullptr, *d_out = nullptr;
-        float* d_disp = nullptr;
-        unsigned char* d_kind = nullptr;
-        bool ok = les_hip_malloc(ctx_, (void**)&d_out, P * sizeof(les_hip_plane)) == LES_HIP_OK;
-        if (labels) ok = ok && les_hip_malloc(ctx_, (void**)&d_lab, P * sizeof(les_hip_plane)) == LES_HIP_OK && les_hip_memcpy_h2d(ctx_, d_lab, labels, P * sizeof(les_hip_plane)) == LES_HIP_OK;
-        if (disp) ok = ok && les_hip_malloc(ctx_, (void**)&d_disp, P * sizeof(float)) == LES_HIP_OK && les_hip_memcpy_h2d(ctx_, d_disp, disp, P * sizeof(float)) == LES_HIP_OK;
-        if (fallback) ok = ok && les_hip_malloc(ctx_, (void**)&d_fb, P * sizeof(les_hip_plane)) == LES_HIP_OK && les_hip_memcpy_h2d(ctx_, d_fb, fallback, P * sizeof(les_hip_plane)) == LES_HIP_OK;
-        if (kind) ok = ok && les_hip_malloc(ctx_, (void**)&d_kind, P) == LES_HIP_OK;
-        ok = ok && les_hip_fit_planes(ctx_, mode, d_lab, d_disp, d_fb, d_out, d_kind, radius, sig, gate0, gate_slope, max_slope, min_support) == LES_HIP_OK &&
-             les_hip_synchronize(ctx_) == LES_HIP_OK;
-        ok = ok && les_hip_memcpy_d2h(ctx_, out, d_out, P * sizeof(les_hip_plane)) == LES_HIP_OK && (!kind || les_hip_memcpy_d2h(ctx_, kind, d_kind, P) == LES_HIP_OK);
-        if (!ok) fprintf(stderr, "HipCostVolumeEnergy: %s\n", les_hip_last_error());
-        for (void* q : {(void*)d_lab, (void*)d_disp, (void*)d_fb, (void*)d_out, (void*)d_kind})
-            if (q) les_hip_free(ctx_, q);
-        return ok;
+        Status st(kWho);
+        DeviceArray<Plane> d_lab(ctx_, st, labels, P), d_fb(ctx_, st, fallback, P), d_out(ctx_, st, P);
+        DeviceArray<float> d_disp(ctx_, st, disp, P);
+        DeviceArray<unsigned char> d_kind(ctx_, st, kind ? P : 0);
+        if (st.ok() && st(les_hip_fit_planes(ctx_, mode, abi(d_lab), d_disp.get(), abi(d_fb), abi(d_out), d_kind.get(), radius, sig, gate0, gate_slope, max_slope, min_support))) st(les_hip_synchronize(ctx_));
+        return d_out.download(out, P) && d_kind.download(kind, P);
     }
 
     // The half-resolution twin of this energy (les_hip_create_half, csrc/les_pyramid.h; no reference counterpart): a new, independent energy of the
@@ -269,19 +229,12 @@ public:
     // kind: width * height elements, all in HOST memory.  Returns false (and reports on stderr) when the library refuses the call.
     bool upsampleLabels(const HipCostVolumeEnergy& half, const Plane* src, Plane* out, unsigned char* kind = nullptr, int mode = 0) const
     {
-        static_assert(sizeof(Plane) == sizeof(les_hip_plane), "ABI layout");
         const size_t P = (size_t)width * height, Ph = (size_t)half.width * half.height;
-        les_hip_plane *d_src = nullptr, *d_out = nullptr;
-        unsigned char* d_kind = nullptr;
-        bool ok = les_hip_malloc(ctx_, (void**)&d_src, Ph * sizeof(les_hip_plane)) == LES_HIP_OK && les_hip_malloc(ctx_, (void**)&d_out, P * sizeof(les_hip_plane)) == LES_HIP_OK &&
-                  (!kind || les_hip_malloc(ctx_, (void**)&d_kind, P) == LES_HIP_OK);
-        ok = ok && les_hip_memcpy_h2d(ctx_, d_src, src, Ph * sizeof(les_hip_plane)) == LES_HIP_OK;
-        ok = ok && les_hip_upsample_labels(ctx_, half.ctx_, mode, d_src, d_out, d_kind) == LES_HIP_OK && les_hip_synchronize(ctx_) == LES_HIP_OK;
-        ok = ok && les_hip_memcpy_d2h(ctx_, out, d_out, P * sizeof(les_hip_plane)) == LES_HIP_OK && (!kind || les_hip_memcpy_d2h(ctx_, kind, d_kind, P) == LES_HIP_OK);
-        if (!ok) fprintf(stderr, "HipCostVolumeEnergy: %s\n", les_hip_last_error());
-        for (void* q : {(void*)d_src, (void*)d_out, (void*)d_kind})
-            if (q) les_hip_free(ctx_, q);
-        return ok;
+        Status st(kWho);
+        DeviceArray<Plane> d_src(ctx_, st, src, Ph), d_out(ctx_, st, P);
+        DeviceArray<unsigned char> d_kind(ctx_, st, kind ? P : 0);
+        if (st.ok() && st(les_hip_upsample_labels(ctx_, half.ctx_, mode, abi(d_src), abi(d_out), d_kind.get()))) st(les_hip_synchronize(ctx_));
+        return d_out.download(out, P) && d_kind.download(kind, P);
     }
 
     // The speckle mask of a label map (les_hip_speckle_mask, csrc/les_speckle.h; no reference counterpart, OpenCV's filterSpeckles convention):
@@ -290,21 +243,13 @@ public:
     // pixel count.  All maps: width * height elements in HOST memory.  Returns false (and reports on stderr) when the library refuses the call.
     bool speckleMask(const Plane* labels, int max_size, float max_diff, unsigned char* mask, int* root = nullptr, int* size = nullptr) const
     {
-        static_assert(sizeof(Plane) == sizeof(les_hip_plane), "ABI layout");
         const size_t P = (size_t)width * height;
-        les_hip_plane* d_lab = nullptr;
-        unsigned char* d_mask = nullptr;
-        int *d_root = nullptr, *d_size = nullptr;
-        bool ok = les_hip_malloc(ctx_, (void**)&d_lab, P * sizeof(les_hip_plane)) == LES_HIP_OK && les_hip_malloc(ctx_, (void**)&d_mask, P) == LES_HIP_OK &&
-                  (!root || les_hip_malloc(ctx_, (void**)&d_root, P * sizeof(int)) == LES_HIP_OK) && (!size || les_hip_malloc(ctx_, (void**)&d_size, P * sizeof(int)) == LES_HIP_OK);
-        ok = ok && les_hip_memcpy_h2d(ctx_, d_lab, labels, P * sizeof(les_hip_plane)) == LES_HIP_OK;
-        ok = ok && les_hip_speckle_mask(ctx_, d_lab, max_size, max_diff, d_mask, d_root, d_size) == LES_HIP_OK;
-        ok = ok && les_hip_memcpy_d2h(ctx_, mask, d_mask, P) == LES_HIP_OK && (!root || les_hip_memcpy_d2h(ctx_, root, d_root, P * sizeof(int)) == LES_HIP_OK) &&
-             (!size || les_hip_memcpy_d2h(ctx_, size, d_size, P * sizeof(int)) == LES_HIP_OK);
-        if (!ok) fprintf(stderr, "HipCostVolumeEnergy: %s\n", les_hip_last_error());
-        for (void* q : {(void*)d_lab, (void*)d_mask, (void*)d_root, (void*)d_size})
-            if (q) les_hip_free(ctx_, q);
-        return ok;
+        Status st(kWho);
+        DeviceArray<Plane> d_lab(ctx_, st, labels, P);
+        DeviceArray<unsigned char> d_mask(ctx_, st, P);
+        DeviceArray<int> d_root(ctx_, st, root ? P : 0), d_size(ctx_, st, size ? P : 0);
+        if (st.ok()) st(les_hip_speckle_mask(ctx_, abi(d_lab), max_size, max_diff, d_mask.get(), d_root.get(), d_size.get()));      // (waits itself)
+        return d_mask.download(mask, P) && d_root.download(root, P) && d_size.download(size, P);
     }
 
     // 3D geometry of a label map of view `mode` (les_hip_reproject, csrc/les_reproject.h; the reference only paints computeNormalMap): per pixel
@@ -315,22 +260,13 @@ public:
     bool reproject(const Plane* labels, const les_hip_calib& calib, float* points, float* normals, unsigned char* valid, int mode = 0,
                    const unsigned char* drop = nullptr, float z_max = 0.f) const
     {
-        static_assert(sizeof(Plane) == sizeof(les_hip_plane), "ABI layout");
         const size_t P = (size_t)width * height;
-        les_hip_plane* d_lab = nullptr;
-        unsigned char *d_drop = nullptr, *d_valid = nullptr;
-        float *d_points = nullptr, *d_normals = nullptr;
-        bool ok = les_hip_malloc(ctx_, (void**)&d_lab, P * sizeof(les_hip_plane)) == LES_HIP_OK && les_hip_malloc(ctx_, (void**)&d_valid, P) == LES_HIP_OK &&
-                  (!drop || les_hip_malloc(ctx_, (void**)&d_drop, P) == LES_HIP_OK) && (!points || les_hip_malloc(ctx_, (void**)&d_points, 3 * P * sizeof(float)) == LES_HIP_OK) &&
-                  (!normals || les_hip_malloc(ctx_, (void**)&d_normals, 3 * P * sizeof(float)) == LES_HIP_OK);
-        ok = ok && les_hip_memcpy_h2d(ctx_, d_lab, labels, P * sizeof(les_hip_plane)) == LES_HIP_OK && (!drop || les_hip_memcpy_h2d(ctx_, d_drop, drop, P) == LES_HIP_OK);
-        ok = ok && les_hip_reproject(ctx_, mode, d_lab, d_drop, &calib, z_max, d_points, d_normals, d_valid) == LES_HIP_OK && les_hip_synchronize(ctx_) == LES_HIP_OK;
-        ok = ok && les_hip_memcpy_d2h(ctx_, valid, d_valid, P) == LES_HIP_OK && (!points || les_hip_memcpy_d2h(ctx_, points, d_points, 3 * P * sizeof(float)) == LES_HIP_OK) &&
-             (!normals || les_hip_memcpy_d2h(ctx_, normals, d_normals, 3 * P * sizeof(float)) == LES_HIP_OK);
-        if (!ok) fprintf(stderr, "HipCostVolumeEnergy: %s\n", les_hip_last_error());
-        for (void* q : {(void*)d_lab, (void*)d_drop, (void*)d_valid, (void*)d_points, (void*)d_normals})
-            if (q) les_hip_free(ctx_, q);
-        return ok;
+        Status st(kWho);
+        DeviceArray<Plane> d_lab(ctx_, st, labels, P);
+        DeviceArray<unsigned char> d_drop(ctx_, st, drop, P), d_valid(ctx_, st, P);
+        DeviceArray<float> d_points(ctx_, st, points ? 3 * P : 0), d_normals(ctx_, st, normals ? 3 * P : 0);
+        if (st.ok() && st(les_hip_reproject(ctx_, mode, abi(d_lab), d_drop.get(), &calib, z_max, d_points.get(), d_normals.get(), d_valid.get()))) st(les_hip_synchronize(ctx_));
+        return d_valid.download(valid, P) && d_points.download(points, 3 * P) && d_normals.download(normals, 3 * P);
     }
 
     // The triangle mesh over the pixel grid (les_hip_mesh): vertex k is the k-th valid pixel in row-major order; neighbours are joined iff both are
@@ -341,31 +277,19 @@ public:
     bool mesh(const Plane* labels, const unsigned char* valid, float max_jump, std::vector<int>& vertex_index, std::vector<int>& vertex_pixel,
               std::vector<int>& triangles, int mode = 0) const
     {
-        static_assert(sizeof(Plane) == sizeof(les_hip_plane), "ABI layout");
         const size_t P = (size_t)width * height, T = std::max<size_t>(1, 2 * (size_t)(width - 1) * (size_t)(height - 1));
-        les_hip_plane* d_lab = nullptr;
-        unsigned char* d_valid = nullptr;
-        int *d_vi = nullptr, *d_vp = nullptr, *d_tri = nullptr;
-        long long* d_counts = nullptr;
+        Status st(kWho);
+        DeviceArray<Plane> d_lab(ctx_, st, labels, P);
+        DeviceArray<unsigned char> d_valid(ctx_, st, valid, P);
+        DeviceArray<int> d_vi(ctx_, st, P), d_vp(ctx_, st, P), d_tri(ctx_, st, 3 * T);
+        DeviceArray<long long> d_counts(ctx_, st, 2);
         long long counts[2] = {0, 0};
-        bool ok = les_hip_malloc(ctx_, (void**)&d_lab, P * sizeof(les_hip_plane)) == LES_HIP_OK && les_hip_malloc(ctx_, (void**)&d_valid, P) == LES_HIP_OK &&
-                  les_hip_malloc(ctx_, (void**)&d_vi, P * sizeof(int)) == LES_HIP_OK && les_hip_malloc(ctx_, (void**)&d_vp, P * sizeof(int)) == LES_HIP_OK &&
-                  les_hip_malloc(ctx_, (void**)&d_tri, 3 * T * sizeof(int)) == LES_HIP_OK && les_hip_malloc(ctx_, (void**)&d_counts, sizeof counts) == LES_HIP_OK;
-        ok = ok && les_hip_memcpy_h2d(ctx_, d_lab, labels, P * sizeof(les_hip_plane)) == LES_HIP_OK && les_hip_memcpy_h2d(ctx_, d_valid, valid, P) == LES_HIP_OK;
-        ok = ok && les_hip_mesh(ctx_, mode, d_lab, d_valid, max_jump, d_vi, d_vp, d_tri, d_counts) == LES_HIP_OK && les_hip_synchronize(ctx_) == LES_HIP_OK;
-        ok = ok && les_hip_memcpy_d2h(ctx_, counts, d_counts, sizeof counts) == LES_HIP_OK;
-        if (ok) {
-            vertex_index.resize(P);
-            vertex_pixel.resize((size_t)counts[0]);
-            triangles.resize(3 * (size_t)counts[1]);
-            ok = les_hip_memcpy_d2h(ctx_, vertex_index.data(), d_vi, P * sizeof(int)) == LES_HIP_OK &&
-                 (!counts[0] || les_hip_memcpy_d2h(ctx_, vertex_pixel.data(), d_vp, vertex_pixel.size() * sizeof(int)) == LES_HIP_OK) &&
-                 (!counts[1] || les_hip_memcpy_d2h(ctx_, triangles.data(), d_tri, triangles.size() * sizeof(int)) == LES_HIP_OK);
-        }
-        if (!ok) fprintf(stderr, "HipCostVolumeEnergy: %s\n", les_hip_last_error());
-        for (void* q : {(void*)d_lab, (void*)d_valid, (void*)d_vi, (void*)d_vp, (void*)d_tri, (void*)d_counts})
-            if (q) les_hip_free(ctx_, q);
-        return ok;
+        if (st.ok() && st(les_hip_mesh(ctx_, mode, abi(d_lab), d_valid.get(), max_jump, d_vi.get(), d_vp.get(), d_tri.get(), d_counts.get()))) st(les_hip_synchronize(ctx_));
+        if (!d_counts.download(counts, 2)) return false;
+        vertex_index.resize(P);
+        vertex_pixel.resize((size_t)counts[0]);
+        triangles.resize(3 * (size_t)counts[1]);
+        return d_vi.download(vertex_index.data(), P) && d_vp.download(vertex_pixel.data(), vertex_pixel.size()) && d_tri.download(triangles.data(), triangles.size());
     }
 
     // PMStereoBase::postProcess with the failure mask widened by the speckle mask (les_hip_post_process_speckle), in place on HOST label maps of
@@ -374,20 +298,11 @@ public:
     // library refuses the call.
     bool postProcessSpeckle(Plane* labelsL, Plane* labelsR, float threshold, float omega, int max_size, float max_diff) const
     {
-        static_assert(sizeof(Plane) == sizeof(les_hip_plane), "ABI layout");
-        const size_t B = (size_t)width * height * sizeof(les_hip_plane);
-        Plane* host[2] = {labelsL, labelsR};
-        les_hip_plane* d[2] = {nullptr, nullptr};
-        bool ok = true;
-        for (int m = 0; m < 2 && ok; m++)
-            if (host[m]) ok = les_hip_malloc(ctx_, (void**)&d[m], B) == LES_HIP_OK && les_hip_memcpy_h2d(ctx_, d[m], host[m], B) == LES_HIP_OK;
-        ok = ok && les_hip_post_process_speckle(ctx_, d[0], d[1], threshold, omega, max_size, max_diff) == LES_HIP_OK;
-        for (int m = 0; m < 2 && ok; m++)
-            if (host[m]) ok = les_hip_memcpy_d2h(ctx_, host[m], d[m], B) == LES_HIP_OK;
-        if (!ok) fprintf(stderr, "HipCostVolumeEnergy: %s\n", les_hip_last_error());
-        for (int m = 0; m < 2; m++)
-            if (d[m]) les_hip_free(ctx_, d[m]);
-        return ok;
+        const size_t P = (size_t)width * height;
+        Status st(kWho);
+        DeviceArray<Plane> d_l(ctx_, st, labelsL, P), d_r(ctx_, st, labelsR, P);
+        if (st.ok()) st(les_hip_post_process_speckle(ctx_, abi(d_l), abi(d_r), threshold, omega, max_size, max_diff));      // (waits itself)
+        return d_l.download(labelsL, P) && d_r.download(labelsR, P);
     }
 
     // CostVolumeEnergy::setInterpolationMethod (LES/CostVolumeEnergy.h:45-48): 0 nearest slice, 1 linear (the default), 2 quadratic.  Like the
@@ -414,6 +329,14 @@ private:
                 for (int x = 0; x < tr.width; x++)
                     costs[(size_t)(tr.y - fr.y + y) * row_stride + (tr.x - fr.x + x)] = (float)COST_FOR_INVALID;
         }
+    }
+
+    // the staged wrappers above: what their Status reports as, and a staged label map as the ABI's type
+    static constexpr const char* kWho = "HipCostVolumeEnergy";
+    static les_hip_plane* abi(const DeviceArray<Plane>& a)
+    {
+        static_assert(sizeof(Plane) == sizeof(les_hip_plane), "ABI layout");
+        return reinterpret_cast<les_hip_plane*>(a.get());
     }
 
     les_hip_ctx* ctx_;

@@ -202,9 +202,8 @@ public:
         if (labeling && (labeling->rows != height || labeling->cols != width)) { fprintf(stderr, "PMStereo::runDevice: the start labelling is not %d x %d\n", width, height); return false; }
         les_hip_ctx* ctx = hip->handle();
         const size_t P = (size_t)width * height;
-        bool ok = true;
-        auto chk = [&](int rc) { if (rc != LES_HIP_OK) { if (ok) fprintf(stderr, "PMStereo::runDevice: %s\n", les_hip_last_error()); ok = false; } };
-        chk(les_hip_set_random_vdisparity(ctx, MAX_VDISPARITY));        // the RANDOM proposals' maxVDisp, as makeHostProposer's
+        Status st("PMStereo::runDevice");       // (declared before every owner below: they report to it)
+        st(les_hip_set_random_vdisparity(ctx, MAX_VDISPARITY));        // the RANDOM proposals' maxVDisp, as makeHostProposer's
         // prepared geometry: one batch per (layer, disjoint set) + the init batch (unit +- windR -> unit)
         // Several ranks (one process per GPU): the cells of every disjoint set are dealt out in contiguous bands, rank r owns
         // cells [n r / world, n (r + 1) / world) of the set; volume, statistics and maps are replicated, and after a set's lock-steps the tiles
@@ -212,108 +211,112 @@ public:
         // then lives on the device and the host keeps no state that would have to follow the exchange.
         if (world > 1 && maxIteration > 0 && (!deviceGraph || checkFlowEnergy)) { fprintf(stderr, "PMStereo::runDevice: several ranks need deviceGraph and no self-check\n"); return false; }
         if (world > 1 && viewModes.size() > 1) { fprintf(stderr, "PMStereo::runDevice: with several ranks give each view its own group of ranks (one view per call)\n"); return false; }
-        struct SetBatch { les_hip_batch* b = nullptr; uint64_t* rng = nullptr; les_hip_plane* planes = nullptr; int n = 0; std::vector<int> cells; les_hip_exchange* x = nullptr; };
+        // a set owns what it creates; these locals go before the energy's context does (a member of *this)
+        struct SetBatch {
+            std::unique_ptr<les_hip_batch, void (*)(les_hip_batch*)> b{nullptr, les_hip_batch_destroy};
+            DeviceArray<uint64_t> rng;
+            DeviceArray<les_hip_plane> planes;
+            int n = 0;
+            std::vector<int> cells;
+            std::unique_ptr<les_hip_exchange, void (*)(les_hip_exchange*)> x{nullptr, les_hip_exchange_destroy};
+            SetBatch(les_hip_ctx* c, Status& s) : rng(c, s), planes(c, s) {}
+        };
         std::vector<std::vector<SetBatch>> batches(layermng.layers.size());
-        // all = the indices of the set's cells into the layer's rect arrays; tr / fr / un / st are indexed by cell
+        // all = the indices of the set's cells into the layer's rect arrays; frs / trs / uns / sts are indexed by cell
         auto make = [&](const std::vector<int>& all, const std::vector<Rect>& frs, const std::vector<Rect>& trs, const std::vector<Rect>& uns, const std::vector<uint64_t>& sts) {
-            SetBatch sb;
+            SetBatch sb(ctx, st);
             const int n = (int)all.size();
             std::vector<int> first((size_t)world + 1);
             for (int r = 0; r <= world; r++) first[(size_t)r] = (int)((long long)n * r / world);
             std::vector<Rect> fr, tr, un;
-            std::vector<uint64_t> st;
+            std::vector<uint64_t> seeds;
             for (int i = first[(size_t)rank]; i < first[(size_t)rank + 1]; i++) {
                 const int c = all[(size_t)i];
-                sb.cells.push_back(c); fr.push_back(frs[(size_t)c]); tr.push_back(trs[(size_t)c]); un.push_back(uns[(size_t)c]); st.push_back(sts[(size_t)c]);
+                sb.cells.push_back(c); fr.push_back(frs[(size_t)c]); tr.push_back(trs[(size_t)c]); un.push_back(uns[(size_t)c]); seeds.push_back(sts[(size_t)c]);
             }
             sb.n = (int)sb.cells.size();
-            chk(les_hip_batch_create(ctx, sb.n, reinterpret_cast<const les_hip_rect*>(fr.data()), reinterpret_cast<const les_hip_rect*>(tr.data()), 0, &sb.b));
-            if (sb.b && sb.n > 0) chk(les_hip_batch_set_units(ctx, sb.b, reinterpret_cast<const les_hip_rect*>(un.data())));
-            chk(les_hip_malloc(ctx, (void**)&sb.rng, sizeof(uint64_t) * std::max(1, sb.n)));
-            chk(les_hip_malloc(ctx, (void**)&sb.planes, sizeof(les_hip_plane) * std::max(1, sb.n)));
-            if (ok && sb.n > 0) chk(les_hip_memcpy_h2d(ctx, sb.rng, st.data(), sizeof(uint64_t) * sb.n));
+            les_hip_batch* b = nullptr;
+            st(les_hip_batch_create(ctx, sb.n, reinterpret_cast<const les_hip_rect*>(fr.data()), reinterpret_cast<const les_hip_rect*>(tr.data()), 0, &b));
+            sb.b.reset(b);
+            if (b && sb.n > 0) st(les_hip_batch_set_units(ctx, b, reinterpret_cast<const les_hip_rect*>(un.data())));
+            sb.rng.alloc((size_t)std::max(1, sb.n));
+            sb.planes.alloc((size_t)std::max(1, sb.n));
+            sb.rng.upload(seeds.data(), (size_t)sb.n);
             if (world > 1) {
                 std::vector<Rect> every;
                 for (int c : all) every.push_back(trs[(size_t)c]);
-                chk(les_hip_exchange_create(ctx, rank, world, n, reinterpret_cast<const les_hip_rect*>(every.data()), first.data(), &sb.x));
+                les_hip_exchange* x = nullptr;
+                st(les_hip_exchange_create(ctx, rank, world, n, reinterpret_cast<const les_hip_rect*>(every.data()), first.data(), &x));
+                sb.x.reset(x);
             }
             return sb;
         };
         // publish the tiles of the set this rank updated: on the host's RCCL communicator, or through gatherFn (another transport / tests)
-        float *d_xsend = nullptr, *d_xrecv = nullptr;
-        long long xcap = 0;
+        DeviceArray<float> d_xsend(ctx, st), d_xrecv(ctx, st);
         auto exchange = [&](SetBatch& sb, les_hip_plane* d_lab, float* d_cost) {
-            if (world == 1 || !sb.x || !ok) return;
-            if (!gatherFn) { chk(les_hip_exchange_tiles(ctx, sb.x, ncclComm, d_lab, d_cost)); return; }
-            const long long slot = les_hip_exchange_slot_floats(sb.x);
+            if (world == 1 || !sb.x || !st.ok()) return;
+            if (!gatherFn) { st(les_hip_exchange_tiles(ctx, sb.x.get(), ncclComm, d_lab, d_cost)); return; }
+            const long long slot = les_hip_exchange_slot_floats(sb.x.get());
             if (slot == 0) return;
-            if (slot > xcap) {
-                if (d_xsend) les_hip_free(ctx, d_xsend);
-                if (d_xrecv) les_hip_free(ctx, d_xrecv);
-                d_xsend = d_xrecv = nullptr;
-                xcap = slot;
-                chk(les_hip_malloc(ctx, (void**)&d_xsend, sizeof(float) * (size_t)slot));
-                chk(les_hip_malloc(ctx, (void**)&d_xrecv, sizeof(float) * (size_t)slot * (size_t)world));
-            }
-            chk(les_hip_exchange_pack(ctx, sb.x, d_lab, d_cost, d_xsend));
-            chk(les_hip_synchronize(ctx));
-            if (ok) gatherFn(rank, d_xsend, d_xrecv, slot);
-            chk(les_hip_exchange_unpack(ctx, sb.x, d_xrecv, d_lab, d_cost));
+            d_xsend.grow((size_t)slot);
+            d_xrecv.grow((size_t)slot * (size_t)world);
+            st(les_hip_exchange_pack(ctx, sb.x.get(), d_lab, d_cost, d_xsend.get()));
+            st(les_hip_synchronize(ctx));
+            if (st.ok()) gatherFn(rank, d_xsend.get(), d_xrecv.get(), slot);
+            st(les_hip_exchange_unpack(ctx, sb.x.get(), d_xrecv.get(), d_lab, d_cost));
         };
         const Rect image(0, 0, width, height);
-        for (size_t li = 0; li < layermng.layers.size() && ok; li++) {
+        for (size_t li = 0; li < layermng.layers.size() && st.ok(); li++) {
             const auto& L = layermng.layers[li];
             for (const auto& set : L.disjointRegionSets) batches[li].push_back(make(set, L.filterRegions, L.sharedRegions, L.unitRegions, rngStates[li]));
         }
-        SetBatch init;
-        {
+        SetBatch init = [&] {
             const auto& L = layermng.layers[0];
             std::vector<Rect> fr;
             std::vector<int> all(L.unitRegions.size());
             const int R = params.windR;
             for (size_t i = 0; i < L.unitRegions.size(); i++) { const Rect& u = L.unitRegions[i]; all[i] = (int)i; fr.push_back(Rect(u.x - R, u.y - R, u.width + 2 * R, u.height + 2 * R) & image); }
-            init = make(all, fr, L.unitRegions, L.unitRegions, rngStates[0]);
-        }
-        les_hip_plane* d_labels = nullptr;
-        float *d_cur = nullptr, *d_prop = nullptr;
-        chk(les_hip_malloc(ctx, (void**)&d_labels, P * sizeof(les_hip_plane)));
-        chk(les_hip_malloc(ctx, (void**)&d_cur, P * sizeof(float)));
-        chk(les_hip_malloc(ctx, (void**)&d_prop, P * sizeof(float)));
+            return make(all, fr, L.unitRegions, L.unitRegions, rngStates[0]);
+        }();
+        static_assert(sizeof(Plane) == sizeof(les_hip_plane), "ABI layout");
+        const auto host_planes = [](LabelMap& m) { return reinterpret_cast<les_hip_plane*>(m.data.data()); };
+        DeviceArray<les_hip_plane> labels(ctx, st, P);
+        DeviceArray<float> cur(ctx, st, P), prop(ctx, st, P);
+        les_hip_plane* const d_labels = labels.get();
+        float *const d_cur = cur.get(), *const d_prop = prop.get();
         const auto t0 = std::chrono::steady_clock::now();
         for (int mode : viewModes) {
-            if (!ok) break;
+            if (!st.ok()) break;
             // initCurrentFast on the device: random label per layer-0 cell, cost of its unit region
-            chk(les_hip_memset(ctx, d_labels, 0, P * sizeof(les_hip_plane)));
-            chk(les_hip_memset(ctx, d_cur, 0, P * sizeof(float)));
+            st(les_hip_memset(ctx, d_labels, 0, P * sizeof(les_hip_plane)));
+            st(les_hip_memset(ctx, d_cur, 0, P * sizeof(float)));
             if (labeling) {
                 // the warm-start branch (LES/FastGCStereo.h:116-130): every rank evaluates the whole map (replicated state, nothing to exchange)
-                chk(les_hip_memcpy_h2d(ctx, d_labels, labeling->data.data(), P * sizeof(les_hip_plane)));
-                chk(les_hip_unary_labels(ctx, mode, nullptr, d_labels, d_cur, 1));
+                labels.upload(reinterpret_cast<const les_hip_plane*>(labeling->data.data()), P);
+                st(les_hip_unary_labels(ctx, mode, nullptr, d_labels, d_cur, 1));
             } else {
                 if (init.n > 0) {
-                    chk(les_hip_batch_propose(ctx, init.b, LES_HIP_PROPOSE_INIT, 0, d_labels, init.rng, init.planes));
-                    chk(les_hip_batch_run(ctx, init.b, mode, init.planes, 1, d_cur, 1));
+                    st(les_hip_batch_propose(ctx, init.b.get(), LES_HIP_PROPOSE_INIT, 0, d_labels, init.rng.get(), init.planes.get()));
+                    st(les_hip_batch_run(ctx, init.b.get(), mode, init.planes.get(), 1, d_cur, 1));
                 }
                 exchange(init, d_labels, d_cur);
             }
-            for (int iteration = 0; iteration < pmInit && ok; iteration++)
+            for (int iteration = 0; iteration < pmInit && st.ok(); iteration++)
                 for (size_t li = 0; li < batches.size(); li++)
                     for (SetBatch& sb : batches[li]) {
                         for (const ProposerSpec& spec : layerProposers[li])
                             for (int it = 0; it < spec.K && sb.n > 0; it++) {
                                 const int m = iteration + it;
                                 if (spec.kind == LES_HIP_PROPOSE_RANDOM && randomWidth(m) < 0.1) break;      // LES/Proposer.h:149-152
-                                chk(les_hip_batch_propose(ctx, sb.b, spec.kind, m, d_labels, sb.rng, sb.planes));
-                                chk(les_hip_batch_run(ctx, sb.b, mode, sb.planes, 1, d_prop, 1));
-                                chk(les_hip_batch_wta(ctx, sb.b, sb.planes, d_cur, d_prop, d_labels));
+                                st(les_hip_batch_propose(ctx, sb.b.get(), spec.kind, m, d_labels, sb.rng.get(), sb.planes.get()));
+                                st(les_hip_batch_run(ctx, sb.b.get(), mode, sb.planes.get(), 1, d_prop, 1));
+                                st(les_hip_batch_wta(ctx, sb.b.get(), sb.planes.get(), d_cur, d_prop, d_labels));
                             }
                         exchange(sb, d_labels, d_cur);
                     }
-            chk(les_hip_synchronize(ctx));
-            if (ok) {
-                chk(les_hip_memcpy_d2h(ctx, currentLabeling_[mode].data.data(), d_labels, P * sizeof(les_hip_plane)));
-                chk(les_hip_memcpy_d2h(ctx, currentCost_[mode].data.data(), d_cur, P * sizeof(float)));
-            }
+            st(les_hip_synchronize(ctx));
+            labels.download(host_planes(currentLabeling_[mode]), P);
+            cur.download(currentCost_[mode].data.data(), P);
             // graph-cut iterations: GPU proposes and evaluates the unary costs of all cells of a set, the host cores
             // cut the cells' graphs, the fused label map returns to the device for the next proposals
             CostMap proposalCost(height, width);
@@ -321,84 +324,68 @@ public:
             std::vector<float> payload;
             std::vector<uint8_t> masks;
             std::vector<long long> goff;
-            float* d_payload = nullptr;
-            unsigned char* d_masks = nullptr;
-            int* d_status = nullptr;
+            // per view, each grown only when a set needs more than any earlier one did
+            DeviceArray<float> d_payload(ctx, st);
+            DeviceArray<unsigned char> d_masks(ctx, st);
+            DeviceArray<int> d_status(ctx, st);
+            DeviceArray<unsigned char> d_tiled(ctx, st);      // scratch of the tiled device max-flow, in bytes (this thread's: one per runDevice call)
             std::vector<int> status;
-            long long payload_cap = 0, status_cap = 0, tiled_cap = 0;
-            void* d_tiled = nullptr;                 // scratch of the tiled device max-flow (this thread's: one per runDevice call)
             // deviceGraph: the solution stays on the GPU; the host receives the ready-made graphs and returns one mask byte
             // per node.  Otherwise (or with the self-check on): host-resident solution and host graph construction.
             const bool devGraph = deviceGraph && !checkFlowEnergy;
-            for (int iteration = 0; iteration < maxIteration && ok; iteration++)
+            for (int iteration = 0; iteration < maxIteration && st.ok(); iteration++)
                 for (size_t li = 0; li < batches.size(); li++)
                     for (SetBatch& sb : batches[li]) {
+                        les_hip_batch* const b = sb.b.get();
+                        les_hip_plane* const d_planes = sb.planes.get();
                         for (const ProposerSpec& spec : layerProposers[li])
-                            for (int it = 0; it < spec.K && ok && sb.n > 0; it++) {
+                            for (int it = 0; it < spec.K && st.ok() && sb.n > 0; it++) {
                                 const int m = iteration + it;
                                 if (spec.kind == LES_HIP_PROPOSE_RANDOM && randomWidth(m) < 0.1) break;
                                 const auto tA = std::chrono::steady_clock::now();
-                                chk(les_hip_batch_propose(ctx, sb.b, spec.kind, m, d_labels, sb.rng, sb.planes));
-                                chk(les_hip_batch_run(ctx, sb.b, mode, sb.planes, 1, d_prop, 1));
+                                st(les_hip_batch_propose(ctx, b, spec.kind, m, d_labels, sb.rng.get(), d_planes));
+                                st(les_hip_batch_run(ctx, b, mode, d_planes, 1, d_prop, 1));
                                 const auto& L = layermng.layers[li];
                                 // team of the host cuts: one thread per cell, at most 24, never more than the CPUs the process is granted
                                 const int nthreads = std::max(1, std::min(sb.n, hostThreads > 0 ? hostThreads : std::min({24, omp_get_max_threads(), std::max(1, cpuBudget())})));
                                 std::chrono::steady_clock::time_point tB, tC;
                                 if (devGraph) {
-                                    const long long nodes = les_hip_batch_graph_nodes(sb.b);
-                                    if (nodes > payload_cap) {
-                                        if (d_payload) les_hip_free(ctx, d_payload);
-                                        if (d_masks) les_hip_free(ctx, d_masks);
-                                        d_payload = nullptr; d_masks = nullptr;
-                                        payload_cap = nodes;
-                                        chk(les_hip_malloc(ctx, (void**)&d_payload, (size_t)nodes * 5 * sizeof(float)));
-                                        chk(les_hip_malloc(ctx, (void**)&d_masks, (size_t)nodes));
-                                    }
-                                    chk(les_hip_batch_expansion_graph(ctx, sb.b, mode, sb.planes, d_labels, d_cur, d_prop, params.lambda, params.th_smooth,
-                                                                      params.omega, params.epsilon, d_payload, nullptr));
+                                    const long long nodes = les_hip_batch_graph_nodes(b);
+                                    d_payload.grow((size_t)nodes * 5);
+                                    d_masks.grow((size_t)nodes);
+                                    st(les_hip_batch_expansion_graph(ctx, b, mode, d_planes, d_labels, d_cur, d_prop, params.lambda, params.th_smooth,
+                                                                     params.omega, params.epsilon, d_payload.get(), nullptr));
                                     // cells that fit a workgroup's LDS (the finest layer) are also CUT on the device: neither their graphs
                                     // nor their masks cross PCIe (LES/FastGCStereo.h:553-559 -> les_hip_batch_solve_graphs)
                                     // ... and since round 5 the larger cells (the coarse layers) as well: their graphs stay in device memory and
                                     // are cut by the tiled solver, one workgroup per tile (les_hip_batch_solve_graphs_tiled)
                                     bool cutOnDevice = false;
-                                    const bool fitsLds = les_hip_batch_max_cell_nodes(sb.b) <= LES_HIP_MAXFLOW_MAX_NODES;
-                                    if (deviceCuts && ok && (fitsLds || deviceCutsCoarse)) {
-                                        if (sb.n > status_cap) {
-                                            if (d_status) les_hip_free(ctx, d_status);
-                                            d_status = nullptr;
-                                            status_cap = sb.n;
-                                            chk(les_hip_malloc(ctx, (void**)&d_status, sizeof(int) * (size_t)sb.n));
-                                        }
+                                    const bool fitsLds = les_hip_batch_max_cell_nodes(b) <= LES_HIP_MAXFLOW_MAX_NODES;
+                                    if (deviceCuts && st.ok() && (fitsLds || deviceCutsCoarse)) {
+                                        d_status.grow((size_t)sb.n);
                                         status.assign((size_t)sb.n, 1);
                                         if (fitsLds) {
-                                            chk(les_hip_batch_solve_graphs(ctx, sb.b, d_payload, d_masks, d_status, nullptr));
+                                            st(les_hip_batch_solve_graphs(ctx, b, d_payload.get(), d_masks.get(), d_status.get(), nullptr));
+                                            d_status.download(status.data(), (size_t)sb.n);
                                         } else {
-                                            const long long need = les_hip_batch_tiled_workspace_bytes(sb.b);
-                                            if (need > tiled_cap) {
-                                                if (d_tiled) les_hip_free(ctx, d_tiled);
-                                                d_tiled = nullptr;
-                                                tiled_cap = need;
-                                                chk(les_hip_malloc(ctx, &d_tiled, (size_t)need));
-                                            }
+                                            d_tiled.grow((size_t)les_hip_batch_tiled_workspace_bytes(b));
                                             int launches = 0, unsolved = 0;
-                                            if (ok) chk(les_hip_batch_solve_graphs_tiled(ctx, sb.b, d_payload, d_masks, d_status, nullptr, d_tiled, tiled_cap, &launches, &unsolved));
+                                            if (st.ok()) st(les_hip_batch_solve_graphs_tiled(ctx, b, d_payload.get(), d_masks.get(), d_status.get(), nullptr, d_tiled.get(), (long long)d_tiled.size(), &launches, &unsolved));
                                             gcTiledLaunches += launches;
                                             status.assign((size_t)sb.n, unsolved ? 1 : 0);       // (reported through a host-mapped word: no copy of d_status)
                                         }
-                                        if (ok && fitsLds) chk(les_hip_memcpy_d2h(ctx, status.data(), d_status, sizeof(int) * (size_t)sb.n));
-                                        cutOnDevice = ok && std::all_of(status.begin(), status.end(), [](int v) { return v == 0; });
+                                        cutOnDevice = st.ok() && std::all_of(status.begin(), status.end(), [](int v) { return v == 0; });
                                     }
                                     if (cutOnDevice) {
                                         tB = tC = std::chrono::steady_clock::now();
-                                        chk(les_hip_batch_apply_masks(ctx, sb.b, sb.planes, d_masks, d_cur, d_prop, d_labels));
+                                        st(les_hip_batch_apply_masks(ctx, b, d_planes, d_masks.get(), d_cur, d_prop, d_labels));
                                         gcCellsCutOnDevice += sb.n;
                                     } else {
                                     payload.resize((size_t)nodes * 5);
                                     masks.resize((size_t)nodes);
                                     goff.resize((size_t)sb.n);
-                                    chk(les_hip_batch_graph_offsets(sb.b, goff.data()));
-                                    if (ok) chk(les_hip_memcpy_d2h(ctx, payload.data(), d_payload, (size_t)nodes * 5 * sizeof(float)));
-                                    if (!ok) break;
+                                    st(les_hip_batch_graph_offsets(b, goff.data()));
+                                    if (!d_payload.download(payload.data(), (size_t)nodes * 5)) break;
                                     tB = std::chrono::steady_clock::now();
                                     // large cells (the coarser layers) split their max-flow over row bands on helper threads, like
                                     // les_gc_solve_prebuilt does for non-C++ hosts (ExpansionMove.h: bandsFor / tuneBandSpin)
@@ -409,14 +396,13 @@ public:
                                         expansionMovePrebuilt(payload.data() + 5 * goff[n], 0.0, region, masks.data() + goff[n], bandsFor(region, sb.n));
                                     }
                                     tC = std::chrono::steady_clock::now();
-                                    chk(les_hip_memcpy_h2d(ctx, d_masks, masks.data(), (size_t)nodes));
-                                    chk(les_hip_batch_apply_masks(ctx, sb.b, sb.planes, d_masks, d_cur, d_prop, d_labels));
+                                    d_masks.upload(masks.data(), (size_t)nodes);
+                                    st(les_hip_batch_apply_masks(ctx, b, d_planes, d_masks.get(), d_cur, d_prop, d_labels));
                                     }
                                 } else {
                                     hplanes.resize(sb.n);
-                                    chk(les_hip_memcpy_d2h(ctx, hplanes.data(), sb.planes, sizeof(les_hip_plane) * sb.n));
-                                    chk(les_hip_memcpy_d2h(ctx, proposalCost.data.data(), d_prop, P * sizeof(float)));
-                                    if (!ok) break;
+                                    sb.planes.download(hplanes.data(), (size_t)sb.n);
+                                    if (!prop.download(proposalCost.data.data(), P)) break;
                                     tB = std::chrono::steady_clock::now();
 #pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads)
                                     for (int n = 0; n < sb.n; n++) {
@@ -424,7 +410,7 @@ public:
                                         fuseProposal(Plane(hp.a, hp.b, hp.c, hp.v), L.sharedRegions[sb.cells[n]], proposalCost, mode, true);
                                     }
                                     tC = std::chrono::steady_clock::now();
-                                    chk(les_hip_memcpy_h2d(ctx, d_labels, currentLabeling_[mode].data.data(), P * sizeof(les_hip_plane)));
+                                    labels.upload(host_planes(currentLabeling_[mode]), P);
                                 }
                                 const auto tD = std::chrono::steady_clock::now();
                                 gcSeconds[0] += std::chrono::duration<double>(tB - tA).count();
@@ -434,26 +420,17 @@ public:
                             }
                         exchange(sb, d_labels, d_cur);
                     }
-            if (devGraph && maxIteration > 0 && ok) {
-                chk(les_hip_synchronize(ctx));
-                chk(les_hip_memcpy_d2h(ctx, currentLabeling_[mode].data.data(), d_labels, P * sizeof(les_hip_plane)));
-                chk(les_hip_memcpy_d2h(ctx, currentCost_[mode].data.data(), d_cur, P * sizeof(float)));
+            if (devGraph && maxIteration > 0 && st.ok()) {
+                st(les_hip_synchronize(ctx));
+                labels.download(host_planes(currentLabeling_[mode]), P);
+                cur.download(currentCost_[mode].data.data(), P);
             }
-            if (d_payload) les_hip_free(ctx, d_payload);
-            if (d_masks) les_hip_free(ctx, d_masks);
-            if (d_status) les_hip_free(ctx, d_status);
-            if (d_tiled) les_hip_free(ctx, d_tiled);
         }
         // two-view runs end with the left-right post-processing (LES/FastGCStereo.h:199-203)
         // (opt-in: with a speckle filter set the mask is widened, and a one-view run is post-processed with the speckle mask alone)
+        bool ok = st.ok();
         if (ok && (viewModes.size() == 2 || speckleSize > 0)) ok = postProcess(1.5f, viewModes);
         if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        for (auto& lb : batches)
-            for (SetBatch& sb : lb) { les_hip_batch_destroy(sb.b); les_hip_free(ctx, sb.rng); les_hip_free(ctx, sb.planes); les_hip_exchange_destroy(sb.x); }
-        les_hip_batch_destroy(init.b); les_hip_free(ctx, init.rng); les_hip_free(ctx, init.planes); les_hip_exchange_destroy(init.x);
-        if (d_xsend) les_hip_free(ctx, d_xsend);
-        if (d_xrecv) les_hip_free(ctx, d_xrecv);
-        les_hip_free(ctx, d_labels); les_hip_free(ctx, d_cur); les_hip_free(ctx, d_prop);
         return ok;
     }
 
@@ -468,25 +445,22 @@ public:
         auto* hip = dynamic_cast<HipCostVolumeEnergy*>(stereoEnergy.get());
         if (!hip) return false;
         les_hip_ctx* ctx = hip->handle();
-        const size_t bytes = (size_t)width * height * sizeof(les_hip_plane);
+        const size_t P = (size_t)width * height;
         bool has[2] = {false, false};
         for (int m : views)
             if (m == 0 || m == 1) has[m] = true;
         if (speckleSize <= 0 && !(has[0] && has[1])) { fprintf(stderr, "PMStereo::postProcess: one view needs a speckle filter (speckleSize > 0)\n"); return false; }
         if (has[0]) rawLabeling0 = currentLabeling_[0];
-        les_hip_plane* d[2] = {nullptr, nullptr};
-        bool ok = true;
-        for (int m = 0; m < 2 && ok; m++)
-            if (has[m]) ok = les_hip_malloc(ctx, (void**)&d[m], bytes) == LES_HIP_OK && les_hip_memcpy_h2d(ctx, d[m], currentLabeling_[m].data.data(), bytes) == LES_HIP_OK;
-        if (ok)
-            ok = (speckleSize > 0 ? les_hip_post_process_speckle(ctx, d[0], d[1], threshold, params.omega, speckleSize, speckleDiff)
-                                  : les_hip_post_process(ctx, d[0], d[1], threshold, params.omega)) == LES_HIP_OK;
-        for (int m = 0; m < 2 && ok; m++)
-            if (has[m]) ok = les_hip_memcpy_d2h(ctx, currentLabeling_[m].data.data(), d[m], bytes) == LES_HIP_OK;
-        if (!ok) fprintf(stderr, "PMStereo::postProcess: %s\n", les_hip_last_error());
+        static_assert(sizeof(Plane) == sizeof(les_hip_plane), "ABI layout");
+        les_hip_plane* host[2] = {nullptr, nullptr};       // (null: a view that is not there -- nothing staged, a null device map)
         for (int m = 0; m < 2; m++)
-            if (d[m]) les_hip_free(ctx, d[m]);
-        return ok;
+            if (has[m]) host[m] = reinterpret_cast<les_hip_plane*>(currentLabeling_[m].data.data());
+        Status st("PMStereo::postProcess");
+        DeviceArray<les_hip_plane> d_l(ctx, st, host[0], P), d_r(ctx, st, host[1], P);
+        // (the speckle entry validates speckleDiff even at size 0: without a filter the plain entry is the one to call)
+        if (st.ok()) st(speckleSize > 0 ? les_hip_post_process_speckle(ctx, d_l.get(), d_r.get(), threshold, params.omega, speckleSize, speckleDiff)
+                                        : les_hip_post_process(ctx, d_l.get(), d_r.get(), threshold, params.omega));
+        return d_l.download(host[0], P) && d_r.download(host[1], P);
     }
     LabelMap rawLabeling0;
 

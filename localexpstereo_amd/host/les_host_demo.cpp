@@ -6,7 +6,9 @@
 //                                              iterations (a) through the drop-in operator from OpenMP
 //                                              threads like the reference loop and (b) device-resident,
 //                                              and checks that both reduce the energy and reach the
-//                                              ground truth (needs an MI355X)
+//                                              ground truth, then the adapter checks (needs an MI355X)
+//   les_host_demo adapter [W H D]              the adapter checks of `run` alone: every host-map wrapper of
+//                                              HipCostVolumeEnergy.h on planted maps, and calls it must refuse
 #include <dlfcn.h>
 #include <cmath>
 #include <cstdio>
@@ -72,6 +74,158 @@ static int cmd_maxflow(int argc, char** argv)
     return 0;
 }
 
+// The host-map wrappers of the adapter (HipCostVolumeEnergy.h), each on a planted map whose result is known: the end of `run`, and all of `adapter`.
+// left_only: an energy over the same scene built without a right view (for a refusal)
+static int adapter_checks(const HipCostVolumeEnergy& hip, const HipCostVolumeEnergy& left_only, int W, int H)
+{
+    int fail = 0;
+    // cross-view fusion's warp through the adapter: a fronto-parallel left-view map at disparity 3 lands three columns to the left with v
+    // negated; the three rightmost columns keep the fallback
+    const size_t P = (size_t)W * H;
+    std::vector<Plane> wsrc(P, Plane(0.f, 0.f, 3.f, 0.5f)), wfb(P, Plane(0.125f, -0.25f, 7.f, 0.f)), wout(P);
+    std::vector<unsigned char> whit(P, 9);
+    const bool okw = hip.warpLabels(0, wsrc.data(), wfb.data(), wout.data(), whit.data());
+    size_t wbad = 0;
+    for (int y = 0; y < H; y++)
+        for (int x = 0; x < W; x++) {
+            const bool in = x + 3 < W;
+            const Plane want = in ? Plane(0.f, 0.f, 3.f, -0.5f) : wfb[(size_t)y * W + x];
+            wbad += memcmp(&wout[(size_t)y * W + x], &want, sizeof(Plane)) != 0 || whit[(size_t)y * W + x] != (in ? 1 : 0);
+        }
+    printf("warpLabels: %zu of %zu pixels differ from the expected map\n", wbad, P);
+    if (!okw || wbad) { printf("FAIL: warpLabels\n"); fail = 1; }
+    // the winner-take-all map of the filtered volume through the adapter: fronto-parallel planes, chunking does not change a bit
+    std::vector<Plane> wta(P), wta2(P);
+    std::vector<float> wcost(P);
+    const bool okt = hip.wtaLabels(wta.data(), wcost.data(), 0) && hip.wtaLabels(wta2.data(), nullptr, 0, true, 3);
+    size_t tbad = 0;
+    for (size_t i = 0; i < P; i++)
+        tbad += !(wta[i].a == 0.f && wta[i].b == 0.f && wta[i].v == 0.f && std::isfinite(wta[i].c) && std::isfinite(wcost[i])) || memcmp(&wta[i], &wta2[i], sizeof(Plane)) != 0;
+    printf("wtaLabels: %zu of %zu pixels are not a finite fronto-parallel plane or depend on the chunking\n", tbad, P);
+    if (!okt || tbad) { printf("FAIL: wtaLabels\n"); fail = 1; }
+    // the confidence of that map through the adapter: in [0, 1], the in-band minimum of a WTA label is the WTA cost itself and no rival lies
+    // below it, and the chunking does not change a bit
+    std::vector<float> conf(P), conf2(P), cown(P), crival(P);
+    std::vector<int> ckr(P);
+    const bool okc = hip.confidence(wta.data(), conf.data(), cown.data(), crival.data(), ckr.data(), 0) &&
+                     hip.confidence(wta.data(), conf2.data(), nullptr, nullptr, nullptr, 0, 1.f, 0.f, 3);
+    size_t qbad = 0, qpos = 0;
+    for (size_t i = 0; i < P; i++) {
+        qbad += !(conf[i] >= 0.f && conf[i] <= 1.f) || memcmp(&conf[i], &conf2[i], sizeof(float)) != 0 || cown[i] != wcost[i] || (ckr[i] >= 0 && crival[i] < cown[i]);
+        qpos += conf[i] > 0.f;
+    }
+    printf("confidence: %zu of %zu pixels are outside [0, 1], disagree with the WTA cost or depend on the chunking; %zu are above 0\n", qbad, P, qpos);
+    if (!okc || qbad || !qpos) { printf("FAIL: confidence\n"); fail = 1; }
+    // the planes fitted to that map through the adapter: every pixel a finite plane of its kind, from the labels and from their disparities alike
+    std::vector<Plane> fit(P), fit2(P);
+    std::vector<unsigned char> kind(P);
+    std::vector<float> wdisp(P);
+    for (size_t i = 0; i < P; i++) wdisp[i] = wta[i].c;            // (fronto-parallel planes: d = c)
+    const bool okf = hip.fitPlanes(wta.data(), nullptr, wta.data(), fit.data(), kind.data(), 0) && hip.fitPlanes(nullptr, wdisp.data(), wta.data(), fit2.data(), nullptr, 0);
+    size_t fbad = 0, slanted = 0;
+    for (size_t i = 0; i < P; i++) {
+        fbad += kind[i] > 2 || !(std::isfinite(fit[i].a) && std::isfinite(fit[i].b) && std::isfinite(fit[i].c)) || memcmp(&fit[i], &fit2[i], sizeof(Plane)) != 0 ||
+                (kind[i] == 1 && !(fit[i].a == 0.f && fit[i].b == 0.f && fit[i].c == wta[i].c));
+        slanted += kind[i] == 2;
+    }
+    printf("fitPlanes: %zu of %zu pixels are not a finite plane of their kind or depend on the input form; %zu slanted fits\n", fbad, P, slanted);
+    if (!okf || fbad || !slanted) { printf("FAIL: fitPlanes\n"); fail = 1; }
+    // the half-resolution twin through the adapter: a fronto-parallel half map at disparity 3 comes up as disparity 6 everywhere, v doubled
+    auto halfE = hip.half();
+    const size_t Ph = (size_t)((W + 1) / 2) * ((H + 1) / 2);
+    std::vector<Plane> hsrc(Ph, Plane(0.f, 0.f, 3.f, 0.25f)), up(P);
+    std::vector<unsigned char> ukind(P, 9);
+    const bool oku = hip.upsampleLabels(*halfE, hsrc.data(), up.data(), ukind.data(), 0);
+    const Plane uwant(0.f, 0.f, 6.f, 0.5f);
+    size_t ubad = 0;
+    for (size_t i = 0; i < P; i++) ubad += memcmp(&up[i], &uwant, sizeof(Plane)) != 0 || ukind[i] != 0;
+    printf("half / upsampleLabels: a %d x %d twin with windR %d; %zu of %zu pixels differ from the expected map\n", (W + 1) / 2, (H + 1) / 2, halfE->params.windR, ubad, P);
+    if (!oku || ubad || halfE->maxDisparity() != 0.5f * hip.maxDisparity()) { printf("FAIL: half / upsampleLabels\n"); fail = 1; }
+    // the speckle filter through the adapter: a fronto-parallel map at disparity 3 with planted 2 x 3 islands at disparity 9.  The mask is the
+    // islands; the one-view post-processing changes every island pixel and nothing else (so nothing outside the dilated mask); with
+    // max_size 0 the two-view form leaves the bytes of les_hip_post_process
+    std::vector<Plane> smap(P, Plane(0.f, 0.f, 3.f, 0.f));
+    std::vector<unsigned char> island(P, 0), smask(P, 9);
+    std::vector<int> sroot(P), ssize(P);
+    size_t planted = 0;
+    for (int y0 = 5; y0 + 2 <= H - 5; y0 += 9)
+        for (int x0 = 6; x0 + 3 <= W - 6; x0 += 11)
+            for (int y = y0; y < y0 + 2; y++)
+                for (int x = x0; x < x0 + 3; x++) { smap[(size_t)y * W + x] = Plane(0.f, 0.f, 9.f, 1.f); island[(size_t)y * W + x] = 255; planted++; }
+    std::vector<Plane> sone = smap, sl = smap, sr = smap, pl = smap, pr = smap;
+    bool oks = hip.speckleMask(smap.data(), 20, 1.0f, smask.data(), sroot.data(), ssize.data());
+    oks = oks && hip.postProcessSpeckle(sone.data(), nullptr, 1.5f, hip.params.omega, 20, 1.0f);
+    oks = oks && hip.postProcessSpeckle(sl.data(), sr.data(), 1.5f, hip.params.omega, 0, 1.0f);
+    {
+        Status ps("les_host_demo");
+        DeviceArray<Plane> d_l(hip.handle(), ps, pl.data(), P), d_r(hip.handle(), ps, pr.data(), P);
+        if (ps.ok()) ps(les_hip_post_process(hip.handle(), (les_hip_plane*)d_l.get(), (les_hip_plane*)d_r.get(), 1.5f, hip.params.omega));
+        oks = oks && d_l.download(pl.data(), P) && d_r.download(pr.data(), P);
+    }
+    size_t mbad = 0, cbad = 0, zbad = 0;
+    for (size_t i = 0; i < P; i++) {
+        mbad += smask[i] != island[i] || ssize[i] != (island[i] ? 6 : (int)(P - planted)) || sroot[i] > (int)i;
+        cbad += (memcmp(&sone[i], &smap[i], sizeof(Plane)) != 0) != (island[i] != 0);
+        zbad += memcmp(&sl[i], &pl[i], sizeof(Plane)) != 0 || memcmp(&sr[i], &pr[i], sizeof(Plane)) != 0;
+    }
+    printf("speckle filter: %zu planted island pixels; %zu mask / size / root errors, %zu pixels changed or kept wrongly, %zu differ from postProcess at max_size 0\n", planted, mbad, cbad, zbad);
+    if (!oks || !planted || mbad || cbad || zbad) { printf("FAIL: speckle filter\n"); fail = 1; }
+    // the 3D reconstruction through the adapter: the speckle scene (disparity 3, islands at 9) as points, normals and a mesh.  Every pixel is a
+    // vertex; fronto-parallel labels have the normal (0, 0, -1) and the depth f baseline / d; at max_jump 1 exactly the quads that touch an
+    // island border lose their triangles, and the triangles of a one-surface map are all 2 (W - 1) (H - 1)
+    const les_hip_calib cal = {1000.f, 0.5f * W, 0.5f * H, 0.f, 100.f};
+    std::vector<float> pts(3 * P), nrm(3 * P);
+    std::vector<unsigned char> rvalid(P, 9);
+    std::vector<int> vindex, vpixel, tris, tris1;
+    std::vector<Plane> flat(P, Plane(0.f, 0.f, 3.f, 0.f));
+    bool okr = hip.reproject(smap.data(), cal, pts.data(), nrm.data(), rvalid.data(), 0) && hip.mesh(smap.data(), rvalid.data(), 1.0f, vindex, vpixel, tris, 0) &&
+               hip.mesh(flat.data(), rvalid.data(), 1.0f, vindex, vpixel, tris1, 0);
+    size_t rbad = 0, torn = 0;
+    for (size_t i = 0; okr && i < P; i++)
+        rbad += rvalid[i] != 255 || nrm[3 * i] != 0.f || nrm[3 * i + 1] != 0.f || nrm[3 * i + 2] != -1.f || pts[3 * i + 2] != (float)(100000.0 / (island[i] ? 9.0 : 3.0)) ||
+                vindex[i] != (int)i || vpixel[i] != (int)i;
+    for (int y = 0; y + 1 < H; y++)
+        for (int x = 0; x + 1 < W; x++) {
+            const unsigned char a = island[(size_t)y * W + x], b = island[(size_t)y * W + x + 1], c = island[(size_t)(y + 1) * W + x], d = island[(size_t)(y + 1) * W + x + 1];
+            torn += (size_t)(!(a == b && a == c)) + (size_t)(!(b == c && b == d));
+        }
+    const size_t all_tris = 2 * (size_t)(W - 1) * (size_t)(H - 1);
+    printf("reproject / mesh: %zu of %zu pixels differ from the expected geometry; %zu triangles, %zu torn at the island borders, %zu on one surface\n", rbad, P, tris.size() / 3, torn,
+           tris1.size() / 3);
+    if (!okr || rbad || !torn || tris.size() / 3 != all_tris - torn || tris1.size() / 3 != all_tris) { printf("FAIL: reproject / mesh\n"); fail = 1; }
+    // refusals, one per kind of wrapper (an argument the library checks, a missing input map, a view the energy was built without): the call
+    // reports on stderr, returns false and leaves the caller's maps as they were
+    const Plane keep(1.f, 2.f, 3.f, 4.f);
+    std::vector<unsigned char> xmask(P, 7), xkind(P, 7);
+    std::vector<Plane> xfit(P, keep);
+    std::vector<float> xconf(P, 7.f);
+    const int refused = !hip.speckleMask(smap.data(), -1, 1.0f, xmask.data()) + !hip.fitPlanes(nullptr, nullptr, wta.data(), xfit.data(), xkind.data(), 0) +
+                        !left_only.confidence(wta.data(), xconf.data(), nullptr, nullptr, nullptr, 1);
+    size_t touched = 0;
+    for (size_t i = 0; i < P; i++) touched += xmask[i] != 7 || xkind[i] != 7 || memcmp(&xfit[i], &keep, sizeof(Plane)) != 0 || xconf[i] != 7.f;
+    printf("refusals: %d of 3 calls refused, %zu output elements touched\n", refused, touched);
+    if (refused != 3 || touched) { printf("FAIL: refusals\n"); fail = 1; }
+    return fail;
+}
+
+// the volume energy of `run` and `adapter` over the synthetic scene; right == false: built without a right view
+static std::unique_ptr<HipCostVolumeEnergy> scene_energy(const Scene& s, int W, int H, int D, const Parameters& param, bool right = true)
+{
+    return std::make_unique<HipCostVolumeEnergy>(s.im.data(), right ? s.im.data() : nullptr, W, H, s.vol.data(), right ? s.vol.data() : nullptr, D, param, (float)D - 1);
+}
+
+// adapter W H D: the adapter checks alone (no PatchMatch or graph-cut run before them)
+static int cmd_adapter(int argc, char** argv)
+{
+    const int W = argc > 2 ? atoi(argv[2]) : 64, H = argc > 3 ? atoi(argv[3]) : 48, D = argc > 4 ? atoi(argv[4]) : 8;
+    Scene s = make_scene(W, H, D);
+    Parameters param(1.0f, 20, "GF", 1e-4f);
+    param.th_col = 0.5f;
+    const int fail = adapter_checks(*scene_energy(s, W, H, D, param), *scene_energy(s, W, H, D, param, false), W, H);
+    printf(fail ? "les_host_demo: FAILED\n" : "les_host_demo: OK\n");
+    return fail;
+}
+
 static int cmd_run(int argc, char** argv)
 {
     const int W = argc > 2 ? atoi(argv[2]) : 240, H = argc > 3 ? atoi(argv[3]) : 160, D = argc > 4 ? atoi(argv[4]) : 32;
@@ -84,7 +238,7 @@ static int cmd_run(int argc, char** argv)
     auto build = [&](uint64_t seed) {
         auto st = std::make_unique<PMStereo>(W, H, param, maxdisp);
         st->setSeed(seed);
-        st->setStereoEnergy(std::make_unique<HipCostVolumeEnergy>(s.im.data(), s.im.data(), W, H, s.vol.data(), s.vol.data(), D, param, maxdisp));
+        st->setStereoEnergy(scene_energy(s, W, H, D, param));
         return st;
     };
     int fail = 0;
@@ -215,20 +369,20 @@ static int cmd_run(int argc, char** argv)
         }
         les_hip_ctx* c = static_cast<const HipCostVolumeEnergy&>(st->getEnergyInstance()).handle();
         les_hip_batch* b = nullptr;
-        void *d_lab = nullptr, *d_rng = nullptr, *d_pl = nullptr;
-        int rc = les_hip_batch_create(c, n, units.data(), units.data(), 0, &b);
-        rc |= les_hip_batch_set_units(c, b, units.data());
-        rc |= les_hip_malloc(c, &d_lab, (size_t)H * W * 16) | les_hip_malloc(c, &d_rng, (size_t)n * 8) | les_hip_malloc(c, &d_pl, (size_t)n * 16);
-        rc |= les_hip_memcpy_h2d(c, d_lab, lab.data.data(), (size_t)H * W * 16) | les_hip_memcpy_h2d(c, d_rng, seeds.data(), (size_t)n * 8);
-        rc |= les_hip_batch_propose(c, b, LES_HIP_PROPOSE_RANSAC, 0, (les_hip_plane*)d_lab, (uint64_t*)d_rng, (les_hip_plane*)d_pl);
-        rc |= les_hip_synchronize(c);
-        rc |= les_hip_memcpy_d2h(c, dev_planes.data(), d_pl, (size_t)n * 16) | les_hip_memcpy_d2h(c, dev_states.data(), d_rng, (size_t)n * 8);
+        Status rs("les_host_demo");
+        rs(les_hip_batch_create(c, n, units.data(), units.data(), 0, &b));
+        if (rs.ok()) rs(les_hip_batch_set_units(c, b, units.data()));
+        DeviceArray<Plane> d_lab(c, rs, lab.data.data(), (size_t)H * W), d_pl(c, rs, (size_t)n);
+        DeviceArray<uint64_t> d_rng(c, rs, seeds.data(), (size_t)n);
+        if (rs.ok()) rs(les_hip_batch_propose(c, b, LES_HIP_PROPOSE_RANSAC, 0, (les_hip_plane*)d_lab.get(), d_rng.get(), (les_hip_plane*)d_pl.get()));
+        if (rs.ok()) rs(les_hip_synchronize(c));
+        d_pl.download(dev_planes.data(), (size_t)n);
+        d_rng.download(dev_states.data(), (size_t)n);
         int diff = 0;
         for (int i = 0; i < n; i++)
             diff += memcmp(&host_planes[(size_t)i], &dev_planes[(size_t)i], 16) != 0 || host_states[(size_t)i] != dev_states[(size_t)i];
-        printf("RANSAC proposer host vs device: %d cells, %d differences (rc %d)\n", n, diff, rc);
-        if (rc || diff) { printf("FAIL: host RansacProposer differs from the device kernels\n"); fail = 1; }
-        les_hip_free(c, d_lab); les_hip_free(c, d_rng); les_hip_free(c, d_pl);
+        printf("RANSAC proposer host vs device: %d cells, %d differences (rc %d)\n", n, diff, rs.rc);
+        if (!rs.ok() || diff) { printf("FAIL: host RansacProposer differs from the device kernels\n"); fail = 1; }
         les_hip_batch_destroy(b);
     }
     // (f) warm start: a device run resumed from the labelling of a previous device run.  Its costs come from one dense pass over the label
@@ -268,124 +422,7 @@ static int cmd_run(int argc, char** argv)
         }
         printf("warm start: label-map operator vs the device run %zu cost differences; vs one operator call per pixel: max |diff| %.2e, %zu sentinel differences\n", bits, worst, sent);
         if (!okd || bits || sent || !(worst <= 2.0 * 2e-6)) { printf("FAIL: the label-map operator disagrees\n"); fail = 1; }
-        // cross-view fusion's warp through the adapter: a fronto-parallel left-view map at disparity 3 lands three columns to the left with v
-        // negated; the three rightmost columns keep the fallback
-        const size_t P = (size_t)W * H;
-        std::vector<Plane> wsrc(P, Plane(0.f, 0.f, 3.f, 0.5f)), wfb(P, Plane(0.125f, -0.25f, 7.f, 0.f)), wout(P);
-        std::vector<unsigned char> whit(P, 9);
-        const bool okw = hip.warpLabels(0, wsrc.data(), wfb.data(), wout.data(), whit.data());
-        size_t wbad = 0;
-        for (int y = 0; y < H; y++)
-            for (int x = 0; x < W; x++) {
-                const bool in = x + 3 < W;
-                const Plane want = in ? Plane(0.f, 0.f, 3.f, -0.5f) : wfb[(size_t)y * W + x];
-                wbad += memcmp(&wout[(size_t)y * W + x], &want, sizeof(Plane)) != 0 || whit[(size_t)y * W + x] != (in ? 1 : 0);
-            }
-        printf("warpLabels: %zu of %zu pixels differ from the expected map\n", wbad, P);
-        if (!okw || wbad) { printf("FAIL: warpLabels\n"); fail = 1; }
-        // the winner-take-all map of the filtered volume through the adapter: fronto-parallel planes, chunking does not change a bit
-        std::vector<Plane> wta(P), wta2(P);
-        std::vector<float> wcost(P);
-        const bool okt = hip.wtaLabels(wta.data(), wcost.data(), 0) && hip.wtaLabels(wta2.data(), nullptr, 0, true, 3);
-        size_t tbad = 0;
-        for (size_t i = 0; i < P; i++)
-            tbad += !(wta[i].a == 0.f && wta[i].b == 0.f && wta[i].v == 0.f && std::isfinite(wta[i].c) && std::isfinite(wcost[i])) || memcmp(&wta[i], &wta2[i], sizeof(Plane)) != 0;
-        printf("wtaLabels: %zu of %zu pixels are not a finite fronto-parallel plane or depend on the chunking\n", tbad, P);
-        if (!okt || tbad) { printf("FAIL: wtaLabels\n"); fail = 1; }
-        // the confidence of that map through the adapter: in [0, 1], the in-band minimum of a WTA label is the WTA cost itself and no rival lies
-        // below it, and the chunking does not change a bit
-        std::vector<float> conf(P), conf2(P), cown(P), crival(P);
-        std::vector<int> ckr(P);
-        const bool okc = hip.confidence(wta.data(), conf.data(), cown.data(), crival.data(), ckr.data(), 0) &&
-                         hip.confidence(wta.data(), conf2.data(), nullptr, nullptr, nullptr, 0, 1.f, 0.f, 3);
-        size_t qbad = 0, qpos = 0;
-        for (size_t i = 0; i < P; i++) {
-            qbad += !(conf[i] >= 0.f && conf[i] <= 1.f) || memcmp(&conf[i], &conf2[i], sizeof(float)) != 0 || cown[i] != wcost[i] || (ckr[i] >= 0 && crival[i] < cown[i]);
-            qpos += conf[i] > 0.f;
-        }
-        printf("confidence: %zu of %zu pixels are outside [0, 1], disagree with the WTA cost or depend on the chunking; %zu are above 0\n", qbad, P, qpos);
-        if (!okc || qbad || !qpos) { printf("FAIL: confidence\n"); fail = 1; }
-        // the planes fitted to that map through the adapter: every pixel a finite plane of its kind, from the labels and from their disparities alike
-        std::vector<Plane> fit(P), fit2(P);
-        std::vector<unsigned char> kind(P);
-        std::vector<float> wdisp(P);
-        for (size_t i = 0; i < P; i++) wdisp[i] = wta[i].c;            // (fronto-parallel planes: d = c)
-        const bool okf = hip.fitPlanes(wta.data(), nullptr, wta.data(), fit.data(), kind.data(), 0) && hip.fitPlanes(nullptr, wdisp.data(), wta.data(), fit2.data(), nullptr, 0);
-        size_t fbad = 0, slanted = 0;
-        for (size_t i = 0; i < P; i++) {
-            fbad += kind[i] > 2 || !(std::isfinite(fit[i].a) && std::isfinite(fit[i].b) && std::isfinite(fit[i].c)) || memcmp(&fit[i], &fit2[i], sizeof(Plane)) != 0 ||
-                    (kind[i] == 1 && !(fit[i].a == 0.f && fit[i].b == 0.f && fit[i].c == wta[i].c));
-            slanted += kind[i] == 2;
-        }
-        printf("fitPlanes: %zu of %zu pixels are not a finite plane of their kind or depend on the input form; %zu slanted fits\n", fbad, P, slanted);
-        if (!okf || fbad || !slanted) { printf("FAIL: fitPlanes\n"); fail = 1; }
-        // the half-resolution twin through the adapter: a fronto-parallel half map at disparity 3 comes up as disparity 6 everywhere, v doubled
-        auto halfE = hip.half();
-        const size_t Ph = (size_t)((W + 1) / 2) * ((H + 1) / 2);
-        std::vector<Plane> hsrc(Ph, Plane(0.f, 0.f, 3.f, 0.25f)), up(P);
-        std::vector<unsigned char> ukind(P, 9);
-        const bool oku = hip.upsampleLabels(*halfE, hsrc.data(), up.data(), ukind.data(), 0);
-        const Plane uwant(0.f, 0.f, 6.f, 0.5f);
-        size_t ubad = 0;
-        for (size_t i = 0; i < P; i++) ubad += memcmp(&up[i], &uwant, sizeof(Plane)) != 0 || ukind[i] != 0;
-        printf("half / upsampleLabels: a %d x %d twin with windR %d; %zu of %zu pixels differ from the expected map\n", (W + 1) / 2, (H + 1) / 2, halfE->params.windR, ubad, P);
-        if (!oku || ubad || halfE->maxDisparity() != 0.5f * hip.maxDisparity()) { printf("FAIL: half / upsampleLabels\n"); fail = 1; }
-        // the speckle filter through the adapter: a fronto-parallel map at disparity 3 with planted 2 x 3 islands at disparity 9.  The mask is the
-        // islands; the one-view post-processing changes every island pixel and nothing else (so nothing outside the dilated mask); with
-        // max_size 0 the two-view form leaves the bytes of les_hip_post_process
-        std::vector<Plane> smap(P, Plane(0.f, 0.f, 3.f, 0.f));
-        std::vector<unsigned char> island(P, 0), smask(P, 9);
-        std::vector<int> sroot(P), ssize(P);
-        size_t planted = 0;
-        for (int y0 = 5; y0 + 2 <= H - 5; y0 += 9)
-            for (int x0 = 6; x0 + 3 <= W - 6; x0 += 11)
-                for (int y = y0; y < y0 + 2; y++)
-                    for (int x = x0; x < x0 + 3; x++) { smap[(size_t)y * W + x] = Plane(0.f, 0.f, 9.f, 1.f); island[(size_t)y * W + x] = 255; planted++; }
-        std::vector<Plane> sone = smap, sl = smap, sr = smap, pl = smap, pr = smap;
-        bool oks = hip.speckleMask(smap.data(), 20, 1.0f, smask.data(), sroot.data(), ssize.data());
-        oks = oks && hip.postProcessSpeckle(sone.data(), nullptr, 1.5f, hip.params.omega, 20, 1.0f);
-        oks = oks && hip.postProcessSpeckle(sl.data(), sr.data(), 1.5f, hip.params.omega, 0, 1.0f);
-        {
-            les_hip_plane* d[2] = {nullptr, nullptr};
-            Plane* h2[2] = {pl.data(), pr.data()};
-            for (int m = 0; m < 2; m++) oks = oks && les_hip_malloc(hip.handle(), (void**)&d[m], P * sizeof(Plane)) == LES_HIP_OK && les_hip_memcpy_h2d(hip.handle(), d[m], h2[m], P * sizeof(Plane)) == LES_HIP_OK;
-            oks = oks && les_hip_post_process(hip.handle(), d[0], d[1], 1.5f, hip.params.omega) == LES_HIP_OK;
-            for (int m = 0; m < 2; m++) {
-                oks = oks && les_hip_memcpy_d2h(hip.handle(), h2[m], d[m], P * sizeof(Plane)) == LES_HIP_OK;
-                if (d[m]) les_hip_free(hip.handle(), d[m]);
-            }
-        }
-        size_t mbad = 0, cbad = 0, zbad = 0;
-        for (size_t i = 0; i < P; i++) {
-            mbad += smask[i] != island[i] || ssize[i] != (island[i] ? 6 : (int)(P - planted)) || sroot[i] > (int)i;
-            cbad += (memcmp(&sone[i], &smap[i], sizeof(Plane)) != 0) != (island[i] != 0);
-            zbad += memcmp(&sl[i], &pl[i], sizeof(Plane)) != 0 || memcmp(&sr[i], &pr[i], sizeof(Plane)) != 0;
-        }
-        printf("speckle filter: %zu planted island pixels; %zu mask / size / root errors, %zu pixels changed or kept wrongly, %zu differ from postProcess at max_size 0\n", planted, mbad, cbad, zbad);
-        if (!oks || !planted || mbad || cbad || zbad) { printf("FAIL: speckle filter\n"); fail = 1; }
-        // the 3D reconstruction through the adapter: the speckle scene (disparity 3, islands at 9) as points, normals and a mesh.  Every pixel is a
-        // vertex; fronto-parallel labels have the normal (0, 0, -1) and the depth f baseline / d; at max_jump 1 exactly the quads that touch an
-        // island border lose their triangles, and the triangles of a one-surface map are all 2 (W - 1) (H - 1)
-        const les_hip_calib cal = {1000.f, 0.5f * W, 0.5f * H, 0.f, 100.f};
-        std::vector<float> pts(3 * P), nrm(3 * P);
-        std::vector<unsigned char> rvalid(P, 9);
-        std::vector<int> vindex, vpixel, tris, tris1;
-        std::vector<Plane> flat(P, Plane(0.f, 0.f, 3.f, 0.f));
-        bool okr = hip.reproject(smap.data(), cal, pts.data(), nrm.data(), rvalid.data(), 0) && hip.mesh(smap.data(), rvalid.data(), 1.0f, vindex, vpixel, tris, 0) &&
-                   hip.mesh(flat.data(), rvalid.data(), 1.0f, vindex, vpixel, tris1, 0);
-        size_t rbad = 0, torn = 0;
-        for (size_t i = 0; okr && i < P; i++)
-            rbad += rvalid[i] != 255 || nrm[3 * i] != 0.f || nrm[3 * i + 1] != 0.f || nrm[3 * i + 2] != -1.f || pts[3 * i + 2] != (float)(100000.0 / (island[i] ? 9.0 : 3.0)) ||
-                    vindex[i] != (int)i || vpixel[i] != (int)i;
-        for (int y = 0; y + 1 < H; y++)
-            for (int x = 0; x + 1 < W; x++) {
-                const unsigned char a = island[(size_t)y * W + x], b = island[(size_t)y * W + x + 1], c = island[(size_t)(y + 1) * W + x], d = island[(size_t)(y + 1) * W + x + 1];
-                torn += (size_t)(!(a == b && a == c)) + (size_t)(!(b == c && b == d));
-            }
-        const size_t all_tris = 2 * (size_t)(W - 1) * (size_t)(H - 1);
-        printf("reproject / mesh: %zu of %zu pixels differ from the expected geometry; %zu triangles, %zu torn at the island borders, %zu on one surface\n", rbad, P, tris.size() / 3, torn,
-               tris1.size() / 3);
-        if (!okr || rbad || !torn || tris.size() / 3 != all_tris - torn || tris1.size() / 3 != all_tris) { printf("FAIL: reproject / mesh\n"); fail = 1; }
+        fail |= adapter_checks(hip, *scene_energy(s, W, H, D, param, false), W, H);
     }
     printf(fail ? "les_host_demo: FAILED\n" : "les_host_demo: OK\n");
     return fail;
@@ -631,10 +668,12 @@ static int cmd_ranks(int argc, char** argv)
 
 int main(int argc, char** argv)
 {
-    if (argc >= 2 && !strcmp(argv[1], "layers")) return cmd_layers(argc, argv);
-    if (argc >= 2 && !strcmp(argv[1], "maxflow")) return cmd_maxflow(argc, argv);
-    if (argc >= 2 && !strcmp(argv[1], "run")) {
-        try {
+    const char* cmd = argc >= 2 ? argv[1] : "";
+    if (!strcmp(cmd, "layers")) return cmd_layers(argc, argv);
+    if (!strcmp(cmd, "maxflow")) return cmd_maxflow(argc, argv);
+    if (!strcmp(cmd, "scene")) return cmd_scene(argc, argv);
+    try {
+        if (!strcmp(cmd, "run")) {
             // The self-test compares the labels of host cuts on device-built graphs with those on host-built graphs BIT FOR BIT.  That
             // only holds when both sides route the flow in the same order: two maximum flows of one graph leave float residuals that
             // differ in the last bit, and at exact ties (pixels whose proposal IS their current label) the segment rule then picks
@@ -644,36 +683,15 @@ int main(int argc, char** argv)
             setenv("LES_GC_PREPUSH", "0", 0);
             setenv("LES_GC_PUSH_RELABEL_MIN_NODES", "0", 0);
             return cmd_run(argc, argv);
-        } catch (const std::exception& e) {
-            printf("les_host_demo: %s\n", e.what());
-            return 3;
         }
+        if (!strcmp(cmd, "adapter")) return cmd_adapter(argc, argv);
+        if (!strcmp(cmd, "ranks")) return cmd_ranks(argc, argv);
+        if (!strcmp(cmd, "percall")) return cmd_percall(argc, argv);
+        if (!strcmp(cmd, "full")) return cmd_full(argc, argv);
+    } catch (const std::exception& e) {
+        printf("les_host_demo: %s\n", e.what());
+        return 3;
     }
-    if (argc >= 2 && !strcmp(argv[1], "ranks")) {
-        try {
-            return cmd_ranks(argc, argv);
-        } catch (const std::exception& e) {
-            printf("les_host_demo: %s\n", e.what());
-            return 3;
-        }
-    }
-    if (argc >= 2 && !strcmp(argv[1], "scene")) return cmd_scene(argc, argv);
-    if (argc >= 2 && !strcmp(argv[1], "percall")) {
-        try {
-            return cmd_percall(argc, argv);
-        } catch (const std::exception& e) {
-            printf("les_host_demo: %s\n", e.what());
-            return 3;
-        }
-    }
-    if (argc >= 2 && !strcmp(argv[1], "full")) {
-        try {
-            return cmd_full(argc, argv);
-        } catch (const std::exception& e) {
-            printf("les_host_demo: %s\n", e.what());
-            return 3;
-        }
-    }
-    fprintf(stderr, "usage: les_host_demo layers W H windR unit | run [W H D iters] | full [W H D iters pmInit coarse] | percall [W H D iters pmInit threads] | scene dir [iters pmInit] | ranks [W H D world]\n");
+    fprintf(stderr, "usage: les_host_demo layers W H windR unit | run [W H D iters] | adapter [W H D] | full [W H D iters pmInit coarse] | percall [W H D iters pmInit threads] | scene dir [iters pmInit] | ranks [W H D world]\n");
     return 2;
 }

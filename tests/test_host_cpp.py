@@ -47,6 +47,27 @@ def test_host_demo_runs_on_gpu(demo):
     assert r.returncode == 0 and "les_host_demo: OK" in r.stdout
 
 
+def test_host_demo_adapter_on_the_simulator():
+    """Every host-map wrapper of HipCostVolumeEnergy.h, and the calls it must refuse (false, outputs untouched), with the demo linked against
+    the CPU simulator build of the library.  64 x 48 x 8: the smallest shape at which the planted 2 x 3 islands, their 9 x 11 pitch and
+    the half-resolution twin all occur more than once."""
+    from localexpstereo_amd import build
+    exe = build.build_host_sim()
+    assert exe
+    env = dict(os.environ, LES_HIP_KERNEL="strip", LES_HIP_QUIET="1")
+    r = subprocess.run([exe, "adapter", "64", "48", "8"], capture_output=True, text=True, timeout=600, env=env)
+    print(r.stdout[-3000:], r.stderr[-2000:])
+    assert r.returncode == 0 and "les_host_demo: OK" in r.stdout
+
+
+@pytest.mark.gpu
+def test_host_demo_adapter_on_gpu(demo):
+    """The same checks on the real library."""
+    r = subprocess.run([demo, "adapter", "64", "48", "8"], capture_output=True, text=True, timeout=300)
+    print(r.stdout[-3000:], r.stderr[-2000:])
+    assert r.returncode == 0 and "les_host_demo: OK" in r.stdout
+
+
 @pytest.mark.gpu
 def test_host_demo_on_the_python_drivers_scene(demo, tmp_path):
     """The C++ driver on the scene of tools/e2e_bench.py (written to raw files by tools/dump_scene.py, left volume as the device ingest
