@@ -281,7 +281,7 @@ int les_hip_batch_expansion_graph(les_hip_ctx* ctx, const les_hip_batch* batch, 
  * second map d_labels1 (H x W planes, device; not the same buffer), pixel by pixel, where the expansion move tries one plane per cell.  Same
  * cells, payload layout, node order and flow0 as les_hip_batch_expansion_graph, so every solver below (and les_gc_solve_prebuilt) cuts the
  * graphs unchanged; mask 255 = the pixel takes d_labels1's label.  d_cur / d_prop: the unary costs of d_labels / of d_labels1 at every pixel
- * (les_hip_unary_labels gives the latter in one dense pass).  Definition and operation order: csrc/les_fusion.h.  Unlike the reference,
+ * (les_hip_unary_labels gives the latter in one dense pass).  Definition and operation order: csrc/les_pairwise.h.  Unlike the reference,
  * which drops cost11 (:255, right only for a one-plane proposal), the term of "both take" enters the graph; a pair that is not submodular
  * (c10 + c01 < c11 + c00) gets arc capacity 0, so the cut minimises an upper bound of the energy that is exact at "all keep" and "all
  * take": the move never raises the energy.  With d_labels1 constant over every cell the payload is that of the expansion graph, bit for bit.

@@ -455,7 +455,7 @@ class Batch:
 
     def fusion_graph(self, labels1_dev, labels_dev, cur_dev, prop_dev, payload_dev, mode=0, lambda_=1.0, th_smooth=1.0, omega=10.0, epsilon=0.01,
                      want_flow0=False, nonsubmodular_dev=None):
-        """Graph capacities of one lock-step of FUSION moves (LES/FastGCStereo.h:241-363; definition: csrc/les_fusion.h): the current map labels_dev
+        """Graph capacities of one lock-step of FUSION moves (LES/FastGCStereo.h:241-363; definition: csrc/les_pairwise.h): the current map labels_dev
         against the second map labels1_dev, whose per-pixel unary costs are cur_dev / prop_dev.  Payload as expansion_graph; a mask byte of 255 means
         the pixel takes labels1's label.  nonsubmodular_dev: n int32 on the device that receive every cell's count of truncated (non-submodular)
         pairs, or None.  Returns the per-cell t-link flow when want_flow0."""

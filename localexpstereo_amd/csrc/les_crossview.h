@@ -1,6 +1,6 @@
 // les_crossview.h -- cross-view fusion: a label map of one view expressed in the coordinates of the other view (PatchMatch Stereo's "view
 // propagation").  The reference has no such step: its two views meet only in the post-processing (LES/FastGCStereo.h:172-203).  The warped map
-// is a second labelling for the fusion move of les_fusion.h, so each view can take what the other one found.
+// is a second labelling for the fusion move of les_pairwise.h, so each view can take what the other one found.
 //
 // DEFINITION (stated here once; tests/crossview_cases.py restates it in numpy).
 //   inputs    src: H x W planes (a, b, c, v) of view s (0 left, 1 right); fallback: H x W planes of the target view t = 1 - s

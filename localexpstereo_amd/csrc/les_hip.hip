@@ -10,7 +10,6 @@
 #include "les_propose.h"
 #include "les_post.h"
 #include "les_pairwise.h"
-#include "les_fusion.h"
 #include "les_eval.h"
 #include "les_maxflow.h"
 #include "les_maxflow_tiled.h"

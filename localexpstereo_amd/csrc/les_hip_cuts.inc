@@ -73,6 +73,51 @@ struct MtHostLease {                       // returns the MtHost to the pool on 
     les_hip_ctx* c; MtHost* m;
     ~MtHostLease() { if (m) mt_host_release(c, m); }
 };
+// the cells of a lock-step as the kernels take them (les_hip_rect has GraphCell's layout: les_hip_batch.inc)
+const les::GraphCell* graph_cells(const les_hip_batch* b) { return reinterpret_cast<const les::GraphCell*>(b->d_targets.p); }
+// The graphs of one lock-step of moves (les_pairwise.h).  map: d_proposal is a label map [H][W] (fusion); otherwise one plane per cell (expansion).
+// flow0_host (may be null): per cell, the chunks' t-link flows summed in chunk order after a synchronise.
+int move_graph(bool map, les_hip_ctx* c, const les_hip_batch* b, int mode, const les_hip_plane* d_proposal, const les_hip_plane* d_labels, const float* d_cur,
+               const float* d_prop, float lambda, float th_smooth, float omega, float epsilon, float* d_payload, double* flow0_host, int* d_nonsubmodular)
+{
+    if (!c || !b || !d_proposal || !d_labels || !d_cur || !d_prop || !d_payload) return fail(LES_HIP_ERR_ARG, "null argument");
+    if (mode < 0 || mode > 1 || !c->v[mode].ipk) return fail(LES_HIP_ERR_ARG, "view %d was not supplied at creation", mode);
+    if (b->n == 0) return LES_HIP_OK;
+    HIPCHECK(hipSetDevice(c->p.device));                     // the calling host thread may be new (one thread per view)
+    const int trc = pw_table(c, omega, epsilon);
+    if (trc) return trc;
+    const les::PairwiseParams pp{c->p.H, c->p.W, lambda, th_smooth};
+    const float4 *pro = reinterpret_cast<const float4*>(d_proposal), *lab = reinterpret_cast<const float4*>(d_labels);
+    if (d_nonsubmodular) HIPCHECK(hipMemsetAsync(d_nonsubmodular, 0, (size_t)b->n * sizeof(int), cur_stream(c)));
+    auto* kernel = map ? les::les_move_graph_kernel<true> : les::les_move_graph_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(b->n, b->graph_chunks), dim3(256), 0, cur_stream(c), graph_cells(b), b->d_graph_off.p, pro, lab, d_cur, d_prop,
+                       c->v[mode].ipk, c->d_pw_tab.p, pp, d_payload, b->d_flow0.p, d_nonsubmodular);
+    HIPCHECK(hipGetLastError());
+    if (flow0_host) {
+        std::vector<double> part((size_t)b->n * b->graph_chunks);
+        HIPCHECK(hipMemcpyAsync(part.data(), b->d_flow0.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream(c)));
+        HIPCHECK(hipStreamSynchronize(cur_stream(c)));
+        for (int i = 0; i < b->n; i++) {
+            double s = 0;
+            for (int k = 0; k < b->graph_chunks; k++) s += part[(size_t)i * b->graph_chunks + k];
+            flow0_host[i] = s;
+        }
+    }
+    return LES_HIP_OK;
+}
+// the mask updates of that lock-step, with the same `map`
+int apply_masks(bool map, les_hip_ctx* c, const les_hip_batch* b, const les_hip_plane* d_proposal, const unsigned char* d_masks, float* d_cur, const float* d_prop,
+                les_hip_plane* d_labels)
+{
+    if (c) (void)hipSetDevice(c->p.device);                 // HIP's current device is per host thread
+    if (!c || !b || !d_proposal || !d_masks || !d_cur || !d_prop || !d_labels) return fail(LES_HIP_ERR_ARG, "null argument");
+    if (b->n == 0) return LES_HIP_OK;
+    auto* kernel = map ? les::les_apply_masks_kernel<true> : les::les_apply_masks_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(b->n, b->wta_chunks), dim3(256), 0, cur_stream(c), graph_cells(b), b->d_graph_off.p, reinterpret_cast<const float4*>(d_proposal),
+                       d_masks, d_cur, d_prop, reinterpret_cast<float4*>(d_labels), c->p.W);
+    HIPCHECK(hipGetLastError());
+    return LES_HIP_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -90,67 +135,14 @@ int les_hip_batch_expansion_graph(les_hip_ctx* c, const les_hip_batch* b, int mo
                                   const float* d_cur, const float* d_prop, float lambda, float th_smooth, float omega, float epsilon,
                                   float* d_payload, double* flow0_host)
 {
-    if (!c || !b || !d_planes || !d_labels || !d_cur || !d_prop || !d_payload) return fail(LES_HIP_ERR_ARG, "null argument");
-    if (mode < 0 || mode > 1 || !c->v[mode].ipk) return fail(LES_HIP_ERR_ARG, "view %d was not supplied at creation", mode);
-    if (b->n == 0) return LES_HIP_OK;
-    HIPCHECK(hipSetDevice(c->p.device));                     // the calling host thread may be new (one thread per view)
-    const int trc = pw_table(c, omega, epsilon);
-    if (trc) return trc;
-    const les::PairwiseParams pp{c->p.H, c->p.W, lambda, th_smooth};
-    const les::GraphCell* cells = reinterpret_cast<const les::GraphCell*>(b->d_targets.p);
-    const long long* offs = b->d_graph_off.p;
-    const float4 *pl = reinterpret_cast<const float4*>(d_planes), *lab = reinterpret_cast<const float4*>(d_labels);
-    const uint32_t* ipk = c->v[mode].ipk;
-    const float* wtab = c->d_pw_tab.p;
-    double* flow0 = b->d_flow0.p;
-    hipLaunchKernelGGL(les::les_expansion_graph_kernel, dim3(b->n, b->graph_chunks), dim3(256), 0, cur_stream(c), cells, offs, pl, lab, d_cur, d_prop, ipk, wtab,
-                       pp, d_payload, flow0);
-    HIPCHECK(hipGetLastError());
-    if (flow0_host) {
-        std::vector<double> part((size_t)b->n * b->graph_chunks);
-        HIPCHECK(hipMemcpyAsync(part.data(), b->d_flow0.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream(c)));
-        HIPCHECK(hipStreamSynchronize(cur_stream(c)));
-        for (int i = 0; i < b->n; i++) {
-            double s = 0;
-            for (int k = 0; k < b->graph_chunks; k++) s += part[(size_t)i * b->graph_chunks + k];
-            flow0_host[i] = s;
-        }
-    }
-    return LES_HIP_OK;
+    return move_graph(false, c, b, mode, d_planes, d_labels, d_cur, d_prop, lambda, th_smooth, omega, epsilon, d_payload, flow0_host, nullptr);
 }
 
 int les_hip_batch_fusion_graph(les_hip_ctx* c, const les_hip_batch* b, int mode, const les_hip_plane* d_labels1, const les_hip_plane* d_labels,
                                const float* d_cur, const float* d_prop, float lambda, float th_smooth, float omega, float epsilon,
                                float* d_payload, double* flow0_host, int* d_nonsubmodular)
 {
-    if (!c || !b || !d_labels1 || !d_labels || !d_cur || !d_prop || !d_payload) return fail(LES_HIP_ERR_ARG, "null argument");
-    if (mode < 0 || mode > 1 || !c->v[mode].ipk) return fail(LES_HIP_ERR_ARG, "view %d was not supplied at creation", mode);
-    if (b->n == 0) return LES_HIP_OK;
-    HIPCHECK(hipSetDevice(c->p.device));                     // the calling host thread may be new (one thread per view)
-    const int trc = pw_table(c, omega, epsilon);
-    if (trc) return trc;
-    const les::PairwiseParams pp{c->p.H, c->p.W, lambda, th_smooth};
-    const les::GraphCell* cells = reinterpret_cast<const les::GraphCell*>(b->d_targets.p);
-    const long long* offs = b->d_graph_off.p;
-    const float4 *lab1 = reinterpret_cast<const float4*>(d_labels1), *lab = reinterpret_cast<const float4*>(d_labels);
-    const uint32_t* ipk = c->v[mode].ipk;
-    const float* wtab = c->d_pw_tab.p;
-    double* flow0 = b->d_flow0.p;
-    if (d_nonsubmodular) HIPCHECK(hipMemsetAsync(d_nonsubmodular, 0, (size_t)b->n * sizeof(int), cur_stream(c)));
-    hipLaunchKernelGGL(les::les_fusion_graph_kernel, dim3(b->n, b->graph_chunks), dim3(256), 0, cur_stream(c), cells, offs, lab1, lab, d_cur, d_prop, ipk, wtab,
-                       pp, d_payload, flow0, d_nonsubmodular);
-    HIPCHECK(hipGetLastError());
-    if (flow0_host) {
-        std::vector<double> part((size_t)b->n * b->graph_chunks);
-        HIPCHECK(hipMemcpyAsync(part.data(), b->d_flow0.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, cur_stream(c)));
-        HIPCHECK(hipStreamSynchronize(cur_stream(c)));
-        for (int i = 0; i < b->n; i++) {
-            double s = 0;
-            for (int k = 0; k < b->graph_chunks; k++) s += part[(size_t)i * b->graph_chunks + k];
-            flow0_host[i] = s;
-        }
-    }
-    return LES_HIP_OK;
+    return move_graph(true, c, b, mode, d_labels1, d_labels, d_cur, d_prop, lambda, th_smooth, omega, epsilon, d_payload, flow0_host, d_nonsubmodular);
 }
 
 long long les_hip_batch_max_cell_nodes(const les_hip_batch* b)
@@ -244,7 +236,7 @@ int les_hip_batch_solve_graphs_counted(les_hip_ctx* c, const les_hip_batch* b, c
         }
     }
 #endif
-    const les::GraphCellMf* cells = reinterpret_cast<const les::GraphCellMf*>(b->d_targets.p);
+    const les::GraphCell* cells = graph_cells(b);
     int max_iter = les::kMfMaxIter;
     if (const char* ev = getenv("LES_HIP_MAXFLOW_MAX_ITER")) max_iter = std::max(0, atoi(ev));      // tests of the callers' host fall-back
     int round_iters = 16;                                   // (8 ... 64 measured on whole runs: flat within 3 %, tools/lab/ab_cell_kernel.sh)
@@ -389,7 +381,7 @@ int les_hip_batch_solve_graphs_tiled_stats(les_hip_ctx* c, const les_hip_batch* 
 #endif
     hipStream_t st = cur_stream(c);
     les::MtArgs a;
-    a.cells = reinterpret_cast<const les::GraphCellMf*>(b->d_targets.p);
+    a.cells = graph_cells(b);
     a.offsets = b->d_graph_off.p;
     a.payload = d_payload;
     a.tiles = b->d_mt_tiles.p;
@@ -544,31 +536,13 @@ int les_hip_debug_mt_probe(void* d_buf, int launches)
 int les_hip_batch_apply_masks(les_hip_ctx* c, const les_hip_batch* b, const les_hip_plane* d_planes, const unsigned char* d_masks, float* d_cur,
                               const float* d_prop, les_hip_plane* d_labels)
 {
-    if (c) (void)hipSetDevice(c->p.device);                 // HIP's current device is per host thread
-    if (!c || !b || !d_planes || !d_masks || !d_cur || !d_prop || !d_labels) return fail(LES_HIP_ERR_ARG, "null argument");
-    if (b->n == 0) return LES_HIP_OK;
-    const les::GraphCell* cells = reinterpret_cast<const les::GraphCell*>(b->d_targets.p);
-    const long long* offs = b->d_graph_off.p;
-    const float4* pl = reinterpret_cast<const float4*>(d_planes);
-    float4* lab = reinterpret_cast<float4*>(d_labels);
-    hipLaunchKernelGGL(les::les_apply_masks_kernel, dim3(b->n, b->wta_chunks), dim3(256), 0, cur_stream(c), cells, offs, pl, d_masks, d_cur, d_prop, lab, c->p.W);
-    HIPCHECK(hipGetLastError());
-    return LES_HIP_OK;
+    return apply_masks(false, c, b, d_planes, d_masks, d_cur, d_prop, d_labels);
 }
 
 int les_hip_batch_apply_masks_labels(les_hip_ctx* c, const les_hip_batch* b, const les_hip_plane* d_labels1, const unsigned char* d_masks, float* d_cur,
                                      const float* d_prop, les_hip_plane* d_labels)
 {
-    if (c) (void)hipSetDevice(c->p.device);                 // HIP's current device is per host thread
-    if (!c || !b || !d_labels1 || !d_masks || !d_cur || !d_prop || !d_labels) return fail(LES_HIP_ERR_ARG, "null argument");
-    if (b->n == 0) return LES_HIP_OK;
-    const les::GraphCell* cells = reinterpret_cast<const les::GraphCell*>(b->d_targets.p);
-    const float4* lab1 = reinterpret_cast<const float4*>(d_labels1);
-    float4* lab = reinterpret_cast<float4*>(d_labels);
-    hipLaunchKernelGGL(les::les_apply_masks_labels_kernel, dim3(b->n, b->wta_chunks), dim3(256), 0, cur_stream(c), cells, b->d_graph_off.p, lab1, d_masks, d_cur, d_prop,
-                       lab, c->p.W);
-    HIPCHECK(hipGetLastError());
-    return LES_HIP_OK;
+    return apply_masks(true, c, b, d_labels1, d_masks, d_cur, d_prop, d_labels);
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 //
 // Replaces, for cells that fit (layer-0 cells: 42 x 42 .. 45 x 45 nodes), the host side of `expansionMoveBK` after the graph
 // construction -- `graph.maxflow()` and `graph.what_segment()` (LES/FastGCStereo.h:553-559) -- on the 5-float node payload of
-// les_expansion_graph_kernel (les_pairwise.h): terminal residual + capacities of the arcs to the E, S, SW, SE neighbours.
+// les_move_graph_kernel (les_pairwise.h): terminal residual + capacities of the arcs to the E, S, SW, SE neighbours.
 //
 // Algorithm: synchronous push-relabel (Goldberg-Tarjan, first phase only) in the data-parallel form that needs no atomics:
 //   per iteration   1. four passes of two grid directions each: every active node pushes along its arcs of those directions when
@@ -21,7 +21,7 @@
 
 #include <cstdint>
 
-#include "les_simt.h"
+#include "les_pairwise.h"      // GraphCell, and the producer of the payload
 
 namespace les {
 
@@ -46,8 +46,6 @@ __host__ __device__ inline size_t mf_lds_bytes(int nodes)
     return bytes < 8256 ? 8256 : bytes;                    // (the final reduction borrows one double per thread: up to 1024)
 }
 
-struct GraphCellMf { int x, y, w, h; };                   // same layout as GraphCell (les_pairwise.h)
-
 // arc directions E W S N SW NE SE NW (sister(k) == k ^ 1) as offsets; packed in nibbles so that a run-time direction index needs
 // no indexed register array
 __host__ __device__ inline int mf_dx(int k) { return (int)((0x02201102u >> (4 * k)) & 0xfu) - 1; }      // +1 -1  0  0 -1 +1 +1 -1
@@ -59,7 +57,7 @@ __host__ __device__ inline int mf_dy(int k) { return (int)((0x02020211u >> (4 * 
 // two workgroups per CU as before -- and <5, 512> (128 VGPRs) for the cells between 2049 and 2304 nodes, where three slots of 1024 threads spill.
 template <int kMfNodesPerThread, int THREADS>
 __global__ void __launch_bounds__(THREADS, THREADS / 128)
-les_maxflow_kernel(const GraphCellMf* __restrict__ cells, const long long* __restrict__ offsets, const float* __restrict__ payload,
+les_maxflow_kernel(const GraphCell* __restrict__ cells, const long long* __restrict__ offsets, const float* __restrict__ payload,
                    int nmax_padded, int max_iter, uint8_t* __restrict__ masks, int* __restrict__ status, double* __restrict__ flows,
                    int* __restrict__ unsolved_total,         // optional: += 1 per cell that hits the iteration limit (callers that check once per several launches)
                    const int* __restrict__ cell_list)      // optional: workgroup -> cell index (a launch over some of the batch's cells)
@@ -80,7 +78,7 @@ les_maxflow_kernel(const GraphCellMf* __restrict__ cells, const long long* __res
     int* flag = reinterpret_cast<int*>(hgt + NP);          // [0] any active, [1..3] relabel sweep changed something (rotating)
 
     const int ci = cell_list ? cell_list[blockIdx.x] : (int)blockIdx.x;
-    const GraphCellMf c = cells[ci];
+    const GraphCell c = cells[ci];
     const int W = c.w, H = c.h, N = W * H;
     const int tid = (int)threadIdx.x;
     const float* p5 = payload + 5 * offsets[ci];

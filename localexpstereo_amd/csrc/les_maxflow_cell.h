@@ -2,7 +2,7 @@
 // the iteration of the tiled solver instead of the one of les_maxflow.h (round 6).
 //
 // Same job as les_maxflow_kernel (les_maxflow.h: `graph.maxflow()` + `graph.what_segment()` of LES/FastGCStereo.h:553-559 on the 5-float node payload
-// of les_expansion_graph_kernel), same outputs, same segment rule.  What differs is the cost of an iteration.  les_maxflow.h keeps the residuals in
+// of les_move_graph_kernel), same outputs, same segment rule.  What differs is the cost of an iteration.  les_maxflow.h keeps the residuals in
 // LDS and pushes two grid directions per pass: ten barriers per push-relabel iteration, and a barrier step of sixteen waves costs about a
 // microsecond whatever happens between two of them (measured on the tiled solver with clock stamps, tools/lab/mt_probe.py) -- the slowest of the 450
 // cells of a lock-step needs 86 iterations and 317 relabel sweeps, and the launch lasts as long as that cell.  Here, as in les_maxflow_tiled.h:
@@ -45,7 +45,7 @@ __host__ __device__ inline bool mc_fits(int w, int h)
 
 // grid = cells (or the cells of cell_list); block = kMcThreads; dynamic LDS = kMcLdsBytes.  Every cell of the launch must satisfy mc_fits (or be empty).
 __global__ void __launch_bounds__(kMcThreads, kMcThreads / 128)          // two workgroups per CU (1024 threads: 8 waves per SIMD -> at most 64 VGPRs)
-les_maxflow_cell_kernel(const GraphCellMf* __restrict__ cells, const long long* __restrict__ offsets, const float* __restrict__ payload,
+les_maxflow_cell_kernel(const GraphCell* __restrict__ cells, const long long* __restrict__ offsets, const float* __restrict__ payload,
                         int max_iter, int round_iters, uint8_t* __restrict__ masks, int* __restrict__ status, double* __restrict__ flows,
                         int* __restrict__ unsolved_total,
                         const int* __restrict__ cell_list)      // optional: workgroup -> cell index (a launch over some of the batch's cells)
@@ -66,7 +66,7 @@ les_maxflow_cell_kernel(const GraphCellMf* __restrict__ cells, const long long* 
     int* rowchg = sflag + 16;                                               // [3][72]: rows (halo rows included) in which a distance fell, per sweep
 
     const int ci = cell_list ? cell_list[blockIdx.x] : (int)blockIdx.x;
-    const GraphCellMf c = cells[ci];
+    const GraphCell c = cells[ci];
     const int W = c.w, H = c.h, N = W * H;
     const int tid = (int)threadIdx.x;
     if (N <= 0) { if (tid == 0) { status[ci] = 0; if (flows) flows[ci] = 0.0; } return; }

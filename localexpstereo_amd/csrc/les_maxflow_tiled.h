@@ -4,7 +4,7 @@
 //
 // Replaces, for the cells les_maxflow.h cannot hold in one workgroup's LDS (the coarse layers: 129 x 129 ... 404 x 387 nodes at the
 // Adirondack shape, 840 x 920 at 3000 x 2000), `graph.maxflow()` and `graph.what_segment()` of FastGCStereo::expansionMoveBK
-// (LES/FastGCStereo.h:553-559) on the 5-float node payload of les_expansion_graph_kernel (les_pairwise.h), i.e. the graph of
+// (LES/FastGCStereo.h:553-559) on the 5-float node payload of les_move_graph_kernel (les_pairwise.h), i.e. the graph of
 // LES/FastGCStereo.h:411-551.
 //
 // Algorithm: push-relabel (Goldberg-Tarjan, first phase), region-parallel.  A cell is cut into tiles of at most 1920 nodes; a
@@ -137,7 +137,7 @@ __device__ int g_mt_probe_launches = 0;
 #endif
 
 struct MtArgs {
-    const GraphCellMf* cells;        // target rects of the lock-step (x, y unused here; w, h = the cell's graph)
+    const GraphCell* cells;          // target rects of the lock-step (x, y unused here; w, h = the cell's graph)
     const long long* offsets;        // node offset of every cell in the payload / masks / workspace arrays
     const float* payload;            // 5 floats per node (les_pairwise.h)
     const MtTile* tiles;
@@ -691,7 +691,7 @@ struct MtHandArgs {
     char* ws;
     long long nodes;
     int ncells;
-    const GraphCellMf* cells;
+    const GraphCell* cells;
     int hand_after;                  // policy, per cell: an open cell goes after this many launches if it has at most `cell_nodes` nodes ...
     int late_after;                  // ... and after this many whatever its size
     long long cell_nodes;

@@ -1,7 +1,7 @@
 // les_planefit.h -- slanted planes from a disparity map: per pixel an edge-aware weighted least-squares plane fit over its window.  The
 // reference has no counterpart: its only start is one random plane per finest-layer cell (LES/FastGCStereo.h:94-115), and every map this
 // project builds without a graph cut (les_wtavol.h) is fronto-parallel.  The fitted map is a start for run() or a second labelling for
-// the fusion move of les_fusion.h.
+// the fusion move of les_pairwise.h.
 //
 // DEFINITION (stated here once; tests/planefit_cases.py restates it in numpy).
 //   inputs    the packed guide ipk of the view (B | G << 8 | R << 16); EITHER labels: H x W planes (a, b, c, v) OR disp: H x W floats;

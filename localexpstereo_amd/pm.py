@@ -602,7 +602,7 @@ class PMRunner:
             self._log_set(i)
         self._sync()
 
-    # -- fusion moves (LES/FastGCStereo.h:241-410; definition and the deviation from the reference: csrc/les_fusion.h) -----------------
+    # -- fusion moves (LES/FastGCStereo.h:241-410; definition and the deviation from the reference: csrc/les_pairwise.h) -----------------
     def fuse(self, labels_b, layers=None, nthreads=0):
         """Fuses the current solution with a second labelling `labels_b` (H x W x 4; a host array, or a float32 tensor on the runner's device, which is
         read in place and must stay unchanged during the call) by graph cuts: after begin_gc, for every disjoint set of the

@@ -1,7 +1,7 @@
-"""Cases of tests/test_fusion.py: fusion moves on the device (csrc/les_fusion.h: les_hip_batch_fusion_graph, les_hip_batch_apply_masks_labels,
+"""Cases of tests/test_fusion.py: fusion moves on the device (csrc/les_pairwise.h: les_hip_batch_fusion_graph, les_hip_batch_apply_masks_labels,
 pm.PMRunner.fuse, stereo.FastGCStereo.fuse) on the CPU simulator build and on the MI355X.
 
-The definition, restated from csrc/les_fusion.h.  Maps L0 (current) and L1 (proposal), cur[p] / prop[p] their unary costs, mask 255 = the pixel
+The definition, restated from csrc/les_pairwise.h.  Maps L0 (current) and L1 (proposal), cur[p] / prop[p] their unary costs, mask 255 = the pixel
 takes L1[p].  For a pixel ee and a forward neighbour le (GE, EG, LG, GG), T(a, b) = min(|a(ee) - b(ee)| + |a(le) - b(le)|, th) * w * lambda with
 pw_dot's operation order: c00 = T(L0[ee], L0[le]), c01 = T(L0[ee], L1[le]), c10 = T(L1[ee], L0[le]), c11 = T(L1[ee], L1[le]).  Per node, one
 t-link replays: add(cur, prop); for k = 0..7 with the neighbour pt outside the cell and inside the image add(term(L0[p], L0[pt]), term(L1[p],
@@ -479,6 +479,64 @@ def case_pin_to_expansion(lib):
         finally:
             d.close()
     return rounding_pairs
+
+
+# ------------------------------------------------------------------------------------------------ 3b. one plane with non-finite coefficients
+NONFINITE_PLANES = np.array([(np.inf, 0, 1, 0), (0, -np.inf, 1, 0), (np.nan, 0, 1, 0), (0, 0, np.nan, 0), (3e38, 3e38, 3e38, 0), (0, 0, np.inf, 0),
+                             (0, 0, -3e38, np.inf), (1e30, -1e30, 0, np.nan)], F)
+NONFINITE_RUNS = (("small", 0), ("small", 1), ("50x50", 0))
+NONFINITE_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "expansion_nonfinite.npz")
+
+
+def one_plane_nonfinite(lib):
+    """Batch.expansion_graph of the scene with NONFINITE_PLANES cycled over the cells -> {"<batch>_<mode>_payload": nn x 5 f32, "..._flow0": n f64}."""
+    out = {}
+    d = Dev(lib)
+    try:
+        for name, mode in NONFINITE_RUNS:
+            b, trs, off, nn = batch_of(d, name)
+            planes = np.ascontiguousarray(NONFINITE_PLANES[np.arange(b.n) % len(NONFINITE_PLANES)])
+            dpl, pay = d.buf(16 * b.n), d.buf(nn * 20)
+            dpl.upload(planes)
+            f0 = b.expansion_graph(dpl.ptr, d.L0.ptr, d.cur.ptr, d.prop.ptr, pay.ptr, mode=mode, want_flow0=True, **PW)
+            d.e.synchronize()
+            out[f"{name}_{mode}_payload"], out[f"{name}_{mode}_flow0"] = pay.download((nn, 5), F), f0
+            b.destroy()
+    finally:
+        d.close()
+    return out
+
+
+def record_one_plane_nonfinite(lib):
+    """Writes tests/golden/expansion_nonfinite.npz (outputs only, compressed).  Called by hand on the commit whose expansion graphs are to be
+    kept -- never by a test."""
+    np.savez_compressed(NONFINITE_GOLDEN, **one_plane_nonfinite(lib))
+
+
+def case_one_plane_nonfinite(lib):
+    """Expansion moves whose plane has an infinite, NaN or near-overflow coefficient.  With one plane P the pair term c11 = T(P, P) is 0 only for
+    finite P (inf - inf = NaN), and the expansion graph never forms it: c01 and c10 are truncated to th_smooth and stay finite where a computed
+    c11 would turn the node's words into NaN.  No restatement decides that, so the expected values are recorded ones: payload and flow0 of
+    Batch.expansion_graph from the CPU simulator build of the commit before the expansion and fusion graph kernels became one template
+    (tests/golden/expansion_nonfinite.npz, written by record_one_plane_nonfinite).  That commit's MI355X build gave the same words, so one
+    recorded set serves both backends.  Every word is bit-equal or NaN on both sides (NaN payload bits are not promised); the 50 x 50 cell, whose
+    plane is (inf, 0, 1, 0), has no NaN word and a finite non-zero one.  -> (words compared, NaN words)"""
+    want = np.load(NONFINITE_GOLDEN)
+    got = one_plane_nonfinite(lib)
+    assert sorted(want.files) == sorted(got)
+    words = nans = 0
+    for key in want.files:
+        g, w = got[key], want[key]
+        assert g.shape == w.shape and g.dtype == w.dtype, key
+        bits = np.uint32 if g.dtype == F else np.uint64
+        same = (g.view(bits) == w.view(bits)) | (np.isnan(g) & np.isnan(w))
+        assert same.all(), f"{key}: {int((~same).sum())} of {same.size} words differ from the recorded ones"
+        words += same.size
+        nans += int(np.isnan(w).sum())
+    big = got["50x50_0_payload"]
+    assert not np.isnan(big).any() and (np.isfinite(big) & (big != 0)).any()
+    assert nans > 0                                                          # the small batch's NaN planes reach the payload
+    return words, nans
 
 
 # ------------------------------------------------------------------------------------------------ 4. cuts on fusion payloads (device solvers)

@@ -1,4 +1,4 @@
-"""Fusion moves on the device (csrc/les_fusion.h): two label maps fused by graph cuts -- les_hip_batch_fusion_graph, les_hip_batch_apply_masks_labels,
+"""Fusion moves on the device (csrc/les_pairwise.h): two label maps fused by graph cuts -- les_hip_batch_fusion_graph, les_hip_batch_apply_masks_labels,
 api.Batch.fusion_graph / apply_masks_labels, pm.PMRunner.fuse, stereo.FastGCStereo.fuse.  CPU simulator build (-m "not gpu": the cuts run on the
 host cores) and MI355X (-m gpu: the device solvers).  The definition, the cases, the references and the tolerances are in tests/fusion_cases.py."""
 import pytest
@@ -38,6 +38,10 @@ def test_sim_pin_to_the_expansion_chain(sim_lib):
     print("pairs one rounding below zero:", fc.case_pin_to_expansion(sim_lib))
 
 
+def test_sim_one_plane_nonfinite(sim_lib):
+    print("words compared, NaN words:", fc.case_one_plane_nonfinite(sim_lib))
+
+
 def test_sim_apply_and_flow_against_energy(sim_lib, host_lib):
     print("cells equal / bounded, pixels moved:", fc.case_apply_and_energy(sim_lib))
 
@@ -56,6 +60,11 @@ def test_gpu_payload_flow0_counts(host_lib):
 @pytest.mark.gpu
 def test_gpu_pin_to_the_expansion_chain(host_lib):
     print("pairs one rounding below zero:", fc.case_pin_to_expansion(None))
+
+
+@pytest.mark.gpu
+def test_gpu_one_plane_nonfinite(host_lib):
+    print("words compared, NaN words:", fc.case_one_plane_nonfinite(None))
 
 
 @pytest.mark.gpu

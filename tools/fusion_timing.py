@@ -1,12 +1,13 @@
 #!/usr/bin/env python
-"""Timings of the fusion moves (csrc/les_fusion.h) on the MI355X -> profiles/fusion_timing.json (summarised in DESIGN 3.4b).
+"""Timings of the fusion moves (csrc/les_pairwise.h) on the MI355X -> profiles/fusion_timing.json (summarised in DESIGN 3.4b).
 
   python tools/fusion_timing.py [--out profiles/fusion_timing.json]
 
 The synthetic "objects" scene of tools/e2e_bench.py at 1436 x 992 x 256 under the MidV3 energy and layers (1 % / 3 % / 9 % of the width).  The
 two label maps are the scene's one-view solutions from seeds 1 and 2 (one PatchMatch and two graph-cut iterations each).  Recorded:
-  * graph_kernels: per layer, the device time of a lock-step of les_fusion_graph_kernel next to les_expansion_graph_kernel on the same batches
-    (every disjoint set of the layer; events around 20 launches back to back, the two kernels alternating, 5 rounds, median), and their ratio;
+  * graph_kernels: per layer, the device time of a lock-step of les_move_graph_kernel<true> (label map: fusion) next to les_move_graph_kernel<false>
+    (one plane per cell: expansion) on the same batches (every disjoint set of the layer; events around 20 launches back to back, the two instances
+    alternating, 5 rounds, median), and their ratio;
   * fuse: the whole stereo.FastGCStereo.fuse pass (warm start excluded) and the dense pass inside it (host clock around a synchronise), the share
     of non-submodular pairs, and the three energies E(a), E(b), E(fuse(a, b)) from the device evaluator.
 Nothing here is a gate."""
