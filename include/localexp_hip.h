@@ -261,6 +261,33 @@ int les_hip_build_cost_volume(const uint8_t* d_imL, const uint8_t* d_imR, float*
  * device milliseconds of the calling thread's last build -- the two census launches, the volume kernel (tools/costvol_timing.py). */
 int les_hip_costvol_last_times(float* census_ms, float* volume_ms);
 
+/* ---- correlation cost volumes from feature maps (csrc/les_featvol.h holds the definitions) ----
+ * replaces: the MC-CNN-fast matcher behind im0.acrt / im1.acrt (LES/main.cpp:353-368) by its last layer alone -- the correlation of two per-pixel
+ * feature vectors -- so that any feature extractor, or the built-in ZNCC patch descriptor, feeds the cost-volume energy.  Feature maps are
+ * float [C][H][W], contiguous, in DEVICE memory (a torch NCHW tensor with N = 1).  Context-free; both calls only enqueue on hip_stream and use
+ * no scratch memory (with LES_HIP_FEATVOL_TIMING=1 they also wait for their launch).  Nothing is launched or written on a refused call. */
+/* the ZNCC descriptor of one H x W x 3 u8 (BGR) device image into d_feat, float [(2 ry + 1)(2 rx + 1)][H][W]: with g the integer grey
+ * (77 R + 150 G + 29 B + 128) >> 8, the N taps of the window visited row-major over (dy, dx), coordinates clamped, S = sum g, Q = sum g^2,
+ * V = N Q - S^2:  channel c = (float)((double)(N g_c - S) / sqrt((double)(N V))), or 0 where V = 0 (a flat patch).  Exact integers, one IEEE
+ * double sqrt and division, one rounding to float: a function of the image alone; unit norm, so the correlation of two descriptors is the
+ * ZNCC of the patches.  LES_HIP_ERR_ARG: null pointers, non-positive sizes, negative radii.  LES_HIP_ERR_UNSUPPORTED: a radius above 4,
+ * H > 65535. */
+int les_hip_patch_features(const uint8_t* d_bgr, float* d_feat, int H, int W, int ry, int rx, int device, void* hip_stream);
+/* the float [D][H][W] volume of one view from the two views' feature maps: slice k is disparity d = k + d0; mode 0 = left view's volume
+ * (I = L, J = R, partner column xp = clamp(x - d, 0, W - 1)), 1 = right view's (I = R, J = L, xp = clamp(x + d, 0, W - 1));
+ *   s = the f32 chain s <- fmaf(fI[c][y][x], fJ[c][y][xp], s) over c = 0 .. C - 1 from +0,      cost = fmaf(-alpha, s, beta).
+ * alpha = beta = 0.5 maps unit-norm features to [0, 1]; alpha = 1, beta = 0 is the raw -dot of MC-CNN-fast.  Features are used as given
+ * (normalising them is the caller's business).  Every entry is written, out-of-view ones through the clamped column:
+ * les_hip_fill_out_of_view comes after it.  Computed by v_mfma_f32_32x32x2_f32 in ascending channel order: the same bytes as the chain
+ * (DESIGN 3.2k), and in any case within alpha gamma_(C+1) sum_c |fI_c fJ_c| + 2^-24 |cost| of the exact value, gamma_n = n 2^-24 / (1 - n 2^-24).
+ * LES_HIP_ERR_ARG: null pointers, non-positive sizes, a mode outside 0 / 1, alpha or beta not finite.  LES_HIP_ERR_UNSUPPORTED: D H W >= 2^32,
+ * H > 65535, C > 512. */
+int les_hip_build_feature_volume(const float* d_featL, const float* d_featR, float* d_vol, int C, int D, int H, int W, int mode, int d0, float alpha,
+                                 float beta, int device, void* hip_stream);
+/* diagnostics: with LES_HIP_FEATVOL_TIMING=1 in the environment the two calls above bracket their launch with events; this returns the device
+ * milliseconds of the calling thread's last descriptor launch and last volume launch, -1 for one not run yet (tools/featvol_timing.py). */
+int les_hip_featvol_last_times(float* features_ms, float* volume_ms);
+
 /* replaces (on the device): the pairwise side of FastGCStereo::expansionMoveBK's graph construction
  * (LES/FastGCStereo.h:425-551) with StereoEnergy::initSmoothnessCoeff / computeSmoothnessTerm /
  * computeSmoothnessTermsExpansion (LES/StereoEnergy.h:131-163, 225-230, 398-453): for every cell i of the batch (its

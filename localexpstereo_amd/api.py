@@ -27,6 +27,7 @@ SYMBOLS = [
     "les_hip_evaluator_create", "les_hip_evaluator_destroy", "les_hip_evaluate", "les_hip_evaluator_rows", "les_hip_batch_region_energy",
     "les_hip_unary_labels", "les_hip_unary_labels_kind",
     "les_hip_costvol_tables", "les_hip_census", "les_hip_build_cost_volume", "les_hip_costvol_last_times",
+    "les_hip_patch_features", "les_hip_build_feature_volume", "les_hip_featvol_last_times",
     "les_hip_warp_labels",
     "les_hip_slab_argmin_state_bytes", "les_hip_slab_argmin", "les_hip_slab_argmin_finish", "les_hip_wta_labels",
     "les_hip_sgm_workspace_bytes", "les_hip_sgm_labels", "les_hip_sgm_last_times",
@@ -184,6 +185,9 @@ def load(path=None):
         "les_hip_census": (ci, [vp, vp, ci, ci, ci, vp]),
         "les_hip_build_cost_volume": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, C.c_float, C.c_float, ci, vp]),
         "les_hip_costvol_last_times": (ci, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+        "les_hip_patch_features": (ci, [vp, vp, ci, ci, ci, ci, ci, vp]),
+        "les_hip_build_feature_volume": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, C.c_float, C.c_float, ci, vp]),
+        "les_hip_featvol_last_times": (ci, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
         "les_hip_warp_labels": (ci, [vp, ci, vp, vp, vp, vp]),
         "les_hip_slab_argmin_state_bytes": (C.c_size_t, [ci, ci]),
         "les_hip_slab_argmin": (ci, [vp, vp, ci, ci, vp]),
@@ -296,6 +300,27 @@ def build_cost_volume(imL_dev_ptr, imR_dev_ptr, vol_dev_ptr, D, H, W, mode, d0=0
     L = load(lib)
     _chk_lib(L, L.les_hip_build_cost_volume(C.c_void_p(int(imL_dev_ptr)), C.c_void_p(int(imR_dev_ptr)), C.c_void_p(int(vol_dev_ptr)), D, H, W, mode, d0,
                                             lambda_ad, lambda_census, device, C.c_void_p(int(stream))))
+
+
+FEATVOL_MAX_CHANNELS = 512     # kFvMaxC of csrc/les_featvol.h (the one source; tests/featvol_cases.py: case_errors holds this copy to it)
+PATCH_MAX_RADIUS = 4           # kFvMaxRadius
+
+
+def patch_features(bgr_dev_ptr, feat_dev_ptr, H, W, ry=2, rx=2, device=0, stream=0, lib=None):
+    """The ZNCC patch descriptor (csrc/les_featvol.h) of a device H x W x 3 u8 BGR image into the device float [(2 ry + 1)(2 rx + 1)][H][W]
+    feature map: the zero-mean, unit-norm grey patch around every pixel (zero where the patch is flat), radii 0 .. 4.  Enqueue only."""
+    L = load(lib)
+    _chk_lib(L, L.les_hip_patch_features(C.c_void_p(int(bgr_dev_ptr)), C.c_void_p(int(feat_dev_ptr)), H, W, ry, rx, device, C.c_void_p(int(stream))))
+
+
+def build_feature_volume(featL_dev_ptr, featR_dev_ptr, vol_dev_ptr, Cn, D, H, W, mode, d0=0, alpha=0.5, beta=0.5, device=0, stream=0, lib=None):
+    """The correlation matching-cost volume of one view (mode 0 left, 1 right) from the two views' device float [Cn][H][W] feature maps into
+    the device float [D][H][W] volume: cost = beta - alpha <fI(x), fJ(xp)> as the f32 fma chain of csrc/les_featvol.h, slice k is disparity
+    k + d0.  The features are used as given.  Every entry is written (out-of-view ones through the clamped column): fill_out_of_view comes
+    after it.  Enqueue only."""
+    L = load(lib)
+    _chk_lib(L, L.les_hip_build_feature_volume(C.c_void_p(int(featL_dev_ptr)), C.c_void_p(int(featR_dev_ptr)), C.c_void_p(int(vol_dev_ptr)), Cn, D, H, W,
+                                               mode, d0, alpha, beta, device, C.c_void_p(int(stream))))
 
 
 def half_size(n):

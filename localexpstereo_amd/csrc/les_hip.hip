@@ -18,6 +18,7 @@
 #include "les_vdisp.h"
 #include "les_dense.h"
 #include "les_costvol.h"
+#include "les_featvol.h"
 #include "les_crossview.h"
 #include "les_wtavol.h"
 #include "les_confidence.h"
@@ -316,6 +317,7 @@ float naive_alpha(const les_hip_ctx* c) { return c->naive_alpha; }
 #include "les_hip_exchange.inc"
 #include "les_hip_dense.inc"
 #include "les_hip_costvol.inc"
+#include "les_hip_featvol.inc"
 #include "les_hip_crossview.inc"
 #include "les_hip_wtavol.inc"
 #include "les_hip_confidence.inc"

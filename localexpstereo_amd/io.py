@@ -106,22 +106,67 @@ def ingest_volumes(volL, volR=None, device="cuda", lib=None):
     return tl, tr
 
 
-def build_volumes(imL, imR, ndisp, device="cuda", lib=None, lambda_ad=10.0, lambda_census=30.0, d0=0):
-    """Both views' matching-cost volumes made on the device from the stereo pair alone: the AD-Census cost of csrc/les_costvol.h in the
-    place of the MC-CNN volumes the reference loads (LES/main.cpp:353-357).  imL / imR: H x W x 3 u8 (BGR) host arrays.  Each view is built
-    directly (mode 0 / mode 1; slice k is disparity k + d0), then filled like a loaded volume (fillOutOfView, :358 / :365).  Returns two
-    torch device tensors [ndisp][H][W], as ingest_volumes does."""
+COSTS = ("adcensus", "zncc")
+
+
+def build_volumes(imL, imR, ndisp, device="cuda", lib=None, lambda_ad=10.0, lambda_census=30.0, d0=0, cost="adcensus", patch=(2, 2), features=None,
+                  alpha=0.5, beta=0.5):
+    """Both views' matching-cost volumes made on the device from the stereo pair alone, in the place of the MC-CNN volumes the reference
+    loads (LES/main.cpp:353-357).  imL / imR: H x W x 3 u8 (BGR) host arrays.  Each view is built directly (mode 0 / mode 1; slice k is
+    disparity k + d0), then filled like a loaded volume (fillOutOfView, :358 / :365).  Returns two torch device tensors [ndisp][H][W], as
+    ingest_volumes does.
+    cost "adcensus" (default): the AD-Census cost of csrc/les_costvol.h (lambda_ad, lambda_census).
+    cost "zncc": beta - alpha ZNCC of the (2 ry + 1) x (2 rx + 1) grey patches, patch = (ry, rx), radii 0 .. 4: both views' patch
+    descriptors (api.patch_features) correlated on the matrix cores (api.build_feature_volume; csrc/les_featvol.h).
+    features: a pair (fL, fR) of float32 [C][H][W] tensors on `device`, or a callable that maps an H x W x 3 u8 image to such a tensor
+    (called once per view, left first): the volumes are beta - alpha <fI(x), fJ(xp)>, and `cost` is ignored.  The pair or the callable's
+    outputs are used AS GIVEN: normalising them is the caller's business (torch.nn.functional.normalize(f, dim=0) makes the costs lie in
+    [0, 1] at alpha = beta = 0.5, the range of AD-Census and of mc_threshold = 0.5; alpha = 1, beta = 0 is MC-CNN-fast's raw -dot)."""
     import torch
     dev = torch.device(device)
     idx = dev.index or 0 if dev.type == "cuda" else 0
     imL, imR = np.ascontiguousarray(imL, np.uint8), np.ascontiguousarray(imR, np.uint8)
     if imL.ndim != 3 or imL.shape[2] != 3 or imL.shape != imR.shape:
         raise ValueError(f"two H x W x 3 images of one shape expected, got {imL.shape} and {imR.shape}")
+    if features is None and cost not in COSTS:
+        raise ValueError(f"unknown cost {cost!r}: one of {COSTS}")
     H, W = imL.shape[:2]
     D = int(ndisp)
-    tiL, tiR = torch.from_numpy(imL.copy()).to(dev), torch.from_numpy(imR.copy()).to(dev)
     stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
     out = []
+    if features is not None or cost == "zncc":
+        if features is None:
+            try:
+                ry, rx = (int(r) for r in patch)
+                ok = (ry, rx) == tuple(patch) and 0 <= ry <= api.PATCH_MAX_RADIUS and 0 <= rx <= api.PATCH_MAX_RADIUS
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError(f"patch {patch!r}: a pair of integer radii (ry, rx), each 0 .. {api.PATCH_MAX_RADIUS}")
+            feats, images = [], []
+            for im in (imL, imR):
+                ti = torch.from_numpy(im.copy()).to(dev)
+                images.append(ti)
+                f = torch.empty(((2 * ry + 1) * (2 * rx + 1), H, W), dtype=torch.float32, device=dev)
+                api.patch_features(ti.data_ptr(), f.data_ptr(), H, W, ry, rx, device=idx, stream=stream, lib=lib)
+                feats.append(f)
+        else:
+            feats = [features(imL), features(imR)] if callable(features) else list(features)
+            if len(feats) != 2 or not all(torch.is_tensor(f) and f.dim() == 3 and f.dtype == torch.float32 and f.device.type == dev.type for f in feats) \
+                    or feats[0].shape != feats[1].shape or tuple(feats[0].shape[1:]) != (H, W):
+                raise ValueError(f"features: two float32 [C][{H}][{W}] tensors on {dev.type} expected")
+            feats = [f.contiguous() for f in feats]
+        Cn = int(feats[0].shape[0])
+        for mode in (0, 1):
+            t = torch.empty((D, H, W), dtype=torch.float32, device=dev)
+            api.build_feature_volume(feats[0].data_ptr(), feats[1].data_ptr(), t.data_ptr(), Cn, D, H, W, mode, d0=int(d0), alpha=alpha, beta=beta,
+                                     device=idx, stream=stream, lib=lib)
+            api.fill_out_of_view(t.data_ptr(), D, H, W, mode, device=idx, stream=stream, lib=lib)
+            out.append(t)
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)          # (the descriptors and the images live until here)
+        return out[0], out[1]
+    tiL, tiR = torch.from_numpy(imL.copy()).to(dev), torch.from_numpy(imR.copy()).to(dev)
     for mode in (0, 1):
         t = torch.empty((D, H, W), dtype=torch.float32, device=dev)
         api.build_cost_volume(tiL.data_ptr(), tiR.data_ptr(), t.data_ptr(), D, H, W, mode, d0=int(d0), lambda_ad=lambda_ad, lambda_census=lambda_census,

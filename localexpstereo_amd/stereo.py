@@ -804,21 +804,27 @@ def MidV2(data, iterations=5, pmIterations=2, doDual=False, smooth_weight=None, 
 
 
 def MidV3(data, volL=None, volR=None, iterations=5, pmIterations=2, doDual=False, smooth_weight=0.5, mc_threshold=0.5, filterRadious=20,
-          error_threshold=1.0, device="cuda", seed=1, lib=None, params=None, interpolate=1, lambda_ad=10.0, lambda_census=30.0, init=None, **kw):
+          error_threshold=1.0, device="cuda", seed=1, lib=None, params=None, interpolate=1, lambda_ad=10.0, lambda_census=30.0, init=None,
+          cost="adcensus", patch=(2, 2), features=None, **kw):
     """MidV3 (LES/main.cpp:330-420): cost-volume energy (volumes ingested on the device), layers 1 % / 3 % / 9 % of the
     image width.  volL / volR: host arrays / memmaps [ndisp][H][W] (volR None: synthesised from the left one).  params: PARAMS_GF
     (default) or PARAMS_BF: filter and eps; smooth_weight, mc_threshold and filterRadious override lambda_, th_col and windR (:351-353).
     interpolate: the energy's setInterpolationMethod (LES/CostVolumeEnergy.h:45-48) -- 0 nearest, 1 linear (default), 2 quadratic.
     volL None: no volume files -- both views' AD-Census volumes (io.build_volumes; lambda_ad, lambda_census) are built on the device from
-    data["imL"], data["imR"] and data["ndisp"].  init: as for MidV2 (None: the random start; "wta": the winner-take-all start; "wta+planes": with its fitted planes fused in), and "sgm" / "sgm+planes": every view starts from the semi-global matching map of its own raw volume (FastGCStereo.run's labeling="sgm" / "sgm+planes"; csrc/les_sgm.h); "half": the coarse-to-fine start over the pooled volumes (labeling="half"; csrc/les_pyramid.h).  Further keywords go to FastGCStereo (cross_view=n with doDual: cross-view fusion after every
+    data["imL"], data["imR"] and data["ndisp"]; cost="zncc" builds the ZNCC volumes of (2 ry + 1) x (2 rx + 1) grey patches instead, patch = (ry, rx), and
+    features= (a pair of float32 [C][H][W] device tensors, or a callable image -> such a tensor) the correlation volumes of those feature maps, used as given
+    (io.build_volumes; csrc/les_featvol.h).  cost / patch / features together with explicit volumes: ValueError.  init: as for MidV2 (None: the random start; "wta": the winner-take-all start; "wta+planes": with its fitted planes fused in), and "sgm" / "sgm+planes": every view starts from the semi-global matching map of its own raw volume (FastGCStereo.run's labeling="sgm" / "sgm+planes"; csrc/les_sgm.h); "half": the coarse-to-fine start over the pooled volumes (labeling="half"; csrc/les_pyramid.h).  Further keywords go to FastGCStereo (cross_view=n with doDual: cross-view fusion after every
     n-th graph-cut iteration)."""
     p = dict(PARAMS_GF if params is None else params)
     maxdisp = float(data["ndisp"] - 1)
     if volL is None:
         if volR is not None:
             raise ValueError("volR without volL")
-        tl, tr = io.build_volumes(data["imL"], data["imR"], data["ndisp"], device=device, lib=lib, lambda_ad=lambda_ad, lambda_census=lambda_census)
+        tl, tr = io.build_volumes(data["imL"], data["imR"], data["ndisp"], device=device, lib=lib, lambda_ad=lambda_ad, lambda_census=lambda_census,
+                                  cost=cost, patch=patch, features=features)
     else:
+        if cost != "adcensus" or features is not None or tuple(patch) != (2, 2):
+            raise ValueError("cost / patch / features build the volumes from the pair: not together with explicit volumes")
         tl, tr = io.ingest_volumes(volL, volR, device=device, lib=lib)
     D, H, W = tl.shape
     e = api.HipCostVolumeEnergy(data["imL"], data["imR"], tl.data_ptr(), tr.data_ptr(), windR=filterRadious, eps=p["eps"],
