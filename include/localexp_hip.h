@@ -653,6 +653,38 @@ int les_hip_mesh(les_hip_ctx* ctx, int mode, const les_hip_plane* d_labels, cons
  * for tests and diagnostics. */
 int les_hip_mesh_tile(int* pixels, int* scan_width);
 
+/* ---- view synthesis and the photometric check: a label map turned back into an image (csrc/les_view.h holds the definitions) ----
+ * No reference counterpart.  All maps are device pointers: an image is H x W x 3 bytes (b, g, r), disp H x W floats, hit / src / vis H x W
+ * bytes.  Every operation is f32, rounded, in the order of csrc/les_view.h: the outputs are a function of the inputs alone.  Each call is one
+ * launch, one workgroup per row, enqueued on the calling thread's stream (les_hip_set_thread_stream is honoured): no allocation, no
+ * synchronisation.  Rows wider than 8192 pixels: LES_HIP_ERR_UNSUPPORTED, nothing is launched.
+ *
+ * les_hip_render_view: the view of a camera at fraction t in [0, 1] of the baseline, counted from view src_mode (0 left, 1 right) towards the
+ * other view, from that view's label map and image (d_image NULL: the context's image of src_mode).  Every source pixel (xs, y) with disparity
+ * d = a xs + b y + c lands on column floor(xs -/+ d t + 0.5) of row y; of the pixels that land on one column the largest d wins (then the
+ * largest xs): d_out_hit 1, d_out_disp its d (in view src_mode's full-baseline units).  A single column without a winner between two winners
+ * whose d differ by at most 1 is a crack of a stretched surface: d_out_hit 2, d_out_disp their mean.  The colour of every hit column is the
+ * source image sampled linearly at rx +/- disp t, clamped to the row, and rounded to nearest.  A hole: d_out_hit 0, colour 0, disp NaN.  t = 0
+ * returns the source image wherever d is finite.  A null pointer (d_image aside), t outside [0, 1] or NaN, d_out_bgr == d_image: LES_HIP_ERR_ARG. */
+int les_hip_render_view(les_hip_ctx* ctx, int src_mode, const les_hip_plane* d_labels, const unsigned char* d_image /* may be NULL */, float t,
+                        unsigned char* d_out_bgr, float* d_out_disp, unsigned char* d_out_hit);
+/* les_hip_blend_views: two renders of one camera -- (d_bgrL, d_dispL, d_hitL) view 0 rendered at t, (d_bgrR, d_dispR, d_hitR) view 1 rendered at
+ * 1 - t; either triple may be NULL as a whole -- as one image.  Per pixel: both hit and |dL - dR| <= tol: colour (1 - t) cL + t cR rounded to
+ * nearest, disp (1 - t) dL + t dR, d_out_src 3; both hit otherwise: the one of larger disp (a tie: the left one), d_out_src 1 (left) or 2
+ * (right); one hit: that one; none: a hole, d_out_src 0, colour 0, disp NaN.  fill != 0: a hole takes colour and disp of the nearest pixel to
+ * its left or to its right on the row that was not a hole, the one of smaller disp (the background; a tie: the left one), and d_out_src 4; a
+ * row without any pixel stays a hole.  tol negative or NaN, t outside [0, 1], a partly given triple, both triples NULL, an output that is one
+ * of the renders: LES_HIP_ERR_ARG. */
+int les_hip_blend_views(les_hip_ctx* ctx, float t, float tol, int fill, const unsigned char* d_bgrL, const float* d_dispL, const unsigned char* d_hitL,
+                        const unsigned char* d_bgrR, const float* d_dispR, const unsigned char* d_hitR, unsigned char* d_out_bgr, float* d_out_disp,
+                        unsigned char* d_out_src);
+/* les_hip_photo_error: the photometric consistency of the label map of view `mode` with the context's two images, without ground truth.  Per
+ * pixel (xs, y): d_vis 0 where its landing column in the other view, floor(xs -/+ d + 0.5), does not exist; 2 where another pixel of the row
+ * wins that column (larger d: the label map itself says the pixel is occluded); 0 where xo = xs -/+ d lies outside [0, W - 1]; else 1, and
+ * d_err = (|db| + |dg| + |dr|) / 3 between the other image sampled linearly at xo and the pixel's own colour.  d_err is NaN wherever d_vis != 1.
+ * A context created with one image, a null pointer: LES_HIP_ERR_ARG. */
+int les_hip_photo_error(les_hip_ctx* ctx, int mode, const les_hip_plane* d_labels, float* d_err, unsigned char* d_vis);
+
 /* ---- multi-GPU: publishing the tiles a rank updated (not in the reference, which is single-process; SURVEY 8(e): the cells of a
  * disjoint set -- LES/LayerManager.h:168-172 -- are split over the ranks, replicas of the label / cost maps are kept coherent by one
  * all-gather per set of the label (16 B/px) and cost (4 B/px) tiles of the shared regions, LES/FastGCStereo.h:22-72).

@@ -36,6 +36,7 @@ SYMBOLS = [
     "les_hip_speckle_mask", "les_hip_speckle_tile", "les_hip_post_process_speckle",
     "les_hip_slab_confidence_state_bytes", "les_hip_slab_confidence", "les_hip_slab_confidence_finish", "les_hip_confidence", "les_hip_post_process_masked",
     "les_hip_reproject", "les_hip_mesh", "les_hip_mesh_tile",
+    "les_hip_render_view", "les_hip_blend_views", "les_hip_photo_error",
 ]
 
 
@@ -211,6 +212,9 @@ def load(path=None):
         "les_hip_confidence": (ci, [vp, ci, vp, ci, C.c_float, C.c_float, vp, vp, vp, vp]),
         "les_hip_post_process_masked": (ci, [vp, vp, vp, C.c_float, C.c_float, ci, C.c_float, vp, vp]),
         "les_hip_reproject": (ci, [vp, ci, vp, vp, C.POINTER(Calib), C.c_float, vp, vp, vp]),
+        "les_hip_render_view": (ci, [vp, ci, vp, vp, C.c_float, vp, vp, vp]),
+        "les_hip_blend_views": (ci, [vp, C.c_float, C.c_float, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "les_hip_photo_error": (ci, [vp, ci, vp, vp, vp]),
         "les_hip_mesh": (ci, [vp, ci, vp, vp, C.c_float, vp, vp, vp, vp]),
         "les_hip_mesh_tile": (ci, [C.POINTER(ci), C.POINTER(ci)]),
     }
@@ -1105,6 +1109,99 @@ class HipCostVolumeEnergy:
         self._staged(dev, True, self.mesh_ptr, mode, s.data_ptr(), m.data_ptr(), max_jump, vi.data_ptr(), vpix.data_ptr(), tri.data_ptr(), counts.data_ptr())
         nv, nt = (int(v) for v in counts.cpu())
         return vi, vpix[:nv], tri[:nt]
+
+    # -- view synthesis and the photometric check (csrc/les_view.h; no reference counterpart) -------------------------------
+    def render_view_ptr(self, src_mode, labels_ptr, image_ptr, t, bgr_ptr, disp_ptr, hit_ptr):
+        """les_hip_render_view on device addresses (image_ptr None: the context's image of src_mode).  Enqueue only.  Rows wider than
+        WARP_MAX_WIDTH raise (error 3)."""
+        self._chk(self.L.les_hip_render_view(self.h, int(src_mode), _vp(labels_ptr), _vp(image_ptr), C.c_float(t), _vp(bgr_ptr), _vp(disp_ptr), _vp(hit_ptr)))
+
+    def _image_map(self, image, dev, who):
+        """The H x W x 3 uint8 image on dev: a uint8 tensor that is there already is used where it is."""
+        import torch
+        m = image.to(device=dev, dtype=torch.uint8).contiguous() if torch.is_tensor(image) else torch.from_numpy(np.array(image, dtype=np.uint8, order="C")).to(dev)
+        if tuple(m.shape) != (self.H, self.W, 3):
+            raise ValueError(f"{who} an {self.H} x {self.W} x 3 uint8 image, not {tuple(m.shape)}")
+        return m
+
+    def render_view(self, labels, src_mode=0, t=1.0, image=None, device=None):
+        """les_hip_render_view: the view of a camera at fraction t in [0, 1] of the baseline, counted from view src_mode (0 left, 1 right) towards the
+        other view, rendered from that view's H x W x 4 label map and its image (image None: the context's; else H x W x 3 uint8 b, g, r) --
+        (bgr, disp, hit): H x W x 3 uint8, H x W float32 (the disparity of what is seen, in view src_mode's units; NaN in holes), H x W uint8
+        (1 a source pixel landed, 2 a one-column crack between two such pixels closed, 0 a hole, colour 0).  The nearest surface wins a column;
+        the colour is the source row sampled linearly (csrc/les_view.h).  t = 0 returns the source image wherever the disparity is finite, t = 1
+        is the other view.  labels / image: torch tensors (on `device`: used where they are) or arrays.  -> new tensors on `device` (None: this
+        context's GPU; the simulator build takes "cpu").  Asynchronous on the calling thread's stream where the maps are used where they are; a
+        map the wrapper had to copy is waited for (_staged)."""
+        import torch
+        dev = self._device(device)
+        s = self._label_map(labels, dev, "render_view:")
+        im = self._image_map(image, dev, "render_view:") if image is not None else None
+        bgr = torch.empty((self.H, self.W, 3), dtype=torch.uint8, device=dev)
+        disp = torch.empty((self.H, self.W), dtype=torch.float32, device=dev)
+        hit = torch.empty((self.H, self.W), dtype=torch.uint8, device=dev)
+        self._staged(dev, s is not labels or im is not image, self.render_view_ptr, src_mode, s.data_ptr(), im.data_ptr() if im is not None else None, t,
+                     bgr.data_ptr(), disp.data_ptr(), hit.data_ptr())
+        return bgr, disp, hit
+
+    def blend_views_ptr(self, t, tol, fill, left_ptrs, right_ptrs, bgr_ptr, disp_ptr, src_ptr):
+        """les_hip_blend_views on device addresses: left_ptrs / right_ptrs are (bgr, disp, hit) or None.  Enqueue only."""
+        l, r = (tuple(q) if q is not None else (None, None, None) for q in (left_ptrs, right_ptrs))
+        self._chk(self.L.les_hip_blend_views(self.h, C.c_float(t), C.c_float(tol), int(bool(fill)), *(_vp(q) for q in l + r), _vp(bgr_ptr), _vp(disp_ptr), _vp(src_ptr)))
+
+    def blend_views(self, t, left=None, right=None, tol=1.0, fill=True, device=None):
+        """les_hip_blend_views: two renders of the camera at fraction t of the baseline (from the left view) as one image.  left: render_view's
+        (bgr, disp, hit) of view 0 at t; right: that of view 1 at 1 - t; either may be None.  Where both see the pixel and their disparities agree
+        within tol the colours are mixed (1 - t) : t, where they disagree the nearer one is taken, where one sees it that one; with `fill` a hole
+        takes the farther of its nearest neighbours to the left and to the right on the row (csrc/les_view.h).  -> (bgr, disp, src): H x W x 3
+        uint8, H x W float32, H x W uint8 (0 hole, 1 left, 2 right, 3 both, 4 filled), new tensors on `device` (None: this context's GPU; the
+        simulator build takes "cpu").  Tensors on `device` are used where they are; a map the wrapper had to copy is waited for (_staged)."""
+        import torch
+        dev = self._device(device)
+        copied, sides = False, []
+        for side in (left, right):
+            if side is None:
+                sides.append(None)
+                continue
+            b, d, h = side
+            tb, td, th = self._image_map(b, dev, "blend_views:"), _float_tensor(d, dev), self._byte_map_raw(h, dev, "blend_views:")
+            if tuple(td.shape) != (self.H, self.W):
+                raise ValueError(f"blend_views: an {self.H} x {self.W} disparity map, not {tuple(td.shape)}")
+            copied |= tb is not b or td is not d or th is not h
+            sides.append((tb, td, th))
+        bgr = torch.empty((self.H, self.W, 3), dtype=torch.uint8, device=dev)
+        disp = torch.empty((self.H, self.W), dtype=torch.float32, device=dev)
+        src = torch.empty((self.H, self.W), dtype=torch.uint8, device=dev)
+        self._staged(dev, copied, self.blend_views_ptr, t, tol, fill, *(tuple(q.data_ptr() for q in s) if s is not None else None for s in sides),
+                     bgr.data_ptr(), disp.data_ptr(), src.data_ptr())
+        return bgr, disp, src
+
+    def _byte_map_raw(self, m, dev, who):
+        """The H x W uint8 map on dev with its values kept (a hit map): a uint8 tensor that is there already is used where it is."""
+        import torch
+        t = m.to(device=dev, dtype=torch.uint8).contiguous() if torch.is_tensor(m) else torch.from_numpy(np.array(m, dtype=np.uint8, order="C")).to(dev)
+        if tuple(t.shape) != (self.H, self.W):
+            raise ValueError(f"{who} an {self.H} x {self.W} uint8 map, not {tuple(t.shape)}")
+        return t
+
+    def photo_error_ptr(self, mode, labels_ptr, err_ptr, vis_ptr):
+        """les_hip_photo_error on device addresses.  Enqueue only."""
+        self._chk(self.L.les_hip_photo_error(self.h, int(mode), _vp(labels_ptr), _vp(err_ptr), _vp(vis_ptr)))
+
+    def photo_error(self, labels, mode=0, device=None):
+        """les_hip_photo_error: the photometric consistency of the H x W x 4 label map of view `mode` with the context's two images, no ground
+        truth needed -- (err, vis): vis H x W uint8, 1 where the pixel is seen in the other view (err = the mean absolute difference over b, g, r
+        between the other image sampled linearly where the label says the pixel is and the pixel's own colour), 2 where the label map itself says
+        it is occluded (a nearer pixel of the row lands on the same column), 0 where it leaves the image or its disparity is not finite; err
+        H x W float32, NaN wherever vis != 1 (csrc/les_view.h).  labels: a torch tensor (on `device`: used where it is) or an array.  -> new
+        tensors on `device` (None: this context's GPU; the simulator build takes "cpu"); a map the wrapper had to copy is waited for (_staged)."""
+        import torch
+        dev = self._device(device)
+        s = self._label_map(labels, dev, "photo_error:")
+        err = torch.empty((self.H, self.W), dtype=torch.float32, device=dev)
+        vis = torch.empty((self.H, self.W), dtype=torch.uint8, device=dev)
+        self._staged(dev, s is not labels, self.photo_error_ptr, mode, s.data_ptr(), err.data_ptr(), vis.data_ptr())
+        return err, vis
 
     # -- a half-resolution solve as a start (csrc/les_pyramid.h; no reference counterpart) ------------------------------------
     def image(self, mode=0):

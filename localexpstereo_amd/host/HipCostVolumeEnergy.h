@@ -292,6 +292,56 @@ public:
         return d_vi.download(vertex_index.data(), P) && d_vp.download(vertex_pixel.data(), vertex_pixel.size()) && d_tri.download(triangles.data(), triangles.size());
     }
 
+    // The view of a camera at fraction t in [0, 1] of the baseline, counted from view src_mode towards the other view, rendered from that view's
+    // label map and image (les_hip_render_view, csrc/les_view.h; no reference counterpart).  image (may be null: the energy's own image of
+    // src_mode): width * height * 3 bytes b, g, r.  bgr: width * height * 3 bytes; disp: width * height floats, the disparity of what is seen
+    // (NaN in holes); hit: width * height bytes, 1 a source pixel landed, 2 a one-column crack closed, 0 a hole.  All maps in HOST memory.
+    // Returns false (and reports on stderr) when the library refuses the call (t outside [0, 1], rows wider than 8192 pixels).
+    bool renderView(int src_mode, const Plane* labels, const unsigned char* image, float t, unsigned char* bgr, float* disp, unsigned char* hit) const
+    {
+        const size_t P = (size_t)width * height;
+        Status st(kWho);
+        DeviceArray<Plane> d_lab(ctx_, st, labels, P);
+        DeviceArray<unsigned char> d_img(ctx_, st, image, 3 * P), d_bgr(ctx_, st, 3 * P), d_hit(ctx_, st, P);
+        DeviceArray<float> d_disp(ctx_, st, P);
+        if (st.ok() && st(les_hip_render_view(ctx_, src_mode, abi(d_lab), d_img.get(), t, d_bgr.get(), d_disp.get(), d_hit.get()))) st(les_hip_synchronize(ctx_));
+        return d_bgr.download(bgr, 3 * P) && d_disp.download(disp, P) && d_hit.download(hit, P);
+    }
+
+    // Two renders of the camera at fraction t of the baseline (from the left view) as one image (les_hip_blend_views): (bgrL, dispL, hitL) is view
+    // 0 rendered at t, (bgrR, dispR, hitR) view 1 rendered at 1 - t; either triple may be null as a whole.  Colours are mixed (1 - t) : t where both
+    // see the pixel and their disparities agree within tol, the nearer one is taken where they do not; with fill a hole takes the farther of its
+    // nearest neighbours on the row.  src: 0 hole, 1 left, 2 right, 3 both, 4 filled.  All maps in HOST memory.  Returns false (and reports on
+    // stderr) when the library refuses the call.
+    bool blendViews(float t, float tol, bool fill, const unsigned char* bgrL, const float* dispL, const unsigned char* hitL, const unsigned char* bgrR,
+                    const float* dispR, const unsigned char* hitR, unsigned char* bgr, float* disp, unsigned char* src) const
+    {
+        const size_t P = (size_t)width * height;
+        Status st(kWho);
+        DeviceArray<unsigned char> d_bl(ctx_, st, bgrL, 3 * P), d_hl(ctx_, st, hitL, P), d_br(ctx_, st, bgrR, 3 * P), d_hr(ctx_, st, hitR, P);
+        DeviceArray<float> d_dl(ctx_, st, dispL, P), d_dr(ctx_, st, dispR, P), d_disp(ctx_, st, P);
+        DeviceArray<unsigned char> d_bgr(ctx_, st, 3 * P), d_src(ctx_, st, P);
+        if (st.ok() && st(les_hip_blend_views(ctx_, t, tol, fill ? 1 : 0, d_bl.get(), d_dl.get(), d_hl.get(), d_br.get(), d_dr.get(), d_hr.get(), d_bgr.get(),
+                                              d_disp.get(), d_src.get())))
+            st(les_hip_synchronize(ctx_));
+        return d_bgr.download(bgr, 3 * P) && d_disp.download(disp, P) && d_src.download(src, P);
+    }
+
+    // The photometric consistency of a label map of view `mode` with the energy's two images, no ground truth needed (les_hip_photo_error): vis 1
+    // where the pixel is seen in the other view, 2 where the label map itself says it is occluded, 0 where it leaves the image; err: the mean
+    // absolute difference over b, g, r between the other image sampled where the label says the pixel is and the pixel's own colour, NaN where
+    // vis != 1.  width * height elements each in HOST memory.  Returns false (and reports on stderr) when the library refuses the call.
+    bool photoError(const Plane* labels, float* err, unsigned char* vis, int mode = 0) const
+    {
+        const size_t P = (size_t)width * height;
+        Status st(kWho);
+        DeviceArray<Plane> d_lab(ctx_, st, labels, P);
+        DeviceArray<float> d_err(ctx_, st, P);
+        DeviceArray<unsigned char> d_vis(ctx_, st, P);
+        if (st.ok() && st(les_hip_photo_error(ctx_, mode, abi(d_lab), d_err.get(), d_vis.get()))) st(les_hip_synchronize(ctx_));
+        return d_err.download(err, P) && d_vis.download(vis, P);
+    }
+
     // PMStereoBase::postProcess with the failure mask widened by the speckle mask (les_hip_post_process_speckle), in place on HOST label maps of
     // width * height planes.  One of labelsL / labelsR may be null: the one-view form, whose mask is the speckle mask alone (threshold is ignored).
     // max_size 0: with both views PMStereoBase::postProcess itself, with one view nothing changes.  Returns false (and reports on stderr) when the

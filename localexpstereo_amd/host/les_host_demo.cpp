@@ -94,6 +94,34 @@ static int adapter_checks(const HipCostVolumeEnergy& hip, const HipCostVolumeEne
         }
     printf("warpLabels: %zu of %zu pixels differ from the expected map\n", wbad, P);
     if (!okw || wbad) { printf("FAIL: warpLabels\n"); fail = 1; }
+    // view synthesis through the adapter, the same map over a planted image (b = x, g = y, r = 7): at t = 1 column x shows source column
+    // x + 3 and the three rightmost columns are holes, which the blend fills from the left; at t = 0 the image comes back; every pixel from
+    // column 3 on is seen in the other view
+    std::vector<unsigned char> vimg(3 * P), vbgr(3 * P, 9), vhit(P, 9), vbgr0(3 * P, 9), vhit0(P, 9), vout(3 * P, 9), vsrc(P, 9), pvis(P, 9);
+    std::vector<float> vdisp(P, -1.f), vdisp0(P, -1.f), vod(P, -1.f), perr(P, -1.f);
+    for (int y = 0; y < H; y++)
+        for (int x = 0; x < W; x++) {
+            unsigned char* q = &vimg[3 * ((size_t)y * W + x)];
+            q[0] = (unsigned char)x; q[1] = (unsigned char)y; q[2] = 7;
+        }
+    const bool okv = hip.renderView(0, wsrc.data(), vimg.data(), 1.f, vbgr.data(), vdisp.data(), vhit.data()) &&
+                     hip.renderView(0, wsrc.data(), vimg.data(), 0.f, vbgr0.data(), vdisp0.data(), vhit0.data()) &&
+                     hip.blendViews(1.f, 1.f, true, vbgr.data(), vdisp.data(), vhit.data(), nullptr, nullptr, nullptr, vout.data(), vod.data(), vsrc.data()) &&
+                     hip.photoError(wsrc.data(), perr.data(), pvis.data(), 0);
+    size_t vbad = 0;
+    for (int y = 0; y < H; y++)
+        for (int x = 0; x < W; x++) {
+            const size_t i = (size_t)y * W + x;
+            const bool in = x + 3 < W;
+            const int xf = in ? x + 3 : W - 1;                     // (a filled hole shows the last rendered column, W - 4, which shows source column W - 1)
+            vbad += vhit[i] != (in ? 1 : 0) || (in ? vdisp[i] != 3.f : !std::isnan(vdisp[i])) || vbgr[3 * i] != (in ? (unsigned char)(x + 3) : 0) ||
+                    vbgr[3 * i + 1] != (in ? (unsigned char)y : 0) || vbgr[3 * i + 2] != (in ? 7 : 0);
+            vbad += vhit0[i] != 1 || vdisp0[i] != 3.f || memcmp(&vbgr0[3 * i], &vimg[3 * i], 3) != 0;
+            vbad += vsrc[i] != (in ? 1 : 4) || vod[i] != 3.f || vout[3 * i] != (unsigned char)xf || vout[3 * i + 1] != (unsigned char)y || vout[3 * i + 2] != 7;
+            vbad += pvis[i] != (x >= 3 ? 1 : 0) || (x >= 3 ? !(perr[i] >= 0.f) : !std::isnan(perr[i]));
+        }
+    printf("renderView / blendViews / photoError: %zu checks of %zu pixels differ from the expected maps\n", vbad, P);
+    if (!okv || vbad) { printf("FAIL: renderView / blendViews / photoError\n"); fail = 1; }
     // the winner-take-all map of the filtered volume through the adapter: fronto-parallel planes, chunking does not change a bit
     std::vector<Plane> wta(P), wta2(P);
     std::vector<float> wcost(P);

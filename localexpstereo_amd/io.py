@@ -395,3 +395,18 @@ def sparsification(disp, gt, conf, valid=None, threshold=1.0):
     counts = np.arange(1, n + 1, dtype=np.float64)
     area = lambda order: float((np.cumsum(bad[order], dtype=np.float64) / counts).mean())
     return dict(bad=float(bad.mean()), auc=area(np.argsort(-c, kind="stable")), auc_optimal=area(np.argsort(err, kind="stable")))
+
+
+def photometric(err, vis, thresh=10.0):
+    """A photometric-error map (FastGCStereo.photo_error, api.HipCostVolumeEnergy.photo_error) summed up, in host numpy: -> dict(mean: the mean
+    of err over the pixels seen in the other view (vis == 1), accumulated in float64, in grey levels; bad: the fraction of those pixels with
+    err > thresh; visible: the fraction of all pixels with vis == 1; occluded: that with vis == 2).  mean and bad are NaN without a visible
+    pixel.  No ground truth is involved: a low mean says the labels explain the other image, not that they are right where the image is flat."""
+    err, vis = np.asarray(err, np.float32), np.asarray(vis)
+    if err.shape != vis.shape:
+        raise ValueError(f"photometric: maps of one shape, not {err.shape}, {vis.shape}")
+    seen = vis == 1
+    n = int(seen.sum())
+    e = err[seen].astype(np.float64)
+    return dict(mean=float(e.mean()) if n else float("nan"), bad=float((e > thresh).mean()) if n else float("nan"),
+                visible=float(n / vis.size) if vis.size else float("nan"), occluded=float((vis == 2).sum() / vis.size) if vis.size else float("nan"))

@@ -26,7 +26,7 @@ PARAMS_BF = dict(PARAMS_GF, lambda_=20.0, windR=20, eps=10.0, filter="BF")
 class FastGCStereo:
     def __init__(self, energy, imL, imR, params, device="cuda", rank=0, world=1, seed=1, host_threads=0, device_cuts=None, random_vdisp=None,
                  evaluate_on_device=False, inner_loop_log=False, check_flow_energy=False, recost_after_post=False, cross_view=0, coarse_params=None,
-                 speckle=None, confidence=False, min_confidence=None, confidence_band=1.0):
+                 speckle=None, confidence=False, min_confidence=None, confidence_band=1.0, max_photo_error=None):
         self.e, self.imL, self.imR, self.p = energy, imL, imR, dict(PARAMS_GF, **params)
         # Opt-in, no reference counterpart (csrc/les_confidence.h): confidence=True -- run(), wta() and sgm() set self.confidences = {view: H x W
         # float32 in [0, 1]}, the confidence of each view's RAW labelling (before the post-processing) under that view's aggregated cost volume
@@ -41,6 +41,13 @@ class FastGCStereo:
         if not self.confidence_band >= 0.0:
             raise ValueError(f"confidence_band {confidence_band}: a half-width in slabs, >= 0")
         self.with_confidence = bool(confidence) or self.min_confidence is not None
+        # Opt-in, no reference counterpart (csrc/les_view.h): max_photo_error=tau >= 0 adds to each view's failure mask of the post-processing every
+        # pixel of that view's RAW labelling that is seen in the other view (les_hip_photo_error: vis == 1) with a photometric error above tau grey
+        # levels -- a wrong match the cost curve may be sure of.  It composes with speckle and min_confidence, and like them gives a one-view call a
+        # post-processing (with that mask alone).  Single rank.  None (the default) changes nothing.
+        self.max_photo_error = None if max_photo_error is None else float(max_photo_error)
+        if self.max_photo_error is not None and not self.max_photo_error >= 0.0:
+            raise ValueError(f"max_photo_error {max_photo_error}: None or a threshold in grey levels, >= 0")
         self.confidences = {}                     # run(), wta(), sgm() with confidence=True: view -> the H x W confidence map of its raw labelling
         # Opt-in, no reference counterpart: (max_size, max_diff) -- the post-processing step of run(), wta() and sgm() also treats as failed every
         # pixel whose connected component of the view's disparity map (4-neighbours within max_diff) has at most max_size pixels
@@ -358,6 +365,35 @@ class FastGCStereo:
                    colors=rgb.reshape(-1, 3)[idx], vertex_pixel=vpixel, triangles=tri)
         return {k: v.cpu().numpy() for k, v in out.items()}
 
+    def synthesize(self, labelings, t=0.5, tol=1.0, fill=True, viewMode=0):
+        """The image a camera at fraction t in [0, 1] of the baseline, counted from the LEFT view, would see (no reference counterpart;
+        csrc/les_view.h; api.HipCostVolumeEnergy.render_view and .blend_views).  labelings: {0: L, 1: R}, H x W x 4 maps of both views -- each view is
+        rendered from its own image (view 0 at t, view 1 at 1 - t) and the two renders are blended: mixed (1 - t) : t where their disparities agree
+        within tol, the nearer one where they do not -- or one H x W x 4 map of view viewMode, rendered alone.  fill: a hole takes the farther of
+        its nearest neighbours on the row.  -> (image H x W x 3 uint8 b, g, r; disparity H x W float32, NaN in holes; source H x W uint8: 0 hole,
+        1 left view, 2 right view, 3 both, 4 filled), host arrays.  It changes no estimate.  Single rank."""
+        if self.world > 1:
+            raise NotImplementedError("FastGCStereo.synthesize is single-rank: the multi-rank form is not implemented")
+        maps = labelings if isinstance(labelings, dict) else {int(viewMode): labelings}
+        if not maps or any(m not in (0, 1) for m in maps):
+            raise ValueError(f"synthesize takes one label map or {{0: L, 1: R}} (views given: {sorted(maps)})")
+        t = float(t)
+        sides = {m: self.e.render_view(maps[m], src_mode=m, t=t if m == 0 else 1.0 - t, device=self.device) for m in sorted(maps)}
+        out = self.e.blend_views(t, left=sides.get(0), right=sides.get(1), tol=tol, fill=fill, device=self.device)
+        self.e.synchronize()
+        return tuple(o.cpu().numpy() for o in out)
+
+    def photo_error(self, labeling, viewMode=0):
+        """The photometric error of any H x W x 4 label map of view viewMode against the two images, no ground truth needed (no reference
+        counterpart; csrc/les_view.h; api.HipCostVolumeEnergy.photo_error).  -> (err H x W float32, vis H x W uint8): vis 1 seen in the other
+        view, 2 occluded by the label map's own account, 0 outside; err the mean absolute colour difference, NaN where vis != 1.  io.photometric
+        sums them up.  Single rank."""
+        if self.world > 1:
+            raise NotImplementedError("FastGCStereo.photo_error is single-rank: the multi-rank form is not implemented")
+        err, vis = self.e.photo_error(labeling, mode=int(viewMode), device=self.device)
+        self.e.synchronize()
+        return err.cpu().numpy(), vis.cpu().numpy()
+
     def _confidences(self, maps):
         """With confidence=True: self.confidences of the device label maps {view: map} as they are (raw), -> {view: the device confidence map};
         otherwise {} (and self.confidences is emptied)."""
@@ -440,16 +476,25 @@ class FastGCStereo:
         return lab, self.raw_labelings.get(0)
 
     def _post_processes(self, views):
-        """Whether a call over `views` ends with the post-processing: two views always, one view when a speckle filter or min_confidence is set."""
-        return len(views) == 2 or self.speckle is not None or self.min_confidence is not None
+        """Whether a call over `views` ends with the post-processing: two views always, one view when a speckle filter, min_confidence or
+        max_photo_error is set."""
+        return len(views) == 2 or self.speckle is not None or self.min_confidence is not None or self.max_photo_error is not None
 
     def _post_process(self, maps, conf=None):
         """The post-processing step of run(), wta() and sgm() in place on the device label maps {view: map}: threshold 1.5, the run's omega
         (LES/FastGCStereo.h:202), (left, right) whatever the order of the views; with self.speckle the widened mask, and the one-view form; with
-        self.min_confidence each view's mask widened by conf[view] < min_confidence (conf: what _confidences returned for the same maps)."""
+        self.min_confidence each view's mask widened by conf[view] < min_confidence (conf: what _confidences returned for the same maps); with
+        self.max_photo_error by vis == 1 and err > max_photo_error of the view's map as it comes in (les_hip_photo_error)."""
         ptr = {m: maps[m].data_ptr() if m in maps else None for m in (0, 1)}
-        if self.min_confidence is not None:
-            low = {m: (conf[m] < self.min_confidence).to(torch.uint8).contiguous() for m in maps}
+        if self.min_confidence is not None or self.max_photo_error is not None:
+            low = {m: torch.zeros(maps[m].shape[:2], dtype=torch.bool, device=maps[m].device) for m in maps}
+            if self.min_confidence is not None:
+                low = {m: low[m] | (conf[m] < self.min_confidence) for m in maps}
+            if self.max_photo_error is not None:
+                photo = {m: self.e.photo_error(maps[m], mode=m, device=self.device) for m in maps}
+                self.e.synchronize()
+                low = {m: low[m] | ((photo[m][1] == 1) & (photo[m][0] > self.max_photo_error)) for m in maps}
+            low = {m: low[m].to(torch.uint8).contiguous() for m in maps}
             if any(t.is_cuda for t in low.values()):     # (torch made the masks on its stream; the library reads them on the context's)
                 torch.cuda.current_stream().synchronize()
             self.e.post_process(ptr[0], ptr[1], 1.5, self.p["omega"], speckle=self.speckle, fail=tuple(low[m].data_ptr() if m in low else None for m in (0, 1)))
@@ -473,6 +518,8 @@ class FastGCStereo:
                 raise NotImplementedError(f"labeling=\"{labeling}\" is single-rank: the multi-rank start is not implemented")
         if self.with_confidence and self.world > 1:
             raise NotImplementedError("confidence / min_confidence are single-rank: the multi-rank form is not implemented")
+        if self.max_photo_error is not None and self.world > 1:
+            raise NotImplementedError("max_photo_error is single-rank: the multi-rank form is not implemented")
         if self.inner_loop_log and self.world > 1:
             raise ValueError("inner_loop_log is a single-rank log: with several ranks a rank holds only its band of a set's cells until the exchange")
         if self.cross_view > 0:
