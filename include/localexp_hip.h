@@ -685,6 +685,37 @@ int les_hip_blend_views(les_hip_ctx* ctx, float t, float tol, int fill, const un
  * A context created with one image, a null pointer: LES_HIP_ERR_ARG. */
 int les_hip_photo_error(les_hip_ctx* ctx, int mode, const les_hip_plane* d_labels, float* d_err, unsigned char* d_vis);
 
+/* ---- rectification: a calibrated raw stereo pair turned into the rectified pair every other entry assumes (csrc/les_rectify.h holds the
+ * definitions; no reference counterpart, the reference reads rectified pairs only) ----
+ * Camera model: a point (X, Y, Z) of a raw camera's frame (X right, Y down, Z forward) is seen at pixel (u, v), pixel centres at integer
+ * coordinates, with dist = (k1, k2, p1, p2, k3, k4, k5, k6):  x' = X / Z, y' = Y / Z, r2 = x'^2 + y'^2,
+ * rad = (1 + k1 r2 + k2 r2^2 + k3 r2^3) / (1 + k4 r2 + k5 r2^2 + k6 r2^3),  x'' = x' rad + 2 p1 x' y' + p2 (r2 + 2 x'^2),
+ * y'' = y' rad + p1 (r2 + 2 y'^2) + 2 p2 x' y',  u = fx x'' + cx, v = fy y'' + cy.  The two cameras of a rig are related by
+ * X1 = R X0 + T (X0, X1: one point in the left and the right raw frame); the rectified pair has doffs = cx1 - cx0 and baseline = |T|
+ * (io.stereo_rectify of the Python package makes the rectifying rotations and the les_hip_calib from K0, dist0, K1, dist1, R, T). */
+typedef struct les_hip_camera {
+    double fx, fy, cx, cy, dist[8];
+} les_hip_camera;
+/* d_map[y][x] = (u, v): where in the raw image rectified pixel (x, y) comes from.  M (row-major 3 x 3, host memory) takes a ray of the
+ * rectified frame into the raw camera's frame -- the transpose of the view's rectifying rotation; f, cx, cy are the rectified view's
+ * intrinsics.  The ray ((x - cx) / f, (y - cy) / f, 1) goes through M and the camera model above in fp64, in the one order of operations
+ * csrc/les_rectify.h states, not contracted, and (u, v) is rounded to f32 once: the map is a function of the arguments alone, bit for bit.
+ * A ray with Z <= 0 behind M, or a denominator of rad that is 0 or not finite, gives (NaN, NaN).  One work-item per pixel; the 25 doubles
+ * travel as kernel arguments.  d_map: H x W x 2 floats on the device, 8-byte aligned.
+ * les_hip_remap: d_dst[y][x][k] = d_src (Hs x Ws x channels bytes, channels 1 or 3) sampled at d_map[y][x]; interp 0 nearest (the tap
+ * floor(u + 0.5)), 1 linear (four taps), 2 cubic (4 x 4 Catmull-Rom, a = -0.5); tap indices clamp to the image, the weights come from the
+ * exact fp64 fractions of the f32 coordinates, the taps are summed in fp64 in one stated order and the result is floor(s + 0.5) clamped to
+ * 0 .. 255: bit for bit a function of the inputs.  A pixel is valid iff its map entry is finite, 0 <= u <= Ws - 1 and 0 <= v <= Hs - 1;
+ * an invalid one gets 0 in every channel and reads nothing from d_src (NaN, +-inf and coordinates beyond the int range never form an index).
+ * d_valid (H x W bytes or NULL): 1 valid / 0.  d_dst may not be d_src.
+ * Both are context-free and enqueue only on hip_stream of `device`.  LES_HIP_ERR_ARG for null pointers, non-positive sizes, a map that is not
+ * 8-byte aligned, f, fx or fy not finite or <= 0, channels or interp out of range; LES_HIP_ERR_UNSUPPORTED for Hs Ws channels >= 2^31 and
+ * for H > 65535 (the launch grid); a refused call launches nothing. */
+int les_hip_rectify_map(const les_hip_camera* raw, const double M[9], double f, double cx, double cy, float* d_map /* [H][W][2] */, int H, int W,
+                        int device, void* hip_stream);
+int les_hip_remap(const uint8_t* d_src, int Hs, int Ws, int channels /* 1 or 3 */, const float* d_map, uint8_t* d_dst,
+                  unsigned char* d_valid /* may be NULL */, int H, int W, int interp /* 0 nearest, 1 linear, 2 cubic */, int device, void* hip_stream);
+
 /* ---- multi-GPU: publishing the tiles a rank updated (not in the reference, which is single-process; SURVEY 8(e): the cells of a
  * disjoint set -- LES/LayerManager.h:168-172 -- are split over the ranks, replicas of the label / cost maps are kept coherent by one
  * all-gather per set of the label (16 B/px) and cost (4 B/px) tiles of the shared regions, LES/FastGCStereo.h:22-72).

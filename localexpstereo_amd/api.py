@@ -37,6 +37,7 @@ SYMBOLS = [
     "les_hip_slab_confidence_state_bytes", "les_hip_slab_confidence", "les_hip_slab_confidence_finish", "les_hip_confidence", "les_hip_post_process_masked",
     "les_hip_reproject", "les_hip_mesh", "les_hip_mesh_tile",
     "les_hip_render_view", "les_hip_blend_views", "les_hip_photo_error",
+    "les_hip_rectify_map", "les_hip_remap",
 ]
 
 
@@ -74,6 +75,11 @@ class EvalRow(C.Structure):
 class Calib(C.Structure):
     """les_hip_calib (include/localexp_hip.h): a rectified pinhole pair; io.calib3d makes one from a Middlebury calib.txt."""
     _fields_ = [("f", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("doffs", C.c_float), ("baseline", C.c_float)]
+
+
+class Camera(C.Structure):
+    """les_hip_camera (include/localexp_hip.h): a raw pinhole camera, dist = (k1, k2, p1, p2, k3, k4, k5, k6)."""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("dist", C.c_double * 8)]
 
 
 class Params(C.Structure):
@@ -215,6 +221,8 @@ def load(path=None):
         "les_hip_render_view": (ci, [vp, ci, vp, vp, C.c_float, vp, vp, vp]),
         "les_hip_blend_views": (ci, [vp, C.c_float, C.c_float, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "les_hip_photo_error": (ci, [vp, ci, vp, vp, vp]),
+        "les_hip_rectify_map": (ci, [C.POINTER(Camera), C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, vp, ci, ci, ci, vp]),
+        "les_hip_remap": (ci, [vp, ci, ci, ci, vp, vp, vp, ci, ci, ci, ci, vp]),
         "les_hip_mesh": (ci, [vp, ci, vp, vp, C.c_float, vp, vp, vp, vp]),
         "les_hip_mesh_tile": (ci, [C.POINTER(ci), C.POINTER(ci)]),
     }
@@ -345,6 +353,43 @@ def pool_volume(src_dev_ptr, dst_dev_ptr, D, H, W, device=0, stream=0, lib=None)
     source indices clamped, in the fixed f32 order of csrc/les_pyramid.h (exact: the same bytes on every build).  Enqueue only."""
     L = load(lib)
     _chk_lib(L, L.les_hip_pool_volume(C.c_void_p(int(src_dev_ptr)), C.c_void_p(int(dst_dev_ptr)), D, H, W, device, C.c_void_p(int(stream))))
+
+
+INTERP_NAMES = {"nearest": 0, "linear": 1, "cubic": 2}          # les_hip_remap's interp
+
+
+def camera(K, dist=()):
+    """A Camera (les_hip_camera) of a 3 x 3 pinhole matrix with zero skew and up to 8 distortion coefficients (k1, k2, p1, p2, k3, k4, k5, k6),
+    shorter inputs padded with zeros.  A Camera passes through."""
+    if isinstance(K, Camera):
+        return K
+    K = np.asarray(K, np.float64)
+    d = np.asarray(dist if dist is not None else (), np.float64).reshape(-1)
+    if K.shape != (3, 3) or K[0, 1] != 0.0:
+        raise ValueError("camera: K is a 3 x 3 pinhole matrix with zero skew")
+    if d.size > 8:
+        raise ValueError(f"camera: {d.size} distortion coefficients, at most 8 (k1, k2, p1, p2, k3, k4, k5, k6)")
+    return Camera(K[0, 0], K[1, 1], K[0, 2], K[1, 2], (C.c_double * 8)(*np.concatenate([d, np.zeros(8 - d.size)])))
+
+
+def rectify_map(raw, M, f, cx, cy, map_dev_ptr, H, W, device=0, stream=0, lib=None):
+    """les_hip_rectify_map: the device H x W x 2 float map of the raw positions (u, v) of the rectified pixels of one view.  raw: a Camera (or
+    what camera() takes as K); M: 3 x 3, a ray of the rectified frame into the raw camera's frame (the transpose of the view's rectifying
+    rotation); f, cx, cy: the rectified view's intrinsics.  fp64 in the fixed order of csrc/les_rectify.h, (NaN, NaN) where there is no raw
+    position.  Enqueue only."""
+    L = load(lib)
+    cam = camera(raw)
+    m = (C.c_double * 9)(*np.asarray(M, np.float64).reshape(9))
+    _chk_lib(L, L.les_hip_rectify_map(C.byref(cam), m, float(f), float(cx), float(cy), _vp(map_dev_ptr), H, W, device, C.c_void_p(int(stream))))
+
+
+def remap(src_dev_ptr, Hs, Ws, channels, map_dev_ptr, dst_dev_ptr, valid_dev_ptr, H, W, interp=1, device=0, stream=0, lib=None):
+    """les_hip_remap: the device Hs x Ws x channels u8 image sampled at the device H x W x 2 float map into the device H x W x channels one;
+    interp 0 nearest, 1 linear, 2 cubic (or their INTERP_NAMES); valid_dev_ptr (H x W bytes, 1 / 0) may be None.  A pixel whose map entry is
+    not finite or lies outside the source is 0 and invalid (csrc/les_rectify.h).  Enqueue only."""
+    L = load(lib)
+    _chk_lib(L, L.les_hip_remap(_vp(src_dev_ptr), Hs, Ws, channels, _vp(map_dev_ptr), _vp(dst_dev_ptr), _vp(valid_dev_ptr), H, W,
+                                INTERP_NAMES.get(interp, interp), device, C.c_void_p(int(stream))))
 
 
 FIT_MAX_RADIUS = 15            # kFitMaxR of csrc/les_planefit.h (the one source; tests/planefit_cases.py: case_independence_and_errors holds this copy to it)

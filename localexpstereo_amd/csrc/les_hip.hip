@@ -28,6 +28,7 @@
 #include "les_speckle.h"
 #include "les_reproject.h"
 #include "les_view.h"
+#include "les_rectify.h"
 
 #include "../host/ResidualCut.h"      // the host cores' finisher of the tiled max-flow (plain C++: search trees / push-relabel on a residual graph)
 
@@ -327,3 +328,4 @@ float naive_alpha(const les_hip_ctx* c) { return c->naive_alpha; }
 #include "les_hip_pyramid.inc"
 #include "les_hip_reproject.inc"
 #include "les_hip_view.inc"
+#include "les_hip_rectify.inc"

@@ -217,6 +217,74 @@ def calib3d(calib):
 
 
 # ------------------------------------------------------------------------------------------------
+# rectification of a calibrated raw pair (the transform; the maps and the sampling run on the device: csrc/les_rectify.h)
+# ------------------------------------------------------------------------------------------------
+def _rotation(w):
+    """The rotation matrix of the rotation vector w (Rodrigues), fp64."""
+    w = np.asarray(w, np.float64).reshape(3)
+    th = float(np.sqrt(w @ w))
+    K = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+    if th < 1e-8:                                           # (sin th / th and (1 - cos th) / th^2 by their series: exact to fp64 below this angle)
+        return np.eye(3) + K + 0.5 * (K @ K)
+    return np.eye(3) + (np.sin(th) / th) * K + ((1.0 - np.cos(th)) / (th * th)) * (K @ K)
+
+
+def _rotation_vector(R):
+    """The rotation vector of a rotation matrix by an angle below pi, fp64."""
+    a = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    s = float(np.sqrt(a @ a))                               # 2 sin th
+    th = float(np.arctan2(0.5 * s, 0.5 * (np.trace(R) - 1.0)))
+    return a * 0.5 if s < 1e-8 else a * (th / s)
+
+
+def stereo_rectify(K0, dist0, K1, dist1, R, T, f=None, principal=None):
+    """The rectifying transform of a calibrated raw stereo pair (Bouguet's construction), numpy fp64.
+    K0, K1: the 3 x 3 pinhole matrices of the raw cameras, zero skew.  dist0, dist1: up to 8 coefficients (k1, k2, p1, p2, k3, k4, k5, k6),
+    shorter inputs padded with zeros (the camera model: csrc/les_rectify.h; pixel centres at integer coordinates).  R, T: the rig in the
+    stereo-calibration convention X1 = R X0 + T, with X0 and X1 one point in the left and in the right raw camera frame.
+    Half of R goes to each camera by the rotation vector +-w/2, which makes the two frames parallel; then both take the smallest rotation that
+    brings the baseline onto the x axis with the left camera on the left.  -> dict(R0, R1: the rectifying rotations, raw camera frame ->
+    rectified frame, so that R1 X1 = R0 X0 - (baseline, 0, 0); f, cx0, cx1, cy: the new intrinsics, f and cy common to both views -- f defaults
+    to (fy0 + fy1) / 2, cy to (cy0 + cy1) / 2, cx0 = K0[0, 2], cx1 = K1[0, 2], principal=(cx0, cx1, cy) overrides the three; baseline = |T|;
+    doffs = cx1 - cx0; calib: the api.Calib of the rectified pair (calib3d), with which d + doffs = f baseline / Z as reconstruct assumes;
+    K0, K1, dist0, dist1: the inputs as fp64 arrays, dist padded to 8).
+    ValueError: a skewed K, more than 8 coefficients, and a rig whose right camera is not to the right of the left one: a baseline nearer
+    the y axis than the x axis (a vertical rig), or a right camera on the left."""
+    K0, K1, R = (np.array(a, np.float64) for a in (K0, K1, R))
+    T = np.array(T, np.float64).reshape(-1)
+    if K0.shape != (3, 3) or K1.shape != (3, 3) or R.shape != (3, 3) or T.shape != (3,):
+        raise ValueError("stereo_rectify: K0, K1 and R are 3 x 3 matrices, T has 3 entries")
+    dist = []
+    for K, d in ((K0, dist0), (K1, dist1)):
+        if K[0, 1] != 0.0:
+            raise ValueError(f"stereo_rectify: a pinhole matrix with skew {K[0, 1]!r}: only zero skew is supported")
+        d = np.array(() if d is None else d, np.float64).reshape(-1)
+        if d.size > 8:
+            raise ValueError(f"stereo_rectify: {d.size} distortion coefficients, at most 8 (k1, k2, p1, p2, k3, k4, k5, k6)")
+        dist.append(np.concatenate([d, np.zeros(8 - d.size)]))
+    baseline = float(np.sqrt(T @ T))
+    if not baseline > 0.0:
+        raise ValueError("stereo_rectify: T is zero: the two cameras share a centre")
+    half = _rotation(0.5 * _rotation_vector(R))             # half half = R: X0' = half X0 and X1' = half^T X1 are parallel frames
+    t = half.T @ T                                          # X1' = X0' + t
+    if abs(t[1]) > abs(t[0]):
+        raise ValueError(f"stereo_rectify: the baseline {t.tolist()} is nearer the y axis than the x axis (a vertical rig)")
+    if not t[0] < 0.0:
+        raise ValueError(f"stereo_rectify: the baseline {t.tolist()} puts camera 1 to the left of camera 0: pass the cameras in the other order")
+    e = np.array([-1.0, 0.0, 0.0])                           # where t / |t| goes: the right camera sits at +baseline on the left one's x axis
+    w = np.cross(t, e)
+    s = float(np.sqrt(w @ w))
+    level = _rotation(w * (np.arctan2(s, float(t @ e)) / s)) if s > 0.0 else np.eye(3)
+    R0, R1 = level @ half, level @ half.T
+    fnew = 0.5 * (K0[1, 1] + K1[1, 1]) if f is None else float(f)
+    cx0, cx1, cy = (K0[0, 2], K1[0, 2], 0.5 * (K0[1, 2] + K1[1, 2])) if principal is None else (float(p) for p in principal)
+    out = dict(R0=R0, R1=R1, f=float(fnew), cx0=float(cx0), cx1=float(cx1), cy=float(cy), baseline=baseline, doffs=float(cx1 - cx0),
+               K0=K0, K1=K1, dist0=dist[0], dist1=dist[1])
+    out["calib"] = calib3d(dict(f=out["f"], cx=out["cx0"], cy=out["cy"], doffs=out["doffs"], baseline=baseline))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # PLY meshes and point clouds
 # ------------------------------------------------------------------------------------------------
 _PLY_TYPES = {"float": "<f4", "float32": "<f4", "uchar": "u1", "uint8": "u1", "int": "<i4", "int32": "<i4"}

@@ -880,3 +880,65 @@ def MidV3(data, volL=None, volR=None, iterations=5, pmIterations=2, doDual=False
     # (tl, tr: the energy reads the volumes in place; they live until the run has returned)
     return _front_end(e, data, dict(p, lambda_=smooth_weight, windR=filterRadious, th_col=mc_threshold), io.Evaluator(data["dispGT"], data["nonocc"], error_threshold), -1.0,
                       (int(W * 0.01), int(W * 0.03), int(W * 0.09)), iterations, pmIterations, doDual, init, device=device, seed=seed, **kw)
+
+
+class Rectifier:
+    """The front end of a calibrated rig (no reference counterpart; csrc/les_rectify.h): two raw, distorted frames -> the rectified pair every
+    other entry of the package assumes, on the device, and the calibration with which reconstruct gives metric points.
+    K0, dist0, K1, dist1, R, T, f, principal: io.stereo_rectify's (X1 = R X0 + T; dist up to (k1, k2, p1, p2, k3, k4, k5, k6); pixel centres at
+    integer coordinates).  raw_size = (Hs, Ws) of the raw frames; size = (H, W) of the rectified ones (default: raw_size; neither crops nor
+    rescales to the valid region).  interp: "nearest", "linear" or "cubic".  Both maps are built on the device once, here
+    (api.rectify_map); a frame then costs one api.remap launch per image, enqueued on torch's current stream of the device.
+    .transform: io.stereo_rectify's dict; .calib: its api.Calib (doffs = cx1 - cx0, baseline = |T|); .maps: the two H x W x 2 float32 device
+    tensors of raw positions, (NaN, NaN) where a rectified pixel has none."""
+
+    def __init__(self, K0, dist0, K1, dist1, R, T, raw_size, size=None, f=None, principal=None, interp="linear", device="cuda", lib=None):
+        if interp not in api.INTERP_NAMES:
+            raise ValueError(f"unknown interp {interp!r}: one of {sorted(api.INTERP_NAMES)}")
+        self.transform = tr = io.stereo_rectify(K0, dist0, K1, dist1, R, T, f=f, principal=principal)
+        self.calib = tr["calib"]
+        self.raw_size = tuple(int(n) for n in raw_size)
+        self.size = self.raw_size if size is None else tuple(int(n) for n in size)
+        self.interp, self.lib = interp, lib
+        self.device = torch.device(device)
+        self.index = self.device.index or 0 if self.device.type == "cuda" else 0
+        H, W = self.size
+        self.maps = []
+        for m in (0, 1):
+            t = torch.empty((H, W, 2), dtype=torch.float32, device=self.device)
+            api.rectify_map(api.camera(tr[f"K{m}"], tr[f"dist{m}"]), tr[f"R{m}"].T, tr["f"], tr[f"cx{m}"], tr["cy"], t.data_ptr(), H, W, device=self.index,
+                            stream=self._stream(), lib=lib)
+            self.maps.append(t)
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
+
+    def rectify(self, rawL, rawR):
+        """rawL, rawR: the raw frames, Hs x Ws x 3 uint8 BGR, numpy arrays or tensors on the device.  -> dict(imL, imR: H x W x 3 uint8, validL,
+        validR: H x W bool -- False where the rectified pixel has no raw position or one outside the frame; such a pixel is black --, calib);
+        host arrays for host frames, device tensors for device frames."""
+        Hs, Ws = self.raw_size
+        H, W = self.size
+        out, on_device = {}, torch.is_tensor(rawL) and torch.is_tensor(rawR)
+        for name, raw, mp in (("L", rawL, self.maps[0]), ("R", rawR, self.maps[1])):
+            src = raw if torch.is_tensor(raw) else torch.from_numpy(np.array(raw, order="C"))
+            if src.dtype != torch.uint8 or tuple(src.shape) != (Hs, Ws, 3):
+                raise ValueError(f"rectify: a {Hs} x {Ws} x 3 uint8 frame expected, got {tuple(src.shape)} {src.dtype}")
+            src = src.to(self.device).contiguous()
+            dst = torch.empty((H, W, 3), dtype=torch.uint8, device=self.device)
+            valid = torch.empty((H, W), dtype=torch.uint8, device=self.device)
+            api.remap(src.data_ptr(), Hs, Ws, 3, mp.data_ptr(), dst.data_ptr(), valid.data_ptr(), H, W, interp=self.interp, device=self.index,
+                      stream=self._stream(), lib=self.lib)
+            out["im" + name], out["valid" + name] = dst, valid != 0
+        if not on_device:
+            out = {k: v.cpu().numpy() for k, v in out.items()}
+        out["calib"] = self.calib
+        return out
+
+    def data(self, rawL, rawR, ndisp):
+        """The data dict of io.load_data for the rectified pair, so that MidV2(data) / MidV3(data) run on it unchanged: imL, imR (host arrays),
+        ndisp, nonocc = validL, dispGT zeros (no ground truth), gt_prec -1."""
+        r = self.rectify(rawL, rawR)
+        host = lambda a: a.cpu().numpy() if torch.is_tensor(a) else a
+        imL, imR, valid = host(r["imL"]), host(r["imR"]), host(r["validL"])
+        return dict(imL=imL, imR=imR, dispGT=np.zeros(imL.shape[:2], np.float32), nonocc=valid, ndisp=int(ndisp), gt_prec=-1.0)
