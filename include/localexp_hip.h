@@ -716,6 +716,37 @@ int les_hip_rectify_map(const les_hip_camera* raw, const double M[9], double f, 
 int les_hip_remap(const uint8_t* d_src, int Hs, int Ws, int channels /* 1 or 3 */, const float* d_map, uint8_t* d_dst,
                   unsigned char* d_valid /* may be NULL */, int H, int W, int interp /* 0 nearest, 1 linear, 2 cubic */, int device, void* hip_stream);
 
+/* ---- the way back: results of the rectified pair registered to the pixels of the raw camera (csrc/les_unrectify.h holds the definitions; no
+ * reference counterpart) ----
+ * les_hip_unrectify_map: d_map[v][u] = (xs, ys), where in the rectified frame raw pixel (u, v) of one view lies -- the inverse of
+ * les_hip_rectify_map's map, in its layout (Hs x Ws x 2 floats on the device, 8-byte aligned), so that les_hip_remap resamples any rectified-grid
+ * byte image onto the raw grid through it.  R (row-major 3 x 3, host memory) is the view's rectifying rotation, a ray of the raw camera's frame
+ * into the rectified frame (the transpose of les_hip_rectify_map's M); f, cx, cy are the rectified view's intrinsics.  The distortion of the
+ * camera model above is inverted by `steps` (1 .. 64) rounds of the additive fixed point x <- x - (distort(x) - xd), which needs no division
+ * beyond the model's own and converges where the distortion is a contraction; the forward model is then evaluated once more and the pixel is
+ * kept only if its residual is at most `tol` (> 0) RAW pixels in u and in v.  A pixel that has not converged, a denominator of rad that is 0 or
+ * not finite in any evaluation, and a ray with Z <= 0 in the rectified frame give (NaN, NaN): a position that fails the residual test is never
+ * stored.  fp64 in the one order of operations csrc/les_unrectify.h states, not contracted, rounded to f32 once: bit for bit a function of
+ * the arguments.
+ * les_hip_unrectify_labels: the H x W label map of one view (d_labels, 16-byte aligned; d_drop: H x W bytes or NULL, nonzero = dropped) as geometry
+ * on that view's raw grid through its inverse map d_invmap (Hs x Ws x 2).  A raw pixel whose (xs, ys) lies in [0, W - 1] x [0, H - 1] takes the label
+ * of the nearest rectified pixel (floor(xs + 0.5), floor(ys + 0.5)) and evaluates that plane at its own position: d = a xs + b ys + c -- exact
+ * on a surface, nothing mixed across a depth edge.  With D = d + doffs, Zr = f baseline / D: valid iff inside, d finite, D > 0, not dropped
+ * and, when z_max > 0, Zr <= z_max.  d_points: M ((xs - cx) Zr / f, (ys - cy) Zr / f, Zr), the point in the RAW camera's frame (X right, Y down,
+ * Z forward, the baseline's unit; the third component is the raw depth); d_normals: the unit normal of the label's plane in that frame, facing
+ * the camera; d_disparity: d; each Hs x Ws (x 3) floats or NULL.  d_valid: Hs x Ws bytes, 255 / 0.  An invalid pixel holds NaN (0x7fc00000) in
+ * every float output; a pixel outside the frame reads no label.  M (row-major 3 x 3, host memory) = R^T takes the rectified frame into the raw
+ * camera's; f, cx, cy, doffs, baseline: the rectified calibration with cx the VIEW'S OWN principal point.  fp64 in one stated order, rounded once.
+ * Both are context-free and enqueue only on hip_stream of `device`, one work-item per raw pixel.  LES_HIP_ERR_ARG for null pointers (the three
+ * optional outputs and d_drop aside), non-positive sizes, a map that is not 8-byte or labels that are not 16-byte aligned, f, fx, fy or baseline
+ * not finite or <= 0, steps outside 1 .. 64, tol not > 0; LES_HIP_ERR_UNSUPPORTED for Hs > 65535 (the launch grid) and H W >= 2^31; a refused
+ * call launches nothing. */
+int les_hip_unrectify_map(const les_hip_camera* raw, const double R[9], double f, double cx, double cy, int steps, double tol,
+                          float* d_map /* [Hs][Ws][2] */, int Hs, int Ws, int device, void* hip_stream);
+int les_hip_unrectify_labels(const les_hip_plane* d_labels, int H, int W, const unsigned char* d_drop /* may be NULL */, const float* d_invmap, int Hs, int Ws,
+                             const double M[9], double f, double cx, double cy, double doffs, double baseline, float z_max, float* d_points /* may be NULL */,
+                             float* d_normals /* may be NULL */, float* d_disparity /* may be NULL */, unsigned char* d_valid, int device, void* hip_stream);
+
 /* ---- multi-GPU: publishing the tiles a rank updated (not in the reference, which is single-process; SURVEY 8(e): the cells of a
  * disjoint set -- LES/LayerManager.h:168-172 -- are split over the ranks, replicas of the label / cost maps are kept coherent by one
  * all-gather per set of the label (16 B/px) and cost (4 B/px) tiles of the shared regions, LES/FastGCStereo.h:22-72).

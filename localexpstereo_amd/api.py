@@ -38,6 +38,7 @@ SYMBOLS = [
     "les_hip_reproject", "les_hip_mesh", "les_hip_mesh_tile",
     "les_hip_render_view", "les_hip_blend_views", "les_hip_photo_error",
     "les_hip_rectify_map", "les_hip_remap",
+    "les_hip_unrectify_map", "les_hip_unrectify_labels",
 ]
 
 
@@ -223,6 +224,9 @@ def load(path=None):
         "les_hip_photo_error": (ci, [vp, ci, vp, vp, vp]),
         "les_hip_rectify_map": (ci, [C.POINTER(Camera), C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, vp, ci, ci, ci, vp]),
         "les_hip_remap": (ci, [vp, ci, ci, ci, vp, vp, vp, ci, ci, ci, ci, vp]),
+        "les_hip_unrectify_map": (ci, [C.POINTER(Camera), C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, ci, C.c_double, vp, ci, ci, ci, vp]),
+        "les_hip_unrectify_labels": (ci, [vp, ci, ci, vp, vp, ci, ci, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                          C.c_float, vp, vp, vp, vp, ci, vp]),
         "les_hip_mesh": (ci, [vp, ci, vp, vp, C.c_float, vp, vp, vp, vp]),
         "les_hip_mesh_tile": (ci, [C.POINTER(ci), C.POINTER(ci)]),
     }
@@ -390,6 +394,37 @@ def remap(src_dev_ptr, Hs, Ws, channels, map_dev_ptr, dst_dev_ptr, valid_dev_ptr
     L = load(lib)
     _chk_lib(L, L.les_hip_remap(_vp(src_dev_ptr), Hs, Ws, channels, _vp(map_dev_ptr), _vp(dst_dev_ptr), _vp(valid_dev_ptr), H, W,
                                 INTERP_NAMES.get(interp, interp), device, C.c_void_p(int(stream))))
+
+
+UNRECTIFY_STEPS, UNRECTIFY_TOL = 20, 1e-3          # les_hip_unrectify_map's defaults: fixed-point steps, residual bound in raw pixels
+
+
+def unrectify_map(raw, R, f, cx, cy, map_dev_ptr, Hs, Ws, steps=UNRECTIFY_STEPS, tol=UNRECTIFY_TOL, device=0, stream=0, lib=None):
+    """les_hip_unrectify_map: the device Hs x Ws x 2 float map of the rectified positions (xs, ys) of the raw pixels of one view, the inverse of
+    rectify_map's map and in its layout (remap takes it).  raw: a Camera (or what camera() takes as K); R: 3 x 3, the view's rectifying
+    rotation, raw frame -> rectified frame (the transpose of rectify_map's M); f, cx, cy: the rectified view's intrinsics.  The distortion is
+    inverted by `steps` (1 .. 64) additive fixed-point steps and a pixel is kept only where the forward model's residual is at most tol (> 0) raw
+    pixels; fp64 in the fixed order of csrc/les_unrectify.h, (NaN, NaN) where a raw pixel has no rectified position.  Enqueue only."""
+    L = load(lib)
+    cam = camera(raw)
+    r = (C.c_double * 9)(*np.asarray(R, np.float64).reshape(9))
+    _chk_lib(L, L.les_hip_unrectify_map(C.byref(cam), r, float(f), float(cx), float(cy), int(steps), float(tol), _vp(map_dev_ptr), Hs, Ws, device,
+                                        C.c_void_p(int(stream))))
+
+
+def unrectify_labels(labels_dev_ptr, H, W, drop_dev_ptr, invmap_dev_ptr, Hs, Ws, M, f, cx, cy, doffs, baseline, valid_dev_ptr, points_dev_ptr=None,
+                     normals_dev_ptr=None, disparity_dev_ptr=None, z_max=None, device=0, stream=0, lib=None):
+    """les_hip_unrectify_labels: the device H x W x 4 label map of one view as geometry on that view's raw grid, through the view's inverse map
+    (unrectify_map's, Hs x Ws x 2): per raw pixel the plane of the nearest rectified pixel evaluated at the pixel's own rectified position.
+    M: 3 x 3, rectified frame -> raw camera frame (the transpose of the rectifying rotation); f, cx, cy, doffs, baseline: the rectified
+    calibration, cx the view's own principal point.  points / normals (Hs x Ws x 3 floats, the raw camera's frame), disparity (Hs x Ws floats)
+    may be None; valid: Hs x Ws bytes, 255 / 0; drop (H x W bytes, nonzero = dropped) may be None; z_max None or <= 0: no limit.  NaN where
+    invalid (csrc/les_unrectify.h).  Enqueue only."""
+    L = load(lib)
+    m = (C.c_double * 9)(*np.asarray(M, np.float64).reshape(9))
+    _chk_lib(L, L.les_hip_unrectify_labels(_vp(labels_dev_ptr), H, W, _vp(drop_dev_ptr), _vp(invmap_dev_ptr), Hs, Ws, m, float(f), float(cx), float(cy),
+                                           float(doffs), float(baseline), float(z_max) if z_max is not None else 0.0, _vp(points_dev_ptr), _vp(normals_dev_ptr),
+                                           _vp(disparity_dev_ptr), _vp(valid_dev_ptr), device, C.c_void_p(int(stream))))
 
 
 FIT_MAX_RADIUS = 15            # kFitMaxR of csrc/les_planefit.h (the one source; tests/planefit_cases.py: case_independence_and_errors holds this copy to it)

@@ -29,6 +29,7 @@
 #include "les_reproject.h"
 #include "les_view.h"
 #include "les_rectify.h"
+#include "les_unrectify.h"
 
 #include "../host/ResidualCut.h"      // the host cores' finisher of the tiled max-flow (plain C++: search trees / push-relabel on a residual graph)
 
@@ -329,3 +330,4 @@ float naive_alpha(const les_hip_ctx* c) { return c->naive_alpha; }
 #include "les_hip_reproject.inc"
 #include "les_hip_view.inc"
 #include "les_hip_rectify.inc"
+#include "les_hip_unrectify.inc"

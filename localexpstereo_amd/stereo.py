@@ -890,11 +890,17 @@ class Rectifier:
     rescales to the valid region).  interp: "nearest", "linear" or "cubic".  Both maps are built on the device once, here
     (api.rectify_map); a frame then costs one api.remap launch per image, enqueued on torch's current stream of the device.
     .transform: io.stereo_rectify's dict; .calib: its api.Calib (doffs = cx1 - cx0, baseline = |T|); .maps: the two H x W x 2 float32 device
-    tensors of raw positions, (NaN, NaN) where a rectified pixel has none."""
+    tensors of raw positions, (NaN, NaN) where a rectified pixel has none.
+    The way back (csrc/les_unrectify.h): .inverse_maps, the two Hs x Ws x 2 device tensors of rectified positions of the raw pixels, built on
+    first use with `steps` fixed-point steps and a residual bound of `tol` raw pixels (api.unrectify_map); .unrectify puts a label map's
+    geometry and .to_raw a rectified-grid image onto the raw grid; .valid_rect and .crop give a rectified pair without invalid borders."""
 
-    def __init__(self, K0, dist0, K1, dist1, R, T, raw_size, size=None, f=None, principal=None, interp="linear", device="cuda", lib=None):
+    def __init__(self, K0, dist0, K1, dist1, R, T, raw_size, size=None, f=None, principal=None, interp="linear", device="cuda", lib=None,
+                 steps=api.UNRECTIFY_STEPS, tol=api.UNRECTIFY_TOL):
         if interp not in api.INTERP_NAMES:
             raise ValueError(f"unknown interp {interp!r}: one of {sorted(api.INTERP_NAMES)}")
+        self.steps, self.tol = int(steps), float(tol)
+        self._inverse_maps = self._valid_rect = None
         self.transform = tr = io.stereo_rectify(K0, dist0, K1, dist1, R, T, f=f, principal=principal)
         self.calib = tr["calib"]
         self.raw_size = tuple(int(n) for n in raw_size)
@@ -942,3 +948,122 @@ class Rectifier:
         host = lambda a: a.cpu().numpy() if torch.is_tensor(a) else a
         imL, imR, valid = host(r["imL"]), host(r["imR"]), host(r["validL"])
         return dict(imL=imL, imR=imR, dispGT=np.zeros(imL.shape[:2], np.float32), nonocc=valid, ndisp=int(ndisp), gt_prec=-1.0)
+
+    # -- the way back to the raw camera (csrc/les_unrectify.h) ------------------------------------------------------------------------------
+    @property
+    def inverse_maps(self):
+        """The two Hs x Ws x 2 float32 device tensors (xs, ys): where in the rectified frame of this Rectifier every raw pixel of a view lies;
+        (NaN, NaN) where the inversion has not converged or the pixel has no rectified position.  Built on first use."""
+        if self._inverse_maps is None:
+            tr, (Hs, Ws) = self.transform, self.raw_size
+            maps = []
+            for m in (0, 1):
+                t = torch.empty((Hs, Ws, 2), dtype=torch.float32, device=self.device)
+                api.unrectify_map(api.camera(tr[f"K{m}"], tr[f"dist{m}"]), tr[f"R{m}"], tr["f"], tr[f"cx{m}"], tr["cy"], t.data_ptr(), Hs, Ws, steps=self.steps,
+                                  tol=self.tol, device=self.index, stream=self._stream(), lib=self.lib)
+                maps.append(t)
+            self._inverse_maps = maps
+        return self._inverse_maps
+
+    def unrectify(self, labeling, viewMode=0, drop=None, z_max=None):
+        """The H x W x 4 label map of rectified view viewMode as geometry registered to the pixels of that view's RAW image: every raw pixel takes the
+        plane of the nearest rectified pixel and evaluates it at its own sub-pixel rectified position.  drop: an H x W map, nonzero = dropped;
+        z_max: a limit on the rectified depth.  -> dict(points, normals: Hs x Ws x 3 float32 in the raw camera's frame (X right, Y down, Z
+        forward, the baseline's unit); disparity: Hs x Ws float32, the rectified disparity at the raw pixel; depth: points[..., 2]; valid:
+        Hs x Ws bool), NaN where invalid; host arrays for a host labeling, device tensors for a device one."""
+        m, tr, (Hs, Ws), (H, W) = int(viewMode), self.transform, self.raw_size, self.size
+        if m not in (0, 1):
+            raise ValueError(f"unrectify: viewMode {viewMode!r} (0 or 1)")
+        on_device = torch.is_tensor(labeling)
+        lab = labeling if on_device else torch.from_numpy(np.array(labeling, dtype=np.float32, order="C"))
+        if tuple(lab.shape) != (H, W, 4):
+            raise ValueError(f"unrectify: a {H} x {W} x 4 label map expected, got {tuple(lab.shape)}")
+        lab = lab.to(device=self.device, dtype=torch.float32).contiguous()
+        mask = None
+        if drop is not None:
+            mask = drop if torch.is_tensor(drop) else torch.from_numpy(np.array(drop, order="C"))
+            if tuple(mask.shape) != (H, W):
+                raise ValueError(f"unrectify: an {H} x {W} drop map expected, got {tuple(mask.shape)}")
+            mask = (mask.to(self.device) != 0).to(torch.uint8).contiguous()
+        points, normals = (torch.empty((Hs, Ws, 3), dtype=torch.float32, device=self.device) for _ in range(2))
+        disparity = torch.empty((Hs, Ws), dtype=torch.float32, device=self.device)
+        valid = torch.empty((Hs, Ws), dtype=torch.uint8, device=self.device)
+        api.unrectify_labels(lab.data_ptr(), H, W, mask.data_ptr() if mask is not None else None, self.inverse_maps[m].data_ptr(), Hs, Ws, tr[f"R{m}"].T,
+                             tr["f"], tr[f"cx{m}"], tr["cy"], tr["doffs"], tr["baseline"], valid.data_ptr(), points.data_ptr(), normals.data_ptr(),
+                             disparity.data_ptr(), z_max=z_max, device=self.index, stream=self._stream(), lib=self.lib)
+        out = dict(points=points, normals=normals, disparity=disparity, depth=points[..., 2], valid=valid != 0)
+        return out if on_device else {k: v.cpu().numpy() for k, v in out.items()}
+
+    def to_raw(self, image, viewMode=0, interp="nearest"):
+        """A rectified-grid H x W or H x W x 3 uint8 image of view viewMode (a mask, a rendered view, the rectified image itself) resampled onto
+        that view's raw grid through the inverse map (api.remap).  -> (image_raw Hs x Ws[ x 3] uint8, valid Hs x Ws bool); a raw pixel without
+        a rectified position inside the frame is 0 and invalid.  Host arrays for a host image, device tensors for a device one."""
+        m, (Hs, Ws), (H, W) = int(viewMode), self.raw_size, self.size
+        if m not in (0, 1) or interp not in api.INTERP_NAMES:
+            raise ValueError(f"to_raw: viewMode {viewMode!r} (0 or 1), interp {interp!r} (one of {sorted(api.INTERP_NAMES)})")
+        on_device = torch.is_tensor(image)
+        src = image if on_device else torch.from_numpy(np.array(image, order="C"))
+        if src.dtype != torch.uint8 or tuple(src.shape) not in ((H, W), (H, W, 3)):
+            raise ValueError(f"to_raw: an {H} x {W}[ x 3] uint8 image expected, got {tuple(src.shape)} {src.dtype}")
+        src = src.to(self.device).contiguous()
+        dst = torch.empty((Hs, Ws) + tuple(src.shape[2:]), dtype=torch.uint8, device=self.device)
+        valid = torch.empty((Hs, Ws), dtype=torch.uint8, device=self.device)
+        api.remap(src.data_ptr(), H, W, 3 if src.dim() == 3 else 1, self.inverse_maps[m].data_ptr(), dst.data_ptr(), valid.data_ptr(), Hs, Ws, interp=interp,
+                  device=self.index, stream=self._stream(), lib=self.lib)
+        valid = valid != 0
+        return (dst, valid) if on_device else (dst.cpu().numpy(), valid.cpu().numpy())
+
+    def valid_rect(self):
+        """(y0, x0, h, w): the largest axis-aligned rectangle of the rectified frame whose pixels are valid in BOTH views, by the sampler's rule on
+        .maps (0 <= u <= Ws - 1 and 0 <= v <= Hs - 1).  Ties: the largest area, then the smallest y0, then the smallest x0, then the larger h.
+        (0, 0, 0, 0) when no pixel is.  Host numpy, computed once."""
+        if self._valid_rect is None:
+            Hs, Ws = self.raw_size
+            both = np.ones(self.size, bool)
+            for mp in self.maps:
+                uv = mp.cpu().numpy().astype(np.float64)
+                with np.errstate(invalid="ignore"):
+                    both &= (uv[..., 0] >= 0.0) & (uv[..., 0] <= Ws - 1.0) & (uv[..., 1] >= 0.0) & (uv[..., 1] <= Hs - 1.0)
+            self._valid_rect = largest_rect(both)
+        return self._valid_rect
+
+    def crop(self, rect=None):
+        """A Rectifier on the same calibration whose rectified frame is the rectangle rect = (y0, x0, h, w) of this one's (None: valid_rect()).
+        Its maps are the slices of this one's, so its rectify returns exactly the crop of this one's output; size, transform (cx0, cx1, cy) and
+        calib (cx, cy) are shifted by (x0, y0), doffs, f and baseline are unchanged; its inverse maps are built from the shifted intrinsics."""
+        import copy
+        y0, x0, h, w = (int(v) for v in (self.valid_rect() if rect is None else rect))
+        H, W = self.size
+        if not (0 <= y0 and 0 <= x0 and h > 0 and w > 0 and y0 + h <= H and x0 + w <= W):
+            raise ValueError(f"crop: the rectangle (y0, x0, h, w) = {(y0, x0, h, w)} is empty or leaves the {H} x {W} frame")
+        c = copy.copy(self)
+        c.size = (h, w)
+        c.maps = [mp[y0:y0 + h, x0:x0 + w].contiguous() for mp in self.maps]
+        c.transform = tr = dict(self.transform)
+        tr["cx0"], tr["cx1"], tr["cy"] = tr["cx0"] - x0, tr["cx1"] - x0, tr["cy"] - y0
+        c.calib = tr["calib"] = io.calib3d(dict(f=tr["f"], cx=tr["cx0"], cy=tr["cy"], doffs=tr["doffs"], baseline=tr["baseline"]))
+        c._inverse_maps = c._valid_rect = None
+        return c
+
+
+def largest_rect(mask):
+    """(y0, x0, h, w) of the largest all-True axis-aligned rectangle of a 2D bool array; ties: the largest area, then the smallest y0, then the
+    smallest x0, then the larger h; (0, 0, 0, 0) when nothing is True.  Every rectangle of the largest area cannot grow, so it is, for the row
+    it ends on, the widest run of columns at least as tall as itself: the histogram scan below meets each such run once per row."""
+    mask = np.asarray(mask, bool)
+    H, W = mask.shape
+    best_key, best = None, (0, 0, 0, 0)
+    height = np.zeros(W + 1, np.int64)                       # (a sentinel column of height 0 closes every run)
+    for y in range(H):
+        height[:W] = np.where(mask[y], height[:W] + 1, 0)
+        hs, stack = height.tolist(), []                      # stack: (first column of the run, height), heights increasing
+        for x, hx in enumerate(hs):
+            start = x
+            while stack and stack[-1][1] >= hx:
+                start, h = stack.pop()
+                if h > 0:
+                    key = (-h * (x - start), y - h + 1, start, -h)
+                    if best_key is None or key < best_key:
+                        best_key, best = key, (y - h + 1, start, h, x - start)
+            stack.append((start, hx))
+    return best
