@@ -237,6 +237,17 @@ int les_hip_wta_update(les_hip_ctx* ctx, int n, const les_hip_rect* rects, const
  * mode 0 = left view, 1 = right view.  Asynchronous on hip_stream (NULL = default stream) of `device`. */
 int les_hip_fill_out_of_view(float* vol_dev, int D, int H, int W, int mode, int device, void* hip_stream);
 int les_hip_convert_volume_l2r(const float* src_dev, float* dst_dev, int D, int H, int W, int device, void* hip_stream);
+/* valid masks in a volume: fillOutOfView with "outside the image" widened to "outside the valid image" (csrc/les_maskvol.h holds the rule and
+ * the kernel; no reference counterpart beyond that).  d_vol: DEVICE float [D][H][W], slice k is disparity d = k + d0; mode 0 = left view's
+ * volume (I = L, J = R), 1 = right view's (I = R, J = L); d_validI, d_validJ: H x W bytes in DEVICE memory, nonzero = valid, NULL = all valid.
+ * An entry is ok iff the reference sees it (mode 0: x >= min(d, W - 1); mode 1: x < max(W - d, 1)), validI[y][x], and validJ[y][c] at its
+ * partner column c = clamp(x -+ d, 0, W - 1).  An ok entry is never written; every other entry takes the 32 bits of the nearest ok entry of
+ * its own row and slice (a tie goes right in mode 0, left in mode 1), and a row of a slice without one is set to `fill`.  In place and
+ * idempotent.  With both masks NULL and d0 = 0 it writes exactly the bytes of les_hip_fill_out_of_view.  Enqueue only, on hip_stream.
+ * LES_HIP_ERR_ARG: a null volume, a mode outside 0 / 1, a size <= 0, a fill that is not finite.  LES_HIP_ERR_UNSUPPORTED: W > 32768,
+ * H > 65535, D > 65535 * 32, D H W >= 2^32.  A refused call launches nothing. */
+int les_hip_fill_invalid(float* d_vol, int D, int H, int W, int mode, int d0, const uint8_t* d_validI, const uint8_t* d_validJ, float fill, int device,
+                         void* hip_stream);
 
 /* ---- matching-cost volumes from the stereo pair (csrc/les_costvol.h holds the definition) ----
  * replaces: the external MC-CNN step whose output the reference loads as im0.acrt / im1.acrt (LES/main.cpp:353-357): the classic AD-Census

@@ -39,6 +39,7 @@ SYMBOLS = [
     "les_hip_render_view", "les_hip_blend_views", "les_hip_photo_error",
     "les_hip_rectify_map", "les_hip_remap",
     "les_hip_unrectify_map", "les_hip_unrectify_labels",
+    "les_hip_fill_invalid",
 ]
 
 
@@ -224,6 +225,7 @@ def load(path=None):
         "les_hip_photo_error": (ci, [vp, ci, vp, vp, vp]),
         "les_hip_rectify_map": (ci, [C.POINTER(Camera), C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, vp, ci, ci, ci, vp]),
         "les_hip_remap": (ci, [vp, ci, ci, ci, vp, vp, vp, ci, ci, ci, ci, vp]),
+        "les_hip_fill_invalid": (ci, [vp, ci, ci, ci, ci, ci, vp, vp, C.c_float, ci, vp]),
         "les_hip_unrectify_map": (ci, [C.POINTER(Camera), C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, ci, C.c_double, vp, ci, ci, ci, vp]),
         "les_hip_unrectify_labels": (ci, [vp, ci, ci, vp, vp, ci, ci, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                           C.c_float, vp, vp, vp, vp, ci, vp]),
@@ -292,6 +294,20 @@ def convert_volume_l2r(src_dev_ptr, dst_dev_ptr, D, H, W, device=0, stream=0, li
 def _chk_lib(L, rc):
     if rc:
         raise LesHipError(f"liblocalexp_hip error {rc}: {L.les_hip_last_error().decode()}")
+
+
+FILL_INVALID_CHUNK, FILL_INVALID_MAX_W = 32, 32768     # les_hip_fill_invalid: slices per workgroup, widest row (kMvDC, kMvMaxW of csrc/les_maskvol.h)
+
+
+def fill_invalid(vol_dev_ptr, D, H, W, mode, validI=None, validJ=None, d0=0, fill=0.5, device=0, stream=0, lib=None):
+    """les_hip_fill_invalid: fill_out_of_view with "outside the image" widened to "outside the valid image", in place on a device volume
+    [D][H][W] (slice k is disparity k + d0; mode 0: the left view's volume, I = L, J = R; mode 1: the right view's).  validI / validJ: device
+    addresses of H x W byte masks of the volume's own view and of its partner view, nonzero = valid, None = all valid.  An entry that the
+    reference sees, whose own pixel is valid and whose partner pixel is valid is never written; every other entry takes the bits of the nearest
+    such entry of its row and slice (a tie goes right in mode 0, left in mode 1); a row of a slice without one is set to `fill` (finite).  With
+    both masks None and d0 = 0: fill_out_of_view's bytes (csrc/les_maskvol.h).  Enqueue only."""
+    L = load(lib)
+    _chk_lib(L, L.les_hip_fill_invalid(_vp(vol_dev_ptr), D, H, W, mode, int(d0), _vp(validI), _vp(validJ), float(fill), device, C.c_void_p(int(stream))))
 
 
 def costvol_tables(lambda_ad=10.0, lambda_census=30.0, lib=None):

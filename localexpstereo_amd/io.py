@@ -74,10 +74,45 @@ def save_cost_volume(path, vol):
     np.ascontiguousarray(vol, "<f4").tofile(path)
 
 
-def ingest_volumes(volL, volR=None, device="cuda", lib=None):
+def _valid_masks(valid, H, W, dev):
+    """build_volumes' / ingest_volumes' `valid`: a pair (validL, validR) of H x W bool or uint8 host arrays or device tensors, nonzero = valid
+    -> the two as contiguous uint8 tensors on dev (None -> None)."""
+    import torch
+    if valid is None:
+        return None
+    try:
+        pair = tuple(valid)
+    except TypeError:
+        pair = ()
+    if len(pair) != 2:
+        raise ValueError("valid: a pair (validL, validR) of H x W masks expected")
+    out = []
+    for v in pair:
+        t = v if torch.is_tensor(v) else torch.from_numpy(np.array(v, order="C"))
+        if tuple(t.shape) != (H, W) or t.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"valid: {H} x {W} bool or uint8 masks expected, got {tuple(t.shape)} {t.dtype}")
+        out.append((t.to(dev) != 0).to(torch.uint8).contiguous())
+    return out
+
+
+def _fill(t, mode, masks, d0, mask_fill, **where):
+    """The fill that follows a built or loaded volume of view `mode`: fillOutOfView, or with masks (_valid_masks') its widening to the valid image
+    (api.fill_invalid with that view's own mask and its partner's; csrc/les_maskvol.h)."""
+    D, H, W = t.shape
+    if masks is None:
+        api.fill_out_of_view(t.data_ptr(), D, H, W, mode, **where)
+    else:
+        api.fill_invalid(t.data_ptr(), D, H, W, mode, validI=masks[mode].data_ptr(), validJ=masks[1 - mode].data_ptr(), d0=d0, fill=mask_fill, **where)
+
+
+def ingest_volumes(volL, volR=None, device="cuda", lib=None, valid=None, mask_fill=0.5):
     """The MiddV3 volume preparation of LES/main.cpp:353-368 on the device.  volL / volR: host arrays (or memmaps) of
     shape [D][H][W]; volR None => synthesised from the left volume (convertVolumeL2R) before the fills, exactly in
-    the reference's order.  Returns two torch device tensors."""
+    the reference's order.  Returns two torch device tensors.
+    valid (opt-in, no reference counterpart): a pair (validL, validR) of H x W bool or uint8 masks, host arrays or device tensors -- each
+    fillOutOfView becomes its widening to the valid image (api.fill_invalid: an entry matched from or against an invalid pixel takes the
+    nearest valid entry of its row and slice; a row of a slice without one is set to mask_fill); the order of the steps is unchanged, and
+    convertVolumeL2R reads the filled left volume.  None: today's code path and bytes."""
     import torch
     dev = torch.device(device)
     idx = dev.index or 0 if dev.type == "cuda" else 0
@@ -93,14 +128,15 @@ def ingest_volumes(volL, volR=None, device="cuda", lib=None):
     tl = upload(volL)
     D, H, W = tl.shape
     stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
-    api.fill_out_of_view(tl.data_ptr(), D, H, W, 0, device=idx, stream=stream, lib=lib)           # LES/main.cpp:358
+    masks = _valid_masks(valid, H, W, dev)
+    _fill(tl, 0, masks, 0, mask_fill, device=idx, stream=stream, lib=lib)                         # LES/main.cpp:358
     if volR is not None:
         tr = upload(volR)
         assert tuple(tr.shape) == (D, H, W)
     else:
         tr = torch.empty_like(tl)
         api.convert_volume_l2r(tl.data_ptr(), tr.data_ptr(), D, H, W, device=idx, stream=stream, lib=lib)   # LES/main.cpp:363
-    api.fill_out_of_view(tr.data_ptr(), D, H, W, 1, device=idx, stream=stream, lib=lib)           # LES/main.cpp:365
+    _fill(tr, 1, masks, 0, mask_fill, device=idx, stream=stream, lib=lib)                         # LES/main.cpp:365
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     return tl, tr
@@ -110,7 +146,7 @@ COSTS = ("adcensus", "zncc")
 
 
 def build_volumes(imL, imR, ndisp, device="cuda", lib=None, lambda_ad=10.0, lambda_census=30.0, d0=0, cost="adcensus", patch=(2, 2), features=None,
-                  alpha=0.5, beta=0.5):
+                  alpha=0.5, beta=0.5, valid=None, mask_fill=0.5):
     """Both views' matching-cost volumes made on the device from the stereo pair alone, in the place of the MC-CNN volumes the reference
     loads (LES/main.cpp:353-357).  imL / imR: H x W x 3 u8 (BGR) host arrays.  Each view is built directly (mode 0 / mode 1; slice k is
     disparity k + d0), then filled like a loaded volume (fillOutOfView, :358 / :365).  Returns two torch device tensors [ndisp][H][W], as
@@ -121,7 +157,9 @@ def build_volumes(imL, imR, ndisp, device="cuda", lib=None, lambda_ad=10.0, lamb
     features: a pair (fL, fR) of float32 [C][H][W] tensors on `device`, or a callable that maps an H x W x 3 u8 image to such a tensor
     (called once per view, left first): the volumes are beta - alpha <fI(x), fJ(xp)>, and `cost` is ignored.  The pair or the callable's
     outputs are used AS GIVEN: normalising them is the caller's business (torch.nn.functional.normalize(f, dim=0) makes the costs lie in
-    [0, 1] at alpha = beta = 0.5, the range of AD-Census and of mc_threshold = 0.5; alpha = 1, beta = 0 is MC-CNN-fast's raw -dot)."""
+    [0, 1] at alpha = beta = 0.5, the range of AD-Census and of mc_threshold = 0.5; alpha = 1, beta = 0 is MC-CNN-fast's raw -dot).
+    valid, mask_fill: as for ingest_volumes -- with a pair of masks each view's fill is api.fill_invalid with that view's mask and its
+    partner's (csrc/les_maskvol.h); None: today's code path and bytes."""
     import torch
     dev = torch.device(device)
     idx = dev.index or 0 if dev.type == "cuda" else 0
@@ -133,6 +171,7 @@ def build_volumes(imL, imR, ndisp, device="cuda", lib=None, lambda_ad=10.0, lamb
     H, W = imL.shape[:2]
     D = int(ndisp)
     stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
+    masks = _valid_masks(valid, H, W, dev)
     out = []
     if features is not None or cost == "zncc":
         if features is None:
@@ -161,7 +200,7 @@ def build_volumes(imL, imR, ndisp, device="cuda", lib=None, lambda_ad=10.0, lamb
             t = torch.empty((D, H, W), dtype=torch.float32, device=dev)
             api.build_feature_volume(feats[0].data_ptr(), feats[1].data_ptr(), t.data_ptr(), Cn, D, H, W, mode, d0=int(d0), alpha=alpha, beta=beta,
                                      device=idx, stream=stream, lib=lib)
-            api.fill_out_of_view(t.data_ptr(), D, H, W, mode, device=idx, stream=stream, lib=lib)
+            _fill(t, mode, masks, int(d0), mask_fill, device=idx, stream=stream, lib=lib)
             out.append(t)
         if dev.type == "cuda":
             torch.cuda.synchronize(dev)          # (the descriptors and the images live until here)
@@ -171,7 +210,7 @@ def build_volumes(imL, imR, ndisp, device="cuda", lib=None, lambda_ad=10.0, lamb
         t = torch.empty((D, H, W), dtype=torch.float32, device=dev)
         api.build_cost_volume(tiL.data_ptr(), tiR.data_ptr(), t.data_ptr(), D, H, W, mode, d0=int(d0), lambda_ad=lambda_ad, lambda_census=lambda_census,
                               device=idx, stream=stream, lib=lib)
-        api.fill_out_of_view(t.data_ptr(), D, H, W, mode, device=idx, stream=stream, lib=lib)
+        _fill(t, mode, masks, int(d0), mask_fill, device=idx, stream=stream, lib=lib)
         out.append(t)
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)

@@ -26,8 +26,22 @@ PARAMS_BF = dict(PARAMS_GF, lambda_=20.0, windR=20, eps=10.0, filter="BF")
 class FastGCStereo:
     def __init__(self, energy, imL, imR, params, device="cuda", rank=0, world=1, seed=1, host_threads=0, device_cuts=None, random_vdisp=None,
                  evaluate_on_device=False, inner_loop_log=False, check_flow_energy=False, recost_after_post=False, cross_view=0, coarse_params=None,
-                 speckle=None, confidence=False, min_confidence=None, confidence_band=1.0, max_photo_error=None):
+                 speckle=None, confidence=False, min_confidence=None, confidence_band=1.0, max_photo_error=None, valid=None):
         self.e, self.imL, self.imR, self.p = energy, imL, imR, dict(PARAMS_GF, **params)
+        # Opt-in, no reference counterpart: valid={view: H x W mask, nonzero = valid} (a rectification's validL / validR, the caller's own masks)
+        # adds each view's own invalid pixels to its failure mask of the post-processing, so that they are filled like a failed left-right
+        # check.  It composes with speckle, min_confidence and max_photo_error, and like them gives a one-view call a post-processing (with that
+        # mask alone); raw_labelings stay raw.  The volumes are another matter (io.build_volumes(valid=), csrc/les_maskvol.h).  Single rank.
+        # None (the default) changes nothing.
+        self.valid = None
+        if valid is not None:
+            H, W = (int(n) for n in np.asarray(imL).shape[:2])
+            self.valid = {}
+            for m, v in dict(valid).items():
+                v = v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+                if int(m) not in (0, 1) or v.shape != (H, W):
+                    raise ValueError(f"valid: {{view 0 / 1: an {H} x {W} mask}} expected, got view {m!r} with shape {v.shape}")
+                self.valid[int(m)] = np.ascontiguousarray(v != 0)
         # Opt-in, no reference counterpart (csrc/les_confidence.h): confidence=True -- run(), wta() and sgm() set self.confidences = {view: H x W
         # float32 in [0, 1]}, the confidence of each view's RAW labelling (before the post-processing) under that view's aggregated cost volume
         # (les_hip_confidence: how much cheaper the cost is within confidence_band slabs of the pixel's own disparity than anywhere else on its cost
@@ -476,18 +490,21 @@ class FastGCStereo:
         return lab, self.raw_labelings.get(0)
 
     def _post_processes(self, views):
-        """Whether a call over `views` ends with the post-processing: two views always, one view when a speckle filter, min_confidence or
-        max_photo_error is set."""
-        return len(views) == 2 or self.speckle is not None or self.min_confidence is not None or self.max_photo_error is not None
+        """Whether a call over `views` ends with the post-processing: two views always, one view when a speckle filter, min_confidence,
+        max_photo_error or valid masks are set."""
+        return len(views) == 2 or self.speckle is not None or self.min_confidence is not None or self.max_photo_error is not None or self.valid is not None
 
     def _post_process(self, maps, conf=None):
         """The post-processing step of run(), wta() and sgm() in place on the device label maps {view: map}: threshold 1.5, the run's omega
         (LES/FastGCStereo.h:202), (left, right) whatever the order of the views; with self.speckle the widened mask, and the one-view form; with
         self.min_confidence each view's mask widened by conf[view] < min_confidence (conf: what _confidences returned for the same maps); with
-        self.max_photo_error by vis == 1 and err > max_photo_error of the view's map as it comes in (les_hip_photo_error)."""
+        self.max_photo_error by vis == 1 and err > max_photo_error of the view's map as it comes in (les_hip_photo_error); with self.valid by
+        the view's own invalid pixels."""
         ptr = {m: maps[m].data_ptr() if m in maps else None for m in (0, 1)}
-        if self.min_confidence is not None or self.max_photo_error is not None:
+        if self.min_confidence is not None or self.max_photo_error is not None or self.valid is not None:
             low = {m: torch.zeros(maps[m].shape[:2], dtype=torch.bool, device=maps[m].device) for m in maps}
+            if self.valid is not None:
+                low = {m: low[m] | ~torch.from_numpy(self.valid[m]).to(maps[m].device) if m in self.valid else low[m] for m in maps}
             if self.min_confidence is not None:
                 low = {m: low[m] | (conf[m] < self.min_confidence) for m in maps}
             if self.max_photo_error is not None:
@@ -520,6 +537,8 @@ class FastGCStereo:
             raise NotImplementedError("confidence / min_confidence are single-rank: the multi-rank form is not implemented")
         if self.max_photo_error is not None and self.world > 1:
             raise NotImplementedError("max_photo_error is single-rank: the multi-rank form is not implemented")
+        if self.valid is not None and self.world > 1:
+            raise NotImplementedError("valid is single-rank: the multi-rank form is not implemented")
         if self.inner_loop_log and self.world > 1:
             raise ValueError("inner_loop_log is a single-rank log: with several ranks a rank holds only its band of a set's cells until the exchange")
         if self.cross_view > 0:
@@ -824,7 +843,7 @@ def _front_end(e, data, params, evaluator, precision, layer_sizes, iterations, p
 
 
 def MidV2(data, iterations=5, pmIterations=2, doDual=False, smooth_weight=None, filterRadious=20, device="cuda", seed=1, lib=None, params=None,
-          vdisp=0.0, random_vdisp=0.0, init=None, **kw):
+          vdisp=0.0, random_vdisp=0.0, init=None, valid=None, **kw):
     """MidV2 (LES/main.cpp:270-328) on a data dict of io.load_data: image-based matching cost, layers 5/15/25, error
     threshold 0.5, disparities quantised to the ground-truth precision before evaluation.  params: PARAMS_GF (the reference's choice,
     default) or PARAMS_BF (or a dict with their keys): filter, eps, alpha, th_col, th_grad; smooth_weight (default: params' lambda_)
@@ -837,9 +856,12 @@ def MidV2(data, iterations=5, pmIterations=2, doDual=False, smooth_weight=None, 
     here: MidV2 uses the image-based energy, which holds no cost volume to run them over.  "half": coarse to fine -- the half-resolution problem
     (both images pooled) is solved first and its planes, upsampled, are the start (FastGCStereo.run's labeling="half"; coarse_params=dict(...)
     among the further keywords sets the nested run's iterations, pmInit and labeling).
+    valid (MidV3's valid masks) raises ValueError here: the masks go into cost volumes, and the image-based energy holds none.
     Further keywords go to FastGCStereo (cross_view=n with doDual: cross-view fusion after every n-th graph-cut iteration)."""
     if isinstance(init, str) and _parse_start(init)[0] == "sgm":
         raise ValueError(f"MidV2(init={init!r}): MidV2 uses the image-based energy, which holds no cost volume; semi-global matching runs over one (MidV3)")
+    if valid is not None and valid is not False:
+        raise ValueError("MidV2(valid=...): MidV2 uses the image-based energy, which holds no cost volume for the masks to go into (MidV3)")
     p = dict(PARAMS_GF if params is None else params)
     lam = p["lambda_"] if smooth_weight is None else smooth_weight
     maxdisp = float(data["ndisp"] - 1)
@@ -852,7 +874,7 @@ def MidV2(data, iterations=5, pmIterations=2, doDual=False, smooth_weight=None, 
 
 def MidV3(data, volL=None, volR=None, iterations=5, pmIterations=2, doDual=False, smooth_weight=0.5, mc_threshold=0.5, filterRadious=20,
           error_threshold=1.0, device="cuda", seed=1, lib=None, params=None, interpolate=1, lambda_ad=10.0, lambda_census=30.0, init=None,
-          cost="adcensus", patch=(2, 2), features=None, **kw):
+          cost="adcensus", patch=(2, 2), features=None, valid=None, **kw):
     """MidV3 (LES/main.cpp:330-420): cost-volume energy (volumes ingested on the device), layers 1 % / 3 % / 9 % of the
     image width.  volL / volR: host arrays / memmaps [ndisp][H][W] (volR None: synthesised from the left one).  params: PARAMS_GF
     (default) or PARAMS_BF: filter and eps; smooth_weight, mc_threshold and filterRadious override lambda_, th_col and windR (:351-353).
@@ -861,18 +883,30 @@ def MidV3(data, volL=None, volR=None, iterations=5, pmIterations=2, doDual=False
     data["imL"], data["imR"] and data["ndisp"]; cost="zncc" builds the ZNCC volumes of (2 ry + 1) x (2 rx + 1) grey patches instead, patch = (ry, rx), and
     features= (a pair of float32 [C][H][W] device tensors, or a callable image -> such a tensor) the correlation volumes of those feature maps, used as given
     (io.build_volumes; csrc/les_featvol.h).  cost / patch / features together with explicit volumes: ValueError.  init: as for MidV2 (None: the random start; "wta": the winner-take-all start; "wta+planes": with its fitted planes fused in), and "sgm" / "sgm+planes": every view starts from the semi-global matching map of its own raw volume (FastGCStereo.run's labeling="sgm" / "sgm+planes"; csrc/les_sgm.h); "half": the coarse-to-fine start over the pooled volumes (labeling="half"; csrc/les_pyramid.h).  Further keywords go to FastGCStereo (cross_view=n with doDual: cross-view fusion after every
-    n-th graph-cut iteration)."""
+    n-th graph-cut iteration).
+    valid (opt-in): a pair (validL, validR) of H x W masks, nonzero = valid, or True for data["validL"] / data["validR"] (Rectifier.data(valid=True)):
+    the volumes' fills become the nearest-valid row fill (io.build_volumes / io.ingest_volumes(valid=); csrc/les_maskvol.h), and each view's
+    invalid pixels join its failure mask of the post-processing (FastGCStereo(valid=))."""
     p = dict(PARAMS_GF if params is None else params)
     maxdisp = float(data["ndisp"] - 1)
+    if valid is False:
+        valid = None
+    if valid is True:
+        valid = (data["validL"], data["validR"])
+    if valid is not None:
+        valid = tuple(valid)
+        if len(valid) != 2:
+            raise ValueError("MidV3(valid=...): a pair (validL, validR) of H x W masks, or True for data['validL'] / data['validR']")
+        kw = dict(kw, valid={0: valid[0], 1: valid[1]})
     if volL is None:
         if volR is not None:
             raise ValueError("volR without volL")
         tl, tr = io.build_volumes(data["imL"], data["imR"], data["ndisp"], device=device, lib=lib, lambda_ad=lambda_ad, lambda_census=lambda_census,
-                                  cost=cost, patch=patch, features=features)
+                                  cost=cost, patch=patch, features=features, valid=valid)
     else:
         if cost != "adcensus" or features is not None or tuple(patch) != (2, 2):
             raise ValueError("cost / patch / features build the volumes from the pair: not together with explicit volumes")
-        tl, tr = io.ingest_volumes(volL, volR, device=device, lib=lib)
+        tl, tr = io.ingest_volumes(volL, volR, device=device, lib=lib, valid=valid)
     D, H, W = tl.shape
     e = api.HipCostVolumeEnergy(data["imL"], data["imR"], tl.data_ptr(), tr.data_ptr(), windR=filterRadious, eps=p["eps"],
                                 th_col=mc_threshold, max_disp=maxdisp, device=torch.device(device).index or 0, volumes_on_device=True,
@@ -941,13 +975,17 @@ class Rectifier:
         out["calib"] = self.calib
         return out
 
-    def data(self, rawL, rawR, ndisp):
+    def data(self, rawL, rawR, ndisp, valid=False):
         """The data dict of io.load_data for the rectified pair, so that MidV2(data) / MidV3(data) run on it unchanged: imL, imR (host arrays),
-        ndisp, nonocc = validL, dispGT zeros (no ground truth), gt_prec -1."""
+        ndisp, nonocc = validL, dispGT zeros (no ground truth), gt_prec -1.  valid=True adds validL, validR (H x W bool host arrays), what
+        MidV3(data, valid=True) feeds into its volumes."""
         r = self.rectify(rawL, rawR)
         host = lambda a: a.cpu().numpy() if torch.is_tensor(a) else a
-        imL, imR, valid = host(r["imL"]), host(r["imR"]), host(r["validL"])
-        return dict(imL=imL, imR=imR, dispGT=np.zeros(imL.shape[:2], np.float32), nonocc=valid, ndisp=int(ndisp), gt_prec=-1.0)
+        imL, imR, validL = host(r["imL"]), host(r["imR"]), host(r["validL"])
+        out = dict(imL=imL, imR=imR, dispGT=np.zeros(imL.shape[:2], np.float32), nonocc=validL, ndisp=int(ndisp), gt_prec=-1.0)
+        if valid:
+            out.update(validL=validL, validR=host(r["validR"]))
+        return out
 
     # -- the way back to the raw camera (csrc/les_unrectify.h) ------------------------------------------------------------------------------
     @property
