@@ -372,7 +372,8 @@ int les_hip_batch_solve_graphs_tiled(les_hip_ctx* ctx, const les_hip_batch* batc
  * that has had 60 launches and has at most 40 000 nodes -- and after 220 launches every open cell -- goes to the host cores: its residual graph
  * (8 residual capacities + the excess per node, 36 bytes) is written to host-mapped memory and finished with FIFO push-relabel from the remaining
  * excess nodes (host/ResidualCut.h; one thread per cell).  The residual graph of a feasible preflow has the minimum cuts of the graph it came
- * from, so masks, status and flows mean what they mean without it.  LES_HIP_MAXFLOW_HANDOVER=0 switches it off.
+ * from, so masks, status and flows mean what they mean without it.  LES_HIP_MAXFLOW_HANDOVER=0 switches it off (the other LES_HIP_MAXFLOW_* variables
+ * -- A/B measurements, tooling, tests -- are listed in one table, above MfKnobs / MtKnobs in csrc/les_hip_cuts.inc).
  * The _stats form reports what happened (the plain form = the _stats form without the report).
  * Both device max-flows keep one property that multi-rank runs (N ranks == 1 rank, bit for bit) and repeatable runs rest on: a cell's cut -- mask,
  * status, flow value -- is a function of its graph and the solver parameters (environment knobs included), not of the other cells of the call, their

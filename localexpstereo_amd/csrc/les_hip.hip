@@ -247,12 +247,14 @@ struct les_hip_batch {
     mutable DevBuf<les::MtTile> d_mt_tiles;
     mutable DevBuf<int> d_mt_tiles_per_cell;
     mutable int mt_ntiles = -1;          // -1: not built yet
-    // one-workgroup device max-flow: the cells grouped by the kernel that cuts them (les_hip_cuts.inc), built on first use per value of
-    // LES_HIP_MAXFLOW_CELL_KERNEL (mf_list_key; -1: not built yet)
+    // one-workgroup device max-flow: the plan of a solve (mf_plan, les_hip_cuts.inc) -- per kernel kind the number of cells and the largest of them, and,
+    // when the cells go to more than one kernel, the cells grouped by kind on the device -- built on first use per value of LES_HIP_MAXFLOW_CELL_KERNEL
+    // (mf_list_key; -1: not built yet)
     mutable std::mutex mf_mu;
     mutable DevBuf<int> d_mf_list;
     mutable int mf_list_key = -1;
     mutable int mf_count[3] = {0, 0, 0};
+    mutable long long mf_max[3] = {0, 0, 0};
     // region energy of the cells (les_hip_eval.inc): partial sums, cells * region_chunks doubles per view (two host threads may run the two views of one
     // batch), built on first use (region_chunks -1: not yet)
     mutable std::mutex re_mu;

@@ -3,17 +3,22 @@
 // system-scope atomics, the host reads them after synchronising its stream -- the progress check of a lock-step costs no copy) and the pinned
 // staging of the hand-over (les_maxflow_tiled.h: residual graphs out, masks and flow values back).  A context keeps a pool of them: a call
 // takes one, returns it at the end; they are freed with the context (round 5 kept two words per host THREAD for ever).
+struct MtStage { float* rc8; float* ex; uint8_t* masks; les::MtHandCell* list; double* flows; };       // the staging's five arrays at one of its two addresses
 struct MtHost {
     // (h_*: the pinned owners; d_*: the addresses the device reaches them at)
-    PinnedBuf<int> h_flags; int* d_flags = nullptr;                    // [0] cells finished, [1] of them: gave up, [2] cells handed over, [3] their nodes
+    PinnedBuf<int> h_flags; int* d_flags = nullptr;                    // les::MtFlag
     PinnedBuf<char> h_stage; char* d_stage = nullptr;                  // rc8 [cap_nodes][8] floats | ex [cap_nodes] floats | masks [cap_nodes] bytes | list [cap_cells] | flows [cap_cells]
     long long cap_nodes = 0;
     int cap_cells = 0;
-    size_t off_ex() const { return (size_t)cap_nodes * 32; }
-    size_t off_masks() const { return (size_t)cap_nodes * 36; }
     size_t off_list() const { return ((size_t)cap_nodes * 37 + 255) & ~(size_t)255; }
     size_t off_flows() const { return off_list() + (size_t)cap_cells * sizeof(les::MtHandCell); }
     size_t bytes() const { return off_flows() + (size_t)cap_cells * sizeof(double); }
+    // that layout at `base`: d_stage for the kernels (MtHandArgs), h_stage.p for the host finish
+    MtStage stage_at(char* base) const
+    {
+        return {reinterpret_cast<float*>(base), reinterpret_cast<float*>(base + (size_t)cap_nodes * 32), reinterpret_cast<uint8_t*>(base + (size_t)cap_nodes * 36),
+                reinterpret_cast<les::MtHandCell*>(base + off_list()), reinterpret_cast<double*>(base + off_flows())};
+    }
 };
 namespace {
 void mt_host_free(MtHost* m) { delete m; }                 // (les_hip_destroy sees MtHost only declared)
@@ -29,6 +34,7 @@ int mt_host_acquire(les_hip_ctx* c, MtHost** out)
         if (!c->mt_idle.empty()) { *out = c->mt_idle.back(); c->mt_idle.pop_back(); return LES_HIP_OK; }
     }
     MtHost* m = new MtHost();
+    static_assert(les::kMtFlagCount <= 16, "the flag words fit the allocation");
     int rc = m->h_flags.alloc(16, kMtHostFlags);
     if (!rc) rc = m->h_flags.dev(&m->d_flags);
     if (rc) { delete m; return rc; }
@@ -40,12 +46,16 @@ void mt_host_release(les_hip_ctx* c, MtHost* m)
     std::lock_guard<std::mutex> lk(c->mu);
     c->mt_idle.push_back(m);
 }
+// The staging is made at a solve's first hand-over check for at most kMtStageFirstNodes nodes of kMtStageFirstCells cells (what the product's checks hand
+// over), and grows, rounded up to kMtStageNodeStep / kMtStageCellStep, when a check selects more.
+constexpr long long kMtStageFirstNodes = 140000, kMtStageNodeStep = 4096;
+constexpr int kMtStageFirstCells = 16, kMtStageCellStep = 16;
 // staging for `nodes` graph nodes (37 bytes each) of `cells` cells, grown on demand
 int mt_host_stage(MtHost* m, long long nodes, int cells, hipStream_t stream)
 {
     if (m->cap_nodes >= nodes && m->cap_cells >= cells) return LES_HIP_OK;
-    m->cap_nodes = std::max(m->cap_nodes, (nodes + 4095) & ~4095ll);
-    m->cap_cells = std::max(m->cap_cells, (cells + 15) & ~15);
+    m->cap_nodes = std::max(m->cap_nodes, (nodes + kMtStageNodeStep - 1) & ~(kMtStageNodeStep - 1));
+    m->cap_cells = std::max(m->cap_cells, (cells + kMtStageCellStep - 1) & ~(kMtStageCellStep - 1));
     int rc = m->h_stage.grow(m->bytes(), 0, stream, kMtHostFlags);      // (bytes() has grown: always a new buffer)
     if (!rc) rc = m->h_stage.dev(&m->d_stage);
     if (rc) { m->h_stage.reset(); m->cap_nodes = 0; m->cap_cells = 0; return rc; }
@@ -73,6 +83,25 @@ struct MtHostLease {                       // returns the MtHost to the pool on 
     les_hip_ctx* c; MtHost* m;
     ~MtHostLease() { if (m) mt_host_release(c, m); }
 };
+// The opt-in to more than 64 KB of dynamic LDS is a per-DEVICE function attribute: it is set once per context (a context is bound to one device;
+// `ready` is the context's flag for these kernels), under the context's mutex, with that device current -- a process-wide flag would leave the second
+// GPU of a process that drives two without it.  A failure is reported with its own message (`who`: the entry point) so that callers can cut on the host.
+struct LdsKernel { const void* fn; size_t bytes; };
+int ensure_dynamic_lds(les_hip_ctx* c, bool& ready, std::initializer_list<LdsKernel> kernels, const char* who)
+{
+#if !defined(LES_SIM)
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (ready) return LES_HIP_OK;
+    HIPCHECK(hipSetDevice(c->p.device));
+    for (const LdsKernel& k : kernels) {
+        const hipError_t arc = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.bytes);
+        if (arc != hipSuccess) return fail(LES_HIP_ERR_DEVICE, "%s: device max-flow unavailable on device %d (hipFuncSetAttribute max dynamic LDS: %s); cut on the host", who,
+                                           c->p.device, hipGetErrorString(arc));
+    }
+    ready = true;
+#endif
+    return LES_HIP_OK;
+}
 // the cells of a lock-step as the kernels take them (les_hip_rect has GraphCell's layout: les_hip_batch.inc)
 const les::GraphCell* graph_cells(const les_hip_batch* b) { return reinterpret_cast<const les::GraphCell*>(b->d_targets.p); }
 // The graphs of one lock-step of moves (les_pairwise.h).  map: d_proposal is a label map [H][W] (fusion); otherwise one plane per cell (expansion).
@@ -152,41 +181,112 @@ long long les_hip_batch_max_cell_nodes(const les_hip_batch* b)
     return m;
 }
 
+// The environment variables of the two device max-flows: THE table (include/localexp_hip.h, INTEGRATION.md and DESIGN.md point here).  Each entry point reads
+// its struct once, at its top, on every call (tests change the variables between calls on one context).  Nothing but A/B measurements, tooling and tests sets
+// any of them: the product runs the defaults.
+//   LES_HIP_MAXFLOW_...     default    clamp   set by
+//   one workgroup per cell (MfKnobs):
+//   CELL_KERNEL             1          -       A/B, tests: 0 sends every cell to les_maxflow.h
+//   MAX_ITER                6000       >= 0    tests of the callers' host fall-back (les::kMfMaxIter)
+//   ROUND_ITERS             16         >= 1    A/B (8 ... 64 measured on whole runs: flat within 3 %, tools/lab/ab_cell_kernel.sh)
+//   tiled (MtKnobs):
+//   TILED_K, TILED_S        8, 12      >= 1    A/B: iterations per discharge sweep, sweeps between exact relabellings (measured: K = 8 / 16 / 32 / 64 ->
+//                                              4.5 / 5.2 / 6.8 / 9.7 ms on a hard layer-1 lock-step); they set K2, S2 as well
+//   TILED_K2, TILED_S2      = K, S     >= 1    A/B: the same in the rounds after the first
+//   MAX_ITER                2000       >= 1    tests of the callers' host fall-back: launches after which an open cell gives up (status 1)
+//   HANDOVER                1          -       A/B, tests: 0 = every cell is cut by launches alone (as in round 5)
+//   HANDOVER_AFTER          60         >= 1    A/B, tests: launches before a small open cell goes to the host cores
+//   HANDOVER_NODES, HANDOVER_CELL_NODES
+//                           40000      >= 1    A/B, tests: "small" (two spellings of one knob; the second wins)
+//   HANDOVER_LATE_AFTER     220        >= 1    A/B: launches before any open cell goes
+//   HANDOVER_SOLVER         1          -       A/B, tests: the host finisher, 1 = FIFO push-relabel, 0 = search trees with the push-relabel continuation
+//                                              (measured slower on what is handed over: tools/residual_probe.py)
+//   HANDOVER_DUMP           unset      -       tooling: a file that receives the residual graphs as handed over (tools/residual_probe.py)
+namespace {
+struct MfKnobs { bool cell_kernel; int max_iter, round_iters; };
+struct MtKnobs {
+    int K, S, K2, S2, max_launches;
+    // Hand-over policy (les_maxflow_tiled.h, host/ResidualCut.h): at the progress checks -- after launch 12 and then every 16 launches, the same
+    // schedule in every lock-step -- the host cores finish from its residual graph every open cell that has had `hand_after` launches and has at
+    // most `hand_cell_nodes` nodes, and after `hand_late_after` launches every open cell whatever its size.  The decision looks at nothing but the
+    // cell itself (its launch count, its size, its phase): the host finisher and the launches may pick different minimum cuts where float capacities
+    // tie, so a rule that looked at the other cells of the lock-step -- how many are open, how large they are together, whether any finished lately
+    // (round 6) -- made a cell's mask depend on its neighbours in the lock-step, and an N-rank run, whose ranks hold other bands of a set's cells,
+    // differ from a single-rank run.  Cell size matters: a coarsest-layer cell (150 000 nodes) costs the host 3 ... 10 ms, more than the further
+    // launches an ordinary straggler of that layer needs, so early on only small cells go (<= hand_cell_nodes: layer-1 cells of 129 x 129).
+    bool hand; int hand_after; long long hand_cell_nodes; int hand_late_after;
+    int finisher; const char* dump;
+};
+MfKnobs mf_knobs()
+{
+    auto num = [](const char* name, int dflt) { const char* ev = getenv(name); return ev ? atoi(ev) : dflt; };
+    return {num("LES_HIP_MAXFLOW_CELL_KERNEL", 1) != 0, std::max(0, num("LES_HIP_MAXFLOW_MAX_ITER", les::kMfMaxIter)), std::max(1, num("LES_HIP_MAXFLOW_ROUND_ITERS", 16))};
+}
+MtKnobs mt_knobs()
+{
+    auto num = [](const char* name, int dflt) { const char* ev = getenv(name); return ev ? atoi(ev) : dflt; };
+    auto count = [&](const char* name, int dflt) { return std::max(1, num(name, dflt)); };
+    MtKnobs k;
+    k.K = count("LES_HIP_MAXFLOW_TILED_K", 8); k.S = count("LES_HIP_MAXFLOW_TILED_S", 12);
+    k.K2 = count("LES_HIP_MAXFLOW_TILED_K2", k.K); k.S2 = count("LES_HIP_MAXFLOW_TILED_S2", k.S);
+    k.max_launches = count("LES_HIP_MAXFLOW_MAX_ITER", 2000);
+    k.hand = num("LES_HIP_MAXFLOW_HANDOVER", 1) != 0;
+    k.hand_after = count("LES_HIP_MAXFLOW_HANDOVER_AFTER", 60);
+    k.hand_cell_nodes = 40000;
+    for (const char* name : {"LES_HIP_MAXFLOW_HANDOVER_NODES", "LES_HIP_MAXFLOW_HANDOVER_CELL_NODES"})
+        if (const char* ev = getenv(name)) k.hand_cell_nodes = std::max(1ll, atoll(ev));
+    k.hand_late_after = count("LES_HIP_MAXFLOW_HANDOVER_LATE_AFTER", 220);
+    k.finisher = num("LES_HIP_MAXFLOW_HANDOVER_SOLVER", 1);
+    k.dump = getenv("LES_HIP_MAXFLOW_HANDOVER_DUMP");
+    return k;
+}
+
 // One workgroup per cell either way, and the kernel is chosen for every cell on its own shape -- never on the other cells of the lock-step: the kernels
 // agree only up to nodes on float ties, and a cell's cut must not depend on the cells it shares a lock-step with (an N-rank run gives each rank
 // another band of a set's cells than one rank has).  A cell that fits it runs the kernel with the tiled solver's two-barrier iteration and the
-// residuals in registers (les_maxflow_cell.h: 0); any other cell -- or every cell with LES_HIP_MAXFLOW_CELL_KERNEL=0 (A/B, tests of the other
-// path) -- runs les_maxflow.h with two nodes per thread (1) or five (2).
-namespace {
-bool mf_cell_kernel_enabled()
-{
-    if (const char* ev = getenv("LES_HIP_MAXFLOW_CELL_KERNEL")) return atoi(ev) != 0;
-    return true;
-}
+// residuals in registers (les_maxflow_cell.h: 0); any other cell -- or every cell with LES_HIP_MAXFLOW_CELL_KERNEL=0 -- runs les_maxflow.h with two
+// nodes per thread (1) or five (2).
 int mf_cell_kind(const les_hip_rect& t, bool cell_kernel)
 {
     if (t.w <= 0 || t.h <= 0) return 0;                      // (an empty cell is closed by whichever kernel gets it)
     if (cell_kernel && les::mc_fits(t.w, t.h)) return 0;
     return (long long)t.w * t.h <= 2048 ? 1 : 2;
 }
-// the batch's cells grouped by kernel (kind 0, then 1, then 2, batch order inside a group) on the device; mf_count[k]: the size of group k
-int mf_build_lists(const les_hip_batch* b, bool cell_kernel)
+// What a solve launches: up to three launches on the same stream over disjoint groups of cells, kind 0, then 1, then 2.  list[k]: the cells of group k on
+// the device, in batch order -- null for a batch whose cells all go to one kernel, which is one launch over the whole batch.
+struct MfPlan { int count[3]; long long max_nodes[3]; const int* list[3]; };
+// ... derived from the batch's targets once per value of cell_kernel and kept with the batch
+int mf_plan(const les_hip_batch* b, bool cell_kernel, MfPlan* plan)
 {
     std::lock_guard<std::mutex> lk(b->mf_mu);
     const int key = cell_kernel ? 1 : 0;
-    if (b->mf_list_key == key) return LES_HIP_OK;
-    std::vector<int> list;
-    list.reserve((size_t)b->n);
-    int count[3] = {0, 0, 0};
-    for (int k = 0; k < 3; k++)
-        for (int i = 0; i < b->n; i++)
-            if (mf_cell_kind(b->targets[i], cell_kernel) == k) { list.push_back(i); count[k]++; }
-    if (!b->d_mf_list.p && b->d_mf_list.alloc(std::max<size_t>(1, list.size())))
-        return fail(LES_HIP_ERR_DEVICE, "les_hip_batch_solve_graphs: cell list allocation failed");
-    if (!list.empty() && hipMemcpy(b->d_mf_list.p, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(LES_HIP_ERR_DEVICE, "les_hip_batch_solve_graphs: cell list upload failed");
-    std::copy(count, count + 3, b->mf_count);
-    b->mf_list_key = key;
+    if (b->mf_list_key != key) {
+        std::vector<int> list;
+        list.reserve((size_t)b->n);
+        int count[3] = {0, 0, 0};
+        long long max_nodes[3] = {0, 0, 0};
+        for (int k = 0; k < 3; k++)
+            for (int i = 0; i < b->n; i++) {
+                const les_hip_rect& t = b->targets[i];
+                if (mf_cell_kind(t, cell_kernel) != k) continue;
+                list.push_back(i); count[k]++;
+                max_nodes[k] = std::max(max_nodes[k], (long long)std::max(0, t.w) * std::max(0, t.h));
+            }
+        if (std::max({count[0], count[1], count[2]}) < b->n) {
+            if (!b->d_mf_list.p && b->d_mf_list.alloc(std::max<size_t>(1, list.size())))
+                return fail(LES_HIP_ERR_DEVICE, "les_hip_batch_solve_graphs: cell list allocation failed");
+            if (hipMemcpy(b->d_mf_list.p, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+                return fail(LES_HIP_ERR_DEVICE, "les_hip_batch_solve_graphs: cell list upload failed");
+        }
+        std::copy(count, count + 3, b->mf_count);
+        std::copy(max_nodes, max_nodes + 3, b->mf_max);
+        b->mf_list_key = key;
+    }
+    std::copy(b->mf_count, b->mf_count + 3, plan->count);
+    std::copy(b->mf_max, b->mf_max + 3, plan->max_nodes);
+    const bool uniform = std::max({plan->count[0], plan->count[1], plan->count[2]}) == b->n;
+    const int* group = uniform ? nullptr : b->d_mf_list.p;
+    for (int k = 0; k < 3; k++) { plan->list[k] = group; if (group) group += plan->count[k]; }
     return LES_HIP_OK;
 }
 }  // namespace
@@ -195,7 +295,7 @@ int les_hip_batch_graph_solver_kind(const les_hip_batch* b)
 {
     if (!b) return -1;
     if (les_hip_batch_max_cell_nodes(b) > LES_HIP_MAXFLOW_MAX_NODES) return -1;
-    const bool cell_kernel = mf_cell_kernel_enabled();
+    const bool cell_kernel = mf_knobs().cell_kernel;
     int kind = 0;
     for (const les_hip_rect& t : b->targets) kind = std::max(kind, mf_cell_kind(t, cell_kernel));
     return kind;
@@ -212,69 +312,32 @@ int les_hip_batch_solve_graphs_counted(les_hip_ctx* c, const les_hip_batch* b, c
     if (c) (void)hipSetDevice(c->p.device);                 // HIP's current device is per host thread
     if (!c || !b || !d_payload || !d_masks || !d_status) return fail(LES_HIP_ERR_ARG, "null argument");
     if (b->n == 0) return LES_HIP_OK;
-    const long long maxn = les_hip_batch_max_cell_nodes(b);
+    const MfKnobs knobs = mf_knobs();
+    MfPlan plan;
+    int rc = mf_plan(b, knobs.cell_kernel, &plan);
+    if (rc) return rc;
+    const long long maxn = std::max({plan.max_nodes[0], plan.max_nodes[1], plan.max_nodes[2]});
     if (maxn > LES_HIP_MAXFLOW_MAX_NODES) return fail(LES_HIP_ERR_ARG, "les_hip_batch_solve_graphs: a cell of %lld nodes exceeds the limit of %d", maxn, LES_HIP_MAXFLOW_MAX_NODES);
     static_assert(LES_HIP_MAXFLOW_MAX_NODES == les::kMfMaxNodes, "header constant out of date");
-#if !defined(LES_SIM)
-    // The opt-in to more than 64 KB of dynamic LDS is a per-DEVICE function attribute: it is set once per context (a context is bound
-    // to one device), under the context's mutex, with that device current -- a process-wide flag would leave the second GPU of a
-    // process that drives two without it.  A failure is reported with its own message so that callers can cut on the host instead.
-    {
-        std::lock_guard<std::mutex> lk(c->mu);
-        if (!c->maxflow_lds_ready) {
-            HIPCHECK(hipSetDevice(c->p.device));
-            hipError_t arc = hipFuncSetAttribute(reinterpret_cast<const void*>(les::les_maxflow_kernel<2, 1024>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)les::mf_lds_bytes(les::kMfMaxNodes));
-            if (arc == hipSuccess)
-                arc = hipFuncSetAttribute(reinterpret_cast<const void*>(les::les_maxflow_kernel<5, 512>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)les::mf_lds_bytes(les::kMfMaxNodes));
-            if (arc == hipSuccess)
-                arc = hipFuncSetAttribute(reinterpret_cast<const void*>(les::les_maxflow_cell_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)les::kMcLdsBytes);
-            if (arc != hipSuccess) return fail(LES_HIP_ERR_DEVICE, "les_hip_batch_solve_graphs: device max-flow unavailable on device %d (hipFuncSetAttribute max dynamic LDS: %s); cut on the host",
-                                               c->p.device, hipGetErrorString(arc));
-            c->maxflow_lds_ready = true;
-        }
-    }
-#endif
+    rc = ensure_dynamic_lds(c, c->maxflow_lds_ready, {{reinterpret_cast<const void*>(les::les_maxflow_kernel<2, 1024>), les::mf_lds_bytes(les::kMfMaxNodes)},
+                                                      {reinterpret_cast<const void*>(les::les_maxflow_kernel<5, 512>), les::mf_lds_bytes(les::kMfMaxNodes)},
+                                                      {reinterpret_cast<const void*>(les::les_maxflow_cell_kernel), les::kMcLdsBytes}}, "les_hip_batch_solve_graphs");
+    if (rc) return rc;
     const les::GraphCell* cells = graph_cells(b);
-    int max_iter = les::kMfMaxIter;
-    if (const char* ev = getenv("LES_HIP_MAXFLOW_MAX_ITER")) max_iter = std::max(0, atoi(ev));      // tests of the callers' host fall-back
-    int round_iters = 16;                                   // (8 ... 64 measured on whole runs: flat within 3 %, tools/lab/ab_cell_kernel.sh)
-    if (const char* ev = getenv("LES_HIP_MAXFLOW_ROUND_ITERS")) round_iters = std::max(1, atoi(ev));
-    const bool cell_kernel = mf_cell_kernel_enabled();
-    const int kind = les_hip_batch_graph_solver_kind(b);
-    // up to three launches on the same stream over disjoint groups of cells; a lock-step whose cells all go to one kernel is one launch over the
-    // whole batch (no list), as before
-    bool uniform = true;
-    for (const les_hip_rect& t : b->targets) uniform = uniform && mf_cell_kind(t, cell_kernel) == kind;
-    int count[3] = {0, 0, 0};
-    const int* lists[3] = {nullptr, nullptr, nullptr};
-    long long group_max[3] = {0, 0, 0};
-    if (uniform) count[kind] = b->n;
-    else {
-        const int rc = mf_build_lists(b, cell_kernel);
-        if (rc) return rc;
-        std::copy(b->mf_count, b->mf_count + 3, count);
-        lists[0] = b->d_mf_list.p; lists[1] = lists[0] + count[0]; lists[2] = lists[1] + count[1];
-    }
-    for (const les_hip_rect& t : b->targets) {
-        const int k = uniform ? kind : mf_cell_kind(t, cell_kernel);
-        group_max[k] = std::max(group_max[k], (long long)std::max(0, t.w) * std::max(0, t.h));
-    }
     for (int k = 0; k < 3; k++) {
-        if (count[k] == 0) continue;
+        if (plan.count[k] == 0) continue;
         // the LDS pitch of les_maxflow.h is the largest cell of the launch: it places the arrays, it does not change the arithmetic
-        const int np = (int)((std::max<long long>(group_max[k], 1) + 7) / 8) * 8;
+        const int np = (int)((std::max<long long>(plan.max_nodes[k], 1) + 7) / 8) * 8;
         const size_t lds = les::mf_lds_bytes(np);
         if (k == 0)
-            hipLaunchKernelGGL(les::les_maxflow_cell_kernel, dim3(count[k]), dim3(les::kMcThreads), les::kMcLdsBytes, cur_stream(c), cells, b->d_graph_off.p, d_payload, max_iter,
-                               round_iters, d_masks, d_status, d_flows, d_unsolved_total, lists[k]);
+            hipLaunchKernelGGL(les::les_maxflow_cell_kernel, dim3(plan.count[k]), dim3(les::kMcThreads), les::kMcLdsBytes, cur_stream(c), cells, b->d_graph_off.p, d_payload,
+                               knobs.max_iter, knobs.round_iters, d_masks, d_status, d_flows, d_unsolved_total, plan.list[k]);
         else if (k == 1)
-            hipLaunchKernelGGL((les::les_maxflow_kernel<2, 1024>), dim3(count[k]), dim3(1024), lds, cur_stream(c), cells, b->d_graph_off.p, d_payload, np, max_iter, d_masks, d_status,
-                               d_flows, d_unsolved_total, lists[k]);
+            hipLaunchKernelGGL((les::les_maxflow_kernel<2, 1024>), dim3(plan.count[k]), dim3(1024), lds, cur_stream(c), cells, b->d_graph_off.p, d_payload, np, knobs.max_iter, d_masks,
+                               d_status, d_flows, d_unsolved_total, plan.list[k]);
         else
-            hipLaunchKernelGGL((les::les_maxflow_kernel<5, 512>), dim3(count[k]), dim3(512), lds, cur_stream(c), cells, b->d_graph_off.p, d_payload, np, max_iter, d_masks, d_status,
-                               d_flows, d_unsolved_total, lists[k]);
+            hipLaunchKernelGGL((les::les_maxflow_kernel<5, 512>), dim3(plan.count[k]), dim3(512), lds, cur_stream(c), cells, b->d_graph_off.p, d_payload, np, knobs.max_iter, d_masks,
+                               d_status, d_flows, d_unsolved_total, plan.list[k]);
         HIPCHECK(hipGetLastError());
     }
     return LES_HIP_OK;
@@ -346,179 +409,177 @@ int les_hip_batch_solve_graphs_tiled(les_hip_ctx* c, const les_hip_batch* b, con
     return rc;
 }
 
-int les_hip_batch_solve_graphs_tiled_stats(les_hip_ctx* c, const les_hip_batch* b, const float* d_payload, unsigned char* d_masks, int* d_status, double* d_flows,
-                                           void* d_workspace, long long workspace_bytes, les_hip_tiled_stats* stats)
+// The steps of one tiled solve, in the order les_hip_batch_solve_graphs_tiled_stats runs them.  (A launch names no MtHost: les_hip_mem.h.)
+namespace {
+constexpr int kMtFirstGroup = 12, kMtGroup = 16;            // launches between two progress checks: the first check comes early, the same schedule in every lock-step
+int mt_check_workspace(const les_hip_batch* b, const void* d_workspace, long long workspace_bytes)
 {
-    int launches_tmp = 0, unsolved_tmp = 0, handed_tmp = 0;
-    int *launches_out = &launches_tmp, *unsolved_out = &unsolved_tmp, *handed_out = &handed_tmp;
-    long long handed_nodes = 0;
-    double host_ms = 0.0;
-    struct Report {                                       // fills *stats on every exit path
-        les_hip_tiled_stats* s; int *l, *u, *h; long long* hn; double* ms;
-        ~Report() { if (s) { s->launches = *l; s->unsolved = *u; s->handed_cells = *h; s->handed_nodes = *hn; s->host_ms = *ms; } }
-    } report{stats, launches_out, unsolved_out, handed_out, &handed_nodes, &host_ms};
-    if (c) (void)hipSetDevice(c->p.device);                 // HIP's current device is per host thread
-    if (!c || !b || !d_payload || !d_masks || !d_status || !d_workspace) return fail(LES_HIP_ERR_ARG, "null argument");
-    if (b->n == 0) return LES_HIP_OK;
     if (workspace_bytes < les_hip_batch_tiled_workspace_bytes(b))
         return fail(LES_HIP_ERR_ARG, "les_hip_batch_solve_graphs_tiled: workspace of %lld bytes, %lld needed (les_hip_batch_tiled_workspace_bytes)", workspace_bytes,
                     les_hip_batch_tiled_workspace_bytes(b));
     if (((uintptr_t)d_workspace & 255) != 0) return fail(LES_HIP_ERR_ARG, "les_hip_batch_solve_graphs_tiled: the workspace must be 256-byte aligned");
     if (b->graph_nodes >= (1ll << 31) - 16) return fail(LES_HIP_ERR_ARG, "les_hip_batch_solve_graphs_tiled: %lld graph nodes exceed the 32-bit height range", b->graph_nodes);
-    int rc = mt_build_tiles(b);
-    if (rc) return rc;
-#if !defined(LES_SIM)
-    {
-        std::lock_guard<std::mutex> lk(c->mu);
-        if (!c->maxflow_tiled_lds_ready) {
-            HIPCHECK(hipSetDevice(c->p.device));
-            const hipError_t arc = hipFuncSetAttribute(reinterpret_cast<const void*>(les::les_maxflow_tiled_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)les::kMtLdsBytes);
-            if (arc != hipSuccess) return fail(LES_HIP_ERR_DEVICE, "les_hip_batch_solve_graphs_tiled: device max-flow unavailable on device %d (hipFuncSetAttribute max dynamic LDS: %s); cut on the host",
-                                               c->p.device, hipGetErrorString(arc));
-            c->maxflow_tiled_lds_ready = true;
-        }
-    }
-#endif
-    hipStream_t st = cur_stream(c);
+    return LES_HIP_OK;
+}
+les::MtArgs mt_args(const les_hip_batch* b, const MtKnobs& k, const float* d_payload, unsigned char* d_masks, int* d_status, double* d_flows, void* d_workspace, int* d_flags)
+{
     les::MtArgs a;
-    a.cells = graph_cells(b);
-    a.offsets = b->d_graph_off.p;
-    a.payload = d_payload;
-    a.tiles = b->d_mt_tiles.p;
-    a.ws = reinterpret_cast<char*>(d_workspace);
-    a.nodes = b->graph_nodes;
-    a.ncells = b->n;
-    a.K = 8; a.S = 12;                                     // short sweeps, a dozen of them between exact relabellings (measured: K = 8 / 16 / 32 / 64 -> 4.5 / 5.2 / 6.8 / 9.7 ms on a hard layer-1 lock-step)
-    a.max_launches = 2000;
-    a.K2 = a.K; a.S2 = a.S;
-    if (const char* ev = getenv("LES_HIP_MAXFLOW_TILED_K")) a.K = a.K2 = std::max(1, atoi(ev));
-    if (const char* ev = getenv("LES_HIP_MAXFLOW_TILED_S")) a.S = a.S2 = std::max(1, atoi(ev));
-    if (const char* ev = getenv("LES_HIP_MAXFLOW_TILED_K2")) a.K2 = std::max(1, atoi(ev));
-    if (const char* ev = getenv("LES_HIP_MAXFLOW_TILED_S2")) a.S2 = std::max(1, atoi(ev));
-    if (const char* ev = getenv("LES_HIP_MAXFLOW_MAX_ITER")) a.max_launches = std::max(1, atoi(ev));      // tests of the callers' host fall-back
-    a.masks = d_masks;
-    a.status = d_status;
-    a.flows = d_flows;
+    a.cells = graph_cells(b); a.offsets = b->d_graph_off.p; a.payload = d_payload; a.tiles = b->d_mt_tiles.p;
+    a.ws = reinterpret_cast<char*>(d_workspace); a.nodes = b->graph_nodes; a.ncells = b->n;
+    a.K = k.K; a.S = k.S; a.K2 = k.K2; a.S2 = k.S2; a.max_launches = k.max_launches;
+    a.masks = d_masks; a.status = d_status; a.flows = d_flows; a.host_flags = d_flags;
+    return a;
+}
+// zeroes the flag words (nothing in flight writes them: the previous user of this MtHost has synchronised) and sets up the cells' control words
+int mt_init(hipStream_t st, const les_hip_batch* b, const les::MtArgs& a, volatile int* flags)
+{
+    for (int i = 0; i < les::kMtFlagCount; i++) flags[i] = 0;
+    hipLaunchKernelGGL(les::les_maxflow_tiled_init_kernel, dim3((b->n + 255) / 256), dim3(256), 0, st, a.ws, a.nodes, a.ncells, b->d_mt_tiles_per_cell.p, a.status, a.flows, a.host_flags);
+    HIPCHECK(hipGetLastError());
+    return LES_HIP_OK;
+}
+// n launches, then the only synchronisation of the loop: the host reads "cells done" after it.  Launches that come after the last cell finished return at once.
+int launch_group(hipStream_t st, const les_hip_batch* b, const les::MtArgs& a, int n, les_hip_tiled_stats* s)
+{
+    for (int i = 0; i < n; i++)
+        hipLaunchKernelGGL(les::les_maxflow_tiled_kernel, dim3(b->mt_ntiles), dim3(les::kMtThreads), les::kMtLdsBytes, st, a);
+    s->launches += n;
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(st));
+    return LES_HIP_OK;
+}
+// is a hand-over check due after `launches` launches?  (the host skips it while no cell of the batch could qualify: `smallest` is the batch's smallest cell)
+bool handover_due(const MtKnobs& k, int launches, long long smallest)
+{
+    return k.hand && launches >= k.hand_after && (launches >= k.hand_late_after || smallest <= k.hand_cell_nodes);
+}
+// Parks the open cells that qualify and writes their residual graphs to the staging; *out: the kernels' arguments, which the unpack takes again.  The
+// staging holds what the collect kernel selects; when it reports more than fits, it has parked nothing: grow the staging, collect again (nothing has run
+// in between, the selection is the same).
+int collect_handover(hipStream_t st, const les_hip_batch* b, const les::MtArgs& a, const MtKnobs& k, MtHost* hf, les::MtHandArgs* out)
+{
+    volatile const int* flags = hf->h_flags.p;
+    les::MtHandArgs ha;
+    ha.tiles = a.tiles; ha.ws = a.ws; ha.nodes = a.nodes; ha.ncells = a.ncells; ha.cells = a.cells;
+    ha.hand_after = k.hand_after; ha.late_after = k.hand_late_after; ha.cell_nodes = k.hand_cell_nodes;
+    ha.masks = a.masks; ha.status = a.status; ha.flows = a.flows; ha.host_flags = a.host_flags;
+    if (hf->cap_nodes == 0) {
+        const int rc = mt_host_stage(hf, std::min(b->graph_nodes, kMtStageFirstNodes), std::min(b->n, kMtStageFirstCells), st);
+        if (rc) return rc;
+    }
+    for (int attempt = 0;; attempt++) {
+        const MtStage d = hf->stage_at(hf->d_stage);
+        ha.cap_nodes = hf->cap_nodes; ha.cap_cells = hf->cap_cells;
+        ha.list = d.list; ha.rc8 = d.rc8; ha.ex = d.ex; ha.hmasks = d.masks; ha.hflows = d.flows;
+        hipLaunchKernelGGL(les::les_maxflow_tiled_collect_kernel, dim3(1), dim3(64), 0, st, ha);
+        hipLaunchKernelGGL(les::les_maxflow_tiled_pack_kernel, dim3(b->mt_ntiles), dim3(les::kMtThreads), 0, st, ha);      // (nothing to pack when no cell qualified)
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipStreamSynchronize(st));
+        const int want_cells = flags[les::kMtFlagCellsWanted], want_nodes = flags[les::kMtFlagNodesWanted];
+        if (flags[les::kMtFlagCellsHanded] > 0 || want_cells == 0) break;
+        if (attempt > 0) return fail(LES_HIP_ERR_DEVICE, "les_hip_batch_solve_graphs_tiled: hand-over staging of %lld nodes refused %d cells of %d nodes", hf->cap_nodes, want_cells, want_nodes);
+        const int rc = mt_host_stage(hf, want_nodes, want_cells, st);
+        if (rc) return rc;
+    }
+    *out = ha;
+    return LES_HIP_OK;
+}
+// tooling: the residual graphs as handed over (tools/residual_probe.py)
+void dump_handover(const char* path, const les_hip_batch* b, const MtStage& h, int cells, long long nodes)
+{
+    FILE* f = fopen(path, "wb");
+    if (!f) return;
+    fwrite(&cells, sizeof(int), 1, f); fwrite(&nodes, sizeof(long long), 1, f);
+    for (int q = 0; q < cells; q++) {
+        const les_hip_rect& t = b->targets[(size_t)h.list[q].cell];
+        const int wh[2] = {t.w, t.h};
+        fwrite(wh, sizeof(int), 2, f); fwrite(&h.list[q].hoff, sizeof(long long), 1, f);
+    }
+    fwrite(h.rc8, sizeof(float), (size_t)nodes * 8, f); fwrite(h.ex, sizeof(float), (size_t)nodes, f);
+    fclose(f);
+}
+// The host cores finish the `cells` parked cells (`nodes` nodes) from the staging: one host thread per cell, at most as many as the process may keep busy (a
+// persistent team owned by the calling thread); the large cells split their phases over row bands as the host cuts do.
+void finish_on_host(const les_hip_batch* b, const MtKnobs& k, const MtHost& hf, int cells, long long nodes, les_hip_tiled_stats* s)
+{
+    const auto h0 = std::chrono::steady_clock::now();
+    const MtStage h = hf.stage_at(hf.h_stage.p);
+    if (k.dump) dump_handover(k.dump, b, h, cells, nodes);
+    const int team = std::max(1, std::min(cells, les_host::cpuBudget()));
+    std::atomic<int> next{0};
+    les_host::BandPool::outer().run(team, [&](int) {
+        for (int q = next.fetch_add(1); q < cells; q = next.fetch_add(1)) {
+            const les_hip_rect& t = b->targets[(size_t)h.list[q].cell];
+            const long long o = h.list[q].hoff;
+            h.flows[q] = les_host::finishResidualCut(h.rc8 + 8 * o, h.ex + o, t.w, t.h, h.masks + o, les_host::residualBands(t.w, t.h), k.finisher);
+        }
+    });
+    s->handed_cells += cells;
+    s->handed_nodes += nodes;
+    s->host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h0).count();
+}
+// copies the host's masks into place and completes the flow values and status words of the parked cells; the staging belongs to the next caller (and the
+// next check) as soon as the unpack kernel has read it
+int unpack_handover(hipStream_t st, const les_hip_batch* b, const les::MtHandArgs& ha)
+{
+    hipLaunchKernelGGL(les::les_maxflow_tiled_unpack_kernel, dim3(b->mt_ntiles), dim3(256), 0, st, ha);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(st));
+    return LES_HIP_OK;
+}
+}  // namespace
+
+int les_hip_batch_solve_graphs_tiled_stats(les_hip_ctx* c, const les_hip_batch* b, const float* d_payload, unsigned char* d_masks, int* d_status, double* d_flows,
+                                           void* d_workspace, long long workspace_bytes, les_hip_tiled_stats* stats)
+{
+    les_hip_tiled_stats s = {};
+    struct Report {                                       // fills *stats on every exit path, with the counts so far
+        les_hip_tiled_stats* out; const les_hip_tiled_stats* s;
+        ~Report() { if (out) *out = *s; }
+    } report{stats, &s};
+    const MtKnobs k = mt_knobs();
+    if (c) (void)hipSetDevice(c->p.device);                 // HIP's current device is per host thread
+    if (!c || !b || !d_payload || !d_masks || !d_status || !d_workspace) return fail(LES_HIP_ERR_ARG, "null argument");
+    if (b->n == 0) return LES_HIP_OK;
+    int rc = mt_check_workspace(b, d_workspace, workspace_bytes);
+    if (!rc) rc = mt_build_tiles(b);
+    if (!rc) rc = ensure_dynamic_lds(c, c->maxflow_tiled_lds_ready, {{reinterpret_cast<const void*>(les::les_maxflow_tiled_kernel), les::kMtLdsBytes}}, "les_hip_batch_solve_graphs_tiled");
     MtHostLease lease{c, nullptr};
-    rc = mt_host_acquire(c, &lease.m);
+    if (!rc) rc = mt_host_acquire(c, &lease.m);
     if (rc) return rc;
     MtHost& hf = *lease.m;
-    volatile int* flags = hf.h_flags.p;
-    for (int i = 0; i < 6; i++) flags[i] = 0;   // (nothing in flight writes them: the previous user of this MtHost has synchronised)
-    a.host_flags = hf.d_flags;
-    hipLaunchKernelGGL(les::les_maxflow_tiled_init_kernel, dim3((b->n + 255) / 256), dim3(256), 0, st, a.ws, a.nodes, a.ncells, b->d_mt_tiles_per_cell.p, d_status, d_flows, a.host_flags);
-    HIPCHECK(hipGetLastError());
+    volatile const int* flags = hf.h_flags.p;
+    const hipStream_t st = cur_stream(c);
+    const les::MtArgs a = mt_args(b, k, d_payload, d_masks, d_status, d_flows, d_workspace, hf.d_flags);
+    rc = mt_init(st, b, a, hf.h_flags.p);
+    if (rc) return rc;
     if (b->mt_ntiles == 0) {                                // every target rect is empty: the init kernel has closed all cells
         HIPCHECK(hipStreamSynchronize(st));
         return LES_HIP_OK;
     }
-    // Hand-over policy (les_maxflow_tiled.h, host/ResidualCut.h): at the progress checks -- after launch 12 and then every 16 launches, the same
-    // schedule in every lock-step -- the host cores finish from its residual graph every open cell that has had `hand_after` launches and has at
-    // most `hand_cell_nodes` nodes, and after `hand_late_after` launches every open cell whatever its size.  The decision looks at nothing but the
-    // cell itself (its launch count, its size, its phase): the host finisher and the launches may pick different minimum cuts where float capacities
-    // tie, so a rule that looked at the other cells of the lock-step -- how many are open, how large they are together, whether any finished lately
-    // (round 6) -- made a cell's mask depend on its neighbours in the lock-step, and an N-rank run, whose ranks hold other bands of a set's cells,
-    // differ from a single-rank run.  Cell size matters: a coarsest-layer cell (150 000 nodes) costs the host 3 ... 10 ms, more than the further
-    // launches an ordinary straggler of that layer needs, so early on only small cells go (<= hand_cell_nodes: layer-1 cells of 129 x 129).
-    // LES_HIP_MAXFLOW_HANDOVER=0 switches it off (every cell is then cut by launches alone, as in round 5); ..._AFTER / _CELL_NODES / _LATE_AFTER
-    // override the thresholds (A/B measurements, tests; ..._NODES sets the node limit as well).
-    int hand_after = 60, hand_late_after = 220;
-    long long hand_cell_nodes = 40000;
-    bool hand = true;
-    if (const char* ev = getenv("LES_HIP_MAXFLOW_HANDOVER")) hand = atoi(ev) != 0;
-    if (const char* ev = getenv("LES_HIP_MAXFLOW_HANDOVER_AFTER")) hand_after = std::max(1, atoi(ev));
-    if (const char* ev = getenv("LES_HIP_MAXFLOW_HANDOVER_NODES")) hand_cell_nodes = std::max(1ll, atoll(ev));
-    if (const char* ev = getenv("LES_HIP_MAXFLOW_HANDOVER_CELL_NODES")) hand_cell_nodes = std::max(1ll, atoll(ev));
-    if (const char* ev = getenv("LES_HIP_MAXFLOW_HANDOVER_LATE_AFTER")) hand_late_after = std::max(1, atoi(ev));
-    long long smallest = b->graph_nodes;                    // (the host skips the check while no cell of the batch could qualify)
+    long long smallest = b->graph_nodes;
     for (const les_hip_rect& t : b->targets)
         if (t.w > 0 && t.h > 0) smallest = std::min(smallest, (long long)t.w * t.h);
-    // Launches are enqueued in groups; after each group the host reads "cells done" (the only synchronisation).  Launches that come
-    // after the last cell finished return at once.
-    int total = 0, group = 12, handed = 0;
-    for (;;) {
-        for (int i = 0; i < group; i++)
-            hipLaunchKernelGGL(les::les_maxflow_tiled_kernel, dim3(b->mt_ntiles), dim3(les::kMtThreads), les::kMtLdsBytes, st, a);
-        total += group;
-        HIPCHECK(hipGetLastError());
-        HIPCHECK(hipStreamSynchronize(st));
-        const int done = flags[0];                          // (cells closed by the launches; the `handed` ones are closed as well)
-        if (done + handed >= b->n) break;
-        if (hand && total >= hand_after && (total >= hand_late_after || smallest <= hand_cell_nodes)) {
+    for (int group = kMtFirstGroup;; group = kMtGroup) {
+        rc = launch_group(st, b, a, group, &s);
+        if (rc) return rc;
+        const int done = flags[les::kMtFlagCellsDone];       // (cells closed by the launches; the handed ones are closed as well)
+        if (done + s.handed_cells >= b->n) break;
+        if (handover_due(k, s.launches, smallest)) {
             les::MtHandArgs ha;
-            ha.tiles = b->d_mt_tiles.p; ha.ws = a.ws; ha.nodes = a.nodes; ha.ncells = a.ncells; ha.cells = a.cells;
-            ha.hand_after = hand_after; ha.late_after = hand_late_after; ha.cell_nodes = hand_cell_nodes;
-            ha.masks = d_masks; ha.status = d_status; ha.flows = d_flows; ha.host_flags = hf.d_flags;
-            // the staging holds what the collect kernel selects; when it reports more than fits, it has parked nothing: grow the staging, collect again
-            // (nothing has run in between, the selection is the same)
-            for (int attempt = 0;; attempt++) {
-                if (attempt == 0 && hf.cap_nodes == 0) {
-                    rc = mt_host_stage(&hf, std::min<long long>(b->graph_nodes, 140000), std::min(b->n, 16), st);
-                    if (rc) return rc;
-                }
-                ha.cap_nodes = hf.cap_nodes; ha.cap_cells = hf.cap_cells;
-                ha.list = reinterpret_cast<les::MtHandCell*>(hf.d_stage + hf.off_list());
-                ha.rc8 = reinterpret_cast<float*>(hf.d_stage);
-                ha.ex = reinterpret_cast<float*>(hf.d_stage + hf.off_ex());
-                ha.hmasks = reinterpret_cast<const uint8_t*>(hf.d_stage + hf.off_masks());
-                ha.hflows = reinterpret_cast<const double*>(hf.d_stage + hf.off_flows());
-                hipLaunchKernelGGL(les::les_maxflow_tiled_collect_kernel, dim3(1), dim3(64), 0, st, ha);
-                hipLaunchKernelGGL(les::les_maxflow_tiled_pack_kernel, dim3(b->mt_ntiles), dim3(les::kMtThreads), 0, st, ha);      // (nothing to pack when no cell qualified)
-                HIPCHECK(hipGetLastError());
-                HIPCHECK(hipStreamSynchronize(st));
-                const int want_cells = flags[4], want_nodes = flags[5];
-                if (flags[2] > 0 || want_cells == 0) break;
-                if (attempt > 0) return fail(LES_HIP_ERR_DEVICE, "les_hip_batch_solve_graphs_tiled: hand-over staging of %lld nodes refused %d cells of %d nodes", hf.cap_nodes, want_cells, want_nodes);
-                rc = mt_host_stage(&hf, want_nodes, want_cells, st);
+            rc = collect_handover(st, b, a, k, &hf, &ha);
+            if (rc) return rc;
+            if (flags[les::kMtFlagCellsHanded] > 0) {
+                finish_on_host(b, k, hf, flags[les::kMtFlagCellsHanded], flags[les::kMtFlagNodesHanded], &s);
+                rc = unpack_handover(st, b, ha);
                 if (rc) return rc;
-            }
-            const int now = flags[2];
-            if (now > 0) {
-                handed += now;
-                handed_nodes += flags[3];
-                const auto h0 = std::chrono::steady_clock::now();
-                const float* h_rc8 = reinterpret_cast<const float*>(hf.h_stage.p);
-                const float* h_ex = reinterpret_cast<const float*>(hf.h_stage.p + hf.off_ex());
-                uint8_t* h_masks = reinterpret_cast<uint8_t*>(hf.h_stage.p + hf.off_masks());
-                const les::MtHandCell* list = reinterpret_cast<const les::MtHandCell*>(hf.h_stage.p + hf.off_list());
-                double* hflows = reinterpret_cast<double*>(hf.h_stage.p + hf.off_flows());
-                const std::vector<les_hip_rect>& tg = b->targets;
-                const char* sev = getenv("LES_HIP_MAXFLOW_HANDOVER_SOLVER");      // 1 (default): FIFO push-relabel; 0: search trees with the push-relabel continuation (measured slower on what is handed over: tools/residual_probe.py)
-                const int solver = sev ? atoi(sev) : 1;
-                if (const char* dump = getenv("LES_HIP_MAXFLOW_HANDOVER_DUMP")) {      // tooling: the residual graphs as handed over (tools/residual_probe.py)
-                    if (FILE* f = fopen(dump, "wb")) {
-                        const long long hn = flags[3];
-                        fwrite(&now, sizeof(int), 1, f); fwrite(&hn, sizeof(long long), 1, f);
-                        for (int q = 0; q < now; q++) { const int wh[2] = {tg[(size_t)list[q].cell].w, tg[(size_t)list[q].cell].h}; fwrite(wh, sizeof(int), 2, f); fwrite(&list[q].hoff, sizeof(long long), 1, f); }
-                        fwrite(h_rc8, sizeof(float), (size_t)hn * 8, f); fwrite(h_ex, sizeof(float), (size_t)hn, f);
-                        fclose(f);
-                    }
-                }
-                // one host thread per cell, at most as many as the process may keep busy (a persistent team owned by the calling thread); the large
-                // cells split their phases over row bands as the host cuts do
-                const int team = std::max(1, std::min(now, les_host::cpuBudget()));
-                std::atomic<int> next{0};
-                les_host::BandPool::outer().run(team, [&](int) {
-                    for (int q = next.fetch_add(1); q < now; q = next.fetch_add(1)) {
-                        const int cell = list[q].cell;
-                        const int w = tg[(size_t)cell].w, h = tg[(size_t)cell].h;
-                        hflows[q] = les_host::finishResidualCut(h_rc8 + 8 * list[q].hoff, h_ex + list[q].hoff, w, h, h_masks + list[q].hoff, les_host::residualBands(w, h), solver);
-                    }
-                });
-                host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h0).count();
-                hipLaunchKernelGGL(les::les_maxflow_tiled_unpack_kernel, dim3(b->mt_ntiles), dim3(256), 0, st, ha);
-                HIPCHECK(hipGetLastError());
-                // the staging belongs to the next caller (and the next check) as soon as the unpack kernel has read it
-                HIPCHECK(hipStreamSynchronize(st));
-                if (done + handed >= b->n) break;
+                if (done + s.handed_cells >= b->n) break;
             }
         }
-        if (total >= a.max_launches + group) return fail(LES_HIP_ERR_DEVICE, "les_hip_batch_solve_graphs_tiled: %d of %d cells still open after %d launches", b->n - done - handed, b->n, total);
-        group = 16;
+        if (s.launches >= a.max_launches + group)
+            return fail(LES_HIP_ERR_DEVICE, "les_hip_batch_solve_graphs_tiled: %d of %d cells still open after %d launches", b->n - done - s.handed_cells, b->n, s.launches);
     }
-    *launches_out = total;
-    *unsolved_out = flags[1];
-    *handed_out = handed;
+    s.unsolved = flags[les::kMtFlagCellsGaveUp];
     return LES_HIP_OK;
 }
 

@@ -136,6 +136,18 @@ __device__ int g_mt_probe_launches = 0;
 #define MT_STAMP(i) ((void)0)
 #endif
 
+// The host-mapped words one solve reports through (host_flags of MtArgs and MtHandArgs): the kernels write them with mt_host_add / mt_store, the host
+// (les_hip_cuts.inc) zeroes all kMtFlagCount of them before the init launch and reads them after synchronising its stream.
+enum MtFlag : int {
+    kMtFlagCellsDone = 0,            // cells the launches have closed (the init kernel: empty cells) ...
+    kMtFlagCellsGaveUp,              // ... of them: at max_launches, status 1
+    kMtFlagCellsHanded,              // what the last collect parked for the host: cells (0: none qualified, or the selection did not fit the staging) ...
+    kMtFlagNodesHanded,              // ... and their nodes
+    kMtFlagCellsWanted,              // what the last collect selected, whether it fitted or not: cells ...
+    kMtFlagNodesWanted,              // ... and their nodes
+    kMtFlagCount
+};
+
 struct MtArgs {
     const GraphCell* cells;          // target rects of the lock-step (x, y unused here; w, h = the cell's graph)
     const long long* offsets;        // node offset of every cell in the payload / masks / workspace arrays
@@ -150,7 +162,7 @@ struct MtArgs {
     uint8_t* masks;
     int* status;
     double* flows;                   // optional
-    int* host_flags;                 // host-mapped (pinned) words the host reads after a stream synchronisation, no copy: [0] cells finished, [1] of them: gave up
+    int* host_flags;                 // host-mapped (pinned) words the host reads after a stream synchronisation, no copy (MtFlag)
 };
 
 // grid = tiles of the lock-step; block = kMtThreads; dynamic LDS = kMtLdsBytes
@@ -632,13 +644,13 @@ les_maxflow_tiled_kernel(MtArgs a)
                 a.status[t.cell] = 0;
                 if (a.flows) a.flows[t.cell] = (double)mt_load_i64(&ctl->flow_fix) * (1.0 / (double)(1ll << kMtFlowShift));      // (every tile's share arrived before its count did)
                 mt_atomic_add(&hdr->cells_done, 1);
-                mt_host_add(a.host_flags, 1);
+                mt_host_add(a.host_flags + kMtFlagCellsDone, 1);
             } else if (launch + 1 >= a.max_launches) {
                 next = kMtDone;                                          // gives up: status stays 1, the caller cuts the cell on the host
                 mt_atomic_add(&hdr->cells_done, 1);
                 mt_atomic_add(&hdr->cells_failed, 1);
-                mt_host_add(a.host_flags + 1, 1);
-                mt_host_add(a.host_flags, 1);
+                mt_host_add(a.host_flags + kMtFlagCellsGaveUp, 1);
+                mt_host_add(a.host_flags + kMtFlagCellsDone, 1);
             }
             ctl->parity = par; ctl->sweeps = sweeps; ctl->rounds = rounds;
             ctl->votes = 0;
@@ -671,7 +683,7 @@ __global__ void les_maxflow_tiled_init_kernel(char* ws, long long nodes, int nce
         c->phase = kMtDone;
         status[i] = 0;
         mt_atomic_add(&reinterpret_cast<MtHeader*>(ws)->cells_done, 1);
-        mt_host_add(host_flags, 1);
+        mt_host_add(host_flags + kMtFlagCellsDone, 1);
     }
 }
 
@@ -705,7 +717,7 @@ struct MtHandArgs {
     uint8_t* masks;
     int* status;
     double* flows;                   // optional
-    int* host_flags;                 // [2] cells handed over, [3] their nodes; [4] / [5] cells / nodes selected (also when they did not fit the staging)
+    int* host_flags;                 // (MtFlag: what this check handed over and what it wanted to)
 };
 
 // does open cell `c` (w x h nodes) go to the host at this check?  (a cell in FINAL closes in the next launch)
@@ -727,9 +739,9 @@ __global__ void les_maxflow_tiled_collect_kernel(MtHandArgs a)
         const long long cn = (long long)a.cells[i].w * a.cells[i].h;
         if (mt_hand_cell(ctl[i], cn, a.hand_after, a.late_after, a.cell_nodes)) { sel++; nodes += cn; }
     }
-    mt_store(a.host_flags + 4, sel);
-    mt_store(a.host_flags + 5, (int)nodes);
-    if (sel == 0 || sel > a.cap_cells || nodes > a.cap_nodes) { mt_store(a.host_flags + 2, 0); mt_store(a.host_flags + 3, 0); return; }
+    mt_store(a.host_flags + kMtFlagCellsWanted, sel);
+    mt_store(a.host_flags + kMtFlagNodesWanted, (int)nodes);
+    if (sel == 0 || sel > a.cap_cells || nodes > a.cap_nodes) { mt_store(a.host_flags + kMtFlagCellsHanded, 0); mt_store(a.host_flags + kMtFlagNodesHanded, 0); return; }
     int slot = 0;
     long long hoff = 0;
     for (int i = 0; i < a.ncells; i++) {
@@ -742,8 +754,8 @@ __global__ void les_maxflow_tiled_collect_kernel(MtHandArgs a)
         hoff += cn;
     }
     mt_fence();
-    mt_store(a.host_flags + 3, (int)hoff);
-    mt_store(a.host_flags + 2, slot);
+    mt_store(a.host_flags + kMtFlagNodesHanded, (int)hoff);
+    mt_store(a.host_flags + kMtFlagCellsHanded, slot);
 }
 
 // grid = tiles of the lock-step; block = kMtThreads

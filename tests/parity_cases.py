@@ -1351,6 +1351,48 @@ def case_tiled_maxflow_hard_cells(pr):
     return switched
 
 
+_HANDOVER_ENV = ("LES_HIP_MAXFLOW_HANDOVER", "LES_HIP_MAXFLOW_HANDOVER_AFTER", "LES_HIP_MAXFLOW_HANDOVER_SOLVER", "LES_GC_RESIDUAL_BAND_NODES", "LES_HIP_MAXFLOW_HANDOVER_NODES")
+
+
+def _handover_vs_launches_alone(pr, monkeypatch, name, shp, pays, dyadic, hand_nodes="1000000"):
+    """One input of case_tiled_maxflow_handover: the lock-step cut by launches alone, then with the hand-over at the first check and either host
+    finisher.  -> the statistics of the two solves with hand-over"""
+    from localexpstereo_amd import gc as lgc
+    monkeypatch.setenv("LES_HIP_MAXFLOW_HANDOVER", "0")
+    off, status0, masks0, flows0 = _solve_cells_on_device(pr, shp, pays, tiled=True)
+    assert not status0.any()
+    stats = []
+    for solver in (0, 1):
+        monkeypatch.setenv("LES_HIP_MAXFLOW_HANDOVER", "1")
+        monkeypatch.setenv("LES_HIP_MAXFLOW_HANDOVER_AFTER", "1")
+        monkeypatch.setenv("LES_HIP_MAXFLOW_HANDOVER_NODES", hand_nodes)
+        monkeypatch.setenv("LES_HIP_MAXFLOW_HANDOVER_SOLVER", str(solver))
+        monkeypatch.setenv("LES_GC_RESIDUAL_BAND_NODES", "2000")      # row bands inside the handed-over cells (a team inside the cell-per-thread team) at test sizes too
+        st = {}
+        off1, status1, masks1, flows1 = _solve_cells_on_device(pr, shp, pays, tiled=True, poison=True, stats=st)
+        assert not status1.any() and np.array_equal(off, off1)
+        assert st["handed_cells"] > 0 and st["handed_nodes"] > 0, f"{name}: nothing was handed over ({st})"
+        stats.append(st)
+        for i, ((w, h), p) in enumerate(zip(shp, pays)):
+            a, b = masks0[off[i]: off[i] + w * h] != 0, masks1[off[i]: off[i] + w * h] != 0
+            tsum = max(1.0, float(np.abs(p[:, 0]).astype(np.float64).sum()))
+            if dyadic:
+                assert np.array_equal(a, b), f"{name} cell {i} ({w}x{h}), solver {solver}: {int((a != b).sum())} nodes differ from the cut without hand-over"
+                assert abs(flows1[i] - flows0[i]) <= 1e-9 * tsum, (flows1[i], flows0[i])
+            else:
+                assert abs(flows1[i] - flows0[i]) <= 1e-6 * tsum + 1e-5 * abs(flows0[i]) + 1e-5, (name, i, flows1[i], flows0[i])
+                if name == "hard":
+                    hm = np.zeros(w * h, np.uint8)
+                    lgc.solve_prebuilt(api._rects(np.array([(0, 0, w, h)], np.int32)), np.ascontiguousarray(p.reshape(-1)), np.array([0], np.int64), hm, nthreads=1)
+                    assert np.array_equal(b, hm != 0), f"hard cell {i}, solver {solver}: {int((b != (hm != 0)).sum())} nodes differ from the host cut"
+                else:
+                    ca, cb = _cut_capacity(p, w, h, a), _cut_capacity(p, w, h, b)
+                    assert abs(ca - cb) <= 1e-6 * tsum, f"{name} cell {i}: the cut after hand-over is not a minimum cut ({cb} vs {ca})"
+    for k in _HANDOVER_ENV:
+        monkeypatch.delenv(k, raising=False)
+    return stats
+
+
 def case_tiled_maxflow_handover(pr, monkeypatch, seed=13, shapes=None):
     """The hand-over of the tiled solver (csrc/les_maxflow_tiled.h, host/ResidualCut.h): with the threshold lowered so that cells ARE still open
     when the host looks (after the first 12 launches), the open cells' residual graphs go to the host cores, which finish them.  The masks must be
@@ -1358,7 +1400,6 @@ def case_tiled_maxflow_handover(pr, monkeypatch, seed=13, shapes=None):
     minimum cut of the same value), the flow values must agree, for both host finishers (search trees / push-relabel).  Also the two committed
     hard crops.  -> cells handed over"""
     import os
-    from localexpstereo_amd import gc as lgc
     rng = np.random.default_rng(seed)
     if shapes is None:
         shapes = [(150, 130), (65, 31), (129, 129), (200, 45), (31, 65), (64, 30)]
@@ -1369,39 +1410,22 @@ def case_tiled_maxflow_handover(pr, monkeypatch, seed=13, shapes=None):
     handed = 0
     for name, shp, pays, dyadic in (("dyadic", shapes, _random_cell_payloads(rng, shapes, True), True), ("float", shapes, _random_cell_payloads(rng, shapes, False), False),
                                     ("hard", hard_shapes, hard_pays, False)):
-        monkeypatch.setenv("LES_HIP_MAXFLOW_HANDOVER", "0")
-        off, status0, masks0, flows0 = _solve_cells_on_device(pr, shp, pays, tiled=True)
-        assert not status0.any()
-        for solver in (0, 1):
-            monkeypatch.setenv("LES_HIP_MAXFLOW_HANDOVER", "1")
-            monkeypatch.setenv("LES_HIP_MAXFLOW_HANDOVER_AFTER", "1")
-            monkeypatch.setenv("LES_HIP_MAXFLOW_HANDOVER_NODES", "1000000")
-            monkeypatch.setenv("LES_HIP_MAXFLOW_HANDOVER_NO_STALL_RULE", "1")   # (the product waits for a group of launches in which no cell finished)
-            monkeypatch.setenv("LES_HIP_MAXFLOW_HANDOVER_SOLVER", str(solver))
-            monkeypatch.setenv("LES_GC_RESIDUAL_BAND_NODES", "2000")      # row bands inside the handed-over cells (a team inside the cell-per-thread team) at test sizes too
-            st = {}
-            off1, status1, masks1, flows1 = _solve_cells_on_device(pr, shp, pays, tiled=True, poison=True, stats=st)
-            assert not status1.any() and np.array_equal(off, off1)
-            assert st["handed_cells"] > 0 and st["handed_nodes"] > 0, f"{name}: nothing was handed over ({st})"
-            handed += st["handed_cells"]
-            for i, ((w, h), p) in enumerate(zip(shp, pays)):
-                a, b = masks0[off[i]: off[i] + w * h] != 0, masks1[off[i]: off[i] + w * h] != 0
-                tsum = max(1.0, float(np.abs(p[:, 0]).astype(np.float64).sum()))
-                if dyadic:
-                    assert np.array_equal(a, b), f"{name} cell {i} ({w}x{h}), solver {solver}: {int((a != b).sum())} nodes differ from the cut without hand-over"
-                    assert abs(flows1[i] - flows0[i]) <= 1e-9 * tsum, (flows1[i], flows0[i])
-                else:
-                    assert abs(flows1[i] - flows0[i]) <= 1e-6 * tsum + 1e-5 * abs(flows0[i]) + 1e-5, (name, i, flows1[i], flows0[i])
-                    if name == "hard":
-                        hm = np.zeros(w * h, np.uint8)
-                        lgc.solve_prebuilt(api._rects(np.array([(0, 0, w, h)], np.int32)), np.ascontiguousarray(p.reshape(-1)), np.array([0], np.int64), hm, nthreads=1)
-                        assert np.array_equal(b, hm != 0), f"hard cell {i}, solver {solver}: {int((b != (hm != 0)).sum())} nodes differ from the host cut"
-                    else:
-                        ca, cb = _cut_capacity(p, w, h, a), _cut_capacity(p, w, h, b)
-                        assert abs(ca - cb) <= 1e-6 * tsum, f"{name} cell {i}: the cut after hand-over is not a minimum cut ({cb} vs {ca})"
-        for k in ("LES_HIP_MAXFLOW_HANDOVER", "LES_HIP_MAXFLOW_HANDOVER_AFTER", "LES_HIP_MAXFLOW_HANDOVER_SOLVER", "LES_GC_RESIDUAL_BAND_NODES", "LES_HIP_MAXFLOW_HANDOVER_NO_STALL_RULE", "LES_HIP_MAXFLOW_HANDOVER_NODES"):
-            monkeypatch.delenv(k, raising=False)
+        handed += sum(st["handed_cells"] for st in _handover_vs_launches_alone(pr, monkeypatch, name, shp, pays, dyadic))
     return handed
+
+
+def case_tiled_maxflow_handover_staging_growth(pr, monkeypatch, which, seed=13):
+    """The hand-over when the first check selects more than the first staging holds (16 cells, 140000 nodes rounded up to 4096): the collect kernel
+    parks nothing and reports what it wanted, the host grows the staging and collects again.  which: "cells" (20 cells of 40 x 30) or "nodes"
+    (2 cells of 300 x 260).  pr must be a FRESH pair: the staging is pooled per context and never shrinks.  Dyadic capacities, the checks of
+    case_tiled_maxflow_handover.  -> (cells, nodes) handed over"""
+    shapes, least = {"cells": ([(40, 30)] * 20, (17, 1)), "nodes": ([(300, 260)] * 2, (1, 143361))}[which]
+    pays = _random_cell_payloads(np.random.default_rng(seed), shapes, True)
+    stats = _handover_vs_launches_alone(pr, monkeypatch, "staging growth by " + which, shapes, pays, True, hand_nodes="100000000")
+    for st in stats:
+        print(f"staging growth by {which}: {st}")
+        assert st["handed_cells"] >= least[0] and st["handed_nodes"] >= least[1], f"{which}: the first selection fitted the first staging ({st})"
+    return stats[0]["handed_cells"], stats[0]["handed_nodes"]
 
 
 def _crop_payload(p, w, h, x0, y0, cw, ch):

@@ -465,6 +465,12 @@ def test_gpu_tiled_maxflow_handover(oracle_mod, monkeypatch):
         assert handed > 0
     finally:
         pr.close()
+    for which in ("cells", "nodes"):                                          # the first selection exceeds the first staging: a fresh context each
+        pr = pc.synth_pair(None, 270, 310, 4)
+        try:
+            pc.case_tiled_maxflow_handover_staging_growth(pr, monkeypatch, which)
+        finally:
+            pr.close()
 
 
 def test_gpu_cut_is_a_function_of_the_cell(mid, monkeypatch):

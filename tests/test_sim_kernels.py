@@ -267,6 +267,12 @@ def test_sim_tiled_maxflow_handover(sim_lib, oracle_mod, monkeypatch):
         assert pc.case_tiled_maxflow_handover(pr, monkeypatch, shapes=[(100, 70), (65, 31), (129, 129), (31, 65)]) > 0
     finally:
         pr.close()
+    for which in ("cells", "nodes"):                                          # the first selection exceeds the first staging: a fresh context each
+        pr = pc.synth_pair(sim_lib, 270, 310, 4)
+        try:
+            pc.case_tiled_maxflow_handover_staging_growth(pr, monkeypatch, which)
+        finally:
+            pr.close()
 
 
 def test_sim_cut_is_a_function_of_the_cell(sim_lib, oracle_mod, monkeypatch):
