@@ -12,16 +12,22 @@ hypotheses (disparity slices) are independent, so every rank aggregates 64 slice
 the evaluation count of the 1-GPU workload) with no data-path collective and replicated guide statistics; at N = 8 the ranks
 together hold exactly the 3000 x 2000 x 512 volume of configs[4].  Per-GPU work is fixed for every N: "weak" scaling (the
 default; `--scaling strong` splits the 512 slices of configs[4] as 512 / N per rank instead -- the two coincide at N = 8 -- and the
-record says which one ran).  N = 1 stays on configs[2] (the configuration the metric is quoted on) and also reports the per-rank
+record says which one ran).  N = 1 stays on configs[2] (the configuration the metric is quoted on) and with --full also reports the per-rank
 shape of the N > 1 runs as the sub-record `n8_rank_shape`, so that a 1 -> 8 curve has a like-for-like baseline.  At N > 1 the line
-also carries `e2e_sharded`: BASELINE configs[3] -- the two-view optimiser at the Adirondack-H shape with the views split over two
+of a --full run also carries `e2e_sharded`: BASELINE configs[3] -- the two-view optimiser at the Adirondack-H shape with the views split over two
 rank groups, the cells of every disjoint set sharded inside a group and one RCCL all-gather of the updated tiles per set -- so
 that the first multi-GPU run measures the path that HAS a collective, not only the collective-free one.
 
-At N = 1 the JSON line also carries the H2 (slanted planes, two volume taps) and H3 (LayerManager cell batches, the
-optimiser's geometry) measurements of the same build as sub-records (`h2`, `h3`), the copy ceiling measured in the same run
-(`roofline.peak_achievable`) and, with --e2e 1 (default), the end-to-end wall-clock of the MidV3 loop at the Adirondack-H shape
-(`e2e`: one view and two views + post-processing; north_star's third target).
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: set-up, warm-up, the K timed steps, the
+dump of `--dump-outputs`, and the result line (the roofline object is worked out from the timed steps themselves and from the committed
+counter passes; it costs no launch).  Everything else the benchmark measures or checks takes runs of its own and waits for `--full`:
+
+With --full, at N = 1 the JSON line also carries the H2 (slanted planes, two volume taps) and H3 (LayerManager cell batches, the
+optimiser's geometry) measurements of the same build as sub-records (`h2`, `h3`, `h3_batched`), the per-rank shapes of the N > 1 runs
+(`n8_rank_shape`, `n8_rank_shape_h2`, `config4_h2_one_gpu`), the copy ceiling measured in the same run (`roofline.peak_achievable`), with
+--e2e 1 (default) the end-to-end wall-clock of the MidV3 loop at the Adirondack-H shape (`e2e`: one view and two views +
+post-processing; north_star's third target) and the CPU baseline with the comparison against the oracle (`cpu_baseline`); at N > 1 it
+carries `e2e_sharded`.  --sub-steps, --e2e, --cpu-planes and --e2e-sharded trim those legs and mean nothing without --full.
 
 Prints ONE JSON line on rank 0.
 """
@@ -74,9 +80,16 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the cost maps of the last step (rank 0) as DIR/<name>.npy: all of them up to 48 MB, else up to two whole "
                          "slices and a fixed seeded sample (at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything besides the headline: the copy ceiling, the H2 / H3 / rank-shape sub-records, the end-to-end legs and the CPU "
+                         "baseline with its oracle comparison (minutes, not seconds); --sub-steps, --e2e, --cpu-planes and --e2e-sharded trim those legs "
+                         "and are ignored without it")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps, the dump, the line -- every leg below that launches or computes for a figure of its own is off
+        args.sub_steps, args.e2e, args.cpu_planes, args.e2e_sharded = 0, 0, 0, 0
 
     import torch
     import torch.distributed as dist
@@ -253,7 +266,7 @@ def main():
     value = evals_per_step * args.steps / elapsed / 1e6
     alg_bytes = evals_rank * bytes_per_eval + float(P) * 48.0        # per step and rank (H1 / H2: one launch)
     achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
-    ceiling = copy_ceiling()
+    ceiling = copy_ceiling() if args.full else None          # (launches of its own: 2 GiB of buffers, six copies)
 
     # HBM bytes per launch from the rocprofv3 PMC passes of the same command (FETCH_SIZE + WRITE_SIZE, separate passes,
     # tools/collect_profiles.sh): cannot be collected live inside this process, so the committed measurement is quoted --
@@ -299,6 +312,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": bool(args.full),
         "ms_per_step": round(elapsed / args.steps * 1e3, 4),
         "higher_is_better": True,
         "scaling": args.scaling if multi else "weak",

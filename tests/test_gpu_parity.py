@@ -1054,14 +1054,14 @@ def test_multi_gpu_rank_shape_whole_image_planes_vs_oracle(oracle_mod):
 
 
 def test_bench_record_fields_on_one_gpu():
-    """The driver's contract for the N = 1 line: one JSON line with the metric fields, the roofline object (with the co-bounds and the
+    """The driver's contract for the N = 1 line of a --full run: one JSON line with the metric fields, the roofline object (with the co-bounds and the
     source of the traffic figure) and the CPU baseline with its H2 / H3 samples; the sub-records of the other workloads."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--sub-steps", "2", "--e2e", "0", "--cpu-planes", "8"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--sub-steps", "2", "--e2e", "0", "--cpu-planes", "8"],
                        cwd=root, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -1100,7 +1100,7 @@ def test_bench_multi_rank_code_path_on_one_gpu(world):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, LES_BENCH_BACKEND="gloo", LES_BENCH_ONE_DEVICE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1", "--master-port", str(29533 + world),
-           os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1", "--height", "500", "--width", "700", "--ndisp", "8", "--cpu-planes", "0"]
+           os.path.join(root, "bench.py"), "--gpus", str(world), "--full", "--steps", "3", "--warmup", "1", "--height", "500", "--width", "700", "--ndisp", "8", "--cpu-planes", "0"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -1142,3 +1142,25 @@ def test_bench_dump_outputs_repeatable(tmp_path):
     assert dumps[0].tobytes() == dumps[1].tobytes()
     v = dumps[0][dumps[0] != 1e6]
     assert v.size > 0 and 0.0 < float(v.mean()) < 0.5         # (U[0,1) costs truncated at 0.5 and aggregated)
+
+
+def test_bench_plain_run_carries_the_headline_only():
+    """`bench.py` without --full: set-up, warm-up, the timed steps and the line -- the metric fields and the roofline figures that come out of the
+    timed steps, none of the legs that take runs of their own (sub-records, copy ceiling, end-to-end runs, CPU baseline), whatever the options
+    that trim those legs say."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--height", "200", "--width", "300", "--ndisp", "16",
+                        "--sub-steps", "2", "--e2e", "1", "--cpu-planes", "4"], cwd=root, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config", "roofline"):
+        assert k in d, k
+    assert d["full"] is False and d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0 and d["higher_is_better"] is True
+    assert d["roofline"]["kernel_ms"] > 0 and d["roofline"]["achieved"] > 0 and d["roofline"]["peak_achievable"] is None
+    for k in ("h2", "h3", "h3_batched", "n8_rank_shape", "n8_rank_shape_h2", "config4_h2_one_gpu", "e2e", "e2e_sharded", "cpu_baseline", "dumped_outputs"):
+        assert k not in d, k

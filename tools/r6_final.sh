@@ -11,5 +11,5 @@ python tools/prof_summary.py $O/e2e_ts --md > $O/round6_e2e_three_surfaces_kerne
 rm -rf $O/e2e $O/e2e_ts
 bash tools/lab/ab_cell_kernel.sh $O/ab_cell > $O/round6_cell_kernel_ab.log 2>&1
 bash tools/r6_e2e_ab.sh $O/ab > $O/round6_e2e_ab.log 2>&1
-python bench.py > $O/round6_bench.json 2> $O/round6_bench.err
+python bench.py --full > $O/round6_bench.json 2> $O/round6_bench.err
 tail -c 600 $O/round6_bench.json
