@@ -12,13 +12,18 @@ import sys
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import timing  # noqa: E402
 from localexpstereo_amd import api, pm, synth  # noqa: E402
 
 VALU_LANE_OPS = 256 * 2.4e9 * 64          # non-packed f32 VALU issue rate of the MI355X (lane-operations / s)
 
 
 def timed(fn, reps):
+    """Sorted ms of `reps` calls queued back to back, every pair of events recorded before the one synchronise: the one loop tools/timing.py does
+    not state (its clock synchronises after every timing); the median is timing.spread's."""
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
     for a, b in ev:
         a.record()
@@ -58,6 +63,7 @@ def main():
     run()
     torch.cuda.synchronize()
     ms = timed(run, args.reps)
+    med = timing.spread(ms, 3)["median"]
     # floor of this kernel in lane-operations per output and plane: per window tap one v_fma_f32, plus one v_sad_u8 and one shift per tap
     # and output shared by the 4 planes of a tile (the LDS reads of weights / costs and the f32 row sums are not counted)
     ops = (2 * R + 1) ** 2 * (1.0 + 2.0 / 4)
@@ -76,10 +82,10 @@ def main():
     ls = timed(step, args.reps * 4)
     bl.destroy()
     e.close()
-    print(json.dumps(dict(shape=[H, W], planes=n, windR=R, whole_image_pass_ms=round(ms[len(ms) // 2], 3), whole_image_pass_ms_all=[round(x, 3) for x in ms],
-                          floor_lane_ops_per_output=ops, floor_ms=round(floor_ms, 3), fraction_of_floor=round(floor_ms / ms[len(ms) // 2], 3),
+    print(json.dumps(dict(shape=[H, W], planes=n, windR=R, whole_image_pass_ms=med, whole_image_pass_ms_all=[round(x, 3) for x in ms],
+                          floor_lane_ops_per_output=ops, floor_ms=round(floor_ms, 3), fraction_of_floor=round(floor_ms / med, 3),
                           target_ms=40.0, finest_layer_unit=unit, finest_layer_cells_per_lockstep=int(len(cells)),
-                          lockstep_ms=round(ls[len(ls) // 2], 4))))
+                          lockstep_ms=timing.spread(ls, 4)["median"])))
 
 
 if __name__ == "__main__":

@@ -7,7 +7,8 @@
 
 Recorded:
   * timing at 1436 x 992 x 256 ("objects" scene of tools/e2e_bench.py, MidV3 energy, left view), chunk 32: the whole les_hip_confidence call (on the
-    view's own WTA map) next to the whole les_hip_wta_labels call -- host clock around enqueue + synchronise, medians of 20 after a warm-up;
+    view's own WTA map) next to the whole les_hip_wta_labels call -- host clock around enqueue + synchronise, each a group of one of
+    tools/timing.py (which states the protocol) after 3 warm-up calls;
   * per kernel: the profiler's job.  `rocprofv3 --kernel-trace --stats -d DIR -o NAME -- python tools/confidence_timing.py --calls` makes 10
     calls each of les_hip_wta_labels and les_hip_confidence on one context (the same slabs: both reduce the chunks the batch path writes for the
     same planes); --kernel-stats reads the *_kernel_stats.csv (or *_results.db) of two such runs (the run-to-run spread of the arg-min kernel, the parent's code,
@@ -31,7 +32,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 os.environ.setdefault("OMP_WAIT_POLICY", "passive")
 
-import speckle_timing as spk      # noqa: E402  (the scenes and the timing helpers)
+import speckle_timing as spk      # noqa: E402  (the scenes)
+import timing                     # noqa: E402
 
 H, W, D, CHUNK = spk.H, spk.W, spk.D, 32
 TAUS = (0.02, 0.05, 0.1)
@@ -40,13 +42,14 @@ KERNELS = ("les_slab_argmin_kernel", "les_slab_confidence_kernel", "les_slab_arg
 _note = spk._note
 
 
-def timing(torch, st, e, n):
-    sync = torch.cuda.synchronize
+def measure(torch, st, e, n):
+    clock = timing.Clock(torch, "cpu", sync=torch.cuda.synchronize)         # the host clock around enqueue + synchronise
+    timed = lambda f: timing.spread(timing.time_one(clock, f, n, warm=3), 4)
     lab, cost = e.wta_labels(0, chunk=CHUNK)
     conf = torch.empty((H, W), dtype=torch.float32, device="cuda")
     scale = float(e.raw_cost_max())
-    wta = spk._host_timed(sync, lambda: e.wta_labels(0, CHUNK, True, lab.data_ptr(), cost.data_ptr()), n)
-    cf = spk._host_timed(sync, lambda: e.confidence_ptr(0, lab.data_ptr(), CHUNK, 1.0, scale, conf.data_ptr()), n)
+    wta = timed(lambda: e.wta_labels(0, CHUNK, True, lab.data_ptr(), cost.data_ptr()))
+    cf = timed(lambda: e.confidence_ptr(0, lab.data_ptr(), CHUNK, 1.0, scale, conf.data_ptr()))
     rec = dict(shape=[W, H, D], chunk=CHUNK, wta_labels_call_ms=wta, confidence_call_ms=cf)
     _note(rec)
     return rec
@@ -173,15 +176,15 @@ def main():
         import torch
         import e2e_bench
         from localexpstereo_amd import api, io as lio, stereo
-        if a.device == "cuda" and not torch.cuda.is_available():
-            raise SystemExit("confidence_timing.py measures on the GPU: no HIP device")
+        if a.device == "cuda":
+            timing.require_gpu("confidence_timing.py")
         if a.calls or (not a.skip_timing and not a.small):
             st, e, ev, keep = spk.synthetic(api, lio, stereo, e2e_bench, "objects", a.device, a.lib)
             if a.calls:
                 calls_only(torch, e)
                 e.close()
                 return
-            rec["timing"] = timing(torch, st, e, a.timings)
+            rec["timing"] = measure(torch, st, e, a.timings)
             e.close()
             del keep
         if not a.skip_quality:
@@ -197,13 +200,11 @@ def main():
                 del keep
             rec["quality"] = rows
     if a.json:
-        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
-        json.dump(rec, open(a.json, "w"), indent=1)
+        timing.write_json(a.json, rec)
     md = markdown(rec)
     print(md)
     if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        open(a.out, "w").write(md + "\n")
+        timing.write_text(a.out, md + "\n")
 
 
 if __name__ == "__main__":

@@ -4,8 +4,8 @@
   python tools/costvol_timing.py [--out profiles/costvol_timing.json] [--reps 20]
 
 Shapes 1436 x 992 x 256 (Adirondack-H) and 1500 x 1000 x 256, both modes, random 8-bit images.  Every group of measurements runs in a child
-process of its own under its own time limit; the first child that fails ends the run.  Each number is the median of `reps` device-event timings
-after two warm-up calls.  Recorded per shape:
+process of its own under its own time limit; the first child that fails ends the run.  Each number is a group of one of tools/timing.py
+(which states the protocol): `reps` timings after two warm-up calls.  Recorded per shape:
   * builder: les_costvol_kernel alone and the two census launches (the library's own events, LES_HIP_COSTVOL_TIMING=1), and the whole
     les_hip_build_cost_volume call (events around it: allocation and release of its scratch included), with plain and with non-temporal stores;
     the dword store path on the same shape one column wider (W % 4 != 0);
@@ -22,33 +22,16 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+import timing  # noqa: E402
 
 SHAPES = [(1436, 992, 256), (1500, 1000, 256)]
 CHILD_SECONDS = 240
 
 
-def _spread(v):
-    v = np.asarray(v, np.float64)
-    return dict(median=round(float(np.median(v)), 4), min=round(float(v.min()), 4), max=round(float(v.max()), 4), n=int(len(v)))
-
-
-def _events(torch, fn, reps, warmup=2):
-    for _ in range(warmup):
-        fn()
-    out = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        torch.cuda.synchronize()
-        out.append(e0.elapsed_time(e1))
-    return out
-
-
-def child_builder(W, H, D, reps):
+def child_builder(torch, W, H, D, reps):
     import ctypes as C
-    import torch
     from localexpstereo_amd import api
     os.environ["LES_HIP_COSTVOL_TIMING"] = "1"
     L = api.load()
@@ -69,24 +52,22 @@ def child_builder(W, H, D, reps):
                     cen.append(a.value)
                     kern.append(b.value)
 
-                whole = _events(torch, call, reps)
-                rec.setdefault(name, {}).setdefault(f"mode{mode}", {})[nt] = dict(volume_kernel_ms=_spread(kern[-reps:]), census_two_images_ms=_spread(cen[-reps:]),
-                                                                                  whole_call_ms=_spread(whole))
+                whole = timing.time_one(timing.Clock(torch, "cuda"), call, reps, warm=2)
+                rec.setdefault(name, {}).setdefault(f"mode{mode}", {})[nt] = {k: timing.spread(v, 4) for k, v in (
+                    ("volume_kernel_ms", kern[-reps:]), ("census_two_images_ms", cen[-reps:]), ("whole_call_ms", whole))}
         del imL, imR, vol
     return rec
 
 
-def child_baselines(W, H, D, reps):
-    import torch
+def child_baselines(torch, W, H, D, reps):
     from localexpstereo_amd import api, synth
     rng = np.random.default_rng(1)
     imL, imR = (rng.integers(0, 256, (H, W, 3), dtype=np.uint8) for _ in range(2))
-    ad = _events(torch, lambda: synth.ad_volume(imL, imR, D, "cuda"), reps)
-    n = D * H * W
-    src, dst = torch.rand(n, device="cuda"), torch.empty(n, device="cuda")
-    copy = _events(torch, lambda: api._chk_lib(api.load(), api.load().les_hip_calib_copy(src.data_ptr(), dst.data_ptr(), n, 0, None)), reps)
-    wide = _events(torch, lambda: api._chk_lib(api.load(), api.load().les_hip_calib_copy_wide(src.data_ptr(), dst.data_ptr(), n, 0, None)), reps)
-    return dict(synth_ad_volume_ms=_spread(ad), calib_copy_ms=_spread(copy), calib_copy_wide_ms=_spread(wide))
+    clock = timing.Clock(torch, "cuda")
+    one = lambda f: timing.spread(timing.time_one(clock, f, reps, warm=2), 4)
+    ad = one(lambda: synth.ad_volume(imL, imR, D, "cuda"))
+    nbytes = 2 * 4 * D * H * W                                 # a copy of D H W floats
+    return dict(synth_ad_volume_ms=ad, calib_copy_ms=one(timing.copy_call(api, nbytes, None)), calib_copy_wide_ms=one(timing.copy_call(api, nbytes, None, wide=True)))
 
 
 def main():
@@ -97,10 +78,8 @@ def main():
     a = ap.parse_args()
     if a.child:
         what, (W, H, D) = a.child[0], (int(v) for v in a.child[1:])
-        import torch
-        if not torch.cuda.is_available():
-            raise SystemExit("costvol_timing.py measures on the GPU: no HIP device")
-        print("RESULT " + json.dumps((child_builder if what == "builder" else child_baselines)(W, H, D, a.reps)))
+        torch = timing.require_gpu("costvol_timing.py")
+        print("RESULT " + json.dumps((child_builder if what == "builder" else child_baselines)(torch, W, H, D, a.reps)))
         return
     shapes = {}
     for W, H, D in SHAPES:
@@ -124,10 +103,7 @@ def main():
                                                       ad_volume_over_builder_call=round(rec["synth_ad_volume_ms"]["median"] / min(v["whole_call_ms"]["median"] for v in by_store.values()), 2))
         shapes[f"{W}x{H}x{D}"] = rec
     out = dict(note="one MI355X, one run; medians of device-event timings after two warm-up calls", reps=a.reps, shapes=shapes)
-    print(json.dumps(out, indent=1))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(out, open(a.out, "w"), indent=1)
+    timing.write_record(a.out, out)
 
 
 if __name__ == "__main__":

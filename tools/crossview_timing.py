@@ -5,8 +5,8 @@
 
 Recorded:
   * warp_kernel: les_warp_labels_kernel at 1436 x 992 and 1500 x 1000 (planes of a piecewise-slanted scene, both source views), next to
-    les_hip_calib_copy of the same number of bytes the warp moves (49 B per pixel: two label maps read, one written, the hit byte) -- medians of
-    20 device-event timings after a warm-up, one launch per timing;
+    les_hip_calib_copy of the same number of bytes the warp moves (49 B per pixel: two label maps read, one written, the hit byte) -- each a
+    group of one of tools/timing.py (which states the protocol) after 3 warm-up calls, one launch per timing;
   * cross_fuse: the whole stereo.FastGCStereo.cross_fuse pass per view on the two views' solutions of the "objects" scene of
     tools/e2e_bench.py at 1436 x 992 x 256 (MidV3 energy and layers);
   * runs: that scene, two views, 2 PatchMatch + 5 graph-cut iterations at cross_view 0 / 1 / 5: seconds, each view's final energy (its labelling
@@ -14,8 +14,6 @@ Recorded:
     (les_hip_consistency_check at 1.5: 255 = inconsistent, 128 = maps outside the other view, per view) and bad-1.0 of the final left labelling.
 Nothing here is a gate: the quality figures are recorded, not asserted."""
 import argparse
-import ctypes as C
-import json
 import os
 import sys
 import time
@@ -27,16 +25,13 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 os.environ.setdefault("OMP_WAIT_POLICY", "passive")
 
+import timing  # noqa: E402
+
 H, W, D = 992, 1436, 256
 
 
 def _note(*a):
     print(*a, file=sys.stderr, flush=True)
-
-
-def _spread(v):
-    v = np.asarray(v, np.float64)
-    return dict(median=round(float(np.median(v)), 3), min=round(float(v.min()), 3), max=round(float(v.max()), 3), n=int(len(v)))
 
 
 def slanted_labels(h, w, seed, cell=40, maxd=200.0, slant=0.3):
@@ -57,28 +52,13 @@ def time_kernel(torch, api, h, w, timings):
     e.set_stream(torch.cuda.current_stream().cuda_stream)
     src, fb = (torch.from_numpy(slanted_labels(h, w, s)).cuda() for s in (1, 2))
     out, hit = torch.empty_like(src), torch.empty((h, w), dtype=torch.uint8, device="cuda")
-    n = (49 * h * w + 7) // 8                                  # floats a copy reads AND writes for the same traffic: 8 n bytes
-    a, b = torch.rand(n, device="cuda"), torch.empty(n, device="cuda")
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-    def timed(f):
-        for _ in range(3):
-            f()
-        torch.cuda.synchronize()
-        t = []
-        for _ in range(timings):
-            ev0.record()
-            f()
-            ev1.record()
-            torch.cuda.synchronize()
-            t.append(1e3 * ev0.elapsed_time(ev1))
-        return t
+    clock = timing.Clock(torch, "cuda")
+    one = lambda f: timing.spread(1e3 * np.asarray(timing.time_one(clock, f, timings, warm=3)), 3)
     rec = dict(shape=[w, h], bytes_moved=49 * h * w)
     for mode in (0, 1):
-        rec[f"warp_us_src_view{mode}"] = _spread(timed(lambda: e.warp_labels(mode, src.data_ptr(), fb.data_ptr(), out.data_ptr(), hit.data_ptr())))
+        rec[f"warp_us_src_view{mode}"] = one(lambda: e.warp_labels(mode, src.data_ptr(), fb.data_ptr(), out.data_ptr(), hit.data_ptr()))
         rec[f"hit_share_src_view{mode}"] = round(float(hit.float().mean()), 4)
-    rec["copy_us"] = _spread(timed(lambda: e._chk(e.L.les_hip_calib_copy(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), C.c_size_t(n), 0, stream))))
+    rec["copy_us"] = one(timing.copy_call(api, rec["bytes_moved"], torch.cuda.current_stream().cuda_stream))
     _note("kernel", rec["shape"], rec["warp_us_src_view0"], rec["warp_us_src_view1"], rec["copy_us"])
     rec["warp_over_copy"] = round(max(rec["warp_us_src_view0"]["median"], rec["warp_us_src_view1"]["median"]) / rec["copy_us"]["median"], 3)
     e.close()
@@ -91,11 +71,9 @@ def main():
     ap.add_argument("--timings", type=int, default=20)
     ap.add_argument("--skip-runs", action="store_true", help="the kernel timings only")
     a = ap.parse_args()
-    import torch
+    torch = timing.require_gpu("crossview_timing.py")
     import e2e_bench
     from localexpstereo_amd import api, io as lio, pm, stereo
-    if not torch.cuda.is_available():
-        raise SystemExit("crossview_timing.py measures on the GPU: no HIP device")
     rec = dict(timings=a.timings, warp_kernel=[time_kernel(torch, api, h, w, a.timings) for h, w in ((992, 1436), (1000, 1500))])
     if not a.skip_runs:
         imL, imR, gt, volL = e2e_bench.scene_inputs("objects", H, W, D, "cuda")
@@ -151,12 +129,9 @@ def main():
             passes.append(dict(driver_seconds_with_warm_starts=round(wall, 4), **{f"view{m}": {k: (round(v, 4) if isinstance(v, float) else v)
                                                                                            for k, v in st.cross_stats[m].items()} for m in (0, 1)}))
         rec.update(shape=[W, H, D], scene="objects", maps="both views' solutions of seed 1 before the post-processing (2 PatchMatch + 5 graph-cut iterations)",
-                   cross_fuse=dict(passes=passes, **{f"fuse_seconds_view{m}": _spread([q[f"view{m}"]["seconds"] for q in passes[1:]]) for m in (0, 1)}), runs=runs)
+                   cross_fuse=dict(passes=passes, **{f"fuse_seconds_view{m}": timing.spread([q[f"view{m}"]["seconds"] for q in passes[1:]], 3) for m in (0, 1)}), runs=runs)
         e.close()
-    print(json.dumps(rec, indent=1))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(rec, open(a.out, "w"), indent=1)
+    timing.write_record(a.out, rec)
 
 
 if __name__ == "__main__":

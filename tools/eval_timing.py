@@ -10,19 +10,24 @@
                                                         (a run of its own): 100 evaluations per shape, region energies of a lock-step per layer
   python tools/eval_timing.py stats <kernel_stats.csv> [--out f.json]    the eval / region kernels' rows of that run, per-call averages
 
+tools/timing.py states the protocol; routes: the two routes are one group (one warm-up call each), the back-to-back device route a group of one
+without a warm-up, both on the host clock, and the enqueued evaluations 5 bursts of 200.
 The traffic floor of one evaluation is 29 B per pixel (16 label + 4 cost + 4 guide + 4 ground truth + 1 mask) over the peak HBM rate."""
 import argparse
 import csv
+import itertools
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 os.environ.setdefault("OMP_WAIT_POLICY", "passive")
+
+import timing  # noqa: E402
 
 SHAPES = ((1000, 1500), (992, 1436))
 PW = dict(lambda_=0.5, th_smooth=1.0, omega=10.0, epsilon=0.01)
@@ -44,9 +49,8 @@ def _scene(H, W, seed=1):
     return e, imL, torch.from_numpy(lab).cuda(), torch.from_numpy(cost).cuda(), gt
 
 
-def _spread(v):
-    v = np.asarray(v, np.float64)
-    return dict(median=float(np.median(v)), min=float(v.min()), max=float(v.max()), n=int(len(v)), samples=[round(float(x), 4) for x in v])
+def spread(v):
+    return timing.spread(v, samples=True)
 
 
 def routes(repeats=15):
@@ -71,35 +75,15 @@ def routes(repeats=15):
             g.costs[0][...] = cost.cpu().numpy()
             return g.data_cost(0), g.smoothness_cost(0), ref.evaluate(disp)
 
-        for f in (device_route, host_route):
-            f()
-        td, th = [], []
-        for _ in range(repeats):
-            for f, acc in ((device_route, td), (host_route, th)):
-                torch.cuda.synchronize()
-                t = time.perf_counter()
-                f()
-                torch.cuda.synchronize()
-                acc.append(1e3 * (time.perf_counter() - t))
-        tb = []                      # the device route alone, back to back (no idle GPU in between)
-        for _ in range(repeats):
-            torch.cuda.synchronize()
-            t = time.perf_counter()
-            device_route()
-            torch.cuda.synchronize()
-            tb.append(1e3 * (time.perf_counter() - t))
+        host = timing.Clock(torch, "cpu", sync=torch.cuda.synchronize)
+        t, _ = timing.time_calls(host, dict(device=device_route, host=host_route), repeats, warm=1)
+        tb = timing.time_one(host, device_route, repeats, warm=0)        # the device route alone, back to back (no idle GPU in between)
         # device time of an enqueued evaluation: events around 200 of them (two kernels each, back to back on one stream)
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        per = []
-        for _ in range(5):
-            a.record()
-            for k in range(200):
-                ev.evaluate(lab.data_ptr(), cost.data_ptr(), mode=0, index=k, **PW)
-            b.record()
-            torch.cuda.synchronize()
-            per.append(1e3 * a.elapsed_time(b) / 200)
+        k = itertools.count()
+        enqueue = lambda: ev.evaluate(lab.data_ptr(), cost.data_ptr(), mode=0, index=next(k) % 200, **PW)
+        per = 1e3 * np.asarray(timing.time_calls(timing.Clock(torch, "cuda"), dict(enqueue=enqueue), 0, warm=0, burst=200, burst_rounds=5)[1]["enqueue"])
         floor_us = 29.0 * H * W / PEAK_HBM * 1e6
-        out[f"{W}x{H}"] = dict(device_route_ms=_spread(td), host_route_ms=_spread(th), device_route_back_to_back_ms=_spread(tb), enqueued_evaluation_us=_spread(per), traffic_floor_us=floor_us,
+        out[f"{W}x{H}"] = dict(device_route_ms=spread(t["device"]), host_route_ms=spread(t["host"]), device_route_back_to_back_ms=spread(tb), enqueued_evaluation_us=spread(per), traffic_floor_us=floor_us,
                                enqueued_over_floor=float(np.median(per)) / floor_us)
         ev.close(); g.close(); e.close()
     return out
@@ -163,8 +147,8 @@ def inner(repeats=3):
                 same = same and ref.tobytes() == lab.tobytes()
             if name == "on":
                 rows = len(st.inner_log)
-    return dict(shape=f"{W}x{H}", iterations="2 + 5", seconds_log_off=_spread(rec["off"]), seconds_rows_on_device=_spread(rec["device_rows"]),
-                seconds_inner_log_on=_spread(rec["on"]), inner_rows=rows, synchronising_calls=syncs, labels_identical=same)
+    return dict(shape=f"{W}x{H}", iterations="2 + 5", seconds_log_off=spread(rec["off"]), seconds_rows_on_device=spread(rec["device_rows"]),
+                seconds_inner_log_on=spread(rec["on"]), inner_rows=rows, synchronising_calls=syncs, labels_identical=same)
 
 
 def kernels():
@@ -203,16 +187,13 @@ def main():
     ap.add_argument("csv", nargs="?")
     ap.add_argument("--out")
     a = ap.parse_args()
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
     if a.what == "kernels":
         kernels()
         return
     rec = {a.what: routes() if a.what == "routes" else inner() if a.what == "inner" else stats(a.csv)}
     print(json.dumps(rec, indent=1))
-    if a.out:
-        old = json.load(open(a.out)) if os.path.exists(a.out) else {}
-        old.update(rec)
-        json.dump(old, open(a.out, "w"), indent=1)
+    if a.out:                                                       # (the file keeps the groups of earlier runs)
+        timing.write_json(a.out, dict(json.load(open(a.out)) if os.path.exists(a.out) else {}, **rec))
 
 
 if __name__ == "__main__":

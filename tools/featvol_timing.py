@@ -6,7 +6,8 @@ the table profiles/featvol.md (summarised in DESIGN 3.2k).
 
 Shape 1436 x 992 x 256 (Adirondack-H), both modes, C = 25 (the ZNCC 5 x 5 descriptors of two random 8-bit images) and C = 64 (unit-normalised
 Gaussian features).  Every group of measurements runs in a child process of its own under its own time limit; the first child that fails ends the
-run.  Each number is the median of `reps` device-event timings (the library's own events, LES_HIP_FEATVOL_TIMING=1) after two warm-up calls.
+run.  Each number is the median of `reps` timings by the library's own events (LES_HIP_FEATVOL_TIMING=1) after two warm-up calls; the copy is a
+group of one of tools/timing.py, which states the protocol.
 Three yardsticks from the same run:
   (a) les_hip_calib_copy of D H W floats (a copy moves twice the bytes the kernel writes);
   (b) les_costvol_kernel at the same shape (LES_HIP_COSTVOL_TIMING=1): the store-bound builder of the AD-Census volume;
@@ -23,6 +24,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+import timing  # noqa: E402
 
 SHAPE = (1436, 992, 256)
 CHANNELS = (25, 64)
@@ -31,19 +35,13 @@ SEG, CHUNK, TILES = 128, 64, 3                      # kFvSeg, kFvChunk, kFvTiles
 SIMDS, HZ, MFMA_CYCLES = 256 * 4, 2.4e9, 64         # MI355X: 256 CUs x 4 SIMDs, 2.4 GHz; v_mfma_f32_32x32x2_f32 issues every 64 cycles per SIMD
 
 
-def _spread(v):
-    v = np.asarray(v, np.float64)
-    return dict(median=round(float(np.median(v)), 4), min=round(float(v.min()), 4), max=round(float(v.max()), 4), n=int(len(v)))
-
-
 def mfma_floor_ms(W, H, D, Cn):
     n = -(-W // SEG) * H * -(-D // CHUNK) * 4 * TILES * -(-Cn // 2)
     return 1e3 * n * MFMA_CYCLES / SIMDS / HZ
 
 
-def child_volume(W, H, D, Cn, reps):
+def child_volume(torch, W, H, D, Cn, reps):
     import ctypes as C
-    import torch
     from localexpstereo_amd import api
     os.environ["LES_HIP_FEATVOL_TIMING"] = "1"
     L = api.load()
@@ -60,7 +58,7 @@ def child_volume(W, H, D, Cn, reps):
                 assert L.les_hip_featvol_last_times(C.byref(a), C.byref(b)) == 0
                 desc.append(a.value)
             feats.append(f)
-        rec["patch_features_5x5_one_image_ms"] = _spread(desc[2:2 + reps] + desc[4 + reps:])
+        rec["patch_features_5x5_one_image_ms"] = timing.spread(desc[2:2 + reps] + desc[4 + reps:], 4)
     else:
         feats = [torch.nn.functional.normalize(torch.randn((Cn, H, W), device="cuda"), dim=0).contiguous() for _ in range(2)]
     vol = torch.empty((D, H, W), dtype=torch.float32, device="cuda")
@@ -70,30 +68,20 @@ def child_volume(W, H, D, Cn, reps):
             api.build_feature_volume(feats[0].data_ptr(), feats[1].data_ptr(), vol.data_ptr(), Cn, D, H, W, mode)
             assert L.les_hip_featvol_last_times(C.byref(a), C.byref(b)) == 0
             ms.append(b.value)
-        rec[f"mode{mode}"] = dict(volume_kernel_ms=_spread(ms[2:]))
+        rec[f"mode{mode}"] = dict(volume_kernel_ms=timing.spread(ms[2:], 4))
     return rec
 
 
-def child_baselines(W, H, D, Cn, reps):
+def child_baselines(torch, W, H, D, Cn, reps):
     import ctypes as C
-    import torch
     from localexpstereo_amd import api
     os.environ["LES_HIP_COSTVOL_TIMING"] = "1"
     L = api.load()
     rng = np.random.default_rng(1)
-    n = D * H * W
-    src, dst = torch.rand(n, device="cuda"), torch.empty(n, device="cuda")
-    copy = []
-    for _ in range(2 + reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        api._chk_lib(L, L.les_hip_calib_copy(src.data_ptr(), dst.data_ptr(), n, 0, None))
-        e1.record()
-        torch.cuda.synchronize()
-        copy.append(e0.elapsed_time(e1))
-    del src
+    copy = timing.copy_call(api, 2 * 4 * D * H * W, None)                       # a copy of D H W floats
+    rec = dict(calib_copy_ms=timing.spread(timing.time_one(timing.Clock(torch, "cuda"), copy, reps, warm=2), 4))
+    dst = copy.buffers[1]                                                       # (the builder writes where the copy wrote)
     imL, imR = (torch.from_numpy(rng.integers(0, 256, (H, W, 3), dtype=np.uint8)).cuda() for _ in range(2))
-    rec = dict(calib_copy_ms=_spread(copy[2:]))
     a, b = C.c_float(), C.c_float()
     for mode in (0, 1):
         ms = []
@@ -101,7 +89,7 @@ def child_baselines(W, H, D, Cn, reps):
             api.build_cost_volume(imL.data_ptr(), imR.data_ptr(), dst.data_ptr(), D, H, W, mode)
             assert L.les_hip_costvol_last_times(C.byref(a), C.byref(b)) == 0
             ms.append(b.value)
-        rec[f"costvol_kernel_mode{mode}_ms"] = _spread(ms[2:])
+        rec[f"costvol_kernel_mode{mode}_ms"] = timing.spread(ms[2:], 4)
     return rec
 
 
@@ -134,10 +122,8 @@ def main():
     a = ap.parse_args()
     W, H, D = SHAPE
     if a.child:
-        import torch
-        if not torch.cuda.is_available():
-            raise SystemExit("featvol_timing.py measures on the GPU: no HIP device")
-        print("RESULT " + json.dumps((child_volume if a.child[0] == "volume" else child_baselines)(W, H, D, int(a.child[1]), a.reps)))
+        torch = timing.require_gpu("featvol_timing.py")
+        print("RESULT " + json.dumps((child_volume if a.child[0] == "volume" else child_baselines)(torch, W, H, D, int(a.child[1]), a.reps)))
         return
     out = dict(note="one MI355X, one run; medians of device-event timings after two warm-up calls", reps=a.reps, shape=f"{W}x{H}x{D}",
                band_efficiency=round(CHUNK / (32 * TILES), 4))
@@ -151,14 +137,10 @@ def main():
         out[key] = json.loads(lines[-1][len("RESULT "):])
         if Cn:
             out[key]["mfma_issue_floor_ms"] = round(mfma_floor_ms(W, H, D, Cn), 4)
-    print(json.dumps(out, indent=1))
+    timing.write_record(a.out, out)
     print(markdown(out))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(out, open(a.out, "w"), indent=1)
     if a.md:
-        os.makedirs(os.path.dirname(os.path.abspath(a.md)), exist_ok=True)
-        open(a.md, "w").write(markdown(out))
+        timing.write_text(a.md, markdown(out))
 
 
 if __name__ == "__main__":

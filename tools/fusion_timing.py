@@ -6,13 +6,12 @@
 The synthetic "objects" scene of tools/e2e_bench.py at 1436 x 992 x 256 under the MidV3 energy and layers (1 % / 3 % / 9 % of the width).  The
 two label maps are the scene's one-view solutions from seeds 1 and 2 (one PatchMatch and two graph-cut iterations each).  Recorded:
   * graph_kernels: per layer, the device time of a lock-step of les_move_graph_kernel<true> (label map: fusion) next to les_move_graph_kernel<false>
-    (one plane per cell: expansion) on the same batches (every disjoint set of the layer; events around 20 launches back to back, the two instances
-    alternating, 5 rounds, median), and their ratio;
+    (one plane per cell: expansion) on the same batches (every disjoint set of the layer; one group of tools/timing.py, which states the
+    protocol: one warm-up call, no single launches, 5 rounds of bursts of 20 launches, median), and their ratio;
   * fuse: the whole stereo.FastGCStereo.fuse pass (warm start excluded) and the dense pass inside it (host clock around a synchronise), the share
     of non-submodular pairs, and the three energies E(a), E(b), E(fuse(a, b)) from the device evaluator.
 Nothing here is a gate."""
 import argparse
-import json
 import os
 import sys
 import time
@@ -24,12 +23,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 os.environ.setdefault("OMP_WAIT_POLICY", "passive")
 
+import timing  # noqa: E402
+
 H, W, D = 992, 1436, 256
-
-
-def _spread(v):
-    v = np.asarray(v, np.float64)
-    return dict(median=round(float(np.median(v)), 3), min=round(float(v.min()), 3), max=round(float(v.max()), 3), n=int(len(v)))
 
 
 def main():
@@ -38,11 +34,9 @@ def main():
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     a = ap.parse_args()
-    import torch
+    torch = timing.require_gpu("fusion_timing.py")
     import e2e_bench
     from localexpstereo_amd import api, gc as lgc, io as lio, pm, stereo
-    if not torch.cuda.is_available():
-        raise SystemExit("fusion_timing.py measures on the GPU: no HIP device")
     imL, imR, gt, volL = e2e_bench.scene_inputs("objects", H, W, D, "cuda")
     p = dict(stereo.PARAMS_GF, lambda_=0.5, windR=20, th_col=0.5)
     tl, tr = lio.ingest_volumes(volL, None, device="cuda")
@@ -72,7 +66,7 @@ def main():
     b_dev = torch.from_numpy(np.ascontiguousarray(lb, np.float32)).cuda()
     e.unary_labels(b_dev.data_ptr(), r.prop.data_ptr(), mode=0, check=True)
     pw = g.params
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    clock = timing.Clock(torch, "cuda")
     kernels = {}
     for li, layer in enumerate(r.shards):
         rec = dict(locksteps=0, cells=0, nodes=0, fusion_us=[], expansion_us=[])
@@ -81,25 +75,15 @@ def main():
             sh.batch.propose(api.PROPOSE_EXPANSION, r.labels.data_ptr(), sh.rng.data_ptr(), sh.planes.data_ptr(), m=0)
             fus = lambda: sh.batch.fusion_graph(b_dev.data_ptr(), r.labels.data_ptr(), r.cur.data_ptr(), r.prop.data_ptr(), sh.payload.data_ptr(), mode=0, **pw)
             exp = lambda: sh.batch.expansion_graph(sh.planes.data_ptr(), r.labels.data_ptr(), r.cur.data_ptr(), r.prop.data_ptr(), sh.payload.data_ptr(), mode=0, **pw)
-            for f in (fus, exp):
-                f()
-            t = {fus: [], exp: []}
-            for _ in range(a.rounds):
-                for f in (fus, exp):
-                    ev0.record()
-                    for _k in range(a.launches):
-                        f()
-                    ev1.record()
-                    torch.cuda.synchronize()
-                    t[f].append(1e3 * ev0.elapsed_time(ev1) / a.launches)
-            rec["fusion_us"].append(float(np.median(t[fus])))
-            rec["expansion_us"].append(float(np.median(t[exp])))
+            _, t = timing.time_calls(clock, dict(fusion=fus, expansion=exp), 0, warm=1, burst=a.launches, burst_rounds=a.rounds)
+            rec["fusion_us"].append(1e3 * float(np.median(t["fusion"])))
+            rec["expansion_us"].append(1e3 * float(np.median(t["expansion"])))
             rec["locksteps"] += 1
             rec["cells"] += sh.n
             rec["nodes"] += sh.graph_nodes
         f_sum, e_sum = sum(rec["fusion_us"]), sum(rec["expansion_us"])
-        kernels[f"layer{li}"] = dict(unit=st.units[li], locksteps=rec["locksteps"], cells=rec["cells"], nodes=rec["nodes"], fusion_us_per_lockstep=_spread(rec["fusion_us"]),
-                                     expansion_us_per_lockstep=_spread(rec["expansion_us"]), fusion_us_layer=round(f_sum, 2), expansion_us_layer=round(e_sum, 2),
+        kernels[f"layer{li}"] = dict(unit=st.units[li], locksteps=rec["locksteps"], cells=rec["cells"], nodes=rec["nodes"], fusion_us_per_lockstep=timing.spread(rec["fusion_us"], 3),
+                                     expansion_us_per_lockstep=timing.spread(rec["expansion_us"], 3), fusion_us_layer=round(f_sum, 2), expansion_us_layer=round(e_sum, 2),
                                      ratio=round(f_sum / e_sum, 3))
     r.close(); g.close()
 
@@ -121,13 +105,10 @@ def main():
     E_b, bad_b = st.log[0]["energy"], st.log[0]["all"]
     rec = dict(shape=[W, H, D], scene="objects", maps="one-view solutions of seeds 1 and 2 (1 PatchMatch + 2 graph-cut iterations)", solve_seconds=solve_seconds,
                launches_per_timing=a.launches, rounds=a.rounds, graph_kernels=kernels,
-               fuse=dict(passes=passes, fuse_seconds=_spread([q["fuse_seconds"] for q in passes[1:]]), dense_seconds=_spread([q["dense_seconds"] for q in passes[1:]]),
+               fuse=dict(passes=passes, fuse_seconds=timing.spread([q["fuse_seconds"] for q in passes[1:]], 3), dense_seconds=timing.spread([q["dense_seconds"] for q in passes[1:]], 3),
                          E_a=passes[-1]["E_a"], E_b=E_b, E_fused=passes[-1]["E_fused"], bad1_a=passes[-1]["bad1_a"], bad1_b=bad_b, bad1_fused=passes[-1]["bad1_fused"],
                          nonsubmodular_share=passes[-1]["nonsubmodular_share"]))
-    print(json.dumps(rec, indent=1))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(rec, open(a.out, "w"), indent=1)
+    timing.write_record(a.out, rec)
     e.close()
 
 

@@ -16,11 +16,16 @@ import sys
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import timing  # noqa: E402
 from localexpstereo_amd import api, pm, synth  # noqa: E402
 
 
 def timed(fn, reps):
+    """Sorted ms of `reps` calls queued back to back, every pair of events recorded before the one synchronise: the one loop tools/timing.py does
+    not state (its clock synchronises after every timing); the median is timing.spread's."""
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
     for a, b in ev:
         a.record()
@@ -76,9 +81,9 @@ def main():
         step()
         torch.cuda.synchronize()
         ls = timed(step, args.reps * 4)
-        res[f"{name}_interp{interp}"] = dict(kernel_kind=b.kernel_kind(0), whole_image_pass_ms=round(ms[len(ms) // 2], 3),
+        res[f"{name}_interp{interp}"] = dict(kernel_kind=b.kernel_kind(0), whole_image_pass_ms=timing.spread(ms, 3)["median"],
                                       whole_image_pass_ms_all=[round(x, 3) for x in ms], lockstep_kernel_kind=bl.kernel_kind(0),
-                                      lockstep_ms=round(ls[len(ls) // 2], 4))
+                                      lockstep_ms=timing.spread(ls, 4)["median"])
     for name in ("clean", "wide"):
         for interp in (0, 2):
             res[f"{name}_interp{interp}_over_linear"] = round(res[f"{name}_interp{interp}"]["whole_image_pass_ms"] /

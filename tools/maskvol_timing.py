@@ -10,11 +10,8 @@ Recorded on a 256 x 992 x 1436 float volume, both views' volumes (mode 0 and mod
   (b) les_hip_fill_invalid with the valid masks of the rig of tools/unrectify_timing.py (2 degree rotations, all eight distortion
       coefficients), on a volume of its own;
   *   les_hip_calib_copy of the bytes each rewrites (it reads and writes that many).
-Every figure is the median of `--timings` device-event timings of ONE launch each, taken in rounds (each round times every call once, so a
-drift of the machine hits them alike) after a warm-up of every call.  Nothing here is a gate."""
+One group of tools/timing.py (which states the protocol): `--timings` rounds after 3 warm-up calls, no bursts.  Nothing here is a gate."""
 import argparse
-import ctypes as C
-import json
 import os
 import sys
 
@@ -24,7 +21,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-import rectify_timing as rt  # noqa: E402  (the rig and the spread are that tool's)
+import rectify_timing as rt  # noqa: E402  (the rig is that tool's)
+import timing  # noqa: E402
 
 H, W, D = rt.H, rt.W, 256
 
@@ -45,15 +43,10 @@ def main():
     ap.add_argument("--out", help="path without extension: <out>.md and <out>.json are written")
     ap.add_argument("--timings", type=int, default=30)
     a = ap.parse_args()
-    import torch
+    torch = timing.require_gpu("maskvol_timing.py")
     from localexpstereo_amd import api, stereo
-    if not torch.cuda.is_available():
-        raise SystemExit("maskvol_timing.py measures on the GPU: no HIP device")
-    L = api.load()
     stream = torch.cuda.current_stream().cuda_stream
-    K0 = np.array([[1500.0, 0, 0.5 * (W - 1) + 3.0], [0, 1495.0, 0.5 * (H - 1) - 2.0], [0, 0, 1]])
-    K1 = np.array([[1490.0, 0, 0.5 * (W - 1) - 4.0], [0, 1502.0, 0.5 * (H - 1) + 1.5], [0, 0, 1]])
-    rect = stereo.Rectifier(K0, rt.DIST0, K1, rt.DIST1, rt._rot(2.0, -2.0, 2.0), (-0.2, 0.004, -0.003), raw_size=(H, W))
+    rect = rt.rig(stereo)
     black = torch.zeros((H, W, 3), dtype=torch.uint8, device="cuda")
     r = rect.rectify(black, black)
     valid = [r["validL"].to(torch.uint8).contiguous(), r["validR"].to(torch.uint8).contiguous()]
@@ -67,11 +60,8 @@ def main():
                                                                                       validJ=valid[1 - mode].data_ptr(), stream=stream)
         entries[f"a_mode{mode}"] = rewritten(ones, ones, mode)
         entries[f"b_mode{mode}"] = rewritten(valid[mode] != 0, valid[1 - mode] != 0, mode)
-    copies = {}
     for k, n in entries.items():
-        copies[k] = (torch.rand(n, device="cuda"), torch.empty(n, device="cuda"), n)
-        s, d_, n_ = copies[k]
-        calls[f"copy_{k}"] = lambda s=s, d_=d_, n_=n_: api._chk_lib(L, L.les_hip_calib_copy(C.c_void_p(s.data_ptr()), C.c_void_p(d_.data_ptr()), C.c_size_t(n_), 0, C.c_void_p(stream)))
+        calls[f"copy_{k}"] = timing.copy_call(api, 8 * n, stream)           # as many floats as the pass rewrites, read and written
     # the two entries write the same bytes: checked here once more, on this volume
     check = vol_a[:8].clone()
     ref = check.clone()
@@ -79,18 +69,8 @@ def main():
     api.fill_invalid(check.data_ptr(), 8, H, W, 0, stream=stream)
     torch.cuda.synchronize()
     assert torch.equal(ref.view(torch.int32), check.view(torch.int32))
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for f in calls.values():
-        for _ in range(3):
-            f()
-    torch.cuda.synchronize()
-    single = {k: [] for k in calls}
-    for _ in range(a.timings):
-        for k, f in calls.items():
-            ev0.record(); f(); ev1.record()
-            torch.cuda.synchronize()
-            single[k].append(1e3 * ev0.elapsed_time(ev1))
-    us = {k: rt._spread(v) for k, v in single.items()}
+    single, _ = timing.time_calls(timing.Clock(torch, "cuda"), calls, a.timings, warm=3)
+    us = {k: timing.spread(1e3 * np.asarray(v), 3) for k, v in single.items()}
     ratios = {}
     for mode in (0, 1):
         old, new, masked = (us[f"{k}_mode{mode}"] for k in ("a_fill_out_of_view", "a_fill_invalid_null", "b_fill_invalid_masks"))
@@ -98,30 +78,26 @@ def main():
                                      null_over_own_copy=round(new["median"] / us[f"copy_a_mode{mode}"]["median"], 3),
                                      fill_out_of_view_over_own_copy=round(old["median"] / us[f"copy_a_mode{mode}"]["median"], 3),
                                      masks_over_own_copy=round(masked["median"] / us[f"copy_b_mode{mode}"]["median"], 3))
-    rec = dict(device=f"{torch.cuda.get_device_name(0)} ({getattr(torch.cuda.get_device_properties(0), 'gcnArchName', '?')})", shape=[D, H, W], timings=a.timings,
+    rec = dict(device=timing.device_label(torch), shape=[D, H, W], timings=a.timings,
                valid_share=[round(float((v != 0).float().mean()), 4) for v in valid], valid_both_share=round(float(((valid[0] != 0) & (valid[1] != 0)).float().mean()), 4),
                rewritten_entries=entries, rewritten_MB={k: round(4e-6 * n, 1) for k, n in entries.items()}, single_launch_us=us, ratios=ratios)
-    print(json.dumps(rec, indent=1))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(rec, open(a.out + ".json", "w"), indent=1)
-        with open(a.out + ".md", "w") as f:
-            f.write(f"# Nearest-valid row fill of a cost volume: kernel timings\n\n`python tools/maskvol_timing.py --out profiles/maskvol` on {rec['device']}, a float volume of "
-                    f"{D} x {H} x {W}; medians of {a.timings} device-event timings of one launch each (rounds over all calls, after a warm-up).  (a): both masks null, "
-                    f"against `les_hip_fill_out_of_view` on the same volume (the same bytes).  (b): the valid masks of a rig with 2 degree rotations "
-                    f"({100 * rec['valid_share'][0]:.1f} % / {100 * rec['valid_share'][1]:.1f} % of the pixels valid, {100 * rec['valid_both_share']:.1f} % in both).  "
-                    f"copy: `les_hip_calib_copy` of as many floats as the pass rewrites (it reads and writes them).  The numbers are in `maskvol.json`.\n\n")
-            f.write("| call | one launch, us (min .. max) | entries rewritten, MB |\n|---|---|---|\n")
-            for k in calls:
-                key = k.split("_")[0] + "_" + k.split("_")[-1] if not k.startswith("copy_") else k[5:]
-                f.write(f"| {k} | {us[k]['median']} ({us[k]['min']} .. {us[k]['max']}) | {rec['rewritten_MB'][key]} |\n")
-            f.write("\n| view | null masks / fill_out_of_view | fill_out_of_view / copy | null masks / copy | masks / copy |\n|---|---|---|---|---|\n")
-            for m, r_ in ratios.items():
-                f.write(f"| {m} | {r_['null_over_fill_out_of_view']} | {r_['fill_out_of_view_over_own_copy']} | {r_['null_over_own_copy']} | {r_['masks_over_own_copy']} |\n")
-            f.write("\nWhat was measured is above; nothing was fixed in advance.  From the code, not from a profile: `les_fill_out_of_view_kernel` launches a "
-                    "work-item per entry of the volume, most of which return at once; `les_fill_invalid_kernel` launches 256 work-items per row and 32 slices, "
-                    "makes the ok flags of a row as words from the staged mask bits, and touches the volume only where a word has a hole.  "
-                    "Not measured: `rocprofv3` kernel times, other sizes.\n")
+    md = (f"# Nearest-valid row fill of a cost volume: kernel timings\n\n`python tools/maskvol_timing.py --out profiles/maskvol` on {rec['device']}, a float volume of "
+          f"{D} x {H} x {W}; medians of {a.timings} device-event timings of one launch each (rounds over all calls, after a warm-up).  (a): both masks null, "
+          f"against `les_hip_fill_out_of_view` on the same volume (the same bytes).  (b): the valid masks of a rig with 2 degree rotations "
+          f"({100 * rec['valid_share'][0]:.1f} % / {100 * rec['valid_share'][1]:.1f} % of the pixels valid, {100 * rec['valid_both_share']:.1f} % in both).  "
+          f"copy: `les_hip_calib_copy` of as many floats as the pass rewrites (it reads and writes them).  The numbers are in `maskvol.json`.\n\n"
+          "| call | one launch, us (min .. max) | entries rewritten, MB |\n|---|---|---|\n")
+    for k in calls:
+        key = k.split("_")[0] + "_" + k.split("_")[-1] if not k.startswith("copy_") else k[5:]
+        md += f"| {k} | {us[k]['median']} ({us[k]['min']} .. {us[k]['max']}) | {rec['rewritten_MB'][key]} |\n"
+    md += "\n| view | null masks / fill_out_of_view | fill_out_of_view / copy | null masks / copy | masks / copy |\n|---|---|---|---|---|\n"
+    for m, r_ in ratios.items():
+        md += f"| {m} | {r_['null_over_fill_out_of_view']} | {r_['fill_out_of_view_over_own_copy']} | {r_['null_over_own_copy']} | {r_['masks_over_own_copy']} |\n"
+    md += ("\nWhat was measured is above; nothing was fixed in advance.  From the code, not from a profile: `les_fill_out_of_view_kernel` launches a "
+           "work-item per entry of the volume, most of which return at once; `les_fill_invalid_kernel` launches 256 work-items per row and 32 slices, "
+           "makes the ok flags of a row as words from the staged mask bits, and touches the volume only where a word has a hole.  "
+           "Not measured: `rocprofv3` kernel times, other sizes.\n")
+    timing.write_record(a.out, rec, md)
 
 
 if __name__ == "__main__":

@@ -7,12 +7,11 @@ Recorded:
   * kernel: les_plane_fit_kernel at 1436 x 992 and 1500 x 1000 for radius 5, 10 and 15, from a label map and from a disparity map (slanted planes in
     cells of 48 pixels, 2 % isolated outliers, 1 % non-finite; the default parameters; fallback and kind map given), next to the kernel's issue floor
     -- LANE_OPS_PER_TAP x (2 r + 1)^2 x pixels / 3.93e13 lane-operations/s, counted from the compiled tap loop -- and to les_hip_calib_copy_wide of
-    the bytes the call reads and writes; medians of 20 device-event timings after a warm-up;
+    the bytes the call reads and writes; each a group of one of tools/timing.py (which states the protocol) after 3 warm-up calls;
   * runs (unless --skip-runs): the two synthetic scenes of tools/e2e_bench.py at 1436 x 992 x 256, two views, MidV3 energy and layers, no PatchMatch
     iteration and 5 graph-cut iterations from labeling="wta" and from labeling="wta+planes": the Evaluator log, the fusion's report, wall clock.
 Nothing here is a gate."""
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -25,6 +24,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 os.environ.setdefault("OMP_WAIT_POLICY", "passive")
 
+import timing  # noqa: E402
+
 D = 256
 SIZES = ((992, 1436), (1000, 1500))
 RADII = (5, 10, 15)
@@ -34,26 +35,6 @@ LANE_OPS_PER_SECOND = 3.93e13
 
 def _note(*a):
     print(*a, file=sys.stderr, flush=True)
-
-
-def _spread(v):
-    v = np.asarray(v, np.float64)
-    return dict(median=round(float(np.median(v)), 4), min=round(float(v.min()), 4), max=round(float(v.max()), 4), n=int(len(v)))
-
-
-def _timed(torch, f, timings):
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(3):
-        f()
-    torch.cuda.synchronize()
-    t = []
-    for _ in range(timings):
-        ev0.record()
-        f()
-        ev1.record()
-        torch.cuda.synchronize()
-        t.append(ev0.elapsed_time(ev1))
-    return t
 
 
 def test_map(h, w, seed):
@@ -82,16 +63,15 @@ def time_size(torch, api, synth, h, w, timings):
     disp = ((lab[..., 0] * xs + lab[..., 1] * ys) + lab[..., 2]).contiguous()
     fb = lab.clone()
     out, kind = torch.empty((h, w, 4), device="cuda"), torch.empty((h, w), device="cuda", dtype=torch.uint8)
-    big = [torch.empty(8 * P, device="cuda") for _ in range(2)]
     rec = dict(shape=[w, h], kernels=[])
+    clock = timing.Clock(torch, "cuda")
+    one = lambda f: timing.spread(timing.time_one(clock, f, timings, warm=3), 4)
     for form in ("labels", "disparities"):
         bytes_moved = P * ((16 if form == "labels" else 4) + 4 + 16 + 16 + 1)            # the input map, the guide, the fallback; the labels and the kind map
-        n = bytes_moved // 8                                                         # the copy reads and writes 4 bytes per element
-        copy = _spread(_timed(torch, lambda: e._chk(e.L.les_hip_calib_copy_wide(C.c_void_p(big[0].data_ptr()), C.c_void_p(big[1].data_ptr()), C.c_size_t(n), 0,
-                                                                                 C.c_void_p(stream.cuda_stream))), timings))
+        copy = one(timing.copy_call(api, bytes_moved, stream.cuda_stream, wide=True, random=False))
         for r in RADII:
             args = (0, lab.data_ptr() if form == "labels" else None, None if form == "labels" else disp.data_ptr(), fb.data_ptr(), out.data_ptr(), kind.data_ptr())
-            ms = _spread(_timed(torch, lambda: e.fit_planes_ptr(*args, radius=r), timings))
+            ms = one(lambda: e.fit_planes_ptr(*args, radius=r))
             floor = LANE_OPS_PER_TAP * (2 * r + 1) ** 2 * P / LANE_OPS_PER_SECOND * 1e3
             k = torch.bincount(kind.flatten().to(torch.int64), minlength=3).tolist()
             row = dict(form=form, radius=r, ms=ms, issue_floor_ms=round(floor, 4), over_issue_floor=round(ms["median"] / floor, 3), bytes_moved=bytes_moved,
@@ -140,11 +120,9 @@ def main():
     ap.add_argument("--skip-runs", action="store_true", help="the kernel timings only")
     ap.add_argument("--skip-kernels", action="store_true", help="the end-to-end runs only")
     a = ap.parse_args()
-    import torch
+    torch = timing.require_gpu("planefit_timing.py")
     import e2e_bench
     from localexpstereo_amd import api, io as lio, stereo, synth
-    if not torch.cuda.is_available():
-        raise SystemExit("planefit_timing.py measures on the GPU: no HIP device")
     rec = dict(timings=a.timings, lane_ops_per_tap=LANE_OPS_PER_TAP)
     if a.out and os.path.exists(a.out):                        # (the two halves may be taken in two runs)
         rec.update({k: v for k, v in json.load(open(a.out)).items() if k in ("sizes", "runs")})
@@ -152,10 +130,7 @@ def main():
         rec["sizes"] = [time_size(torch, api, synth, h, w, a.timings) for h, w in SIZES]
     if not a.skip_runs:
         rec["runs"] = [time_runs(torch, api, stereo, lio, e2e_bench, scene) for scene in ("objects", "three_surfaces")]
-    print(json.dumps(rec, indent=1))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(rec, open(a.out, "w"), indent=1)
+    timing.write_record(a.out, rec)
 
 
 if __name__ == "__main__":

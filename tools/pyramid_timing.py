@@ -4,9 +4,9 @@
   python tools/pyramid_timing.py [--out profiles/pyramid_timing.json] [--reps 20] [--skip-runs] [--skip-kernels] [--scenes objects,three_surfaces,cones]
 
 Every group of measurements runs in a child process of its own under its own time limit; the first child that fails ends the run.
-  * kernels, at 1436 x 992 x 256 (medians of `reps` device-event timings after two warm-up calls): les_pool_volume_kernel with non-temporal and
-    with plain loads, and on the dword path (the same shape one column wider); les_pool_image_kernel; les_upsample_labels_kernel; the whole
-    HipCostVolumeEnergy.half() call (wall clock: pools, guide statistics, march tables, tiled copy of both views); each next to
+  * kernels, at 1436 x 992 x 256 (each a group of one of tools/timing.py, which states the protocol: `reps` timings after two warm-up calls):
+    les_pool_volume_kernel with non-temporal and with plain loads, and on the dword path (the same shape one column wider); les_pool_image_kernel;
+    les_upsample_labels_kernel; the whole HipCostVolumeEnergy.half() call (wall clock: pools, guide statistics, march tables, tiled copy of both views); each next to
     les_hip_calib_copy of the bytes the kernel moves (read + written) / 8 floats -- a copy of n floats moves 8 n bytes;
   * runs: the two synthetic scenes of tools/e2e_bench.py at 1436 x 992 x 256 and the cones crop of tests/golden (64 disparities, AD-Census
     volumes), two views, MidV3 energy and layers: the Evaluator log of the default run (2 PatchMatch + 5 graph-cut iterations) and of the "half"
@@ -26,45 +26,22 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
+import timing  # noqa: E402
+
 W, H, D = 1436, 992, 256
 CHILD_SECONDS = {"kernels": 240, "objects": 420, "three_surfaces": 420, "cones": 240}
 
 
-def _spread(v):
-    v = np.asarray(v, np.float64)
-    return dict(median=round(float(np.median(v)), 4), min=round(float(v.min()), 4), max=round(float(v.max()), 4), n=int(len(v)))
-
-
-def _events(torch, fn, reps, warmup=2):
-    for _ in range(warmup):
-        fn()
-    out = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        torch.cuda.synchronize()
-        out.append(e0.elapsed_time(e1))
-    return out
-
-
-def child_kernels(reps):
-    import torch
+def child_kernels(torch, reps):
     from localexpstereo_amd import api
-    L = api.load()
     hs = api.half_size
     rec = dict(shape=[W, H, D])
-    copy_src = torch.rand(D * H * W, device="cuda")
-    copy_dst = torch.empty_like(copy_src)
-
-    def copy_of(nbytes):
-        n = max(1, int(nbytes) // 8)
-        return _spread(_events(torch, lambda: api._chk_lib(L, L.les_hip_calib_copy(copy_src.data_ptr(), copy_dst.data_ptr(), n, 0, None)), reps))
+    clock = timing.Clock(torch, "cuda")
+    timed = lambda f: timing.time_one(clock, f, reps, warm=2)
 
     def entry(ms, nbytes):
-        c = copy_of(nbytes)
-        return dict(ms=_spread(ms), bytes=int(nbytes), GBps=round(nbytes / float(np.median(ms)) / 1e6, 1), calib_copy_same_bytes_ms=c,
+        c = timing.spread(timed(timing.copy_call(api, nbytes, None)), 4)
+        return dict(ms=timing.spread(ms, 4), bytes=int(nbytes), GBps=round(nbytes / float(np.median(ms)) / 1e6, 1), calib_copy_same_bytes_ms=c,
                     over_copy=round(float(np.median(ms)) / c["median"], 3))
 
     for name, w in (("pool_volume", W), ("pool_volume_dword_path_W_plus_1", W + 1)):
@@ -73,13 +50,13 @@ def child_kernels(reps):
         nbytes = 4 * (vol.numel() + out.numel())
         for nt in (("nontemporal", "plain") if w == W else ("plain",)):
             os.environ["LES_HIP_PYRAMID_NT"] = "1" if nt == "nontemporal" else "0"
-            ms = _events(torch, lambda: api.pool_volume(vol.data_ptr(), out.data_ptr(), D, H, w), reps)
+            ms = timed(lambda: api.pool_volume(vol.data_ptr(), out.data_ptr(), D, H, w))
             rec[name if w != W else f"{name}_{nt}"] = entry(ms, nbytes)
         os.environ.pop("LES_HIP_PYRAMID_NT", None)
         del vol, out
     im = torch.randint(0, 256, (H, W, 3), dtype=torch.uint8, device="cuda")
     imh = torch.empty((hs(H), hs(W), 3), dtype=torch.uint8, device="cuda")
-    rec["pool_image"] = entry(_events(torch, lambda: api.pool_image(im.data_ptr(), imh.data_ptr(), H, W), reps), im.numel() + imh.numel())
+    rec["pool_image"] = entry(timed(lambda: api.pool_image(im.data_ptr(), imh.data_ptr(), H, W)), im.numel() + imh.numel())
     # the upsample and the whole half() call on a context of that shape
     rng = np.random.default_rng(1)
     imL = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
@@ -93,12 +70,12 @@ def child_kernels(reps):
         walls.append(1e3 * (time.perf_counter() - t0))
         if len(walls) < 3:
             half.close()
-    rec["half_call_wall_ms"] = _spread(walls)
+    rec["half_call_wall_ms"] = timing.spread(walls, 4)
     src = torch.zeros((half.H, half.W, 4), device="cuda")
     src[..., 2] = torch.rand((half.H, half.W), device="cuda") * 100 + 5
     up = lambda: e.upsample_labels(half, src, with_kind=True)
     # per full pixel: its guide word, a plane written, a kind byte; per half pixel (through the cache): a guide word and a plane
-    rec["upsample_labels"] = entry(_events(torch, up, reps), H * W * (4 + 16 + 1) + half.H * half.W * (4 + 16))
+    rec["upsample_labels"] = entry(timed(up), H * W * (4 + 16 + 1) + half.H * half.W * (4 + 16))
     half.close()
     e.close()
     return rec
@@ -174,10 +151,8 @@ def main():
     ap.add_argument("--child")
     a = ap.parse_args()
     if a.child:
-        import torch
-        if not torch.cuda.is_available():
-            raise SystemExit("pyramid_timing.py measures on the GPU: no HIP device")
-        rec = child_kernels(a.reps) if a.child == "kernels" else child_cones() if a.child == "cones" else child_scene(a.child)
+        torch = timing.require_gpu("pyramid_timing.py")
+        rec = child_kernels(torch, a.reps) if a.child == "kernels" else child_cones() if a.child == "cones" else child_scene(a.child)
         print("RESULT " + json.dumps(rec))
         return
     out = dict(note="one MI355X, one run; kernel numbers are medians of device-event timings after two warm-up calls", reps=a.reps)
@@ -200,8 +175,7 @@ def main():
             out["runs"] = [r for r in out.get("runs", []) if r["scene"] != rec["scene"]] + [rec]
         print(json.dumps(rec, indent=1), flush=True)
         if a.out:                                                   # (written after every group: a later group's failure keeps the earlier ones)
-            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-            json.dump(out, open(a.out, "w"), indent=1)
+            timing.write_json(a.out, out)
 
 
 if __name__ == "__main__":

@@ -6,9 +6,9 @@
   python tools/reproject_timing.py --kernel-trace CSV --out profiles/reproject_timing.json     # merge the profiler's per-kernel figures
 
 Recorded, at 1436 x 992 and 1500 x 1000, for slanted planes in 48-pixel cells and for the same map with 10 % of the pixels invalid (NaN):
-  * les_hip_reproject (one kernel) and les_hip_mesh (four launches together): medians of 20 device-event timings after a warm-up, the events
-    recorded on the stream the context launches on, each next to les_hip_calib_copy_wide over the bytes the call reads and writes (counted from
-    the shapes and the mesh's own counts: BYTES below);
+  * les_hip_reproject (one kernel) and les_hip_mesh (four launches together): each a group of one of tools/timing.py (which states the protocol),
+    20 timings after 3 warm-up calls, the events recorded on the stream the context launches on, each next to les_hip_calib_copy_wide over
+    the bytes the call reads and writes (counted from the shapes and the mesh's own counts: bytes_moved below);
   * the whole FastGCStereo.reconstruct call (host clock: it ends with the results on the host);
   * each of the four mesh launches: the profiler's job.  `rocprofv3 --kernel-trace --output-format csv -d DIR -o NAME -- python
     tools/reproject_timing.py --calls` in a run of its own makes 20 calls per shape and input; --kernel-trace reads the *_kernel_trace.csv it
@@ -17,28 +17,24 @@ Recorded, at 1436 x 992 and 1500 x 1000, for slanted planes in 48-pixel cells an
 Nothing here is a gate."""
 import argparse
 import csv
-import ctypes as C
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 os.environ.setdefault("OMP_WAIT_POLICY", "passive")
+
+import timing  # noqa: E402
 
 SHAPES = ((992, 1436), (1000, 1500))
 CELL = 48
 CALIB = dict(f=3997.684, cx=700.0, cy=500.0, doffs=131.111, baseline=193.001)
 KERNELS = ("les_reproject_kernel", "les_mesh_count_kernel", "les_mesh_scan_kernel", "les_mesh_vertices_kernel", "les_mesh_triangles_kernel")
 N = 20
-
-
-def _med(v):
-    v = np.asarray(v, np.float64)
-    return dict(median=round(float(np.median(v)), 4), min=round(float(v.min()), 4), max=round(float(v.max()), 4), n=int(len(v)))
 
 
 def make_labels(H, W, invalid, seed=5):
@@ -59,40 +55,6 @@ def bytes_moved(P, nv, nt):
     return dict(reproject=P * (16 + 12 + 12 + 1),
                 mesh_count=P * (16 + 1), mesh_vertices=P * (1 + 4) + nv * 4, mesh_triangles=P * (16 + 1 + 4) + nt * 12,
                 mesh=P * (16 + 1) + P * (1 + 4) + nv * 4 + P * (16 + 1 + 4) + nt * 12)
-
-
-class Clock:
-    """Device events on the stream the context launches on (GPU), or the host clock around a synchronise (the simulator rehearsal)."""
-
-    def __init__(self, torch, e, device):
-        self.torch, self.e, self.gpu = torch, e, device != "cpu"
-        self.stream = None
-        if self.gpu:
-            self.stream = torch.cuda.Stream()
-            e.set_stream(self.stream.cuda_stream)
-
-    def stream_ptr(self):
-        return C.c_void_p(self.stream.cuda_stream) if self.gpu else None
-
-    def timed(self, f, n=N, warm=3):
-        for _ in range(warm):
-            f()
-        self.e.synchronize()
-        out = []
-        for _ in range(n):
-            if self.gpu:
-                a, b = self.torch.cuda.Event(enable_timing=True), self.torch.cuda.Event(enable_timing=True)
-                a.record(self.stream)
-                f()
-                b.record(self.stream)
-                b.synchronize()
-                out.append(a.elapsed_time(b))
-            else:
-                t0 = time.perf_counter()
-                f()
-                self.e.synchronize()
-                out.append((time.perf_counter() - t0) * 1e3)
-        return _med(out)
 
 
 def context(api, H, W, lib):
@@ -126,7 +88,12 @@ def measure(torch, api, lio, stereo, shapes, lib, device):
         P = H * W
         e, im = context(api, H, W, lib)
         try:
-            clock = Clock(torch, e, device)
+            stream = None
+            if device != "cpu":                                 # (the events go on the stream the context launches on)
+                stream = torch.cuda.Stream()
+                e.set_stream(stream.cuda_stream)
+            clock = timing.Clock(torch, device, stream=stream, sync=e.synchronize)
+            timed = lambda f: timing.spread(timing.time_one(clock, f, N, warm=3), 4)
             st = stereo.FastGCStereo(e, im, im, dict(lambda_=0.5, windR=2, th_col=0.5), device=device, seed=1)
             calib, jump = lio.calib3d(CALIB), float(st.p["th_smooth"])
             row = {}
@@ -137,21 +104,16 @@ def measure(torch, api, lio, stereo, shapes, lib, device):
                 rp(); ms(); e.synchronize()
                 nv, nt = (int(v) for v in b["counts"].cpu())
                 by = bytes_moved(P, nv, nt)
-                r = dict(vertices=nv, triangles=nt, bytes=by, reproject_ms=clock.timed(rp), mesh_four_launches_ms=clock.timed(ms))
-                big = [torch.empty(max(by.values()) // 8 + 4, dtype=torch.float32, device=device) for _ in range(2)]
+                r = dict(vertices=nv, triangles=nt, bytes=by, reproject_ms=timed(rp), mesh_four_launches_ms=timed(ms))
                 for k in ("reproject", "mesh", "mesh_count", "mesh_vertices", "mesh_triangles"):
-                    nfl = by[k] // 8 // 4 * 4                               # the copy reads and writes 4 bytes per float
-                    r[f"copy_wide_{k}_bytes_ms"] = clock.timed(lambda: e._chk(e.L.les_hip_calib_copy_wide(C.c_void_p(big[0].data_ptr()), C.c_void_p(big[1].data_ptr()),
-                                                                                                          C.c_size_t(nfl), 0, clock.stream_ptr())))
+                    r[f"copy_wide_{k}_bytes_ms"] = timed(timing.copy_call(api, by[k], stream.cuda_stream if stream else None, wide=True,
+                                                                          device="cpu" if device == "cpu" else 0, lib=lib, random=False))
                 r["reproject_over_copy"] = round(r["reproject_ms"]["median"] / r["copy_wide_reproject_bytes_ms"]["median"], 2)
                 r["mesh_over_copy"] = round(r["mesh_four_launches_ms"]["median"] / r["copy_wide_mesh_bytes_ms"]["median"], 2)
-                t = []
-                for k in range(3 + N):
-                    t0 = time.perf_counter()
-                    out = st.reconstruct(lab, calib)
-                    t.append((time.perf_counter() - t0) * 1e3)
+                out = {}                                        # (host clock, no synchronise: the call ends with the results on the host)
+                whole = timing.time_one(timing.Clock(torch, "cpu"), lambda: out.update(st.reconstruct(lab, calib)), N, warm=3)
                 assert len(out["vertices"]) == nv and len(out["triangles"]) == nt
-                r["reconstruct_whole_call_host_ms"] = _med(t[3:])
+                r["reconstruct_whole_call_host_ms"] = timing.spread(whole, 4)
                 row[name] = r
                 print(f"{W} x {H} {name}:", json.dumps({k: v for k, v in r.items() if k != "bytes"}), file=sys.stderr, flush=True)
             rec["shapes"][f"{W}x{H}"] = row
@@ -218,11 +180,7 @@ def main():
             calls_only(torch, api, lio, shapes, args.lib, args.device)
             return
         rec = measure(torch, api, lio, stereo, shapes, args.lib, args.device)
-    text = json.dumps(rec, indent=1)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        open(args.out, "w").write(text + "\n")
-    print(text)
+    timing.write_record(args.out, rec)
 
 
 if __name__ == "__main__":

@@ -6,15 +6,14 @@
 Recorded:
   * sizes: les_hip_sgm_labels over a resident 256-slice U[0,1) volume at 1436 x 992 and 1500 x 1000, 4 and 8 paths -- the whole call (device events
     around it, LES_HIP_SGM_TIMING off) and every kernel of it (transpose, each direction, read-out: the library's own event brackets,
-    LES_HIP_SGM_TIMING=1), medians of 20 timings after a warm-up; next to them the bytes each kernel has to move, computed from the shapes
-    (byte_model below), and les_hip_calib_copy_wide moving the same number of bytes in the same run (whole copies of the volume, 2 V bytes each);
+    LES_HIP_SGM_TIMING=1), the whole call a group of one of tools/timing.py (which states the protocol) after 3 warm-up calls; next to them the
+    bytes each kernel has to move, computed from the shapes (byte_model below), and les_hip_calib_copy_wide moving the same number of bytes in the same
+    run (whole copies of the volume, 2 V bytes each);
   * runs (unless --skip-runs): the two synthetic scenes of tools/e2e_bench.py at 1436 x 992 x 256, two views, MidV3 energy and layers: the
     Evaluator log of the default run (2 PatchMatch + 5 graph-cut iterations) and of the "wta", "wta+planes", "sgm" and "sgm+planes" starts at
     0 + 5 iterations -- energy after 1 / 3 / 5 iterations, bad-1.0 after the post-processing, seconds -- and FastGCStereo.sgm((0, 1)) alone.
 Nothing here is a gate."""
 import argparse
-import ctypes as C
-import json
 import os
 import sys
 import time
@@ -26,6 +25,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 os.environ.setdefault("OMP_WAIT_POLICY", "passive")
 
+import timing  # noqa: E402
+
 D = 256
 SIZES = ((992, 1436), (1000, 1500))
 PATHS = (4, 8)
@@ -33,11 +34,6 @@ PATHS = (4, 8)
 
 def _note(*a):
     print(*a, file=sys.stderr, flush=True)
-
-
-def _spread(v):
-    v = np.asarray(v, np.float64)
-    return dict(median=round(float(np.median(v)), 4), min=round(float(v.min()), 4), max=round(float(v.max()), 4), n=int(len(v)))
 
 
 def byte_model(h, w, k, paths):
@@ -49,21 +45,6 @@ def byte_model(h, w, k, paths):
     return dict(V=v, per_kernel=per, total=sum(per))
 
 
-def _timed(torch, f, timings, warm=3):
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(warm):
-        f()
-    torch.cuda.synchronize()
-    t = []
-    for _ in range(timings):
-        ev0.record()
-        f()
-        ev1.record()
-        torch.cuda.synchronize()
-        t.append(ev0.elapsed_time(ev1))
-    return t
-
-
 def time_size(torch, api, synth, h, w, timings):
     P = h * w
     gen = torch.Generator(device="cuda")
@@ -73,22 +54,20 @@ def time_size(torch, api, synth, h, w, timings):
                                 volumes_on_device=True, shape=(D, h, w))
     stream = torch.cuda.current_stream()
     e.set_stream(stream.cuda_stream)
-    out = torch.empty((D, h, w), device="cuda", dtype=torch.float32)
     labels, cost = torch.empty((h, w, 4), device="cuda"), torch.empty((h, w), device="cuda")
     rec = dict(shape=[w, h, D], workspace_bytes=e.sgm_workspace_bytes(), penalties=[float(x) for x in e.sgm_penalties()])
-    n = D * P
-
-    def copy():
-        e._chk(e.L.les_hip_calib_copy_wide(C.c_void_p(vol.data_ptr()), C.c_void_p(out.data_ptr()), C.c_size_t(n), 0, C.c_void_p(stream.cuda_stream)))
+    clock = timing.Clock(torch, "cuda")
+    one = lambda f: timing.spread(timing.time_one(clock, f, timings, warm=3), 4)
+    copy = timing.copy_call(api, 2 * 4 * D * P, stream.cuda_stream, wide=True)          # one whole copy of the volume: 2 V bytes
     for paths in PATHS:
         bm = byte_model(h, w, D, paths)
         r = dict(byte_model=bm)
         call = lambda: e.sgm_labels(0, paths, None, None, True, labels.data_ptr(), cost.data_ptr())
         os.environ.pop("LES_HIP_SGM_TIMING", None)
-        r["whole_call_ms"] = _spread(_timed(torch, call, timings))
+        r["whole_call_ms"] = one(call)
         copies = bm["total"] // (2 * bm["V"])                  # whole copies of the volume that move the call's bytes
         assert copies * 2 * bm["V"] == bm["total"]
-        r["copy_wide_same_bytes_ms"] = _spread(_timed(torch, lambda: [copy() for _ in range(copies)], timings))
+        r["copy_wide_same_bytes_ms"] = one(lambda: [copy() for _ in range(copies)])
         r["copy_wide_copies"] = copies
         r["whole_call_over_copy"] = round(r["whole_call_ms"]["median"] / r["copy_wide_same_bytes_ms"]["median"], 3)
         r["whole_call_GBps"] = round(bm["total"] / r["whole_call_ms"]["median"] / 1e6, 1)
@@ -100,7 +79,7 @@ def time_size(torch, api, synth, h, w, timings):
         os.environ.pop("LES_HIP_SGM_TIMING", None)
         per = np.asarray(per)
         names = ["transpose"] + [f"direction_{i}" for i in range(paths)] + ["readout"]
-        r["kernels"] = {nm: dict(ms=_spread(per[:, i]), bytes=bm["per_kernel"][i], GBps=round(bm["per_kernel"][i] / float(np.median(per[:, i])) / 1e6, 1))
+        r["kernels"] = {nm: dict(ms=timing.spread(per[:, i], 4), bytes=bm["per_kernel"][i], GBps=round(bm["per_kernel"][i] / float(np.median(per[:, i])) / 1e6, 1))
                         for i, nm in enumerate(names)}
         r["kernels_sum_ms"] = round(float(np.median(per.sum(1))), 4)
         rec[f"paths{paths}"] = r
@@ -158,20 +137,15 @@ def main():
     ap.add_argument("--skip-runs", action="store_true", help="the kernel and whole-call timings only")
     ap.add_argument("--skip-kernels", action="store_true", help="the end-to-end runs only")
     a = ap.parse_args()
-    import torch
+    torch = timing.require_gpu("sgm_timing.py")
     import e2e_bench
     from localexpstereo_amd import api, io as lio, stereo, synth
-    if not torch.cuda.is_available():
-        raise SystemExit("sgm_timing.py measures on the GPU: no HIP device")
     rec = dict(timings=a.timings)
     if not a.skip_kernels:
         rec["sizes"] = [time_size(torch, api, synth, h, w, a.timings) for h, w in SIZES]
     if not a.skip_runs:
         rec["runs"] = [time_runs(torch, api, stereo, lio, e2e_bench, scene) for scene in ("objects", "three_surfaces")]
-    print(json.dumps(rec, indent=1))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(rec, open(a.out, "w"), indent=1)
+    timing.write_record(a.out, rec)
 
 
 if __name__ == "__main__":

@@ -8,7 +8,8 @@
 Recorded:
   * timing at 1436 x 992 ("objects" scene of tools/e2e_bench.py, MidV3 energy, one view): les_hip_speckle_mask (100, 1.0) on a finished graph-cut map
     (2 PatchMatch + 5 graph-cut iterations: few large components) and on the raw winner-take-all map (very many small ones): the whole call (host
-    clock around it: it synchronises, and allocates and frees its 12 B/px of scratch) -- medians of 20 after a warm-up -- next to
+    clock around it: it synchronises, and allocates and frees its 12 B/px of scratch) -- each a group of one of tools/timing.py (which states the
+    protocol) after 3 warm-up calls -- next to
     les_hip_calib_copy of the bytes it cannot avoid (16 B/px of labels read, 1 B/px written) and to the one-view les_hip_post_process_speckle
     (mask + dilation + fill + weighted median, windR 20) on the same map.  The two maps are saved under --maps (default: the temporary directory);
   * per kernel: the profiler's job.  `rocprofv3 --kernel-trace --stats -d DIR -o NAME -- python tools/speckle_timing.py --calls gc --maps ...` (and
@@ -20,7 +21,6 @@ Recorded:
 Nothing here is a gate."""
 import argparse
 import csv
-import ctypes as C
 import json
 import os
 import sys
@@ -34,6 +34,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 os.environ.setdefault("OMP_WAIT_POLICY", "passive")
 
+import timing  # noqa: E402
+
 H, W, D = 992, 1436, 256
 PAIRS = ((100, 1.0), (400, 1.0), (100, 2.0))      # at most three; the first is where the issue starts
 TIMED = (100, 1.0)
@@ -43,24 +45,6 @@ KERNELS = ("les_disparity_kernel", "les_speckle_tile_kernel", "les_speckle_merge
 
 def _note(*a):
     print(*a, file=sys.stderr, flush=True)
-
-
-def _med(v):
-    v = np.asarray(v, np.float64)
-    return dict(median=round(float(np.median(v)), 4), min=round(float(v.min()), 4), max=round(float(v.max()), 4), n=int(len(v)))
-
-
-def _host_timed(sync, f, n):
-    for _ in range(3):
-        f()
-    t = []
-    for _ in range(n):
-        sync()
-        t0 = time.perf_counter()
-        f()
-        sync()
-        t.append((time.perf_counter() - t0) * 1e3)
-    return _med(t)
 
 
 def synthetic(api, lio, stereo, e2e_bench, scene, device, lib, h=H, w=W, d=D):
@@ -116,8 +100,9 @@ def quality(stereo, st, e, ev, name, pm, it):
     return rows
 
 
-def timing(torch, api, stereo, st, e, maps_dir, n):
-    sync = torch.cuda.synchronize                           # (the calibration copy runs on the default stream)
+def measure(torch, api, stereo, st, e, maps_dir, n, lib):
+    clock = timing.Clock(torch, "cpu", sync=torch.cuda.synchronize)         # the host clock: the calls synchronise themselves
+    timed = lambda f, n: timing.spread(timing.time_one(clock, f, n, warm=3), 4)
     P = H * W
     st.log = []
     gc, _ = st.run(5, (0,), 2)
@@ -126,23 +111,21 @@ def timing(torch, api, stereo, st, e, maps_dir, n):
     np.save(os.path.join(maps_dir, "gc.npy"), gc)
     np.save(os.path.join(maps_dir, "wta.npy"), wta)
     np.save(os.path.join(maps_dir, "imL.npy"), np.asarray(st.imL))
-    big = [torch.empty(3 * P, device="cuda") for _ in range(2)]
-    nfl = 17 * P // 8                                            # the copy reads and writes 4 bytes per float
-    copy = _host_timed(sync, lambda: e._chk(e.L.les_hip_calib_copy(C.c_void_p(big[0].data_ptr()), C.c_void_p(big[1].data_ptr()), C.c_size_t(nfl), 0, None)), n)
+    copy = timed(timing.copy_call(api, 17 * P, None, lib=lib, random=False), n)             # (on the default stream)
     rec = dict(shape=[W, H], pair=list(TIMED), calib_copy_17_bytes_per_pixel_ms=copy, maps={})
     for name, lab in (("gc", gc), ("wta", wta)):
         t = torch.from_numpy(np.ascontiguousarray(lab)).cuda()
         mask = torch.empty((H, W), dtype=torch.uint8, device="cuda")
         root = torch.empty((H, W), dtype=torch.int32, device="cuda")
         size = torch.empty((H, W), dtype=torch.int32, device="cuda")
-        call = _host_timed(sync, lambda: e.speckle_mask_ptr(t.data_ptr(), *TIMED, mask.data_ptr()), n)
+        call = timed(lambda: e.speckle_mask_ptr(t.data_ptr(), *TIMED, mask.data_ptr()), n)
         e.speckle_mask_ptr(t.data_ptr(), *TIMED, mask.data_ptr(), root.data_ptr(), size.data_ptr())
         work = t.clone()
 
         def post():
             work.copy_(t)
             e.post_process(work.data_ptr(), None, 1.5, st.p["omega"], speckle=TIMED)
-        post_ms = _host_timed(sync, post, max(3, n // 4))
+        post_ms = timed(post, max(3, n // 4))
         rec["maps"][name] = dict(components=int(torch.unique(root).numel()), largest=int(size.max()), speckle_pixels=int((mask > 0).sum()),
                                  speckle_mask_call_ms=call, one_view_post_process_call_ms=post_ms)
         _note(name, rec["maps"][name])
@@ -230,14 +213,14 @@ def main():
         import torch
         import e2e_bench
         from localexpstereo_amd import api, io as lio, stereo
-        if a.device == "cuda" and not torch.cuda.is_available():
-            raise SystemExit("speckle_timing.py measures on the GPU: no HIP device")
+        if a.device == "cuda":
+            timing.require_gpu("speckle_timing.py")
         if a.calls:
             calls_only(torch, api, a.calls, a.maps)
             return
         if not a.skip_timing and not a.small:
             st, e, ev, keep = synthetic(api, lio, stereo, e2e_bench, "objects", a.device, a.lib)
-            rec["timing"] = timing(torch, api, stereo, st, e, a.maps, a.timings)
+            rec["timing"] = measure(torch, api, stereo, st, e, a.maps, a.timings, a.lib)
             e.close()
             del keep
         if not a.skip_quality:
@@ -253,13 +236,11 @@ def main():
                 del keep
             rec["quality"] = rows
     if a.json:
-        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
-        json.dump(rec, open(a.json, "w"), indent=1)
+        timing.write_json(a.json, rec)
     md = markdown(rec)
     print(md)
     if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        open(a.out, "w").write(md + "\n")
+        timing.write_text(a.out, md + "\n")
 
 
 if __name__ == "__main__":

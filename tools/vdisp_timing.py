@@ -6,7 +6,6 @@ energy and random proposer.  Writes profiles/vdisp_timing.json and prints it.  N
     python tools/vdisp_timing.py [--planes 256] [--reps 5] [--no-midv2]
 """
 import argparse
-import json
 import os
 import sys
 import time
@@ -16,10 +15,14 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import timing  # noqa: E402
 from localexpstereo_amd import api, io, stereo, synth  # noqa: E402
 
 
 def timed(fn, reps):
+    """Sorted ms of `reps` calls queued back to back, every pair of events recorded before the one synchronise: the one loop tools/timing.py does
+    not state (its clock synchronises after every timing); the median is timing.spread's."""
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
     for a, b in ev:
         a.record()
@@ -60,7 +63,7 @@ def main():
             run()
             torch.cuda.synchronize()
             t = timed(run, args.reps)
-            ms[v] = t[len(t) // 2]
+            ms[v] = timing.spread(t)["median"]
             res[f"windR{windR}_v{v}"] = dict(kernel_kind=b.kernel_kind(0), whole_image_pass_ms=round(ms[v], 3), all_ms=[round(x, 3) for x in t])
         res[f"windR{windR}_v0.37_over_v0"] = round(ms[0.37] / ms[0.0], 3)
         b.destroy()
@@ -75,10 +78,7 @@ def main():
             torch.cuda.synchronize()
             _, bad2 = io.Evaluator(data["dispGT"], data["nonocc"], 2.0).evaluate(stereo.disparities(lab))
             res[f"midv2_cones_{name}"] = dict(seconds=round(time.perf_counter() - t0, 3), bad2_nonocc=round(bad2, 3))
-    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "vdisp_timing.json"), "w") as f:
-        f.write(json.dumps(res) + "\n")
-    print(json.dumps(res))
+    timing.write_record(os.path.join(ROOT, "profiles", "vdisp_timing.json"), res)
 
 
 if __name__ == "__main__":

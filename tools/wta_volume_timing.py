@@ -7,7 +7,8 @@
 Recorded:
   * reduction: les_slab_argmin_kernel + the finish over a resident 256-slab volume at 1436 x 992 and 1500 x 1000 in chunks of 32 (8 step launches and
     the finish per timing; the volume, 1.4 - 1.5 GB, is streamed once per timing, so no chunk is re-read from the Infinity Cache), next to
-    les_hip_calib_copy_wide over the same number of bytes read (which also writes them) -- medians of 20 device-event timings after a warm-up;
+    les_hip_calib_copy_wide over the same number of bytes read (which also writes them) -- each a group of one of tools/timing.py (which states
+    the protocol) after 3 warm-up calls;
   * whole_call: les_hip_wta_labels on bench.py's H1 context (U[0,1) volume, guided filter, windR 20) at those sizes with chunks of 16 / 32 / 64, next
     to the H1 pass of the same build (one launch of the 256 fronto-parallel planes into 256 slabs);
   * runs (unless --skip-runs): the two synthetic scenes of tools/e2e_bench.py at 1436 x 992 x 256, two views, MidV3 energy and layers: the Evaluator
@@ -15,8 +16,6 @@ Recorded:
     clock; and FastGCStereo.wta alone.
 Nothing here is a gate."""
 import argparse
-import ctypes as C
-import json
 import os
 import sys
 import time
@@ -28,32 +27,14 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 os.environ.setdefault("OMP_WAIT_POLICY", "passive")
 
+import timing  # noqa: E402
+
 D = 256
 SIZES = ((992, 1436), (1000, 1500))
 
 
 def _note(*a):
     print(*a, file=sys.stderr, flush=True)
-
-
-def _spread(v):
-    v = np.asarray(v, np.float64)
-    return dict(median=round(float(np.median(v)), 4), min=round(float(v.min()), 4), max=round(float(v.max()), 4), n=int(len(v)))
-
-
-def _timed(torch, f, timings):
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(3):
-        f()
-    torch.cuda.synchronize()
-    t = []
-    for _ in range(timings):
-        ev0.record()
-        f()
-        ev1.record()
-        torch.cuda.synchronize()
-        t.append(ev0.elapsed_time(ev1))
-    return t
 
 
 def time_size(torch, api, synth, h, w, timings):
@@ -69,17 +50,17 @@ def time_size(torch, api, synth, h, w, timings):
     labels, cost = torch.empty((h, w, 4), device="cuda"), torch.empty((h, w), device="cuda")
     state = torch.empty(e.slab_argmin_state_bytes() // 4, device="cuda")
     rec = dict(shape=[w, h, D], bytes_read=4 * D * P)
+    clock = timing.Clock(torch, "cuda")
+    one = lambda f: timing.spread(timing.time_one(clock, f, timings, warm=3), 4)
 
     # ---- the reduction alone, over the raw volume (any resident [256][H][W] floats do)
     def reduce(chunk=32):
         for k0 in range(0, D, chunk):
             e.slab_argmin(vol.data_ptr() + 4 * k0 * P, min(chunk, D - k0), k0, state.data_ptr())
         e.slab_argmin_finish(state.data_ptr(), D, labels.data_ptr(), cost.data_ptr())
-    rec["reduction_ms_chunk32"] = _spread(_timed(torch, reduce, timings))
-    rec["reduction_ms_one_chunk"] = _spread(_timed(torch, lambda: reduce(D), timings))
-    n = D * P
-    rec["copy_wide_ms"] = _spread(_timed(torch, lambda: e._chk(e.L.les_hip_calib_copy_wide(C.c_void_p(vol.data_ptr()), C.c_void_p(out.data_ptr()), C.c_size_t(n), 0,
-                                                                                         C.c_void_p(stream.cuda_stream))), timings))
+    rec["reduction_ms_chunk32"] = one(reduce)
+    rec["reduction_ms_one_chunk"] = one(lambda: reduce(D))
+    rec["copy_wide_ms"] = one(timing.copy_call(api, 2 * rec["bytes_read"], stream.cuda_stream, wide=True))
     rec["reduction_over_copy"] = round(rec["reduction_ms_chunk32"]["median"] / rec["copy_wide_ms"]["median"], 3)
     rec["reduction_GBps"] = round(rec["bytes_read"] / rec["reduction_ms_chunk32"]["median"] / 1e6, 1)
     _note("reduction", rec["shape"], rec["reduction_ms_chunk32"], rec["reduction_ms_one_chunk"], rec["copy_wide_ms"])
@@ -89,10 +70,10 @@ def time_size(torch, api, synth, h, w, timings):
     batch = api.Batch(e, full, full, out_slabs=True)
     planes = torch.from_numpy(synth.fronto_planes(D)).cuda()
     rec["h1_kernel_kind"] = batch.kernel_kind(0)
-    rec["h1_ms"] = _spread(_timed(torch, lambda: batch.run(planes.data_ptr(), out.data_ptr(), mode=0, check=False, planes_on_device=True), timings))
+    rec["h1_ms"] = one(lambda: batch.run(planes.data_ptr(), out.data_ptr(), mode=0, check=False, planes_on_device=True))
     _note("H1", rec["h1_ms"])
     for chunk in (16, 32, 64):
-        rec[f"wta_labels_ms_chunk{chunk}"] = _spread(_timed(torch, lambda: e.wta_labels(0, chunk, True, labels.data_ptr(), cost.data_ptr()), timings))
+        rec[f"wta_labels_ms_chunk{chunk}"] = one(lambda: e.wta_labels(0, chunk, True, labels.data_ptr(), cost.data_ptr()))
         rec[f"wta_labels_minus_h1_ms_chunk{chunk}"] = round(rec[f"wta_labels_ms_chunk{chunk}"]["median"] - rec["h1_ms"]["median"], 4)
         _note("wta_labels chunk", chunk, rec[f"wta_labels_ms_chunk{chunk}"])
     batch.destroy()
@@ -143,20 +124,15 @@ def main():
     ap.add_argument("--skip-runs", action="store_true", help="the kernel and whole-call timings only")
     ap.add_argument("--skip-kernels", action="store_true", help="the end-to-end runs only")
     a = ap.parse_args()
-    import torch
+    torch = timing.require_gpu("wta_volume_timing.py")
     import e2e_bench
     from localexpstereo_amd import api, io as lio, stereo, synth
-    if not torch.cuda.is_available():
-        raise SystemExit("wta_volume_timing.py measures on the GPU: no HIP device")
     rec = dict(timings=a.timings)
     if not a.skip_kernels:
         rec["sizes"] = [time_size(torch, api, synth, h, w, a.timings) for h, w in SIZES]
     if not a.skip_runs:
         rec["runs"] = [time_runs(torch, api, stereo, lio, e2e_bench, scene) for scene in ("objects", "three_surfaces")]
-    print(json.dumps(rec, indent=1))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(rec, open(a.out, "w"), indent=1)
+    timing.write_record(a.out, rec)
 
 
 if __name__ == "__main__":
