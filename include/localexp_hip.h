@@ -759,6 +759,29 @@ int les_hip_unrectify_labels(const les_hip_plane* d_labels, int H, int W, const 
                              const double M[9], double f, double cx, double cy, double doffs, double baseline, float z_max, float* d_points /* may be NULL */,
                              float* d_normals /* may be NULL */, float* d_disparity /* may be NULL */, unsigned char* d_valid, int device, void* hip_stream);
 
+/* ---- a fisheye raw camera: the two maps above for the equidistant (Kannala-Brandt) model (csrc/les_fisheye.h holds the camera model and the
+ * definitions; no reference counterpart) ----
+ * Camera model: a point (X, Y, Z) of the raw camera's frame is seen at (u, v), pixel centres at integer coordinates, zero skew, with
+ * k = (k1, k2, k3, k4):  a = X / Z, b = Y / Z, r = sqrt(a^2 + b^2), theta = atan(r), theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6
+ * + k4 theta^8), u = fx (theta_d / r) a + cx, v = fy (theta_d / r) b + cy (r = 0: the principal point).  theta_max in (0, pi] is the largest
+ * theta the lens is calibrated for: a ray beyond it has no pixel (the guard against the polynomial folding back; io.fisheye_theta_max of the
+ * Python package finds the fold).  Rays with Z <= 0 have no pixel either.
+ * les_hip_rectify_map_fisheye is les_hip_rectify_map and les_hip_unrectify_map_fisheye is les_hip_unrectify_map for such a camera: the same
+ * arguments, the same map layout (so les_hip_remap and les_hip_unrectify_labels take the maps unchanged), (NaN, NaN) where a pixel has no
+ * position.  atan, sin and cos are stated in csrc/les_fisheye.h in plain fp64 operations in a fixed order (within 2.3e-16 of the C library's),
+ * so both maps are, like the pinhole ones, a function of their arguments alone, bit for bit.  The inverse solves theta P(theta) = theta_d by
+ * `steps` (1 .. 64) Newton steps -- it converges wherever d theta_d / d theta > 0, the whole field of a lens of 180 degrees and more -- and
+ * keeps a pixel only where the forward model's residual is at most `tol` (> 0) RAW pixels: a position that fails the test is never stored.
+ * Both are context-free and enqueue only on hip_stream of `device`.  The refusals and codes of the pinhole entries, and LES_HIP_ERR_ARG for a
+ * k that is not finite and for a theta_max that is NaN or outside (0, pi]; a refused call launches nothing. */
+typedef struct les_hip_fisheye {
+    double fx, fy, cx, cy, k[4], theta_max;
+} les_hip_fisheye;
+int les_hip_rectify_map_fisheye(const les_hip_fisheye* raw, const double M[9], double f, double cx, double cy, float* d_map /* [H][W][2] */, int H, int W,
+                                int device, void* hip_stream);
+int les_hip_unrectify_map_fisheye(const les_hip_fisheye* raw, const double R[9], double f, double cx, double cy, int steps, double tol,
+                                  float* d_map /* [Hs][Ws][2] */, int Hs, int Ws, int device, void* hip_stream);
+
 /* ---- multi-GPU: publishing the tiles a rank updated (not in the reference, which is single-process; SURVEY 8(e): the cells of a
  * disjoint set -- LES/LayerManager.h:168-172 -- are split over the ranks, replicas of the label / cost maps are kept coherent by one
  * all-gather per set of the label (16 B/px) and cost (4 B/px) tiles of the shared regions, LES/FastGCStereo.h:22-72).

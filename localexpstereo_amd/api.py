@@ -5,6 +5,7 @@ This is plumbing for tests and bench.py: the product is the shared library and t
 device is present, everything here raises -- there is no CPU fallback.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -39,6 +40,7 @@ SYMBOLS = [
     "les_hip_render_view", "les_hip_blend_views", "les_hip_photo_error",
     "les_hip_rectify_map", "les_hip_remap",
     "les_hip_unrectify_map", "les_hip_unrectify_labels",
+    "les_hip_rectify_map_fisheye", "les_hip_unrectify_map_fisheye",
     "les_hip_fill_invalid",
 ]
 
@@ -82,6 +84,11 @@ class Calib(C.Structure):
 class Camera(C.Structure):
     """les_hip_camera (include/localexp_hip.h): a raw pinhole camera, dist = (k1, k2, p1, p2, k3, k4, k5, k6)."""
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("dist", C.c_double * 8)]
+
+
+class Fisheye(C.Structure):
+    """les_hip_fisheye (include/localexp_hip.h): a raw equidistant fisheye camera, k = (k1, k2, k3, k4), theta_max in (0, pi]."""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("k", C.c_double * 4), ("theta_max", C.c_double)]
 
 
 class Params(C.Structure):
@@ -227,6 +234,8 @@ def load(path=None):
         "les_hip_remap": (ci, [vp, ci, ci, ci, vp, vp, vp, ci, ci, ci, ci, vp]),
         "les_hip_fill_invalid": (ci, [vp, ci, ci, ci, ci, ci, vp, vp, C.c_float, ci, vp]),
         "les_hip_unrectify_map": (ci, [C.POINTER(Camera), C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, ci, C.c_double, vp, ci, ci, ci, vp]),
+        "les_hip_rectify_map_fisheye": (ci, [C.POINTER(Fisheye), C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, vp, ci, ci, ci, vp]),
+        "les_hip_unrectify_map_fisheye": (ci, [C.POINTER(Fisheye), C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, ci, C.c_double, vp, ci, ci, ci, vp]),
         "les_hip_unrectify_labels": (ci, [vp, ci, ci, vp, vp, ci, ci, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                           C.c_float, vp, vp, vp, vp, ci, vp]),
         "les_hip_mesh": (ci, [vp, ci, vp, vp, C.c_float, vp, vp, vp, vp]),
@@ -441,6 +450,46 @@ def unrectify_labels(labels_dev_ptr, H, W, drop_dev_ptr, invmap_dev_ptr, Hs, Ws,
     _chk_lib(L, L.les_hip_unrectify_labels(_vp(labels_dev_ptr), H, W, _vp(drop_dev_ptr), _vp(invmap_dev_ptr), Hs, Ws, m, float(f), float(cx), float(cy),
                                            float(doffs), float(baseline), float(z_max) if z_max is not None else 0.0, _vp(points_dev_ptr), _vp(normals_dev_ptr),
                                            _vp(disparity_dev_ptr), _vp(valid_dev_ptr), device, C.c_void_p(int(stream))))
+
+
+FISHEYE_STEPS = 10                                 # les_hip_unrectify_map_fisheye's default: Newton steps (quadratic convergence; five reach 2e-16 rad at 95 degrees)
+
+
+def fisheye(K, k=(), theta_max=math.pi / 2):
+    """A Fisheye (les_hip_fisheye) of a 3 x 3 camera matrix with zero skew, up to 4 coefficients (k1, k2, k3, k4) of the equidistant model of
+    csrc/les_fisheye.h, shorter inputs padded with zeros, and the largest calibrated angle theta_max in (0, pi] (io.fisheye_theta_max finds the
+    fold of a lens).  A Fisheye passes through."""
+    if isinstance(K, Fisheye):
+        return K
+    K = np.asarray(K, np.float64)
+    d = np.asarray(k if k is not None else (), np.float64).reshape(-1)
+    if K.shape != (3, 3) or K[0, 1] != 0.0:
+        raise ValueError("fisheye: K is a 3 x 3 camera matrix with zero skew")
+    if d.size > 4:
+        raise ValueError(f"fisheye: {d.size} coefficients, at most 4 (k1, k2, k3, k4)")
+    return Fisheye(K[0, 0], K[1, 1], K[0, 2], K[1, 2], (C.c_double * 4)(*np.concatenate([d, np.zeros(4 - d.size)])), float(theta_max))
+
+
+def rectify_map_fisheye(raw, M, f, cx, cy, map_dev_ptr, H, W, device=0, stream=0, lib=None):
+    """les_hip_rectify_map_fisheye: rectify_map for a raw fisheye camera -- raw: a Fisheye (or what fisheye() takes as K); everything else and the
+    map's layout as there.  fp64 in the fixed order of csrc/les_fisheye.h, its own atan included; (NaN, NaN) where a rectified pixel's ray lies
+    behind the camera or beyond theta_max.  Enqueue only."""
+    L = load(lib)
+    cam = fisheye(raw)
+    m = (C.c_double * 9)(*np.asarray(M, np.float64).reshape(9))
+    _chk_lib(L, L.les_hip_rectify_map_fisheye(C.byref(cam), m, float(f), float(cx), float(cy), _vp(map_dev_ptr), H, W, device, C.c_void_p(int(stream))))
+
+
+def unrectify_map_fisheye(raw, R, f, cx, cy, map_dev_ptr, Hs, Ws, steps=FISHEYE_STEPS, tol=UNRECTIFY_TOL, device=0, stream=0, lib=None):
+    """les_hip_unrectify_map_fisheye: unrectify_map for a raw fisheye camera -- raw: a Fisheye (or what fisheye() takes as K); everything else and
+    the map's layout as there.  The radial polynomial is inverted by `steps` (1 .. 64) Newton steps and a pixel is kept only where the forward
+    model's residual is at most tol (> 0) raw pixels; fp64 in the fixed order of csrc/les_fisheye.h, its own sin and cos included; (NaN, NaN)
+    where a raw pixel lies beyond the lens's fold or theta_max, or has no rectified position.  Enqueue only."""
+    L = load(lib)
+    cam = fisheye(raw)
+    r = (C.c_double * 9)(*np.asarray(R, np.float64).reshape(9))
+    _chk_lib(L, L.les_hip_unrectify_map_fisheye(C.byref(cam), r, float(f), float(cx), float(cy), int(steps), float(tol), _vp(map_dev_ptr), Hs, Ws, device,
+                                                C.c_void_p(int(stream))))
 
 
 FIT_MAX_RADIUS = 15            # kFitMaxR of csrc/les_planefit.h (the one source; tests/planefit_cases.py: case_independence_and_errors holds this copy to it)

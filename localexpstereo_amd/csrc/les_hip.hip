@@ -30,6 +30,7 @@
 #include "les_view.h"
 #include "les_rectify.h"
 #include "les_unrectify.h"
+#include "les_fisheye.h"
 #include "les_maskvol.h"
 
 #include "../host/ResidualCut.h"      // the host cores' finisher of the tiled max-flow (plain C++: search trees / push-relabel on a residual graph)
@@ -334,4 +335,5 @@ float naive_alpha(const les_hip_ctx* c) { return c->naive_alpha; }
 #include "les_hip_view.inc"
 #include "les_hip_rectify.inc"
 #include "les_hip_unrectify.inc"
+#include "les_hip_fisheye.inc"
 #include "les_hip_maskvol.inc"

@@ -276,7 +276,34 @@ def _rotation_vector(R):
     return a * 0.5 if s < 1e-8 else a * (th / s)
 
 
-def stereo_rectify(K0, dist0, K1, dist1, R, T, f=None, principal=None):
+def fisheye_theta_max(k, fov=None):
+    """The largest angle off the axis, radians, at which the fisheye model of csrc/les_fisheye.h with k = (k1, k2, k3, k4) may be used: the
+    smallest theta in (0, pi / 2] at which Q(theta) = d theta_d / d theta = 1 + 3 k1 theta^2 + 5 k2 theta^4 + 7 k3 theta^6 + 9 k4 theta^8 reaches
+    0 -- where the polynomial folds back and two rays share a pixel --, shrunk by a relative 1e-6 so that Q > 0 up to it; pi / 2 where there is no
+    such root (the roots of the quartic in theta^2: np.roots).  fov: the lens's full field of view in degrees; the result is at most half of it.
+    Host numpy."""
+    k = np.array(() if k is None else k, np.float64).reshape(-1)
+    if k.size > 4:
+        raise ValueError(f"fisheye_theta_max: {k.size} coefficients, at most 4 (k1, k2, k3, k4)")
+    k = np.concatenate([k, np.zeros(4 - k.size)])
+    out = 0.5 * np.pi
+    coef = np.array([9.0 * k[3], 7.0 * k[2], 5.0 * k[1], 3.0 * k[0], 1.0])
+    if np.any(coef[:4] != 0.0):
+        t = np.roots(coef)
+        t = t.real[(np.abs(t.imag) <= 1e-9 * np.maximum(1.0, np.abs(t.real))) & (t.real > 0.0)]
+        th = np.sqrt(t)
+        th = th[th <= 0.5 * np.pi]
+        if th.size:
+            out = float(th.min()) * (1.0 - 1e-6)
+    if fov is not None:
+        out = min(out, 0.5 * float(np.radians(float(fov))))
+    return float(out)
+
+
+RECTIFY_MODELS = ("pinhole", "fisheye")
+
+
+def stereo_rectify(K0, dist0, K1, dist1, R, T, f=None, principal=None, model="pinhole", fov=None):
     """The rectifying transform of a calibrated raw stereo pair (Bouguet's construction), numpy fp64.
     K0, K1: the 3 x 3 pinhole matrices of the raw cameras, zero skew.  dist0, dist1: up to 8 coefficients (k1, k2, p1, p2, k3, k4, k5, k6),
     shorter inputs padded with zeros (the camera model: csrc/les_rectify.h; pixel centres at integer coordinates).  R, T: the rig in the
@@ -287,8 +314,15 @@ def stereo_rectify(K0, dist0, K1, dist1, R, T, f=None, principal=None):
     to (fy0 + fy1) / 2, cy to (cy0 + cy1) / 2, cx0 = K0[0, 2], cx1 = K1[0, 2], principal=(cx0, cx1, cy) overrides the three; baseline = |T|;
     doffs = cx1 - cx0; calib: the api.Calib of the rectified pair (calib3d), with which d + doffs = f baseline / Z as reconstruct assumes;
     K0, K1, dist0, dist1: the inputs as fp64 arrays, dist padded to 8).
-    ValueError: a skewed K, more than 8 coefficients, and a rig whose right camera is not to the right of the left one: a baseline nearer
-    the y axis than the x axis (a vertical rig), or a right camera on the left."""
+    model="fisheye": the raw cameras are equidistant fisheye cameras (the camera model: csrc/les_fisheye.h): dist0, dist1 hold up to 4
+    coefficients (k1, k2, k3, k4), padded to 4; the rotations and the new intrinsics are built the same way -- they do not depend on the
+    distortion --, and the dict adds model="fisheye" and theta_max0, theta_max1 = fisheye_theta_max(dist, fov) (fov: the lenses' full field of
+    view, degrees).  With model="pinhole" the dict is the one above, without these keys.
+    ValueError: a skewed K, more than 8 coefficients (4 for "fisheye"), an unknown model, and a rig whose right camera is not to the right of
+    the left one: a baseline nearer the y axis than the x axis (a vertical rig), or a right camera on the left."""
+    if model not in RECTIFY_MODELS:
+        raise ValueError(f"stereo_rectify: unknown model {model!r}: one of {RECTIFY_MODELS}")
+    ncoef, names = (8, "k1, k2, p1, p2, k3, k4, k5, k6") if model == "pinhole" else (4, "k1, k2, k3, k4")
     K0, K1, R = (np.array(a, np.float64) for a in (K0, K1, R))
     T = np.array(T, np.float64).reshape(-1)
     if K0.shape != (3, 3) or K1.shape != (3, 3) or R.shape != (3, 3) or T.shape != (3,):
@@ -298,9 +332,9 @@ def stereo_rectify(K0, dist0, K1, dist1, R, T, f=None, principal=None):
         if K[0, 1] != 0.0:
             raise ValueError(f"stereo_rectify: a pinhole matrix with skew {K[0, 1]!r}: only zero skew is supported")
         d = np.array(() if d is None else d, np.float64).reshape(-1)
-        if d.size > 8:
-            raise ValueError(f"stereo_rectify: {d.size} distortion coefficients, at most 8 (k1, k2, p1, p2, k3, k4, k5, k6)")
-        dist.append(np.concatenate([d, np.zeros(8 - d.size)]))
+        if d.size > ncoef:
+            raise ValueError(f"stereo_rectify: {d.size} distortion coefficients, at most {ncoef} ({names})")
+        dist.append(np.concatenate([d, np.zeros(ncoef - d.size)]))
     baseline = float(np.sqrt(T @ T))
     if not baseline > 0.0:
         raise ValueError("stereo_rectify: T is zero: the two cameras share a centre")
@@ -320,6 +354,8 @@ def stereo_rectify(K0, dist0, K1, dist1, R, T, f=None, principal=None):
     out = dict(R0=R0, R1=R1, f=float(fnew), cx0=float(cx0), cx1=float(cx1), cy=float(cy), baseline=baseline, doffs=float(cx1 - cx0),
                K0=K0, K1=K1, dist0=dist[0], dist1=dist[1])
     out["calib"] = calib3d(dict(f=out["f"], cx=out["cx0"], cy=out["cy"], doffs=out["doffs"], baseline=baseline))
+    if model == "fisheye":
+        out.update(model="fisheye", theta_max0=fisheye_theta_max(dist[0], fov), theta_max1=fisheye_theta_max(dist[1], fov))
     return out
 
 

@@ -927,15 +927,20 @@ class Rectifier:
     tensors of raw positions, (NaN, NaN) where a rectified pixel has none.
     The way back (csrc/les_unrectify.h): .inverse_maps, the two Hs x Ws x 2 device tensors of rectified positions of the raw pixels, built on
     first use with `steps` fixed-point steps and a residual bound of `tol` raw pixels (api.unrectify_map); .unrectify puts a label map's
-    geometry and .to_raw a rectified-grid image onto the raw grid; .valid_rect and .crop give a rectified pair without invalid borders."""
+    geometry and .to_raw a rectified-grid image onto the raw grid; .valid_rect and .crop give a rectified pair without invalid borders.
+    model="fisheye": the raw cameras are equidistant fisheye cameras (csrc/les_fisheye.h): dist0, dist1 are (k1, k2, k3, k4), fov the lenses' full
+    field of view in degrees (io.stereo_rectify's); both maps come from api.rectify_map_fisheye / api.unrectify_map_fisheye, `steps` counts
+    Newton steps (default api.FISHEYE_STEPS), and everything that works on the maps is unchanged.  Frame a wide lens with f=, principal=, size=
+    and crop(): a pinhole frame cannot hold rays near 90 degrees off its axis."""
 
     def __init__(self, K0, dist0, K1, dist1, R, T, raw_size, size=None, f=None, principal=None, interp="linear", device="cuda", lib=None,
-                 steps=api.UNRECTIFY_STEPS, tol=api.UNRECTIFY_TOL):
+                 steps=None, tol=api.UNRECTIFY_TOL, model="pinhole", fov=None):
         if interp not in api.INTERP_NAMES:
             raise ValueError(f"unknown interp {interp!r}: one of {sorted(api.INTERP_NAMES)}")
-        self.steps, self.tol = int(steps), float(tol)
+        self.transform = tr = io.stereo_rectify(K0, dist0, K1, dist1, R, T, f=f, principal=principal, model=model, fov=fov)
+        self.model = model
+        self.steps, self.tol = int((api.FISHEYE_STEPS if model == "fisheye" else api.UNRECTIFY_STEPS) if steps is None else steps), float(tol)
         self._inverse_maps = self._valid_rect = None
-        self.transform = tr = io.stereo_rectify(K0, dist0, K1, dist1, R, T, f=f, principal=principal)
         self.calib = tr["calib"]
         self.raw_size = tuple(int(n) for n in raw_size)
         self.size = self.raw_size if size is None else tuple(int(n) for n in size)
@@ -946,9 +951,17 @@ class Rectifier:
         self.maps = []
         for m in (0, 1):
             t = torch.empty((H, W, 2), dtype=torch.float32, device=self.device)
-            api.rectify_map(api.camera(tr[f"K{m}"], tr[f"dist{m}"]), tr[f"R{m}"].T, tr["f"], tr[f"cx{m}"], tr["cy"], t.data_ptr(), H, W, device=self.index,
-                            stream=self._stream(), lib=lib)
+            if model == "fisheye":
+                api.rectify_map_fisheye(self._fisheye(m), tr[f"R{m}"].T, tr["f"], tr[f"cx{m}"], tr["cy"], t.data_ptr(), H, W, device=self.index,
+                                        stream=self._stream(), lib=lib)
+            else:
+                api.rectify_map(api.camera(tr[f"K{m}"], tr[f"dist{m}"]), tr[f"R{m}"].T, tr["f"], tr[f"cx{m}"], tr["cy"], t.data_ptr(), H, W, device=self.index,
+                                stream=self._stream(), lib=lib)
             self.maps.append(t)
+
+    def _fisheye(self, m):
+        tr = self.transform
+        return api.fisheye(tr[f"K{m}"], tr[f"dist{m}"], tr[f"theta_max{m}"])
 
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
@@ -997,8 +1010,12 @@ class Rectifier:
             maps = []
             for m in (0, 1):
                 t = torch.empty((Hs, Ws, 2), dtype=torch.float32, device=self.device)
-                api.unrectify_map(api.camera(tr[f"K{m}"], tr[f"dist{m}"]), tr[f"R{m}"], tr["f"], tr[f"cx{m}"], tr["cy"], t.data_ptr(), Hs, Ws, steps=self.steps,
-                                  tol=self.tol, device=self.index, stream=self._stream(), lib=self.lib)
+                if self.model == "fisheye":
+                    api.unrectify_map_fisheye(self._fisheye(m), tr[f"R{m}"], tr["f"], tr[f"cx{m}"], tr["cy"], t.data_ptr(), Hs, Ws, steps=self.steps,
+                                              tol=self.tol, device=self.index, stream=self._stream(), lib=self.lib)
+                else:
+                    api.unrectify_map(api.camera(tr[f"K{m}"], tr[f"dist{m}"]), tr[f"R{m}"], tr["f"], tr[f"cx{m}"], tr["cy"], t.data_ptr(), Hs, Ws, steps=self.steps,
+                                      tol=self.tol, device=self.index, stream=self._stream(), lib=self.lib)
                 maps.append(t)
             self._inverse_maps = maps
         return self._inverse_maps
